@@ -4,6 +4,8 @@ Scenes/cornell-box, 1920x1080, 64 spp, depth 8, persistent-thread HIP on MI355X.
 
   python bench.py --gpus N --steps K --warmup W      (N > 1 without a launcher: starts the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py ... --full                         (everything below beside the headline; a plain run prints the headline only)
+  python bench.py ... --dump-outputs DIR             (the frame the last timed step computed, DIR/accumulation.npy: dump_outputs())
 
 One "step" = one full render of the workload (W*H*spp samples).  With N > 1 the frame is cut into 64x64 tiles dealt
 round-robin to the ranks (tile t -> rank t % N); each rank renders its tiles, packs them, the packed HDR
@@ -11,7 +13,8 @@ buffers are gathered to rank 0 over RCCL and rank 0 un-permutes them into the fu
 region.  The total work is fixed, so scaling is "strong".  Scene + BVH are resident in HBM before the timed region
 starts; nothing is read from the host inside it.
 
-What one JSON line carries:
+What one JSON line carries: metric, value (Msamples/s of the timed steps), unit, higher_is_better, dtype,
+ms_per_step, steps, warmup, n_gpus, scaling, data, config -- and, with --full only:
   "roofline"          the timed kernel on the timed workload.  cornell-box is LDS-resident, so the resource is VALU
                       issue: frac = SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x launch time x 2.4 GHz); the instruction
                       count per launch comes from the committed rocprofv3 PMC pass of this command
@@ -126,7 +129,14 @@ def parse_args(argv=None):
     ap.add_argument("--sync-steps", action="store_true")    # N = 1: wait for every render before enqueuing the next
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
     ap.add_argument("--selftest-cpu", action="store_true")  # plumbing test without a GPU (tests/test_bench_spawn.py)
+    # A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds everything else the line can carry:
+    # the roofline blocks, the roofline_<leg> / scale_<leg> workloads, pcie_inclusive, the CPU baseline, the parity gate and, at N > 1,
+    # the per-stage breakdown, expected_speedup and the assembled-frame check.  The --no-* / --legs / --leg-steps options act within it.
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)   # after the timed steps: the frame the last one computed, DIR/<name>.npy
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.builder is None:
         a.builder = 4 if a.scene.startswith("proc") else 1
     if a.legs is None:
@@ -664,6 +674,27 @@ class TileSplit:
         return bool(np.array_equal(assembled.view(np.uint32), whole.view(np.uint32)))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(np, out_dir, frame):
+    """--dump-outputs DIR: what the timed path hands its caller after a step -- the W x H RGBA32F accumulation (.xyz radiance sums,
+    .w the sample weight; tb_read_accum) the last timed step left -- as DIR/accumulation.npy, float32, H x W x 4.  A frame above
+    64 MB (4K) is written as a fixed sample instead: accumulation_sample.npy (n x 4) of the pixels whose row-major indices
+    accumulation_sample_pixels.npy holds (float64, seed 0).  The inputs are fixed (scene file or seeded generator, Time = 0), so two
+    builds run with the same arguments can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    if a.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "accumulation.npy"), a)
+        return
+    flat = a.reshape(-1, a.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // (flat.shape[1] * 4)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "accumulation_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "accumulation_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def timed_steps(step, barrier, warmup, steps):
     for _ in range(warmup):
         step()
@@ -1051,6 +1082,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def finish(result):
+        """Rank 0 prints the line; the context and the process group end."""
+        if rank == 0:
+            print(json.dumps(result))
+        tb.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
     # ---- the timed region -----------------------------------------------------------------------------------------
     pipelined = world > 1 or args.async_steps
     kernel_ms = []
@@ -1084,10 +1124,10 @@ def main():
     if pipelined or not args.sync_steps:
         tb.Sync()
         kernel_ms.append(tb.GetOption("last_kernel_us") / 1e3)   # HIP events of the last render of the timed region
-    # the frame the last timed step left in HBM, for the parity gate below (N = 1: the accumulation surface; N > 1: what rank 0
-    # assembled from the gathered tiles)
+    # the frame the last timed step left in HBM, for --dump-outputs and the parity gate below (N = 1: the accumulation surface; N > 1:
+    # what rank 0 assembled from the gathered tiles)
     timed_frame = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_outputs):
         torch.cuda.synchronize()
         timed_frame = ts.frame.cpu().numpy() if world > 1 else tb.ReadAccumulation()
     if world > 1:
@@ -1108,20 +1148,28 @@ def main():
                    "kernel_variant": VARIANTS[tb.GetOption("last_variant")], "scene_load_s": round(load_s, 3)},
     }
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, args.dump_outputs, timed_frame)
+
     if world > 1:
         tl = torch.tensor([load_s], device=dev, dtype=torch.float64)
         dist.all_reduce(tl, op=dist.ReduceOp.MAX)
         result["config"]["scene_load_s"] = round(float(tl.item()), 3)
         result["config"]["scene_load_s_note"] = "max over ranks (every rank loads and builds the scene itself)"
-        result["scale_breakdown"] = ts.breakdown(SPP, s, barrier)
-        exp = expected_speedup(args.scene, W, H, SPP, args.depth, world)
-        if exp:
-            result["expected_speedup"] = exp
+        if args.full:
+            result["scale_breakdown"] = ts.breakdown(SPP, s, barrier)
+            exp = expected_speedup(args.scene, W, H, SPP, args.depth, world)
+            if exp:
+                result["expected_speedup"] = exp
         result["rccl_ranks"] = int(dist.get_world_size())
         result["collective_backend"] = backend
-        if rank == 0:
+        if rank == 0 and args.full:
             result["config"]["assembled_frame_equals_single_gpu"] = ts.assembled_equals_single_gpu(np, SPP, s)
         dist.barrier()
+
+    if not args.full:
+        finish(result)
+        return
 
     # ---- roofline of the dominant (only) kernel of the timed workload: pt_persistent (rank 0) -------------------------
     if rank == 0:
@@ -1224,11 +1272,7 @@ def main():
             parity = parity_strips(tb, np, timed_frame, W, H, SPP, s, oracle_threads())
         if parity is not None:
             gate(parity, result)
-        print(json.dumps(result))
-    tb.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(result)
 
 
 if __name__ == "__main__":

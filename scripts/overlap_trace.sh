@@ -7,7 +7,7 @@ set -u
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 NAME=${1:-c2_overlap_trace}; shift || true
 OUT=gpurun_out/overlap_$NAME; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-c3 --no-readback "$@" > $OUT/bench.json 2> $OUT/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-c3 --no-readback "$@" > $OUT/bench.json 2> $OUT/err.txt
 python3 - "$OUT" "$NAME" <<'PY'
 import csv, glob, sys
 out, name = sys.argv[1], sys.argv[2]

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 TAG=$1; OPT=${2%%=*}; VALS=${2#*=}; shift 2
 OUT=gpurun_out/pmcab_$TAG; rm -rf $OUT; mkdir -p $OUT
 for V in ${VALS//,/ }; do
-  ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback --sync-steps --opt $OPT=$V $*"
+  ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback --sync-steps --opt $OPT=$V $*"
   pass() { timeout 200 rocprofv3 --pmc "${@:2}" --output-format csv -d $OUT/v$V/$1 -o $1 -- python3 bench.py $ARGS > /dev/null 2> $OUT/v$V.$1.err || echo "pass $1 failed / timed out"; }
   python3 bench.py $ARGS > $OUT/v$V.bench.json 2> $OUT/v$V.bench.err
   pass a SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES

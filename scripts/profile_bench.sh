@@ -12,7 +12,7 @@ OUT=gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
 # --sync-steps: one launch at a time, so that a kernel's duration in the trace is its own (bench.py's default overlaps the launches of
 # consecutive steps; its roofline block times non-overlapped launches the same way)
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-c3 --sync-steps ${BENCH_ARGS:-}"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-c3 --sync-steps ${BENCH_ARGS:-}"
 python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py $ARGS > /dev/null 2> $OUT/trace.err
 pass() { rocprofv3 --pmc "${@:2}" --output-format csv -d $OUT/pmc_$1 -o $1 -- python3 bench.py $ARGS > /dev/null 2> $OUT/$1.err; }

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=gpurun_out/r5; mkdir -p $O
 python3 -m pytest tests -m gpu -x -q > $O/gpu_suite.log 2>&1; echo "suite rc $?"; tail -5 $O/gpu_suite.log
 python3 __graft_entry__.py --smoke 2>&1 | tail -2
-python3 bench.py --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench_steps20.err; echo "bench rc $?"
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench_steps20.err; echo "bench rc $?"
 python3 - <<'PY'
 import json
 d=json.load(open('gpurun_out/r5/bench_steps20_warmup5.json'))

@@ -11,5 +11,5 @@ python3 scripts/rank_imbalance.py $O/rank_imbalance_32spp.json --spp 32 --steps 
 timeout 900 python3 scripts/costly_first_stress.py 300 > $O/costly_first_stress.txt 2>&1; tail -1 $O/costly_first_stress.txt
 timeout 1500 python3 -m pytest tests -m gpu -q > $O/gpu_suite.log 2>&1; tail -1 $O/gpu_suite.log
 python3 scripts/collect_profiles.py r6 > /dev/null; cp $O/*_spill_share.json $O/rank_imbalance.json $O/rank_imbalance_32spp.json profiles/r6/
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; cut -c1-200 $O/bench_default.json
-python3 bench.py --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2>/dev/null; cut -c1-200 $O/bench_steps20_warmup5.json
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cut -c1-200 $O/bench_default.json
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2>/dev/null; cut -c1-200 $O/bench_steps20_warmup5.json

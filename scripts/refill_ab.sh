@@ -7,9 +7,9 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=gpurun_out/refill_ab; rm -rf $OUT; mkdir -p $OUT
 run() { # tag, bench args...
   TAG=$1; shift
-  timeout 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-c3 --no-readback "$@" > $OUT/$TAG.bench.json 2> $OUT/$TAG.err
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$TAG.trace -o t -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback "$@" > /dev/null 2>> $OUT/$TAG.err
-  timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $OUT/$TAG.pmc -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback "$@" > /dev/null 2>> $OUT/$TAG.err
+  timeout 300 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-c3 --no-readback "$@" > $OUT/$TAG.bench.json 2> $OUT/$TAG.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$TAG.trace -o t -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback "$@" > /dev/null 2>> $OUT/$TAG.err
+  timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $OUT/$TAG.pmc -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback "$@" > /dev/null 2>> $OUT/$TAG.err
 }
 C3="--scene proc0:870000 --spp 32 --depth 6"
 C5="--scene proc2:2980000 --builder 4 --width 3840 --height 2160 --spp 4 --depth 16"

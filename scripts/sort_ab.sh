@@ -7,8 +7,8 @@ TAG=$1; shift
 for SORT in 0 1; do
   python3 bench.py --no-c3 --no-cpu-baseline --pipeline 2 --opt wavefront_sort=$SORT --steps 3 "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$TAG sort=$SORT', d['value'], 'Msamples/s', d['ms_per_step'], 'ms/step', d['config']['kernel_variant'])"
   OUT=gpurun_out/sort_${TAG}_$SORT; rm -rf $OUT; mkdir -p $OUT
-  rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $OUT -o p -- python3 bench.py --no-c3 --no-cpu-baseline --pipeline 2 --opt wavefront_sort=$SORT --steps 1 --warmup 0 "$@" > /dev/null 2> $OUT/err.txt
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -o t -- python3 bench.py --no-c3 --no-cpu-baseline --pipeline 2 --opt wavefront_sort=$SORT --steps 1 --warmup 0 "$@" > /dev/null 2>> $OUT/err.txt
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $OUT -o p -- python3 bench.py --full --no-c3 --no-cpu-baseline --pipeline 2 --opt wavefront_sort=$SORT --steps 1 --warmup 0 "$@" > /dev/null 2> $OUT/err.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -o t -- python3 bench.py --full --no-c3 --no-cpu-baseline --pipeline 2 --opt wavefront_sort=$SORT --steps 1 --warmup 0 "$@" > /dev/null 2>> $OUT/err.txt
   python3 - "$OUT" "$TAG" "$SORT" <<'PY'
 import csv, glob, collections, sys, json, re
 out, tag, sort = sys.argv[1:4]

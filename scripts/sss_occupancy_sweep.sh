@@ -12,7 +12,7 @@ for W in 3 4 5 6; do
   cp tracerboy_amd/_sweep/libtracerboy_hip_sss$W.so tracerboy_amd/libtracerboy_hip.so
   for CFG in c4 c5; do
     if [ $CFG = c4 ]; then SC="--scene proc1:700000 --depth 6"; else SC="--scene proc2:2980000 --depth 16"; fi
-    ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback --sync-steps --builder 4 --width 3840 --height 2160 --spp 8 $SC"
+    ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-c3 --no-readback --sync-steps --builder 4 --width 3840 --height 2160 --spp 8 $SC"
     timeout 200 python3 bench.py $ARGS > $OUT/${CFG}_w$W.bench.json 2> $OUT/${CFG}_w$W.bench.err
     pass() { timeout 200 rocprofv3 --pmc "${@:2}" --output-format csv -d $OUT/${CFG}_w$W/$1 -o $1 -- python3 bench.py $ARGS > /dev/null 2> $OUT/${CFG}_w$W.$1.err || echo "pass $1 failed"; }
     pass a WRITE_SIZE

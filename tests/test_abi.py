@@ -61,17 +61,20 @@ def test_create_without_gpu_fails_loudly(built):
     assert e.value.code == -2  # TB_E_NO_DEVICE: no CPU fallback
 
 
-def test_host_scene_errors_are_codes_not_aborts(built, tmp_path):
+def test_host_scene_errors_are_codes_not_aborts(built, tmp_path, monkeypatch):
     from tracerboy_amd import api
+    # relative names: the loader's message starts with the file's path, and the code is chosen from the message's words, so a
+    # temporary directory whose path holds one of them ("popen-gw1" under pytest-xdist, a user name) must not reach it
+    monkeypatch.chdir(tmp_path)
     with pytest.raises(api.TracerBoyError) as e:
-        api.HostScene(str(tmp_path / "missing.pbrt"))
+        api.HostScene("missing.pbrt")
     assert e.value.code == -3
     bad = tmp_path / "bad.pbrt"
     bad.write_text('Camera "perspective"\nWorldBegin\nBogusDirective 1 2 3\nWorldEnd\n')
     with pytest.raises(api.TracerBoyError) as e:
-        api.HostScene(str(bad))
+        api.HostScene("bad.pbrt")
     assert e.value.code == -4
     empty = tmp_path / "empty.pbrt"
     empty.write_text('Camera "perspective" "float fov" [30]\nWorldBegin\nWorldEnd\n')
     with pytest.raises(api.TracerBoyError):
-        api.HostScene(str(empty))
+        api.HostScene("empty.pbrt")

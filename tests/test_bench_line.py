@@ -2,8 +2,9 @@
 
 CPU half: one BVH builder per workload at every N, `expected_speedup_leg` reads the committed per-rank
 measurements, the N > 1 record copies -- never measures -- the CPU baseline.
-GPU half: a short N = 1 run asserts that `frac` of every roofline block is achieved / peak of WORK (the SURVEY 8d
-algorithmic byte rate over 8 TB/s; not a pipe's busy counter), with the pipe figures beside it and marked as committed."""
+GPU half: a short N = 1 --full run asserts that `frac` of every roofline block is achieved / peak of WORK (the SURVEY 8d
+algorithmic byte rate over 8 TB/s; not a pipe's busy counter), with the pipe figures beside it and marked as committed; a plain
+run carries the headline only and dumps the frame its last timed step computed."""
 import json
 import os
 import subprocess
@@ -85,7 +86,7 @@ def _check_roofline_block(r, hbm=True):
 @pytest.mark.gpu
 def test_n1_line_fields(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--legs", "teapot,vwvan",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--legs", "teapot,vwvan",
                         "--leg-steps", "1", "--cpu-baseline-seconds", "1"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -113,6 +114,57 @@ def test_n1_line_fields(tmp_path):
     for leg in ("teapot", "vwvan"):
         lp = out["roofline_" + leg]["parity"]
         assert lp["ok"] is True and lp["bit_equal"] is True and lp["pixels"] >= 2 * 8 * 1920 and lp["frames"] == bench.WORKLOADS[leg]["spp"]
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config")
+FULL_ONLY_KEYS = ("roofline", "cpu_baseline", "pcie_inclusive", "parity", "scale_breakdown", "expected_speedup")
+
+
+def test_plain_run_and_dump_options(tmp_path, monkeypatch):
+    """A plain run is the default (--full adds the rest); --steps is the number of timed steps and must be >= 1.  dump_outputs writes
+    the frame as float32, or -- above the byte limit -- a fixed seeded sample of its pixels with their indices, within the limit."""
+    import numpy as np
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    frame = np.random.default_rng(1).uniform(0, 4, (48, 64, 4)).astype(np.float32)
+    bench.dump_outputs(np, str(tmp_path / "whole"), frame)
+    got = np.load(tmp_path / "whole" / "accumulation.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(np, str(tmp_path / d), frame)
+    names = sorted(os.listdir(tmp_path / "s1"))
+    assert names == ["accumulation_sample.npy", "accumulation_sample_pixels.npy"]
+    smp, idx = np.load(tmp_path / "s1" / names[0]), np.load(tmp_path / "s1" / names[1])
+    assert smp.dtype == np.float32 and idx.dtype == np.float64 and smp.nbytes + idx.nbytes <= 4096 and len(idx) > 0
+    assert np.array_equal(smp, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / names[1]))      # the same pixels every run
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_the_timed_frame(tmp_path):
+    """`bench.py` without --full: the headline fields and none of the --full blocks; --dump-outputs writes the accumulation the last
+    timed step left, which for the 64 x 48 x 3 cornell-box frame (builder 0, depth 4) is the committed oracle image bit for bit."""
+    import numpy as np
+    from conftest import GOLDEN
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "64",
+                        "--height", "48", "--spp", "3", "--depth", "4", "--builder", "0", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert all(k in out for k in HEADLINE_KEYS) and not any(k in out for k in FULL_ONLY_KEYS)
+    assert not any(k.startswith(("roofline_", "scale_")) for k in out)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+    frame = np.load(tmp_path / "accumulation.npy")
+    gold = np.load(os.path.join(GOLDEN, "cornell_oracle_64x48x3.npy"))
+    assert frame.dtype == np.float32 and frame.shape == (48, 64, 4)
+    assert np.array_equal(frame.view(np.uint32), gold.view(np.uint32))
 
 
 def test_parity_gate_blocks_a_value_whose_frame_is_wrong():
