@@ -224,6 +224,8 @@ int tb_unpack_gathered_host(uint32_t width, uint32_t height, uint32_t world, uin
  * "compact_hits", "camera_constants", "texture_use_hint", "node_layout", "node_order" -- each described where launch_plan.h / context_render.cpp use it.
  * An unknown name is an error. */
 int tb_set_option(tb_context* ctx, const char* name, int64_t value);
+/* tb_get_option also reads what the last render did ("last_*") and "debug_live_device_bytes": the device bytes the library holds for all
+ * contexts of the process together (a context that is destroyed gives back all it took). */
 int64_t tb_get_option(tb_context* ctx, const char* name);
 
 /* The launch policy of tb_render as a pure function (no device, no context): which pipeline, which copy of the feature set (and how

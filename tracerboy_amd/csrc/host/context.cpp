@@ -13,6 +13,7 @@ using namespace tbctx;
 namespace tbctx {
 
 std::string g_createError;
+std::atomic<int64_t> g_liveDeviceBytes{0};
 #ifndef __HIP_DEVICE_COMPILE__ /* host data: the file goes through hipcc's device pass too, which has no use for a table of host functions */
 const Variant kVariants[] = {
     {0u, pt_launch_persistent_matte, "matte", pt_launch_persistent_matte5, TB_MATTE_WAVES, 0, wf_launch_matte, true, pt_launch_split_matte, 0u},
@@ -36,6 +37,7 @@ void ensure(DevBuf& b, size_t bytes)
     if (bytes == 0) return;
     HIP_TRY(hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    g_liveDeviceBytes += (int64_t)bytes;
 }
 } // namespace tbctx
 
@@ -114,6 +116,7 @@ void tb_destroy(tb_context* c)
     c->wfHitA.release(); c->wfHitG.release(); c->wfSamples.release(); c->wfCounts.release(); c->workCounter.release(); c->fgSamples[0].release();
         c->fgSamples[1].release(); c->fgHits[0].release(); c->fgHits[1].release(); c->fgSlotLog[0].release(); c->fgSlotLog[1].release();
         c->stackOverflow.release();
+    c->regionCost.release(); c->regionOrder[0].release(); c->regionOrder[1].release(); c->regionCostKey = ~0ull;
     c->postOut.release(); c->postRgba8.release(); c->postHistogram.release(); c->postAverage.release();
     for (int i = 0; i < 2; i++) { c->rtIndirect[i].release(); c->rtMoment[i].release(); c->rtFinal[i].release(); c->rtDenoise[i].release(); }
     c->rtComposited.release();
@@ -693,6 +696,7 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "last_plan_costly_first")) return c->lastPlan.costly_first;
     if (!strcmp(name, "debug_region_order_ptr")) return (int64_t)(uintptr_t)c->regionOrder[c->lastFgPar].p;
     if (!strcmp(name, "debug_region_cost_ptr")) return (int64_t)(uintptr_t)c->regionCost.p;
+    if (!strcmp(name, "debug_live_device_bytes")) return g_liveDeviceBytes.load(); /* every context of the process (DevBuf), not this one only */
     if (!strcmp(name, "last_plan_stack_overflow")) return c->lastPlan.stack_overflow_entries;
     if (!strcmp(name, "last_split_waves")) return c->lastSplitWaves; /* traversal waves * 100 + shading waves per workgroup of the last pipeline-4 launch */
     /* the pipeline the last render actually ran (2 / 3 fall back to 0 for feature sets they lack) */

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <limits>
 #include <cmath>
@@ -113,9 +114,12 @@ struct Variant { uint32_t features; pt_variant_fn fn; const char* name; pt_varia
 extern const Variant kVariants[];
 extern const int kNumVariants;
 
+/* device bytes the library holds, all contexts of the process together (option "debug_live_device_bytes"): added at the two hipMalloc sites
+ * (ensure, upload), taken back in DevBuf::release -- a context that is destroyed must leave it where it found it */
+extern std::atomic<int64_t> g_liveDeviceBytes;
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    void release() { if (p) { (void)hipFree(p); g_liveDeviceBytes -= (int64_t)bytes; } p = nullptr; bytes = 0; }
 };
 
 } // namespace tbctx
@@ -237,6 +241,7 @@ template <class T> const T* upload(tb_context* c, const std::vector<T>& v)
     b.bytes = v.size() * sizeof(T);
     if (b.bytes == 0) return nullptr;
     HIP_TRY(hipMalloc(&b.p, b.bytes));
+    g_liveDeviceBytes += (int64_t)b.bytes;
     c->sceneBufs.push_back(b);
     HIP_TRY(hipMemcpyAsync(b.p, v.data(), b.bytes, hipMemcpyHostToDevice, c->stream));
     return (const T*)b.p;
