@@ -289,6 +289,9 @@ void tb_plan_defaults(tb_plan_input* in);  /* zeroes, then the option defaults *
 /* waves per SIMD the higher-occupancy copy of a feature set ("matte", "env", "surf", "vol", "full", "sss") is compiled for -- what
  * renderImpl puts into tb_plan_input::variant_waves_hi; 0 = the set has no such copy, -1 = no such set.  Needs no context. */
 int tb_variant_waves_hi(const char* variant_name);
+/* waves per SIMD of the feature set's copy for scenes in LDS (frame-group launches with the whole stack in LDS, where that many workgroups per CU fit;
+ * option last_copy_waves tells which copy a launch ran); 0 = the set has no such copy, -1 = no such set.  Needs no context. */
+int tb_variant_waves_lds(const char* variant_name);
 /* LDS entries per lane (1 KB per workgroup each) the frame-group kernels of that copy keep behind the traversal stacks for a path's cold state --
  * tb_plan_input::variant_stash_entries; 0 = none, -1 = no such set */
 int tb_variant_stash_entries(const char* variant_name);

@@ -77,6 +77,7 @@ def lib():
         "tb_plan_defaults": (None, [P(abi.tb_plan_input)]),
         "tb_plan_launch": (C.c_int, [P(abi.tb_plan_input), P(abi.tb_launch_plan)]),
         "tb_variant_waves_hi": (C.c_int, [C.c_char_p]),
+        "tb_variant_waves_lds": (C.c_int, [C.c_char_p]),
         "tb_invalidate_history": (None, [vp]),
         "tb_samples_rendered": (C.c_uint32, [vp]),
         "tb_select_pixel": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
@@ -140,6 +141,11 @@ def GetDefaultPostProcessSettings():
 def VariantWavesHi(name):
     """Waves per SIMD the higher-occupancy copy of feature set `name` is compiled for (0: no such copy; tb_variant_waves_hi)."""
     return int(lib().tb_variant_waves_hi(name.encode()))
+
+
+def VariantWavesLds(name):
+    """Waves per SIMD the copy of feature set `name` for scenes in LDS is compiled for (0: no such copy; tb_variant_waves_lds)."""
+    return int(lib().tb_variant_waves_lds(name.encode()))
 
 
 def VariantStashEntries(name):

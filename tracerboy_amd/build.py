@@ -35,8 +35,11 @@ DEVICE = ["--offload-arch=" + ARCH, "-fno-slp-vectorize", "-mllvm", "-amdgpu-sch
 #   surf (Teapot): +1.6 % at 3 waves per SIMD, and with it 4 waves beat 3 for the first time (2 913 -> 3 116, +7 %: pt_variant_surf.hip);
 # and where it loses it stays off: sss4 (van- / bistro-class 4K) -3 % / -4 % although its spill stores fall 17 %, env5 (870 k scene) -12 %,
 # matte5 (cornell-box) +-0.  iterative-minreg: spill stores -10 % ... -34 %, every scene 10-13 % slower.
+# matte6 (cornell-box, 6 waves per SIMD; docs/experiments/r7.md) runs best under LLVM's own scheduler (SCHED_DEFAULT): max-ilp 7 396, max-memory-clause
+# 7 434, default 7 440 Msamples/s, same box, three alternations.
 SCHED_MEMORY_CLAUSE = ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
-TU_SCHEDULER = {"kernels/pt_variant_vol4.hip": SCHED_MEMORY_CLAUSE, "kernels/pt_variant_surf.hip": SCHED_MEMORY_CLAUSE}
+SCHED_DEFAULT = []
+TU_SCHEDULER = {"kernels/pt_variant_vol4.hip": SCHED_MEMORY_CLAUSE, "kernels/pt_variant_surf.hip": SCHED_MEMORY_CLAUSE, "kernels/pt_variant_matte6.hip": SCHED_DEFAULT}
 
 
 def device_flags(src):
@@ -48,7 +51,7 @@ def device_flags(src):
     return base + TU_SCHEDULER[src]
 
 HOST_SRCS = ["host/pbrt_loader.cpp", "host/pbf_loader.cpp", "host/host_scene.cpp", "host/images.cpp", "host/image_decode.cpp", "host/image_formats.cpp", "host/bvh_build.cpp", "host/procedural.cpp", "host/context.cpp", "host/context_scene.cpp", "host/context_render.cpp", "host/pbrt_dump.cpp"]
-KERNEL_SRCS = ["kernels/pt_kernels.hip", "kernels/post_kernels.hip", "kernels/bvh_kernels.hip", "kernels/rt_kernels.hip", "kernels/pt_variant_matte.hip", "kernels/pt_variant_matte5.hip", "kernels/pt_variant_env.hip", "kernels/pt_variant_env5.hip", "kernels/pt_variant_surf.hip",
+KERNEL_SRCS = ["kernels/pt_kernels.hip", "kernels/post_kernels.hip", "kernels/bvh_kernels.hip", "kernels/rt_kernels.hip", "kernels/pt_variant_matte.hip", "kernels/pt_variant_matte5.hip", "kernels/pt_variant_matte6.hip", "kernels/pt_variant_env.hip", "kernels/pt_variant_env5.hip", "kernels/pt_variant_surf.hip",
                "kernels/pt_variant_sss.hip", "kernels/pt_variant_sss4.hip",
                "kernels/pt_variant_vol.hip", "kernels/pt_variant_vol4.hip", "kernels/pt_variant_full.hip",
                "kernels/pt_split_matte.hip", "kernels/pt_split_env.hip", "kernels/pt_split_surf.hip", "kernels/pt_split_sss.hip"]

@@ -16,7 +16,8 @@ std::string g_createError;
 std::atomic<int64_t> g_liveDeviceBytes{0};
 #ifndef __HIP_DEVICE_COMPILE__ /* host data: the file goes through hipcc's device pass too, which has no use for a table of host functions */
 const Variant kVariants[] = {
-    {0u, pt_launch_persistent_matte, "matte", pt_launch_persistent_matte5, TB_MATTE_WAVES, 0, wf_launch_matte, true, pt_launch_split_matte, 0u},
+    {0u, pt_launch_persistent_matte, "matte", pt_launch_persistent_matte5, TB_MATTE_WAVES, 0, wf_launch_matte, true, pt_launch_split_matte, 0u,
+        pt_launch_persistent_matte6, TB_MATTE_LDS_WAVES},
         {PT_FEAT_ENV, pt_launch_persistent_env, "env", pt_launch_persistent_env5, TB_ENV_WAVES, 1, wf_launch_env, true, pt_launch_split_env, TB_ENV_STASH},
     {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES, pt_launch_persistent_surf, "surf", nullptr, 0, 2, wf_launch_surf, true, pt_launch_split_surf, 0u},
         {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS, pt_launch_persistent_sss, "sss", pt_launch_persistent_sss4, TB_SSS_WAVES, 5,
@@ -224,8 +225,6 @@ int tb_set_material(tb_context* c, int id, const TbMaterial* in)
         if (!in || !c->hasScene || id < 0 || id >= (int)c->scene.materials.size()) return fail(c, TB_E_INVALID, "material id out of range");
         c->scene.materials[(size_t)id] = *in;
         HIP_TRY(hipMemcpy((void*)&c->ds.materials[id].m, in, sizeof *in, hipMemcpyHostToDevice));
-        if (c->sceneInLds) HIP_TRY(hipMemcpy((void*)(c->ds.ldsBlob + c->ds.offMaterials + sizeof(TbDevMaterial) * (size_t)id), in, sizeof *in,
-            hipMemcpyHostToDevice));
         c->sceneFeatures = sceneFeatureMask(c->scene);
         c->ds.textureUse = sceneTextureUse(c); /* the edit may be the scene's first texture or normal map */
         c->samplesRendered = 0;
@@ -556,6 +555,12 @@ int tb_variant_waves_hi(const char* name)
         name)) return tbctx::kVariants[i].fnHi ? (int)tbctx::kVariants[i].wavesHi : 0;
     return -1;
 }
+int tb_variant_waves_lds(const char* name)
+{
+    if (!name) return -1;
+    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return tbctx::kVariants[i].fnLds ? (int)tbctx::kVariants[i].wavesLds : 0;
+    return -1;
+}
 uint32_t tb_frame_groups(uint32_t frames, uint32_t frameGroup, uint32_t guided, uint32_t group, uint32_t* firstFrame, uint32_t* numFrames)
 {
     uint32_t lg = 0; while ((2u << lg) <= frameGroup) lg++;
@@ -701,6 +706,7 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "last_split_waves")) return c->lastSplitWaves; /* traversal waves * 100 + shading waves per workgroup of the last pipeline-4 launch */
     /* the pipeline the last render actually ran (2 / 3 fall back to 0 for feature sets they lack) */
     if (!strcmp(name, "last_pipeline")) return c->lastPipeline;
+    if (!strcmp(name, "last_copy_waves")) return c->lastCopyWaves;
     /* 0 matte 1 env 2 surf 3 vol 4 full 5 sss */
     if (!strcmp(name, "last_variant")) { for (int i = 0; i < kNumVariants; i++) if (c->lastVariant == kVariants[i].name) return kVariants[i].id; return -1; }
     auto it = c->options.find(name); return it == c->options.end() ? 0 : it->second;

@@ -36,6 +36,8 @@ hipError_t pt_launch_persistent_surf(hipStream_t, const TbDeviceScene*, const Tb
     uint32_t, const TbTileMap*, int, int, int);
 hipError_t pt_launch_persistent_matte5(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
     uint32_t, const TbTileMap*, int, int, int);
+hipError_t pt_launch_persistent_matte6(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
 hipError_t pt_launch_persistent_env5(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
     uint32_t, const TbTileMap*, int, int, int);
 hipError_t pt_launch_persistent_sss(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
@@ -90,6 +92,9 @@ extern std::string g_createError;
 #ifndef TB_MATTE_WAVES
 #define TB_MATTE_WAVES 5
 #endif
+#ifndef TB_MATTE_LDS_WAVES
+#define TB_MATTE_LDS_WAVES 6 /* pt_variant_matte6.hip */
+#endif
 #ifndef TB_ENV_WAVES
 #define TB_ENV_WAVES 6
 #endif
@@ -108,9 +113,11 @@ extern std::string g_createError;
 #ifndef TB_SSS_STASH
 #define TB_SSS_STASH 0
 #endif
-/* stashHi: LDS entries per lane the frame-group kernels of the fnHi copy keep behind the stacks (scenes fetched from memory, one level) */
+/* stashHi: LDS entries per lane the frame-group kernels of the fnHi copy keep behind the stacks (scenes fetched from memory, one level)
+ * fnLds: a copy at `wavesLds` waves per SIMD with the frame-group kernels of scenes in LDS only (whole stack in LDS), used in place of fnHi where the
+ * plan picks fnHi for such a launch and wavesLds workgroups per CU fit (launch_plan.h LdsCopyFits); null for the sets without one */
 struct Variant { uint32_t features; pt_variant_fn fn; const char* name; pt_variant_fn fnHi; uint32_t wavesHi; int id; wf_variant_fn wf; bool pooled;
-    pt_split_fn split; uint32_t stashHi; };
+    pt_split_fn split; uint32_t stashHi; pt_variant_fn fnLds; uint32_t wavesLds; };
 extern const Variant kVariants[];
 extern const int kNumVariants;
 
@@ -169,6 +176,7 @@ struct tb_context {
     std::map<std::string, int64_t> options;
     float lastMs = 0.0f;
     std::string lastVariant;
+    uint32_t lastCopyWaves = 0; /* waves per SIMD of the copy the last lock-step launch ran (option last_copy_waves; 0 = the base copy) */
     int lastNodeLayout = 0; /* 1: the last render walked the compact layout-C nodes */
     int lastSlotLogCap = 0;
     /* renderImpl */

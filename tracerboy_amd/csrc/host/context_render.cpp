@@ -370,6 +370,11 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
         dsLaunch.stackDepth = plan.stack_lds_entries; dsLaunch.stackOverflow = (uint32_t*)c->stackOverflow.p; dsLaunch.stackOverflowLanes = lanes;
     }
     if (plan.full_variant && v != &kVariants[kNumVariants - 1]) { v = &kVariants[kNumVariants - 1]; launch = v->fn; c->lastVariant = v->name; }
+    /* the set's copy for scenes in LDS (fnLds) in place of fnHi where its workgroups fit with the whole stack: the frame-group kernels of a
+     * one-level scene in LDS without counters (the launcher refuses anything else) */
+    c->lastCopyWaves = launch == v->fnHi ? v->wavesHi : 0u;
+    if (launch == v->fnHi && v->fnLds && groups && c->sceneInLds && !twoLevel && !count && !plan.stack_overflow_entries && !plan.prepass &&
+        LdsCopyFits(v->wavesLds, c->ds.stackDepth, c->ds.ldsBlobBytes)) { launch = v->fnLds; c->lastCopyWaves = v->wavesLds; }
     /* layout C on first demand; the plan is made again with what came of it */
     if (opt("node_layout", 0) == 1 && !twoLevel && !c->sceneInLds && !c->ds.nodesC && !c->compactTried) {
         ensureCompactNodes(c); dsLaunch.nodesC = c->ds.nodesC; dsLaunch.quant = c->ds.quant;
@@ -536,9 +541,10 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
              * full grid of workgroups that exit at once) down BOTH side streams, so that the one-off cost falls into that first
              * call and not into whichever later call happens to reach the second stream.  Two-level scenes in the tuned copies have no
              * one-pixel-per-lane form (pt_variant.inc refuses it: the first render of an instanced scene in a fresh context used to fail
-             * here and then for good): they are warmed with the frame-group form itself. */
+             * here and then for good): they are warmed with the frame-group form itself, and so is a copy for scenes in LDS (fnLds),
+             * which has no other form. */
             if (overlap && std::find(c->warmedLaunchers.begin(), c->warmedLaunchers.end(), (const void*)launch) == c->warmedLaunchers.end()) {
-                if (twoLevel) { for (uint32_t par = 0; par < 2; par++) warmFrameGroupForm(par, false); }
+                if (twoLevel || launch == v->fnLds) { for (uint32_t par = 0; par < 2; par++) warmFrameGroupForm(par, false); }
                 else {
                     TbDeviceTargets none = tg; none.samples = nullptr;
                     TbDeviceScene dsWarm = c->ds; dsWarm.nodesC = nullptr; /* the one-pixel-per-lane twin fetches layout B */

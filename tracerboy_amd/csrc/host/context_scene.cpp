@@ -350,7 +350,7 @@ void finalizeScene(tb_context* c, bool build)
     d.stackDepth = s.bvhMaxDepth < 2 ? 2 : s.bvhMaxDepth;
     d.alphaTest = opt("alpha_test", 0) ? 1u : 0u;
     d.textureUse = sceneTextureUse(c);
-    /* whole-scene LDS image */
+    /* LDS image of the walk: nodes and permuted triangles (pt_scene.h) */
     {
         std::vector<uint8_t> blob;
         auto put = [&](const void* p, size_t bytes) { while (blob.size() % 16) blob.push_back(0); uint32_t off = (uint32_t)blob.size();
@@ -379,14 +379,13 @@ void finalizeScene(tb_context* c, bool build)
                     }
             d.offTris = put(perm.data(), perm.size() * sizeof(TbTriB));
         }
-        d.offHitGroups = put(devHit.data(), devHit.size() * sizeof(TbDevHitGroup));
-        d.offIndices = put(s.indexBuffer.data(), s.indexBuffer.size() * 4);
-        d.offVertices = put(s.vertexBuffer.data(), s.vertexBuffer.size() * 4);
-        d.offMaterials = put(devMat.data(), devMat.size() * sizeof(TbDevMaterial));
-        d.offLights = put(devLight.data(), devLight.size() * sizeof(TbDevLight));
         while (blob.size() % 16) blob.push_back(0);
+        /* the shading records stay in memory (pt_scene.h); the budget still counts them, so that which scenes are LDS-resident is as before */
+        auto r16 = [](size_t b) { return (b + 15) / 16 * 16; };
+        const size_t shadingBytes = r16(devHit.size() * sizeof(TbDevHitGroup)) + r16(s.indexBuffer.size() * 4) + r16(s.vertexBuffer.size() * 4) +
+            r16(devMat.size() * sizeof(TbDevMaterial)) + r16(devLight.size() * sizeof(TbDevLight));
         size_t budget = (size_t)opt("lds_scene_budget", 40 * 1024);
-        c->sceneInLds = blob.size() + (size_t)d.stackDepth * 256 * 4 <= budget && opt("scene_in_lds", 1) != 0 && !twoLevel;
+        c->sceneInLds = blob.size() + shadingBytes + (size_t)d.stackDepth * 256 * 4 <= budget && opt("scene_in_lds", 1) != 0 && !twoLevel;
         if (c->sceneInLds) { d.ldsBlob = upload(c, blob); d.ldsBlobBytes = (uint32_t)blob.size(); }
         else { d.ldsBlob = nullptr; d.ldsBlobBytes = 0; }
         /* measured on MI355X: LDS-resident scenes are nearly insensitive (at five waves per SIMD 1-2 is best: 6 745 / 6 730 against

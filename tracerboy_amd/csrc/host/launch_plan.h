@@ -10,6 +10,16 @@
 
 namespace tbhost {
 
+/* Does a copy held to `waves` per SIMD keep `waves` workgroups per CU resident with the whole stack and the scene's LDS image in LDS?  The plan's
+ * arithmetic below: a workgroup's share of 160 KB and its need, in 512-B granules, with 128 B of static LDS.  renderImpl asks it of the copies
+ * for scenes in LDS (Variant::fnLds, context_internal.h). */
+inline bool LdsCopyFits(uint32_t waves, uint32_t stackDepth, uint32_t ldsBlobBytes)
+{
+    if (!waves) return false;
+    const uint64_t share = (160u * 1024u / waves) / 512u * 512u, need = ((uint64_t)stackDepth * 1024u + ldsBlobBytes + 128u + 511u) / 512u * 512u;
+    return need <= share;
+}
+
 inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
 {
     p = tb_launch_plan{};

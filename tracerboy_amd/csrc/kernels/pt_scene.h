@@ -56,9 +56,11 @@ struct TbDeviceScene {
      * entries >= stackDepth live in global memory, entry e of lane L at stackOverflow[(e - stackDepth) * stackOverflowLanes + L],
      * L = blockIdx.x * 256 + threadIdx.x */
     uint32_t* stackOverflow;     uint32_t stackOverflowLanes;
-    /* whole-scene-in-LDS image (small scenes): byte offsets inside one contiguous device blob */
+    /* LDS image of a small scene: what the walk reads at every step -- nodes and permuted triangles, byte offsets inside one contiguous device
+     * blob.  The shading records (hit groups, indices, vertices, materials, lights) stay in memory above: read about once per hit, they cost a
+     * workgroup LDS that the stacks of one more workgroup per CU need more (docs/experiments/r7.md). */
     const uint8_t* ldsBlob;      uint32_t ldsBlobBytes;
-    uint32_t offNodes, offTris, offHitGroups, offIndices, offVertices, offMaterials, offLights;
+    uint32_t offNodes, offTris;
 };
 
 /* Output surfaces of one dispatch (u0..u7, u10 of SharedRaytracing.h:13-23) */

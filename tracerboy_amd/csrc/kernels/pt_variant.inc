@@ -59,6 +59,12 @@ extern "C" hipError_t PT_CAT(pt_launch_persistent_, PT_NAME)(hipStream_t stream,
 #define PT_PICK(L, C) do { if (pipeline != 0) return hipErrorInvalidValue; PT_LAUNCH(pt_persistent<PT_FEATURES, L, C, false>); } while (0)
 #endif
     if (tg->samples && (countRays || pipeline != 0)) return hipErrorInvalidValue; /* frame groups: pt_persistent without counters only */
+#ifdef PT_ONLY_LDS_GROUPS
+    /* a copy for scenes in LDS (pt_variant_matte6.hip): the frame-group kernels with the whole stack in LDS, nothing else */
+    if (!tg->samples || !sceneInLds || countRays || ds->numInstances || tg->primaryHits || ds->nodesC || ds->stackOverflow) return hipErrorInvalidValue;
+    if (guidedLaunch) PT_LAUNCH(pt_persistent<PT_FEATURES, true, false, true, false, false, false, false, false, true>);
+    else PT_LAUNCH(pt_persistent<PT_FEATURES, true, false, true>);
+#else
 #if PT_COUNT
     if (countRays) { if (sceneInLds) PT_PICK(true, true); else PT_PICK(false, true); return hipGetLastError(); }
 #else
@@ -159,6 +165,7 @@ extern "C" hipError_t PT_CAT(pt_launch_persistent_, PT_NAME)(hipStream_t stream,
         else PT_LAUNCH(pt_persistent<PT_FEATURES, false, false, true>); }
 #endif
     else if (sceneInLds) PT_PICK(true, false); else PT_PICK(false, false);
+#endif /* PT_ONLY_LDS_GROUPS */
 #undef PT_PICK
 #undef PT_LAUNCH
     return hipGetLastError();
