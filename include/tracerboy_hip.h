@@ -46,7 +46,7 @@ typedef struct tb_output_settings {
     float DebugValue, DebugValue2;    /* m_debugSettings                                      */
     float DOFFocalDistance, ApertureWidth; uint32_t FilterType; float FilterWidth; /* m_cameraSettings */
     float FireflyClampValue, MaxZ;    /* m_denoiserSettings                                   */
-    float ConvergencePercentage;      /* m_performanceSettings...                             */
+    float ConvergencePercentage;      /* m_performanceSettings... -> MinConvergence; takes effect with option "adaptive" (skip converged pixels) */
     uint32_t EnableNextEventEstimation, EnableSamplingImportanceResampling, EnableBlueNoise;
     int32_t MaxBounces;
     int32_t SampleTarget;
@@ -237,7 +237,7 @@ enum { TB_PLAN_FEAT_SSS = 8, TB_PLAN_FEAT_EXT = 32 }; /* bits of variant_feature
 enum { TB_PLAN_PREPASS_OFF = 0, TB_PLAN_PREPASS_ON = 1, TB_PLAN_PREPASS_TRIAL = 2 };
 /* rule_pipeline */
 enum { TB_PLAN_RULE_ONE_PIXEL_PER_LANE = 1, TB_PLAN_RULE_FRAME_GROUPS, TB_PLAN_RULE_WAVEFRONT, TB_PLAN_RULE_POOLED, TB_PLAN_RULE_SPLIT,
-    TB_PLAN_RULE_SPLIT_NO_ROOM,
+    TB_PLAN_RULE_SPLIT_NO_ROOM, TB_PLAN_RULE_ADAPTIVE /* = 7: the adaptive launch (option "adaptive", frames past adaptive_min_frames) */,
        /* rule_copy */
        TB_PLAN_RULE_COPY_NONE = 10, TB_PLAN_RULE_COPY_FITS, TB_PLAN_RULE_COPY_SPLIT_STACK, TB_PLAN_RULE_COPY_TOO_DEEP, TB_PLAN_RULE_COPY_NO_ROOM,
            TB_PLAN_RULE_COPY_FULL_FOR_INSTANCES,
@@ -271,6 +271,8 @@ typedef struct tb_plan_input {
     /* the regions where paths were long in the launches before are handed out first (option costly_first: 0 never, 1 = feature sets with interior walks, calls
      * below 3 x 2^24 samples [default], 2 = those feature sets at any size) */
     uint32_t costly_first /* 1 */;
+    /* the call runs the adaptive launch: option "adaptive" on, not real-time, and its last frame past option adaptive_min_frames (renderImpl) */
+    uint32_t adaptive;
 } tb_plan_input;
 typedef struct tb_launch_plan {
     int32_t pipeline;                 /* 0 lock-step, 1 streaming, 2 wavefront, 3 pooled, 4 split-role: what will run */

@@ -450,6 +450,11 @@ class TracerBoy:
     def GetOption(self, name):
         return int(self._L.tb_get_option(self._ctx, name.encode()))
 
+    def LivePixels(self):
+        """Option "last_live_pixels": the owned pixels that were live at the first frame of the last call (all owned pixels of a call that did not run the
+        adaptive launch, option "adaptive").  Waits for the call."""
+        return self.GetOption("last_live_pixels")
+
     def SceneInfo(self):
         i = abi.tb_scene_info()
         self._check(self._L.tb_scene_info_get(self._ctx, C.byref(i)))

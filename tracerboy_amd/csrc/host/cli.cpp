@@ -2,7 +2,7 @@
  *   tracerboy-hip scene.pbrt [--width W] [--height H] [--spp N] [--depth D] [--seed-time T] [--device I]
  *                 [--builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu] [--blue-noise 0|1] [--tonemap 0..7] [--exposure E|auto]
  *                 [--out frame.png|frame.pfm|frame.exr]
- *                 [--ranks N]
+ *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C]]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -16,7 +16,12 @@
  * one-GPU machine.
  * Output by extension: .png = what the reference presents (auto exposure + PostProcessCS tonemap, 8-bit back buffer,
  * tb_post_process); .pfm = linear radiance sum(rgb*w)/sum(w), the value PostProcessCS divides out before tonemapping
- * (PostProcessCS.hlsl:23-47), RGB float32, bottom row first; .exr = the same radiance as OpenEXR (RGBA float32, A = 1). */
+ * (PostProcessCS.hlsl:23-47), RGB float32, bottom row first; .exr = the same radiance as OpenEXR (RGBA float32, A = 1).
+ *
+ * --adaptive P: stop sampling converged pixels (option "adaptive", ConvergencePercentage = P).  One plain call of
+ * min(F + 1, N) frames (F = --adaptive-after, default 1024, the reference's threshold), then adaptive calls of C frames (--adaptive-chunk, default
+ * 64) until N frames are rendered or no pixel is live; one line per call: frames so far, live pixels at the call's start, milliseconds.  With
+ * --ranks every rank runs the schedule over its own tiles. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -114,10 +119,11 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
+    float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64;
     for (int i = 2; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--width") W = (uint32_t)atoi(v); else if (k == "--height") H = (uint32_t)atoi(v); else if (k == "--spp") spp = (uint32_t)atoi(v);
@@ -125,6 +131,8 @@ int main(int argc, char** argv)
         else if (k == "--builder") builder = !strcmp(v, "sah") ? 1 : !strcmp(v, "lbvh-gpu") ? 2 : !strcmp(v, "treelets") ? 3 : !strcmp(v,
             "treelets-gpu") ? 4 : 0; /* tb_set_option "bvh_builder" */ else if (k == "--blue-noise") blue = atoi(v); else if (k == "--out") out = v;
             else if (k == "--ranks") ranks = atoi(v);
+        else if (k == "--adaptive") adaptive = (float)atof(v); else if (k == "--adaptive-after") adaptiveAfter = atoll(v);
+        else if (k == "--adaptive-chunk") adaptiveChunk = atoll(v);
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -134,6 +142,7 @@ int main(int argc, char** argv)
     const char* envRank = getenv("TB_CLI_RANK");
     const bool forceRccl = getenv("TB_CLI_FORCE_RCCL") && atoi(getenv("TB_CLI_FORCE_RCCL")) != 0;
     if (ranks < 1) { fprintf(stderr, "--ranks must be at least 1\n"); return 2; }
+    if (adaptiveAfter < 0 || adaptiveChunk < 1) { fprintf(stderr, "--adaptive-after must not be negative, --adaptive-chunk must be at least 1\n"); return 2; }
     if (ranks > 1 && !envRank) return spawnRanks(argc, argv, ranks);
     if (envRank && (!getenv("TB_CLI_WORLD") || atoi(getenv("TB_CLI_WORLD")) < 1 || atoi(envRank) < 0 || atoi(envRank) >= atoi(getenv("TB_CLI_WORLD")) ||
                     (atoi(getenv("TB_CLI_WORLD")) > 1 && !getenv("TB_CLI_ID_FILE")))) {
@@ -158,8 +167,28 @@ int main(int argc, char** argv)
     const uint32_t TILE = 64;
     if (world > 1 && (rc = tb_set_tile_assignment(ctx, (uint32_t)rank, (uint32_t)world, TILE, TILE))) return fail(ctx, "tb_set_tile_assignment", rc);
     auto r0 = std::chrono::steady_clock::now();
-    if ((rc = tb_render(ctx, W, H, spp, &s, t))) return fail(ctx, "tb_render", rc);
-    float ms = tb_last_render_ms(ctx);
+    float ms = 0.0f;
+    if (adaptive < 0.0f) {
+        if ((rc = tb_render(ctx, W, H, spp, &s, t))) return fail(ctx, "tb_render", rc);
+        ms = tb_last_render_ms(ctx);
+    } else {
+        s.ConvergencePercentage = adaptive;
+        if ((rc = tb_set_option(ctx, "adaptive", 1)) || (rc = tb_set_option(ctx, "adaptive_min_frames", adaptiveAfter))) return fail(ctx, "tb_set_option", rc);
+        uint32_t done = (uint32_t)std::min<long long>(adaptiveAfter + 1, spp); /* the plain call: no pixel can skip before frame F + 1 */
+        if ((rc = tb_render(ctx, W, H, done, &s, t))) return fail(ctx, "tb_render", rc);
+        ms = tb_last_render_ms(ctx);
+        while (done < spp) {
+            const uint32_t n = (uint32_t)std::min<long long>(adaptiveChunk, (long long)spp - done);
+            if ((rc = tb_render(ctx, W, H, n, &s, t))) return fail(ctx, "tb_render", rc);
+            const float callMs = tb_last_render_ms(ctx);
+            const long long live = (long long)tb_get_option(ctx, "last_live_pixels");
+            done += n; ms += callMs;
+            if (world > 1) printf("adaptive rank %d: %u frames, %lld live pixels, %.3f ms\n", rank, done, live, callMs);
+            else printf("adaptive: %u frames, %lld live pixels, %.3f ms\n", done, live, callMs);
+            if (live == 0) break;
+        }
+        spp = done;
+    }
     if (world > 1 || forceRccl) {
         /* ---- the gather: packed tiles of every rank -> rank 0's accumulation surface ---- */
         Rccl nccl; if (!nccl.load()) { tb_destroy(ctx); return 1; }

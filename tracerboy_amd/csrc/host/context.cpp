@@ -17,14 +17,16 @@ std::atomic<int64_t> g_liveDeviceBytes{0};
 #ifndef __HIP_DEVICE_COMPILE__ /* host data: the file goes through hipcc's device pass too, which has no use for a table of host functions */
 const Variant kVariants[] = {
     {0u, pt_launch_persistent_matte, "matte", pt_launch_persistent_matte5, TB_MATTE_WAVES, 0, wf_launch_matte, true, pt_launch_split_matte, 0u,
-        pt_launch_persistent_matte6, TB_MATTE_LDS_WAVES},
-        {PT_FEAT_ENV, pt_launch_persistent_env, "env", pt_launch_persistent_env5, TB_ENV_WAVES, 1, wf_launch_env, true, pt_launch_split_env, TB_ENV_STASH},
-    {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES, pt_launch_persistent_surf, "surf", nullptr, 0, 2, wf_launch_surf, true, pt_launch_split_surf, 0u},
+        pt_launch_persistent_matte6, TB_MATTE_LDS_WAVES, pt_launch_adaptive_matte},
+        {PT_FEAT_ENV, pt_launch_persistent_env, "env", pt_launch_persistent_env5, TB_ENV_WAVES, 1, wf_launch_env, true, pt_launch_split_env, TB_ENV_STASH,
+            nullptr, 0u, pt_launch_adaptive_env},
+    {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES, pt_launch_persistent_surf, "surf", nullptr, 0, 2, wf_launch_surf, true, pt_launch_split_surf, 0u,
+        nullptr, 0u, pt_launch_adaptive_surf},
         {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS, pt_launch_persistent_sss, "sss", pt_launch_persistent_sss4, TB_SSS_WAVES, 5,
-            wf_launch_sss, false, pt_launch_split_sss, TB_SSS_STASH},
+            wf_launch_sss, false, pt_launch_split_sss, TB_SSS_STASH, nullptr, 0u, pt_launch_adaptive_sss},
     {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS | PT_FEAT_MIX, pt_launch_persistent_vol, "vol", pt_launch_persistent_vol4, TB_VOL_WAVES,
-        3, wf_launch_vol, false, nullptr, TB_VOL_STASH},
-        {PT_FEAT_ALL, pt_launch_persistent_full, "full", nullptr, 0, 4, nullptr, false, nullptr, 0u},
+        3, wf_launch_vol, false, nullptr, TB_VOL_STASH, nullptr, 0u, pt_launch_adaptive_vol},
+        {PT_FEAT_ALL, pt_launch_persistent_full, "full", nullptr, 0, 4, nullptr, false, nullptr, 0u, nullptr, 0u, pt_launch_adaptive_full},
 };
 const int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 #endif
@@ -118,6 +120,7 @@ void tb_destroy(tb_context* c)
         c->fgSamples[1].release(); c->fgHits[0].release(); c->fgHits[1].release(); c->fgSlotLog[0].release(); c->fgSlotLog[1].release();
         c->stackOverflow.release();
     c->regionCost.release(); c->regionOrder[0].release(); c->regionOrder[1].release(); c->regionCostKey = ~0ull;
+    c->liveList.release();
     c->postOut.release(); c->postRgba8.release(); c->postHistogram.release(); c->postAverage.release();
     for (int i = 0; i < 2; i++) { c->rtIndirect[i].release(); c->rtMoment[i].release(); c->rtFinal[i].release(); c->rtDenoise[i].release(); }
     c->rtComposited.release();
@@ -665,7 +668,12 @@ int tb_set_option(tb_context* c, const char* name, int64_t v)
         "alpha_test", "node_order", "node_order_top_levels", "frame_group", "overlap_launches", "high_occupancy", "stack_lds_cap", "stack_overflow_max",
         "flip_texture_uvs", "wavefront_sort", "banded_items", "node_layout", "wavefront_refill",
                                   "split_trav", "split_shade", "split_ready", "split_refill", "split_wi", "split_wl", "split_frame_group", "split_stack_cap",
-                                      "split_spin_limit", "split_profile", "split_trav_last", "split_shade_prio"};
+                                      "split_spin_limit", "split_profile", "split_trav_last", "split_shade_prio", "adaptive", "adaptive_min_frames"};
+    /* the adaptive launch has no counting copy; its frame threshold is a frame index */
+    auto on = [&](const char* k) { auto it = c->options.find(k); return it != c->options.end() && it->second != 0; };
+    if (!strcmp(name, "adaptive_min_frames") && v < 0) return fail(c, TB_E_INVALID, "tb_set_option: adaptive_min_frames must not be negative");
+    if ((!strcmp(name, "adaptive") && v && on("count_rays")) || (!strcmp(name, "count_rays") && v && on("adaptive")))
+        return fail(c, TB_E_INVALID, "tb_set_option: options \"adaptive\" and \"count_rays\" exclude each other (the counting kernels have no adaptive copy)");
     for (const char* k : known) if (!strcmp(k, name)) { c->options[name] = v; if (!strcmp(name, "count_rays") || !strcmp(name, "aov")) c->samplesRendered = 0;
         return TB_OK; }
     return fail(c, TB_E_INVALID, std::string("unknown option '") + name + "'");
@@ -707,6 +715,21 @@ int64_t tb_get_option(tb_context* c, const char* name)
     /* the pipeline the last render actually ran (2 / 3 fall back to 0 for feature sets they lack) */
     if (!strcmp(name, "last_pipeline")) return c->lastPipeline;
     if (!strcmp(name, "last_copy_waves")) return c->lastCopyWaves;
+    /* the adaptive launch: did the last call run it; the owned pixels that were live at its first frame (all owned pixels of a call that did not run
+     * it) -- a device word: reading it waits for the call.  A group's owner counts its peers' too. */
+    if (!strcmp(name, "last_adaptive")) return c->lastAdaptive ? 1 : 0;
+    if (!strcmp(name, "adaptive_min_frames")) { auto it = c->options.find(name); return it == c->options.end() ? 1024 : it->second; } /* the reference's */
+    if (!strcmp(name, "last_live_pixels")) {
+        int64_t sum = 0;
+        std::vector<tb_context*> all(1, c); for (tb_context* p : c->peers) all.push_back(p);
+        for (tb_context* x : all) {
+            if (!x->lastAdaptive || !x->liveList.p) { sum += (int64_t)x->lastOwnedPixels; continue; }
+            uint32_t v = 0; DeviceScope scope(x->device);
+            if (hipStreamSynchronize(x->stream) != hipSuccess || hipMemcpy(&v, x->liveList.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+            sum += v;
+        }
+        return sum;
+    }
     /* 0 matte 1 env 2 surf 3 vol 4 full 5 sss */
     if (!strcmp(name, "last_variant")) { for (int i = 0; i < kNumVariants; i++) if (c->lastVariant == kVariants[i].name) return kVariants[i].id; return -1; }
     auto it = c->options.find(name); return it == c->options.end() ? 0 : it->second;

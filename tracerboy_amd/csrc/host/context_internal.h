@@ -50,6 +50,19 @@ hipError_t pt_launch_persistent_vol(hipStream_t, const TbDeviceScene*, const TbP
     uint32_t, const TbTileMap*, int, int, int);
 hipError_t pt_launch_persistent_full(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
     uint32_t, const TbTileMap*, int, int, int);
+/* the adaptive launch of the six base copies (pt_variant.inc; option "adaptive") */
+hipError_t pt_launch_adaptive_matte(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
+hipError_t pt_launch_adaptive_env(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
+hipError_t pt_launch_adaptive_surf(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
+hipError_t pt_launch_adaptive_sss(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
+hipError_t pt_launch_adaptive_vol(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
+hipError_t pt_launch_adaptive_full(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
+    uint32_t, const TbTileMap*, int, int, int);
 /* pipeline 4, the split-role kernel (pt_split.inc): shading waves + traversal waves over an LDS ray queue */
 typedef hipError_t (*pt_split_fn)(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t,
     uint32_t, uint32_t, uint32_t,
@@ -116,8 +129,9 @@ extern std::string g_createError;
 /* stashHi: LDS entries per lane the frame-group kernels of the fnHi copy keep behind the stacks (scenes fetched from memory, one level)
  * fnLds: a copy at `wavesLds` waves per SIMD with the frame-group kernels of scenes in LDS only (whole stack in LDS), used in place of fnHi where the
  * plan picks fnHi for such a launch and wavesLds workgroups per CU fit (launch_plan.h LdsCopyFits); null for the sets without one */
+/* fnAdaptive: the base copy's adaptive launch (pt_variant.inc pt_launch_adaptive_*) */
 struct Variant { uint32_t features; pt_variant_fn fn; const char* name; pt_variant_fn fnHi; uint32_t wavesHi; int id; wf_variant_fn wf; bool pooled;
-    pt_split_fn split; uint32_t stashHi; pt_variant_fn fnLds; uint32_t wavesLds; };
+    pt_split_fn split; uint32_t stashHi; pt_variant_fn fnLds; uint32_t wavesLds; pt_variant_fn fnAdaptive; };
 extern const Variant kVariants[];
 extern const int kNumVariants;
 
@@ -146,6 +160,8 @@ struct tb_context {
     DevBuf fgSlotLog[2]; /* frame-group mode: the workgroups' logs of bound slots (TbDeviceTargets::slotLog) */
     DevBuf fgHits[2];   /* primary-visibility pre-pass: 16-B or 32-B record of every sample's first hit (TbDeviceTargets::primaryHits) */
     DevBuf regionCost, regionOrder[2]; uint64_t regionCostKey = ~0ull; /* costly regions first (TbDeviceTargets::regionCost / regionOrder): 2^20 counts; per side stream 1 + 2 x regions words */
+    /* the adaptive launch (option "adaptive"): live list, its count and the list pass's scratch (pt_launch_live_list); what the last call was */
+    DevBuf liveList; bool lastAdaptive = false; uint64_t lastOwnedPixels = 0;
     DevBuf stackOverflow; /* split traversal stack of the higher-occupancy kernel copies on deep trees (pt_scene.h) */
     std::vector<const void*> warmedLaunchers; /* frame-group kernels that have run once on both side streams (renderImpl) */
     uint32_t fgLaunch = 0; bool sideOrdered = false; /* sideOrdered: the side streams have been ordered after everything else on `stream` */

@@ -289,6 +289,17 @@ void fillPlanInput(tb_context* c, const Variant* v, uint32_t W, uint32_t H, uint
     in.costly_first = opt("banded_items", 0) == 0 ? (uint32_t)std::max<int64_t>(0, std::min<int64_t>(2, opt("costly_first", 1))) : 0u;
 }
 
+/* the pixels of the frame a context renders: all of them, or those of its tiles (tile t of a row-major grid belongs to rank t % world) */
+static uint64_t ownedFramePixels(uint32_t W, uint32_t H, const TbTileMap& t)
+{
+    if (t.world <= 1) return (uint64_t)W * H;
+    const uint32_t tilesX = (W + t.tileW - 1) / t.tileW, tilesY = (H + t.tileH - 1) / t.tileH;
+    uint64_t n = 0;
+    for (uint32_t i = t.rank; i < tilesX * tilesY; i += t.world)
+        n += (uint64_t)std::min(t.tileW, W - (i % tilesX) * t.tileW) * std::min(t.tileH, H - (i / tilesX) * t.tileH);
+    return n;
+}
+
 int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* settings, float timeSeed, bool sync)
 {
     if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "tb_render: no scene loaded");
@@ -308,6 +319,11 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     if (n == 0) return TB_OK;
     auto opt = [&](const char* k, int64_t d) { auto it = c->options.find(k); return it == c->options.end() ? d : it->second; };
     const bool aov = opt("aov", 0) != 0, count = opt("count_rays", 0) != 0;
+    /* The adaptive launch (option "adaptive"): not in real time (the reference's !IsRealTime), and only for a call whose last frame
+     * is past option adaptive_min_frames -- before that no pixel can skip, and every other call takes the plan and the kernels it always took. */
+    const int64_t adaptiveMin = std::min<int64_t>(opt("adaptive_min_frames", 1024), 0xffffffffll);
+    const bool adaptive = opt("adaptive", 0) != 0 && !count && !s.RenderModeRealTime && (int64_t)c->samplesRendered + (int64_t)n - 1 > adaptiveMin;
+    c->lastAdaptive = adaptive; c->lastOwnedPixels = ownedFramePixels(W, H, c->tiles);
     /* 4 = the split-role kernel where it exists, the lock-step kernel (0) elsewhere */
     const int64_t pipeAsked = opt("pipeline", 0), pipe = pipeAsked == 4 ? 0 : pipeAsked;
     c->ds.alphaTest = opt("alpha_test", 0) ? 1u : 0u;
@@ -346,11 +362,11 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     c->lastVariant = v->name;
     const int variantIndex = (int)(v - kVariants);
     const bool twoLevel = c->ds.numInstances != 0; /* instanced scene (flatten_instances = 0): pipeline 0 only */
-    if (twoLevel && pipe != 0) return fail(c, TB_E_UNSUPPORTED,
+    if (twoLevel && pipe != 0 && !adaptive) return fail(c, TB_E_UNSUPPORTED,
         "tb_render: two-level (instanced) scenes are not supported by pipelines 1-3; use pipeline 0 or flatten_instances = 1");
     /* WHAT to launch is decided by a pure function of scene statistics, call size and options (launch_plan.h; tests/test_launch_plan.py
      * walks its branches on the CPU); what follows executes the plan. */
-    tb_plan_input pin; fillPlanInput(c, v, W, H, n, s, aov, count, sync, pin);
+    tb_plan_input pin; fillPlanInput(c, v, W, H, n, s, aov, count, sync, pin); pin.adaptive = adaptive ? 1u : 0u;
     tb_launch_plan plan; PlanLaunch(pin, plan);
     if (plan.pipeline == 4 && !splitLaunchable(c, v, W, H, pf)) { /* the launcher's own refusal: the lock-step kernel, by the plan's rules for it */
         pin.pipeline = 0; PlanLaunch(pin, plan); plan.rule_pipeline = TB_PLAN_RULE_SPLIT_NO_ROOM;
@@ -375,6 +391,7 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     c->lastCopyWaves = launch == v->fnHi ? v->wavesHi : 0u;
     if (launch == v->fnHi && v->fnLds && groups && c->sceneInLds && !twoLevel && !count && !plan.stack_overflow_entries && !plan.prepass &&
         LdsCopyFits(v->wavesLds, c->ds.stackDepth, c->ds.ldsBlobBytes)) { launch = v->fnLds; c->lastCopyWaves = v->wavesLds; }
+    if (adaptive) launch = v->fnAdaptive; /* the base copy's adaptive form (pt_variant.inc) */
     /* layout C on first demand; the plan is made again with what came of it */
     if (opt("node_layout", 0) == 1 && !twoLevel && !c->sceneInLds && !c->ds.nodesC && !c->compactTried) {
         ensureCompactNodes(c); dsLaunch.nodesC = c->ds.nodesC; dsLaunch.quant = c->ds.quant;
@@ -480,9 +497,20 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     c->kernelEventStamp++; /* this render records evKernelStart / evKernel */
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     if (clearStats && !overlap) HIP_TRY(hipMemsetAsync(c->stats.p, 0, 16, c->stream));
+    if (adaptive) {
+        /* the live list of the call's first frame (pt_kernels.hip live_list_*): count word, scratch, then W x H entries at most.  Between ev0 and
+         * evKernelStart, so that option last_kernel_us times the path-tracing launch alone */
+        const uint32_t regions = tb_persistent_grid(W, H, c->tiles);
+        const size_t scratch = (tb_live_list_scratch_bytes(regions) + 15u) / 16u * 16u;
+        ensure(c->liveList, 16u + scratch + (size_t)W * H * 4u);
+        uint8_t* base = (uint8_t*)c->liveList.p;
+        tg.liveCount = (const uint32_t*)base; tg.liveList = (const uint32_t*)(base + 16u + scratch); tg.adaptiveMinFrames = (uint32_t)adaptiveMin;
+        HIP_TRY(pt_launch_live_list(c->stream, tg.output, tg.jittered, &c->tiles, W, H, c->samplesRendered, (uint32_t)adaptiveMin, pf.MinConvergence,
+            tg.aovNormals, tg.aovCustom, s.OutputType == TB_OUTPUT_TYPE_LIVE_PIXELS ? 1 : 0, base + 16u, (uint32_t*)tg.liveList, (uint32_t*)base));
+    }
     if (!groups) HIP_TRY(hipEventRecord(c->evKernelStart, c->stream));
     c->lastKernelFrames = 0;
-    c->lastPipeline = split ? 4 : (wavefront ? 2 : (pooled ? 3 : (int)(pipe == 1 ? 1 : 0)));
+    c->lastPipeline = split ? 4 : (wavefront ? 2 : (pooled ? 3 : (int)(pipe == 1 && !adaptive ? 1 : 0)));
     if (split) renderSplit(c, v, W, H, n, pf, tg);
     else if (wavefront) renderWavefront(c, variantIndex, W, H, c->samplesRendered, n, pf);
     else if (pooled) renderPooled(c, variantIndex, W, H, c->samplesRendered, n, pf);
@@ -492,7 +520,8 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
          * to an ordered sample buffer and accumulate_samples_kernel folds them in frame order (bit-identical sums).  Keeps all
          * lanes of a workgroup busy to its end and gives a rank of a tile split enough workgroups; on whenever a call renders
          * enough frames to form groups.  Option "frame_group" = G > 0 forces the group size, < 0 forbids the mode. */
-        if (!groups) HIP_TRY(launch(c->stream, &dsLaunch, &pf, &tg, W, H, c->samplesRendered, n, &c->tiles, c->sceneInLds ? 1 : 0, count ? 1 : 0, (int)pipe));
+        if (!groups) HIP_TRY(launch(c->stream, &dsLaunch, &pf, &tg, W, H, c->samplesRendered, n, &c->tiles, c->sceneInLds ? 1 : 0, count ? 1 : 0,
+            adaptive ? 0 : (int)pipe));
         else {
             /* batch and group sizes: launch_plan.h (with the measurements they come from) */
             const uint64_t pixels = (uint64_t)W * H;

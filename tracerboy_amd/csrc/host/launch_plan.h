@@ -23,6 +23,16 @@ inline bool LdsCopyFits(uint32_t waves, uint32_t stackDepth, uint32_t ldsBlobByt
 inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
 {
     p = tb_launch_plan{};
+    if (in.adaptive) {
+        /* The adaptive launch (option "adaptive"): converged pixels are left out and the live ones packed 256 to a workgroup.
+         * A pixel's samples must run in frame order -- the skip test before each frame reads the sums of the frames before it -- so: the lock-step
+         * kernel's one-pixel-per-lane form in the base copy of the feature set (pt_variant.inc pt_launch_adaptive_*), no frame groups, no pre-pass,
+         * no overlapping launches; two-level scenes in the full feature set, whose kernels walk two levels in every form. */
+        p.pipeline = 0; p.rule_pipeline = TB_PLAN_RULE_ADAPTIVE; p.stack_lds_entries = in.stack_depth;
+        p.rule_copy = TB_PLAN_RULE_COPY_NONE; p.prepass = TB_PLAN_PREPASS_OFF; p.rule_prepass = TB_PLAN_RULE_PREPASS_NO_KERNEL;
+        if (in.two_level) { p.full_variant = 1; p.rule_copy = TB_PLAN_RULE_COPY_FULL_FOR_INSTANCES; }
+        return;
+    }
     const bool plain = !in.count_rays && !in.aov && !in.realtime && !in.selected_pixel; /* the call writes nothing but radiance */
     const int64_t pipe = in.pipeline == 4 ? 0 : in.pipeline; /* 4 = the split-role kernel where it exists, the lock-step kernel (0) elsewhere */
     p.pipeline = (int32_t)pipe;

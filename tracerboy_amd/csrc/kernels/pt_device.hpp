@@ -811,6 +811,7 @@ enum : uint32_t {
 enum : uint32_t {
     F_SPECULAR = 1u << 0, F_PERFECT = 1u << 1, F_PREV_PERFECT = 1u << 2, F_EXITING = 1u << 3, F_NOSCATTER = 1u << 4,
     F_AOV_DEPTH = 1u << 5, F_AOV_EMISSIVE = 1u << 6, F_HEATMAP = 1u << 7,
+    F_AOV_ALBEDO = 1u << 8, /* the adaptive launch only (path_scatter MARK): the path stored its primary albedo */
 };
 
 /* Fields that a feature set never touches are dead after inlining and cost no registers. */
@@ -833,6 +834,17 @@ struct Path {
     uint32_t lastBoxes, lastTris;
     uint32_t nMat, nLight; /* GetMaterial / GetOneLightSample calls of the current sample (byte model) */
 };
+
+/* The adaptive launch's skip test: the reference's ShouldSkipRay past its frame threshold (VarianceUtil.h:1-30) on a pixel's sums o (OutputTexture)
+ * and q (JitteredOutputTexture).  IEEE division and square root, no contraction (tb_math.h), the same order of sums as DESIGN.md section 10 states;
+ * NaNs compare false, so a pixel without a sample (o.w == 0) stays live. */
+TBD bool tb_adaptive_skip(const TbFloat4& o, const TbFloat4& q, float minConvergence)
+{
+    const float cr = o.x / o.w, cg = o.y / o.w, cb = o.z / o.w, jr = q.x / q.w, jg = q.y / q.w, jb = q.z / q.w;
+    if (cr <= 0.0f && cg <= 0.0f && cb <= 0.0f) return true; /* black: converged to black (a camera ray that misses, no environment) */
+    const float err = ((tb_abs(jr - cr) + tb_abs(jg - cg)) + tb_abs(jb - cb)) / tb_sqrt((cr + cg) + cb);
+    return err < minConvergence;
+}
 
 /* kernel.glsl:1786-1798 with the identity view matrix (GetRotationFactor() == 0.5) */
 TBD tb3 lens_position(const TbPerFrameConstants& pf, float lensHeight, float u, float v, float aspect)
@@ -1179,8 +1191,9 @@ TBD bool refract_or_reflect(Path& p, const TbPerFrameConstants& pf, tb3 normal, 
     return true;
 }
 
-/* kernel.glsl:1519-1772: next direction + throughput.  Sets up the next pending ray. */
-template <uint32_t F>
+/* kernel.glsl:1519-1772: next direction + throughput.  Sets up the next pending ray.  MARK (the adaptive launch): flag the store of the primary
+ * albedo (F_AOV_ALBEDO), which decides that sample's LIVE_PIXELS AOV (pt_persistent.inc) */
+template <uint32_t F, bool MARK = false>
 TBD void path_scatter(Path& p, const TbPerFrameConstants& pf)
 {
     const bool first = p.bounce == 0;
@@ -1260,7 +1273,7 @@ TBD void path_scatter(Path& p, const TbPerFrameConstants& pf)
     } else { /* :1766-1769 */
         p.T = p.T * (albedo * diffuse_brdf(p.rd, p.Nd));
     }
-    if ((F & FEAT_EXT) && first) p.aovAlbedo = p.albedo; /* :1771 */
+    if ((F & FEAT_EXT) && first) { p.aovAlbedo = p.albedo; if (MARK) p.flags |= F_AOV_ALBEDO; } /* :1771 */
     finish_bounce(p, pf);
 }
 

@@ -177,6 +177,72 @@ __global__ __launch_bounds__(1024) void region_order_kernel(const uint32_t* __re
     }
 }
 
+/* The live list of the adaptive launch (TbDeviceTargets::liveList, pt_scene.h): one pass over the context's owned regions in tb_persistent_grid /
+ * block_region order -- the regions of its tiles, or the whole frame.  live_list_count applies the skip test (tb_adaptive_skip, pt_device.hpp) at the
+ * launch's first frame to the 256 pixels of a region in the lock-step kernel's own lane mapping (wave w = the 8x8 tile (w & 1, w >> 1), lane =
+ * (lane & 7, lane >> 3)), keeps the four waves' ballots and the region's count, and leaves a skipped pixel's AOVs (the reference's ClearAOVs +
+ * OutputLivePixels); live_list_scan turns the counts into every region's first entry (exclusive, in place) and the total; live_list_scatter writes
+ * x | y << 16 of each live pixel at its region's first entry + the live pixels of the waves before + mbcnt.  Region, then wave, then lane: a wholly
+ * live region gives the dense launch's own waves.  Nothing is ordered by atomics, so the list depends on the surfaces alone. */
+__global__ __launch_bounds__(256) void live_list_count(const TbFloat4* __restrict__ output, const TbFloat4* __restrict__ jittered, TbTileMap tiles, uint32_t W,
+    uint32_t H, uint32_t frame, uint32_t minFrames, float minConvergence, unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts,
+    TbFloat4* __restrict__ aovNormals, TbFloat4* __restrict__ aovCustom, uint32_t livePixelsMode)
+{
+    __shared__ uint32_t waveLive[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, region = blockIdx.x;
+    uint32_t bx, by; block_region(tiles, W, H, region, bx, by);
+    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u), y = by * 16u + (wave >> 1) * 8u + (lane >> 3);
+    bool live = x < W && y < H;
+    if (live && frame > minFrames) {
+        const size_t pix = (size_t)y * W + x;
+        const TbFloat4 o = output[pix];
+        if (tb_adaptive_skip(o, jittered[pix], minConvergence)) {
+            live = false;
+            if (aovNormals) aovNormals[pix] = TbFloat4{0, 0, 0, 1.0f};
+            if (aovCustom) aovCustom[pix] = livePixelsMode ? TbFloat4{o.x / o.w, o.y / o.w, o.z / o.w, o.w / o.w} : TbFloat4{0, 0, 0, 1.0f};
+        }
+    }
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) { masks[(size_t)region * 4u + wave] = m; waveLive[wave] = (uint32_t)__popcll(m); }
+    __syncthreads();
+    if (threadIdx.x == 0) counts[region] = waveLive[0] + waveLive[1] + waveLive[2] + waveLive[3];
+}
+
+/* one workgroup: thread t sums a contiguous run of the counts, the 1024 sums are scanned in LDS, the runs are rewritten as first entries */
+__global__ __launch_bounds__(1024) void live_list_scan(uint32_t* __restrict__ counts, uint32_t regions, uint32_t* __restrict__ total)
+{
+    __shared__ uint32_t sums[1024];
+    const uint32_t t = threadIdx.x, per = (regions + 1023u) / 1024u;
+    const uint32_t b = t * per < regions ? t * per : regions, e = b + per < regions ? b + per : regions;
+    uint32_t own = 0;
+    for (uint32_t i = b; i < e; i++) own += counts[i];
+    sums[t] = own;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024u; off <<= 1) {
+        const uint32_t v = t >= off ? sums[t - off] : 0u;
+        __syncthreads();
+        sums[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = sums[t] - own;
+    for (uint32_t i = b; i < e; i++) { const uint32_t c = counts[i]; counts[i] = run; run += c; }
+    if (t == 1023u) *total = sums[1023];
+}
+
+__global__ __launch_bounds__(256) void live_list_scatter(TbTileMap tiles, uint32_t W, uint32_t H, const unsigned long long* __restrict__ masks,
+    const uint32_t* __restrict__ first, uint32_t* __restrict__ list)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, region = blockIdx.x;
+    const unsigned long long* m = masks + (size_t)region * 4u;
+    const unsigned long long mine = m[wave];
+    if (!((mine >> lane) & 1ull)) return;
+    uint32_t pos = first[region];
+    for (uint32_t w = 0; w < wave; w++) pos += (uint32_t)__popcll(m[w]);
+    pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+    uint32_t bx, by; block_region(tiles, W, H, region, bx, by);
+    list[pos] = (bx * 16u + (wave & 1u) * 8u + (lane & 7u)) | (by * 16u + (wave >> 1) * 8u + (lane >> 3)) << 16;
+}
+
 extern "C" {
 
 hipError_t pt_launch_accumulate_samples(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
@@ -192,6 +258,22 @@ hipError_t pt_launch_region_order(hipStream_t stream, const uint32_t* cost, cons
                                   uint32_t numGroups, uint32_t lateFrom, uint32_t* order, uint32_t* keys)
 {
     hipLaunchKernelGGL(region_order_kernel, dim3(1), dim3(1024), 0, stream, cost, *tiles, W, H, regions, numGroups, lateFrom, order, keys);
+    return hipGetLastError();
+}
+
+/* TbDeviceTargets::liveList / liveCount for the launch whose first frame is `frame` (live_list_* above).  scratch: tb_live_list_scratch_bytes(regions). */
+hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const TbTileMap* tiles, uint32_t W, uint32_t H,
+                               uint32_t frame, uint32_t minFrames, float minConvergence, TbFloat4* aovNormals, TbFloat4* aovCustom, int livePixelsMode,
+                               void* scratch, uint32_t* list, uint32_t* count)
+{
+    const uint32_t regions = tb_persistent_grid(W, H, *tiles);
+    unsigned long long* masks = (unsigned long long*)scratch;
+    uint32_t* counts = (uint32_t*)(masks + (size_t)regions * 4u);
+    if (regions) hipLaunchKernelGGL(live_list_count, dim3(regions), dim3(256), 0, stream, output, jittered, *tiles, W, H, frame, minFrames, minConvergence, masks,
+        counts, aovNormals, aovCustom, livePixelsMode ? 1u : 0u);
+    hipLaunchKernelGGL(live_list_scan, dim3(1), dim3(1024), 0, stream, counts, regions, count);
+    if (regions) hipLaunchKernelGGL(live_list_scatter, dim3(regions), dim3(256), 0, stream, *tiles, W, H, (const unsigned long long*)masks,
+        (const uint32_t*)counts, list);
     return hipGetLastError();
 }
 

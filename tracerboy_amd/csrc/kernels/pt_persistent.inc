@@ -151,11 +151,16 @@ __global__ __launch_bounds__(BLOCK) PT_FIRST_ATTR void pt_first(TbDeviceScene ds
 /* GUIDED: the launch's frame groups shrink over its end (TbDeviceTargets::fgGuided, pt_scene.h tb_fg_groups) -- a copy of its own, because the three
  * instructions per drawn sample that read a slot's size cost the VALU-bound cornell-box kernel 0.6 % of its asynchronous step (1.0 % behind a uniform
  * branch: same box, 7 140 / 7 105 against 7 185 Msamples/s) and only launches of calls that wait use it */
+/* ADAPTIVE: the adaptive launch (TbDeviceTargets::liveList, pt_scene.h) -- the one-pixel-per-lane form over the packed live pixels, each lane testing
+ * its pixel again before every later frame (DESIGN.md section 10) */
 template <uint32_t F, bool SCENE_LDS, bool COUNT, bool GROUPS, bool HYBRID = false, bool NODEC = false, bool TWOLEVEL = false, bool PRIMARY = false,
-          bool FIRST = false, bool GUIDED = false>
+          bool FIRST = false, bool GUIDED = false, bool ADAPTIVE = false>
 __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDeviceScene ds, TbPerFrameConstants pf, TbDeviceTargets tg, uint32_t W, uint32_t H,
                                                         uint32_t firstFrame, uint32_t numFrames, TbTileMap tiles)
 {
+    /* the adaptive launch: the grid is the owned region count, an upper bound; a workgroup whose first entry is past the live count has no pixel */
+    uint32_t liveCount = 0;
+    if constexpr (ADAPTIVE) { liveCount = *tg.liveCount; if (blockIdx.x * BLOCK >= liveCount) return; }
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     /* what the walks of this kernel carry besides the hit: per-ray box / triangle counters for the counting launch and for the full feature
      * set's heatmap (RayGenCommon.h:537-543), the IsValidHit filter in the full feature set only; the wave-occupancy profile rides on COUNT */
@@ -225,6 +230,8 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
     block_region(tiles, W, H, blockIdx.x, bx, by);
     /* the lane's pixel, x | y << 16: one pixel for the whole launch, or in frame-group mode the pixel of the sample in flight */
     uint32_t xy = (bx * 16u + (wave & 1u) * 8u + (lane & 7u)) | (by * 16u + (wave >> 1) * 8u + (lane >> 3)) << 16;
+    /* (the adaptive launch: entry 256 b + t of the live list; a lane past the count has no pixel -- 0xffff is beyond any frame) */
+    if constexpr (ADAPTIVE) { const uint32_t i = blockIdx.x * BLOCK + threadIdx.x; xy = i < liveCount ? tg.liveList[i] : 0xffffffffu; }
 #define PX (xy & 0xffffu)
 #define PY (xy >> 16)
 #define PIX ((size_t)PY * W + PX)
@@ -353,6 +360,8 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             if (ok) { o0 += s0; o1 += s1; o2 += s2; o3 += s3; }
             float coin = rnd(p.seed, pf.Time);
             const size_t pix = PIX;
+            TbFloat4 before{0, 0, 0, 0}; /* the adaptive launch: the sums before this sample (its LIVE_PIXELS AOV) */
+            if constexpr (ADAPTIVE && (F & FEAT_EXT) != 0) before = acc;
             if (GROUPS) tg.samples[(size_t)(frame - firstFrame) * W * H + pix] = TbFloat4{o0, o1, o2, coin < 0.5f ? -o3 : o3};
             else {
                 if (((F & FEAT_EXT) && pf.IsRealTime) || frame == 0) acc = TbFloat4{0, 0, 0, 0};
@@ -366,7 +375,11 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             if (tg.aovNormals) tg.aovNormals[pix] = TbFloat4{p.aovNormal.x, p.aovNormal.y, p.aovNormal.z, 1.0f};
             if (tg.aovWorldPos0 && (frame % 2) == 0) tg.aovWorldPos0[pix] = TbFloat4{p.aovWorldPos.x, p.aovWorldPos.y, p.aovWorldPos.z, p.aovNeighbor};
             if (tg.aovWorldPos1 && (frame % 2) == 1) tg.aovWorldPos1[pix] = TbFloat4{p.aovWorldPos.x, p.aovWorldPos.y, p.aovWorldPos.z, p.aovNeighbor};
-            if (tg.aovCustom) tg.aovCustom[pix] = (p.flags & F_HEATMAP) ? TbFloat4{(float)p.lastTris, (float)p.lastBoxes, 0, 0} : TbFloat4{p.aovAlbedo.x,
+            /* (the adaptive launch in LIVE_PIXELS mode: a sample that stored no primary albedo -- a camera ray that missed -- leaves the reference's
+             * OutputLivePixels(false) tint of the sums before it, RayGenCommon.h:545-551) */
+            if (ADAPTIVE && tg.aovCustom && pf.OutputMode == TB_OUTPUT_TYPE_LIVE_PIXELS && !(p.flags & F_AOV_ALBEDO))
+                tg.aovCustom[pix] = TbFloat4{before.x / before.w, 0.2f * (before.y / before.w), 0.2f * (before.z / before.w), before.w / before.w};
+            else if (tg.aovCustom) tg.aovCustom[pix] = (p.flags & F_HEATMAP) ? TbFloat4{(float)p.lastTris, (float)p.lastBoxes, 0, 0} : TbFloat4{p.aovAlbedo.x,
                 p.aovAlbedo.y, p.aovAlbedo.z, 1.0f};
             if (tg.aovDepth && (p.flags & F_AOV_DEPTH)) tg.aovDepth[pix] = p.aovDepth;
             if (tg.aovEmissive && (p.flags & F_AOV_EMISSIVE)) tg.aovEmissive[pix] = TbFloat4{p.aovEmissive.x, p.aovEmissive.y, p.aovEmissive.z, 1.0f};
@@ -374,6 +387,19 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             if (COUNT) { cSamples++; cMats += p.nMat; cLights += p.nLight; }
             if (GROUPS) { const int r = next_sample(0, false); if (r == 2) { alive = false; break; } if (r == 0) { p.state = ST_WAIT; continue; } }
             else { frame++; if (frame >= endFrame) { alive = false; break; } }
+            if constexpr (ADAPTIVE) {
+                /* the skip test before every later frame, on the sums in the lane's registers (behind the cheap frame guard: seven divisions and a
+                 * square root).  A pixel that skips keeps skipping -- its sums and the threshold no longer change -- so the lane retires: its sums
+                 * go back unchanged below, and an AOV call leaves the reference's ClearAOVs + OutputLivePixels(true) of a skipped pixel */
+                if (frame > tg.adaptiveMinFrames && tb_adaptive_skip(acc, jacc, pf.MinConvergence)) {
+                    if constexpr ((F & FEAT_EXT) != 0) {
+                        if (tg.aovNormals) tg.aovNormals[pix] = TbFloat4{0, 0, 0, 1.0f};
+                        if (tg.aovCustom) tg.aovCustom[pix] = pf.OutputMode == TB_OUTPUT_TYPE_LIVE_PIXELS ? TbFloat4{acc.x / acc.w, acc.y / acc.w, acc.z / acc.w,
+                            acc.w / acc.w} : TbFloat4{0, 0, 0, 1.0f};
+                    }
+                    alive = false; break;
+                }
+            }
             begin();
             if (p.state == ST_DONE) continue; /* MaxBounces == 0 */
         }
@@ -483,7 +509,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
               path_scatter<F>(q, pf);
               if (exp_never(q.T.x + q.T.y + q.T.z, q.seed + q.rd.x + q.rd.y + q.rd.z, q.ro.x + q.ro.y + q.ro.z, (float)(q.state + q.flags + (uint32_t)q.bounce))) p.flags |= 0x40000000u; }
 #endif
-            if (p.state == ST_SCATTER) { if (COUNT) prof_hit(prof, PROF_SCATTER); path_scatter<F>(p, pf); }
+            if (p.state == ST_SCATTER) { if (COUNT) prof_hit(prof, PROF_SCATTER); path_scatter<F, ADAPTIVE>(p, pf); }
             if (feeler) {
                 Hit h; uint32_t nb = 0, nt = 0;
                 bool isHit;
@@ -540,7 +566,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             p.lastBoxes = nb; p.lastTris = nt;
             path_on_shadow<F>(p, sc, ds, pf, isHit, h);
         }
-        if (p.state == ST_SCATTER) { if (COUNT) prof_hit(prof, PROF_SCATTER); path_scatter<F>(p, pf); }
+        if (p.state == ST_SCATTER) { if (COUNT) prof_hit(prof, PROF_SCATTER); path_scatter<F, ADAPTIVE>(p, pf); }
         }
         if (PRIMARY && (p.state == ST_EXTEND || p.state == ST_SSS)) slot1();
     }

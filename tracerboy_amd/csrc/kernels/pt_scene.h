@@ -83,7 +83,10 @@ struct TbDeviceTargets {
      * samples[(frame - firstFrame) * W * H + pixel] as (rgb*w, +-w; sign bit = jitter coin < 0.5) and
      * accumulate_samples_kernel then sums them in frame order, which keeps the fp32 accumulation of RayGenCommon.h:704-727
      * bit for bit while no lane waits for its neighbours' longer paths. */
-    TbFloat4* samples; uint32_t frameGroup; uint32_t* workCounter;
+    TbFloat4* samples;
+    /* (the adaptive launch -- below -- has no frame groups: it keeps its frame threshold and its live count in these two members) */
+    union { uint32_t frameGroup; uint32_t adaptiveMinFrames; };
+    union { uint32_t* workCounter; const uint32_t* liveCount; };
     /* 1: the work items of a region shrink towards the end of the launch (tb_fg_groups below): half of the frames in groups of frameGroup, half of
      * the rest in groups half that size, ... single frames last -- what is left bound to slow workgroups when the lists run dry is then a few
      * hundred samples instead of two whole groups (docs/experiments/r6.md: the end of a launch that has the chip to itself) */
@@ -124,7 +127,13 @@ struct TbDeviceTargets {
      * (pt_kernels.hip) turns the counts into the order in which the NEXT launch hands its items out: regionOrder[1 + i] = group << 20 | region
      * of the i-th claim, a permutation of the usual list in which the items of counted regions that would come late are first.  Any permutation
      * gives the same picture (a sample depends on pixel and frame alone); only the end of the launch moves. */
-    uint32_t* regionCost; const uint32_t* regionOrder;
+    /* The adaptive launch (pt_persistent ADAPTIVE).  liveList: the pixels (x | y << 16) that passed the skip test at the launch's
+     * first frame, in region / wave / lane order (live_list_* kernels, pt_kernels.hip); *liveCount of them.  Lane t of workgroup b renders
+     * liveList[256 b + t]; before each later frame whose global index exceeds adaptiveMinFrames it applies the skip test again (tb_adaptive_skip,
+     * pt_device.hpp) and retires if it holds.  The three share storage with frame-group members, which that launch does not have: a member
+     * appended to this struct would move every kernel argument behind it (W, H, the frames, the tile map, the split-role kernel's parameters). */
+    uint32_t* regionCost;
+    union { const uint32_t* regionOrder; const uint32_t* liveList; };
 };
 
 /* Split-role kernel (pipeline 4, pt_split.inc): a workgroup is `travWaves` traversal waves followed by `shadeWaves` shading waves.

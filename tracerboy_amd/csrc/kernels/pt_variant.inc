@@ -171,6 +171,34 @@ extern "C" hipError_t PT_CAT(pt_launch_persistent_, PT_NAME)(hipStream_t stream,
     return hipGetLastError();
 }
 
+#ifndef PT_ONLY_PERSISTENT
+/* The adaptive launch (TbDeviceTargets::liveList, pt_scene.h; the host has run pt_launch_live_list on the same stream): the one-pixel-per-lane form of
+ * the base copy over the packed live pixels.  The grid is the owned region count, an upper bound, so that the host reads nothing back; a workgroup
+ * past the live count exits at once.  The full feature set's copy walks two-level scenes too, like its dense copy. */
+extern "C" hipError_t PT_CAT(pt_launch_adaptive_, PT_NAME)(hipStream_t stream, const TbDeviceScene* ds, const TbPerFrameConstants* pf, const TbDeviceTargets* tg,
+                                                          uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames, const TbTileMap* tiles,
+                                                          int sceneInLds, int countRays, int pipeline)
+{
+    if (!tg->liveList || !tg->liveCount || tg->samples || tg->primaryHits || countRays || pipeline != 0 || ds->stackOverflow || ds->nodesC)
+        return hipErrorInvalidValue;
+#if !(PT_FEATURES & PT_FEAT_EXT)
+    if (ds->numInstances) return hipErrorInvalidValue;
+#endif
+    const uint32_t blocks = tb_persistent_grid(W, H, *tiles);
+    if (blocks == 0 || numFrames == 0) return hipSuccess;
+    const size_t lds = (size_t)ds->stackDepth * BLOCK * 4 + (sceneInLds ? ds->ldsBlobBytes : 0);
+#define PT_ADAPTIVE(L) do { \
+        hipError_t e = hipFuncSetAttribute((const void*)pt_persistent<PT_FEATURES, L, false, false, false, false, false, false, false, false, true>, \
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e != hipSuccess) return e; \
+        hipLaunchKernelGGL((pt_persistent<PT_FEATURES, L, false, false, false, false, false, false, false, false, true>), dim3(blocks), dim3(BLOCK), lds, \
+            stream, *ds, *pf, *tg, W, H, firstFrame, numFrames, *tiles); } while (0)
+    if (sceneInLds) PT_ADAPTIVE(true); else PT_ADAPTIVE(false);
+#undef PT_ADAPTIVE
+    return hipGetLastError();
+}
+#endif
+
 /* ---- wavefront pipeline (pipeline 2): one launcher per feature set, one stage per call ---------------------- */
 #if !(PT_FEATURES & PT_FEAT_EXT) && !defined(PT_ONLY_PERSISTENT)
 #include "wf_types.h"
