@@ -222,6 +222,8 @@ int tb_unpack_gathered_host(uint32_t width, uint32_t height, uint32_t world, uin
  * measured to raise box tests).  Launch policy: "frame_group", "guided_groups" (0 never, 1 = calls that wait [default], 2 always: the frame
  * groups of a region shrink over the last groups of a launch), "primary_prepass", "overlap_launches", "costly_first" (+ "costly_late_samples"), "high_occupancy", "stack_lds_cap",
  * "compact_hits", "camera_constants", "texture_use_hint", "node_layout", "node_order" -- each described where launch_plan.h / context_render.cpp use it.
+ * Adaptive sampling: "adaptive" (0/1), "adaptive_min_frames", "adaptive_test" (0 = the skip test runs before every frame
+ * [default], 1 = once per call, at its first frame: a live pixel gets all the call's frames, a converged one none; any other value is refused).
  * An unknown name is an error. */
 int tb_set_option(tb_context* ctx, const char* name, int64_t value);
 /* tb_get_option also reads what the last render did ("last_*") and "debug_live_device_bytes": the device bytes the library holds for all
@@ -238,6 +240,7 @@ enum { TB_PLAN_PREPASS_OFF = 0, TB_PLAN_PREPASS_ON = 1, TB_PLAN_PREPASS_TRIAL = 
 /* rule_pipeline */
 enum { TB_PLAN_RULE_ONE_PIXEL_PER_LANE = 1, TB_PLAN_RULE_FRAME_GROUPS, TB_PLAN_RULE_WAVEFRONT, TB_PLAN_RULE_POOLED, TB_PLAN_RULE_SPLIT,
     TB_PLAN_RULE_SPLIT_NO_ROOM, TB_PLAN_RULE_ADAPTIVE /* = 7: the adaptive launch (option "adaptive", frames past adaptive_min_frames) */,
+    TB_PLAN_RULE_ADAPTIVE_GROUPS /* = 8: the adaptive launch tested per call (option "adaptive_test" = 1) through the frame-group kernels */,
        /* rule_copy */
        TB_PLAN_RULE_COPY_NONE = 10, TB_PLAN_RULE_COPY_FITS, TB_PLAN_RULE_COPY_SPLIT_STACK, TB_PLAN_RULE_COPY_TOO_DEEP, TB_PLAN_RULE_COPY_NO_ROOM,
            TB_PLAN_RULE_COPY_FULL_FOR_INSTANCES,
@@ -271,7 +274,10 @@ typedef struct tb_plan_input {
     /* the regions where paths were long in the launches before are handed out first (option costly_first: 0 never, 1 = feature sets with interior walks, calls
      * below 3 x 2^24 samples [default], 2 = those feature sets at any size) */
     uint32_t costly_first /* 1 */;
-    /* the call runs the adaptive launch: option "adaptive" on, not real-time, and its last frame past option adaptive_min_frames (renderImpl) */
+    /* 1: the call runs the adaptive launch: option "adaptive" on, not real-time, and its last frame past option adaptive_min_frames (renderImpl).
+     * 2: the same tested once per call (option "adaptive_test" = 1; the call's FIRST frame is past adaptive_min_frames): the pixels live at the
+     * call's first frame get every frame of the call, through the frame-group kernels where a plain call would take them (rule
+     * TB_PLAN_RULE_ADAPTIVE_GROUPS), else through the one-pixel-per-lane adaptive kernel with its per-frame test switched off (TB_PLAN_RULE_ADAPTIVE) */
     uint32_t adaptive;
 } tb_plan_input;
 typedef struct tb_launch_plan {

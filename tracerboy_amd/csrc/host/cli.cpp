@@ -2,7 +2,7 @@
  *   tracerboy-hip scene.pbrt [--width W] [--height H] [--spp N] [--depth D] [--seed-time T] [--device I]
  *                 [--builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu] [--blue-noise 0|1] [--tonemap 0..7] [--exposure E|auto]
  *                 [--out frame.png|frame.pfm|frame.exr]
- *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C]]
+ *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C] [--adaptive-test frame|call]]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -21,7 +21,9 @@
  * --adaptive P: stop sampling converged pixels (option "adaptive", ConvergencePercentage = P).  One plain call of
  * min(F + 1, N) frames (F = --adaptive-after, default 1024, the reference's threshold), then adaptive calls of C frames (--adaptive-chunk, default
  * 64) until N frames are rendered or no pixel is live; one line per call: frames so far, live pixels at the call's start, milliseconds.  With
- * --ranks every rank runs the schedule over its own tiles. */
+ * --ranks every rank runs the schedule over its own tiles.  --adaptive-test call (option "adaptive_test" = 1; default frame): a pixel is tested once
+ * per call, at the call's first frame, and the live ones get all C frames at the frame-group kernels' speed -- the form to prefer for scenes that
+ * are fetched from memory. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -119,11 +121,11 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
-    float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64;
+    float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
     for (int i = 2; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
         if (k == "--width") W = (uint32_t)atoi(v); else if (k == "--height") H = (uint32_t)atoi(v); else if (k == "--spp") spp = (uint32_t)atoi(v);
@@ -133,6 +135,8 @@ int main(int argc, char** argv)
             else if (k == "--ranks") ranks = atoi(v);
         else if (k == "--adaptive") adaptive = (float)atof(v); else if (k == "--adaptive-after") adaptiveAfter = atoll(v);
         else if (k == "--adaptive-chunk") adaptiveChunk = atoll(v);
+        else if (k == "--adaptive-test") { if (!strcmp(v, "call")) adaptiveTest = 1; else if (!strcmp(v, "frame")) adaptiveTest = 0;
+            else { fprintf(stderr, "--adaptive-test is frame or call\n"); return 2; } }
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -173,7 +177,8 @@ int main(int argc, char** argv)
         ms = tb_last_render_ms(ctx);
     } else {
         s.ConvergencePercentage = adaptive;
-        if ((rc = tb_set_option(ctx, "adaptive", 1)) || (rc = tb_set_option(ctx, "adaptive_min_frames", adaptiveAfter))) return fail(ctx, "tb_set_option", rc);
+        if ((rc = tb_set_option(ctx, "adaptive", 1)) || (rc = tb_set_option(ctx, "adaptive_min_frames", adaptiveAfter)) ||
+            (rc = tb_set_option(ctx, "adaptive_test", adaptiveTest))) return fail(ctx, "tb_set_option", rc);
         uint32_t done = (uint32_t)std::min<long long>(adaptiveAfter + 1, spp); /* the plain call: no pixel can skip before frame F + 1 */
         if ((rc = tb_render(ctx, W, H, done, &s, t))) return fail(ctx, "tb_render", rc);
         ms = tb_last_render_ms(ctx);

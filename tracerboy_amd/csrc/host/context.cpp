@@ -668,10 +668,12 @@ int tb_set_option(tb_context* c, const char* name, int64_t v)
         "alpha_test", "node_order", "node_order_top_levels", "frame_group", "overlap_launches", "high_occupancy", "stack_lds_cap", "stack_overflow_max",
         "flip_texture_uvs", "wavefront_sort", "banded_items", "node_layout", "wavefront_refill",
                                   "split_trav", "split_shade", "split_ready", "split_refill", "split_wi", "split_wl", "split_frame_group", "split_stack_cap",
-                                      "split_spin_limit", "split_profile", "split_trav_last", "split_shade_prio", "adaptive", "adaptive_min_frames"};
+                                      "split_spin_limit", "split_profile", "split_trav_last", "split_shade_prio", "adaptive", "adaptive_min_frames", "adaptive_test"};
     /* the adaptive launch has no counting copy; its frame threshold is a frame index */
     auto on = [&](const char* k) { auto it = c->options.find(k); return it != c->options.end() && it->second != 0; };
     if (!strcmp(name, "adaptive_min_frames") && v < 0) return fail(c, TB_E_INVALID, "tb_set_option: adaptive_min_frames must not be negative");
+    /* 0: the skip test runs before every frame (the reference's); 1: once per call, at its first frame */
+    if (!strcmp(name, "adaptive_test") && v != 0 && v != 1) return fail(c, TB_E_INVALID, "tb_set_option: adaptive_test is 0 (before every frame) or 1 (once per call)");
     if ((!strcmp(name, "adaptive") && v && on("count_rays")) || (!strcmp(name, "count_rays") && v && on("adaptive")))
         return fail(c, TB_E_INVALID, "tb_set_option: options \"adaptive\" and \"count_rays\" exclude each other (the counting kernels have no adaptive copy)");
     for (const char* k : known) if (!strcmp(k, name)) { c->options[name] = v; if (!strcmp(name, "count_rays") || !strcmp(name, "aov")) c->samplesRendered = 0;
@@ -725,7 +727,7 @@ int64_t tb_get_option(tb_context* c, const char* name)
         for (tb_context* x : all) {
             if (!x->lastAdaptive || !x->liveList.p) { sum += (int64_t)x->lastOwnedPixels; continue; }
             uint32_t v = 0; DeviceScope scope(x->device);
-            if (hipStreamSynchronize(x->stream) != hipSuccess || hipMemcpy(&v, x->liveList.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+            if (hipStreamSynchronize(x->stream) != hipSuccess || hipMemcpy(&v, (const uint8_t*)x->liveList.p + x->liveCountOffset, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
             sum += v;
         }
         return sum;

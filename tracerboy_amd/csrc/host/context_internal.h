@@ -161,7 +161,7 @@ struct tb_context {
     DevBuf fgHits[2];   /* primary-visibility pre-pass: 16-B or 32-B record of every sample's first hit (TbDeviceTargets::primaryHits) */
     DevBuf regionCost, regionOrder[2]; uint64_t regionCostKey = ~0ull; /* costly regions first (TbDeviceTargets::regionCost / regionOrder): 2^20 counts; per side stream 1 + 2 x regions words */
     /* the adaptive launch (option "adaptive"): live list, its count and the list pass's scratch (pt_launch_live_list); what the last call was */
-    DevBuf liveList; bool lastAdaptive = false; uint64_t lastOwnedPixels = 0;
+    DevBuf liveList; size_t liveCountOffset = 0; /* bytes of scratch before the count word */ bool lastAdaptive = false; uint64_t lastOwnedPixels = 0;
     DevBuf stackOverflow; /* split traversal stack of the higher-occupancy kernel copies on deep trees (pt_scene.h) */
     std::vector<const void*> warmedLaunchers; /* frame-group kernels that have run once on both side streams (renderImpl) */
     uint32_t fgLaunch = 0; bool sideOrdered = false; /* sideOrdered: the side streams have been ordered after everything else on `stream` */

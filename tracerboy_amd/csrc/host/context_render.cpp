@@ -322,7 +322,11 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     /* The adaptive launch (option "adaptive"): not in real time (the reference's !IsRealTime), and only for a call whose last frame
      * is past option adaptive_min_frames -- before that no pixel can skip, and every other call takes the plan and the kernels it always took. */
     const int64_t adaptiveMin = std::min<int64_t>(opt("adaptive_min_frames", 1024), 0xffffffffll);
-    const bool adaptive = opt("adaptive", 0) != 0 && !count && !s.RenderModeRealTime && (int64_t)c->samplesRendered + (int64_t)n - 1 > adaptiveMin;
+    /* Option adaptive_test = 1: one test per call, at its first frame -- the call is adaptive iff THAT frame is past the threshold (a call that starts
+     * at or below it is a plain call even if it ends above), and the pixels live then get every frame of the call. */
+    const bool perCall = opt("adaptive_test", 0) == 1;
+    const bool adaptive = opt("adaptive", 0) != 0 && !count && !s.RenderModeRealTime &&
+        (perCall ? (int64_t)c->samplesRendered : (int64_t)c->samplesRendered + (int64_t)n - 1) > adaptiveMin;
     c->lastAdaptive = adaptive; c->lastOwnedPixels = ownedFramePixels(W, H, c->tiles);
     /* 4 = the split-role kernel where it exists, the lock-step kernel (0) elsewhere */
     const int64_t pipeAsked = opt("pipeline", 0), pipe = pipeAsked == 4 ? 0 : pipeAsked;
@@ -366,7 +370,7 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
         "tb_render: two-level (instanced) scenes are not supported by pipelines 1-3; use pipeline 0 or flatten_instances = 1");
     /* WHAT to launch is decided by a pure function of scene statistics, call size and options (launch_plan.h; tests/test_launch_plan.py
      * walks its branches on the CPU); what follows executes the plan. */
-    tb_plan_input pin; fillPlanInput(c, v, W, H, n, s, aov, count, sync, pin); pin.adaptive = adaptive ? 1u : 0u;
+    tb_plan_input pin; fillPlanInput(c, v, W, H, n, s, aov, count, sync, pin); pin.adaptive = adaptive ? (perCall ? 2u : 1u) : 0u;
     tb_launch_plan plan; PlanLaunch(pin, plan);
     if (plan.pipeline == 4 && !splitLaunchable(c, v, W, H, pf)) { /* the launcher's own refusal: the lock-step kernel, by the plan's rules for it */
         pin.pipeline = 0; PlanLaunch(pin, plan); plan.rule_pipeline = TB_PLAN_RULE_SPLIT_NO_ROOM;
@@ -391,7 +395,8 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     c->lastCopyWaves = launch == v->fnHi ? v->wavesHi : 0u;
     if (launch == v->fnHi && v->fnLds && groups && c->sceneInLds && !twoLevel && !count && !plan.stack_overflow_entries && !plan.prepass &&
         LdsCopyFits(v->wavesLds, c->ds.stackDepth, c->ds.ldsBlobBytes)) { launch = v->fnLds; c->lastCopyWaves = v->wavesLds; }
-    if (adaptive) launch = v->fnAdaptive; /* the base copy's adaptive form (pt_variant.inc) */
+    /* the base copy's adaptive form (pt_variant.inc); the list-driven frame-group launch (rule TB_PLAN_RULE_ADAPTIVE_GROUPS) keeps the copy chosen above */
+    if (adaptive && !groups) launch = v->fnAdaptive;
     /* layout C on first demand; the plan is made again with what came of it */
     if (opt("node_layout", 0) == 1 && !twoLevel && !c->sceneInLds && !c->ds.nodesC && !c->compactTried) {
         ensureCompactNodes(c); dsLaunch.nodesC = c->ds.nodesC; dsLaunch.quant = c->ds.quant;
@@ -498,15 +503,19 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     if (clearStats && !overlap) HIP_TRY(hipMemsetAsync(c->stats.p, 0, 16, c->stream));
     if (adaptive) {
-        /* the live list of the call's first frame (pt_kernels.hip live_list_*): count word, scratch, then W x H entries at most.  Between ev0 and
-         * evKernelStart, so that option last_kernel_us times the path-tracing launch alone */
+        /* the live list of the call's first frame (pt_kernels.hip live_list_*): scratch, the count in 16 bytes of its own, then W x H entries at most --
+         * the count directly before the list, where the list-driven frame-group kernels look for it (pt_scene.h TB_LIVE_COUNT_WORDS; the
+         * one-pixel-per-lane kernel takes it by its own pointer).  Between ev0 and evKernelStart, so that option last_kernel_us times the path-tracing
+         * launch alone */
         const uint32_t regions = tb_persistent_grid(W, H, c->tiles);
         const size_t scratch = (tb_live_list_scratch_bytes(regions) + 15u) / 16u * 16u;
-        ensure(c->liveList, 16u + scratch + (size_t)W * H * 4u);
+        ensure(c->liveList, scratch + 4u * TB_LIVE_COUNT_WORDS + (size_t)W * H * 4u);
         uint8_t* base = (uint8_t*)c->liveList.p;
-        tg.liveCount = (const uint32_t*)base; tg.liveList = (const uint32_t*)(base + 16u + scratch); tg.adaptiveMinFrames = (uint32_t)adaptiveMin;
+        c->liveCountOffset = scratch;
+        /* (tested per call, the one-pixel-per-lane kernel's guard `frame > adaptiveMinFrames` before each later frame must never hold) */
+        tg.liveCount = (const uint32_t*)(base + scratch); tg.liveList = tg.liveCount + TB_LIVE_COUNT_WORDS; tg.adaptiveMinFrames = perCall ? 0xffffffffu : (uint32_t)adaptiveMin;
         HIP_TRY(pt_launch_live_list(c->stream, tg.output, tg.jittered, &c->tiles, W, H, c->samplesRendered, (uint32_t)adaptiveMin, pf.MinConvergence,
-            tg.aovNormals, tg.aovCustom, s.OutputType == TB_OUTPUT_TYPE_LIVE_PIXELS ? 1 : 0, base + 16u, (uint32_t*)tg.liveList, (uint32_t*)base));
+            tg.aovNormals, tg.aovCustom, s.OutputType == TB_OUTPUT_TYPE_LIVE_PIXELS ? 1 : 0, base, (uint32_t*)tg.liveList, (uint32_t*)tg.liveCount));
     }
     if (!groups) HIP_TRY(hipEventRecord(c->evKernelStart, c->stream));
     c->lastKernelFrames = 0;
@@ -535,6 +544,9 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
                 if (c->regionCostKey != key) { HIP_TRY(hipMemsetAsync(c->regionCost.p, 0, 4u << 20, c->stream)); c->regionCostKey = key; c->sideOrdered = false; }
             }
             tg.bandedItems = (uint32_t)opt("banded_items", 0);
+            /* (an adaptive frame-group launch: frameGroup and workCounter take the storage of the one-pixel-per-lane form's threshold and count pointer,
+             * pt_scene.h; the list pointer stays, in regionOrder's place) */
+            const uint32_t* const liveList = adaptive ? tg.liveList : nullptr;
             tg.frameGroup = plan.frame_group; tg.fgGuided = plan.guided_groups;
             uint32_t lgGroup = 0; while ((2u << lgGroup) <= tg.frameGroup) lgGroup++;
             if (overlap && !c->sideOrdered) { /* first overlapped launch after other work on the main stream: order the side streams behind it once */
@@ -638,10 +650,13 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
                     HIP_TRY(hipEventRecord(c->evKernelStart, ptStream)); }
                 /* the launch before may still be draining on the other stream */
                 TbDeviceScene dsPar = dsLaunch; if (dsPar.stackOverflow) dsPar.stackOverflow += par * overflowHalf;
-                HIP_TRY(launch(ptStream, &dsPar, &pf, &tg, W, H, c->samplesRendered + f0, nf, &c->tiles, c->sceneInLds ? 1 : 0, 0, 0));
+                /* (the adaptive launch tested per call: the same copy's kernel over the live list, and the fold over the list) */
+                HIP_TRY(launch(ptStream, &dsPar, &pf, &tg, W, H, c->samplesRendered + f0, nf, &c->tiles, c->sceneInLds ? 1 : 0, 0, adaptive ? PT_LAUNCH_LIVE_GROUPS : 0));
                 if (f0 == 0) { HIP_TRY(hipEventRecord(c->evKernel, ptStream)); c->lastKernelFrames = nf; }
                 if (overlap) { HIP_TRY(hipEventRecord(c->evPt[par], ptStream)); HIP_TRY(hipStreamWaitEvent(c->stream, c->evPt[par], 0)); }
-                HIP_TRY(pt_launch_accumulate_samples(c->stream, tg.samples, W, H, c->samplesRendered + f0, nf, &c->tiles, tg.output, tg.jittered));
+                if (adaptive) HIP_TRY(pt_launch_accumulate_live(c->stream, tg.samples, W, H, c->samplesRendered + f0, nf, liveList, c->lastOwnedPixels, tg.output,
+                    tg.jittered));
+                else HIP_TRY(pt_launch_accumulate_samples(c->stream, tg.samples, W, H, c->samplesRendered + f0, nf, &c->tiles, tg.output, tg.jittered));
                 if (overlap) HIP_TRY(hipEventRecord(c->evFold[par], c->stream));
             }
         }

@@ -23,7 +23,14 @@ inline bool LdsCopyFits(uint32_t waves, uint32_t stackDepth, uint32_t ldsBlobByt
 inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
 {
     p = tb_launch_plan{};
-    if (in.adaptive) {
+    /* The adaptive launch tested once per call (tb_plan_input::adaptive = 2, option "adaptive_test" = 1): the pixels live at
+     * the call's first frame get every frame of the call, so their samples may run in any order -- the frame-group machinery, driven by the live
+     * list, wherever a plain call of this shape would be a frame-group call (decided below, by the plain call's own rules).  Every other shape --
+     * AOV targets, a selected pixel, frame_group < 0, one frame from memory, pipelines 1-4 -- runs the one-pixel-per-lane adaptive kernel of the
+     * branch below with its per-frame test switched off (renderImpl), which is what makes the semantics independent of the kernel that runs. */
+    const bool listGroups = in.adaptive == 2 && !in.count_rays && !in.aov && !in.realtime && !in.selected_pixel && in.pipeline == 0 && in.frame_group >= 0 &&
+        (in.frame_group > 0 || in.frames >= (in.scene_in_lds ? 1u : 2u));
+    if (in.adaptive && !listGroups) {
         /* The adaptive launch (option "adaptive"): converged pixels are left out and the live ones packed 256 to a workgroup.
          * A pixel's samples must run in frame order -- the skip test before each frame reads the sums of the frames before it -- so: the lock-step
          * kernel's one-pixel-per-lane form in the base copy of the feature set (pt_variant.inc pt_launch_adaptive_*), no frame groups, no pre-pass,
@@ -59,6 +66,7 @@ inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
      * +17 % with the scene in LDS, -9 % on the 870 k scene.  Option frame_group > 0 forces it (and the group size), < 0 forbids it. */
     p.groups = pipe == 0 && plain && in.frame_group >= 0 && (in.frame_group > 0 || in.frames >= (in.scene_in_lds ? 1u : 2u));
     if (p.rule_pipeline != TB_PLAN_RULE_SPLIT_NO_ROOM) p.rule_pipeline = p.groups ? TB_PLAN_RULE_FRAME_GROUPS : TB_PLAN_RULE_ONE_PIXEL_PER_LANE;
+    if (listGroups) p.rule_pipeline = TB_PLAN_RULE_ADAPTIVE_GROUPS; /* (p.groups holds: listGroups is the line above with pipe == 0 and plain) */
     /* Which copy of the feature set: the higher-occupancy one when its workgroups fit in LDS.  LDS per workgroup = 1 KB per stack entry
      * (+ the scene image); where the tree is too deep for that, a frame-group launch may still use the copy with a split stack -- as
      * many entries in LDS as fit, the deepest few (option stack_overflow_max) in global memory.  Default 24 since round 4 (16 before): the
@@ -88,7 +96,7 @@ inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
         p.stack_overflow_entries = 0; p.rule_copy = TB_PLAN_RULE_COPY_FULL_FOR_INSTANCES; }
     const bool ext = p.full_variant || (in.variant_features & TB_PLAN_FEAT_EXT) != 0, sss = !p.full_variant && (in.variant_features & TB_PLAN_FEAT_SSS) != 0;
     /* Compact nodes (option node_layout = 1): frame-group kernels of the higher-occupancy copies, scenes fetched from memory */
-    p.compact_nodes = in.node_layout == 1 && in.has_compact_nodes && p.high_occupancy_copy && p.groups && !in.scene_in_lds && !in.two_level;
+    p.compact_nodes = in.node_layout == 1 && in.has_compact_nodes && p.high_occupancy_copy && p.groups && !in.scene_in_lds && !in.two_level && !listGroups;
     /* Primary-visibility pre-pass (option primary_prepass: 0 never, 2 wherever the kernels have it, 1 = the default policy):
      * the kernels that have it -- frame-group launches of the higher-occupancy copies, and of `surf`, whose only copy carries it --
      * on one-level scenes fetched from memory.  Default policy: calls of 2^24 samples or more (a second launch and its tail cost a
@@ -99,7 +107,8 @@ inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
      * calls of a kind both ways and keeps the faster (the pictures are the same bits either way). */
     const bool prepassKernels = ((in.variant_waves_hi && p.high_occupancy_copy) || (!in.variant_waves_hi && in.variant_prepass_in_base && !p.full_variant &&
         !p.stack_overflow_entries))
-                                && p.groups && !in.scene_in_lds && !in.two_level && !ext && in.max_bounces > 0;
+                                && p.groups && !in.scene_in_lds && !in.two_level && !ext && in.max_bounces > 0
+                                && !listGroups; /* the list-driven frame-group kernels take no hit records (follow-ups) */
     p.prepass = TB_PLAN_PREPASS_OFF; p.rule_prepass = TB_PLAN_RULE_PREPASS_NO_KERNEL;
     if (prepassKernels) {
         p.rule_prepass = TB_PLAN_RULE_PREPASS_OPTION_OFF;
@@ -118,7 +127,7 @@ inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
     }
     /* launches of the kernels without the EXT features (no selected pixel, no AOVs: nothing but the sample buffer is written) may
      * overlap the drain of the launch before them */
-    p.overlap_launches = p.groups && !ext && in.overlap_launches != 0;
+    p.overlap_launches = p.groups && !ext && in.overlap_launches != 0 && !listGroups; /* (the list pass reads what the call before has folded) */
     if (!p.groups) return;
     /* batches: the sample buffer holds option pooled_samples entries (16 B each, default 2^28); a slot entry holds 15 bits of relative
      * frame; equal batches (128 frames under a 123-frame budget run as 64 + 64, not 123 + 5) */
@@ -166,6 +175,9 @@ inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
     const uint64_t ownSamples = std::min<uint64_t>((uint64_t)in.width * in.height, regions * 256u) * frames;
     p.costly_first = in.costly_first != 0 && (in.variant_features & TB_PLAN_FEAT_SSS) != 0 && !in.scene_in_lds && (in.costly_first == 2 || ownSamples < (3ull << 24));
     p.guided_groups = 0;
+    /* the list-driven launch: equal groups in list order -- costly_first's order table shares its pointer with the live list (pt_scene.h), and the
+     * copy whose groups shrink has no list-driven form */
+    if (listGroups) { p.costly_first = 0; return; }
     /* (compiled into the frame-group kernels of LDS-resident scenes, whole stack in LDS: the other feature sets' kernels gained 0-2 % from it when measured
      * -- 870 k scene +1.3 %, Teapot +1.8 %, the 4K scenes nothing -- and do not carry the copy) */
     if ((in.guided_groups == 2 || (in.guided_groups == 1 && in.sync_call)) && in.scene_in_lds && !p.stack_overflow_entries) {

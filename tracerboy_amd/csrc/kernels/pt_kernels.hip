@@ -133,6 +133,33 @@ __global__ __launch_bounds__(256) void accumulate_samples_kernel(const TbFloat4*
     }
 }
 
+/* The same fold for the list-driven frame-group launch (TbDeviceTargets::liveList, pt_scene.h): one lane per list entry, the same fp32 sums in the
+ * same order; the pixels that are not on the list have no samples in the buffer and keep their sums.  The count is read here, from the 16 bytes
+ * before the list; the grid is sized by an upper bound. */
+__global__ __launch_bounds__(256) void accumulate_live_kernel(const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
+    const uint32_t* __restrict__ list, TbFloat4* output, TbFloat4* jittered)
+{
+    const uint32_t n = W * H, count = list[-TB_LIVE_COUNT_WORDS];
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < count; i += gridDim.x * 256u) {
+        const uint32_t xy = list[i], pix = (xy >> 16) * W + (xy & 0xffffu);
+        TbFloat4 acc = {0, 0, 0, 0}, jacc = {0, 0, 0, 0};
+        if (firstFrame > 0) { acc = output[pix]; jacc = jittered[pix]; }
+        for (uint32_t f = 0; f < numFrames; f++) {
+            const TbFloat4 s = samples[(size_t)f * n + pix];
+            const uint32_t frame = firstFrame + f;
+            const float o3 = tb_abs(s.w);
+            const bool coinLow = (__float_as_uint(s.w) >> 31) != 0;
+            if (frame == 0) acc = TbFloat4{0, 0, 0, 0};
+            acc = TbFloat4{s.x + acc.x, s.y + acc.y, s.z + acc.z, o3 + acc.w};
+            if (frame == 0 || coinLow) {
+                if (frame == 0) jacc = TbFloat4{0, 0, 0, 0};
+                jacc = TbFloat4{s.x + jacc.x, s.y + jacc.y, s.z + jacc.z, o3 + jacc.w};
+            }
+        }
+        output[pix] = acc; jittered[pix] = jacc;
+    }
+}
+
 } // namespace
 
 /* TbDeviceTargets::regionOrder from TbDeviceTargets::regionCost (pt_scene.h): one workgroup of 1024.  order[0] = items moved to the front, order[1 ...] =
@@ -253,6 +280,14 @@ hipError_t pt_launch_accumulate_samples(hipStream_t stream, const TbFloat4* samp
     return hipGetLastError();
 }
 
+hipError_t pt_launch_accumulate_live(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
+                                     const uint32_t* list, uint64_t maxEntries, TbFloat4* output, TbFloat4* jittered)
+{
+    const uint64_t blocks = (maxEntries + 255u) / 256u;
+    if (blocks) hipLaunchKernelGGL(accumulate_live_kernel, dim3((uint32_t)(blocks < 2048u ? blocks : 2048u)), dim3(256), 0, stream, samples, W, H, firstFrame,
+        numFrames, list, output, jittered);
+    return hipGetLastError();
+}
 
 hipError_t pt_launch_region_order(hipStream_t stream, const uint32_t* cost, const TbTileMap* tiles, uint32_t W, uint32_t H, uint32_t regions,
                                   uint32_t numGroups, uint32_t lateFrom, uint32_t* order, uint32_t* keys)

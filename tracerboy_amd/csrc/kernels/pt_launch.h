@@ -22,6 +22,13 @@ hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const
 hipError_t pt_launch_accumulate_samples(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
     const TbTileMap* tiles,
                                         TbFloat4* output, TbFloat4* jittered);
+/* The list-driven frame-group launch (pt_scene.h TB_LIVE_COUNT_WORDS): the last argument of pt_launch_persistent_* in place of a pipeline number --
+ * the frame-group kernels over the live list (tg->samples and tg->liveList set, the count in the 16 bytes before the list) -- and the fold over the
+ * same list: accumulate_samples_kernel's sums for the listed pixels only (the other pixels' samples were never written).  maxEntries: an upper
+ * bound of the count, the owned pixels; the count itself stays on the device. */
+#define PT_LAUNCH_LIVE_GROUPS (-2)
+hipError_t pt_launch_accumulate_live(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
+                                     const uint32_t* list, uint64_t maxEntries, TbFloat4* output, TbFloat4* jittered);
 hipError_t pt_launch_device_math(hipStream_t stream, int fn, uint32_t n, const float* a, const float* b, float* out);
 hipError_t pt_launch_unpack_gathered(hipStream_t stream, const TbFloat4* gathered, size_t capacity, TbFloat4* full, uint32_t W, uint32_t H, uint32_t world,
     uint32_t tileW, uint32_t tileH);

@@ -153,6 +153,10 @@ __global__ __launch_bounds__(BLOCK) PT_FIRST_ATTR void pt_first(TbDeviceScene ds
  * branch: same box, 7 140 / 7 105 against 7 185 Msamples/s) and only launches of calls that wait use it */
 /* ADAPTIVE: the adaptive launch (TbDeviceTargets::liveList, pt_scene.h) -- the one-pixel-per-lane form over the packed live pixels, each lane testing
  * its pixel again before every later frame (DESIGN.md section 10) */
+/* GROUPS + ADAPTIVE: the adaptive launch tested once per call -- the frame-group form over the live list.  A work item is one 256-entry block of
+ * the list x G frames: the "regions" of the binding below are the list's blocks, a slot's entry carries the block's number where it carries a
+ * region's coordinates, and a sample number finds its pixel on the list (resolve()).  Everything else -- claims, slots, the ordered sample buffer --
+ * is the frame-group form's. */
 template <uint32_t F, bool SCENE_LDS, bool COUNT, bool GROUPS, bool HYBRID = false, bool NODEC = false, bool TWOLEVEL = false, bool PRIMARY = false,
           bool FIRST = false, bool GUIDED = false, bool ADAPTIVE = false>
 __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDeviceScene ds, TbPerFrameConstants pf, TbDeviceTargets tg, uint32_t W, uint32_t H,
@@ -160,7 +164,8 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
 {
     /* the adaptive launch: the grid is the owned region count, an upper bound; a workgroup whose first entry is past the live count has no pixel */
     uint32_t liveCount = 0;
-    if constexpr (ADAPTIVE) { liveCount = *tg.liveCount; if (blockIdx.x * BLOCK >= liveCount) return; }
+    if constexpr (ADAPTIVE && !GROUPS) { liveCount = *tg.liveCount; if (blockIdx.x * BLOCK >= liveCount) return; }
+    if constexpr (ADAPTIVE && GROUPS) { if (tg.liveList[-TB_LIVE_COUNT_WORDS] == 0u) return; } /* nothing is live: the whole grid leaves at once */
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     /* what the walks of this kernel carry besides the hit: per-ray box / triangle counters for the counting launch and for the full feature
      * set's heatmap (RayGenCommon.h:537-543), the IsValidHit filter in the full feature set only; the wave-occupancy profile rides on COUNT */
@@ -200,13 +205,20 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
         atomicAdd(&tlStat[0], (uint32_t)(wall_clock64() - t0)); atomicAdd(&tlStat[3], 1u); };
 #else
     const uint32_t logCapUse = tg.slotLogCap;
-    auto bind_next = [&]() { fg_bind_next(groupConst, bindState, slotTable, tg.workCounter, tg.slotLog + (size_t)blockIdx.x * tg.slotLogCap, logCapUse,
+    auto bind_next = [&]() {
+        /* (the list form: block b of the list goes through block_region as region (b & 1023, b >> 10) of a frame 1024 regions wide, so the entry's 20
+         * region bits are b itself; no order table -- its pointer is the list's) */
+        if constexpr (ADAPTIVE) fg_bind_next(groupConst, bindState, slotTable, tg.workCounter, tg.slotLog + (size_t)blockIdx.x * tg.slotLogCap, logCapUse,
+            tg.bandedItems, TbTileMap{0u, 1u, 16u, 16u}, 16384u, 16384u, nullptr);
+        else fg_bind_next(groupConst, bindState, slotTable, tg.workCounter, tg.slotLog + (size_t)blockIdx.x * tg.slotLogCap, logCapUse,
         tg.bandedItems, tiles, W, H, (F & FEAT_SSS) ? tg.regionOrder : nullptr); };
 #endif
     if (threadIdx.x == 0) {
         drawn = BLOCK; for (int i = 0; i < 8; i++) slotTable[i] = 0;
         if (GROUPS) {
-            const uint32_t regions = tb_persistent_grid(W, H, tiles), lg = 31u - (uint32_t)__clz((int)tg.frameGroup);
+            /* (the list form: the 256-entry blocks of the live list in place of the regions) */
+            const uint32_t regions = ADAPTIVE ? (tg.liveList[-TB_LIVE_COUNT_WORDS] + 255u) >> 8 : tb_persistent_grid(W, H, tiles),
+                lg = 31u - (uint32_t)__clz((int)tg.frameGroup);
             groupConst[3] = 0; groupConst[4] = (tg.launchEpoch & 0xffu) << 16; bindState[0] = 0; bindState[1] = 0;
             /* frame groups per region (< 4096: group << 20 | region) */
             groupConst[0] = regions; groupConst[1] = lg; groupConst[2] = tb_fg_groups(numFrames, lg, GUIDED ? 1u : 0u, 0xffffffffu, nullptr, nullptr);
@@ -231,7 +243,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
     /* the lane's pixel, x | y << 16: one pixel for the whole launch, or in frame-group mode the pixel of the sample in flight */
     uint32_t xy = (bx * 16u + (wave & 1u) * 8u + (lane & 7u)) | (by * 16u + (wave >> 1) * 8u + (lane >> 3)) << 16;
     /* (the adaptive launch: entry 256 b + t of the live list; a lane past the count has no pixel -- 0xffff is beyond any frame) */
-    if constexpr (ADAPTIVE) { const uint32_t i = blockIdx.x * BLOCK + threadIdx.x; xy = i < liveCount ? tg.liveList[i] : 0xffffffffu; }
+    if constexpr (ADAPTIVE && !GROUPS) { const uint32_t i = blockIdx.x * BLOCK + threadIdx.x; xy = i < liveCount ? tg.liveList[i] : 0xffffffffu; }
 #define PX (xy & 0xffffu)
 #define PY (xy >> 16)
 #define PIX ((size_t)PY * W + PX)
@@ -291,6 +303,14 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
         }
         if ((K & 255u) == 0u && f == (1u << lgS) - 1u) bind_next(); /* the first sample of the slot's last frame: one more slot is bound */
         const uint32_t fr = firstFrame + ((uint32_t)(e >> 24) & 0x7fffu) + f;
+        if constexpr (ADAPTIVE) {
+            /* the list form: entry 256 x block + (K & 255) -- the list is in region / wave / lane order and K & 255 is the dense kernel's (wave, lane)
+             * numbering, so a wholly live region's block is the slot above; an entry past the count is no sample, like a pixel outside the frame */
+            const uint32_t i = ((uint32_t)e & 0xfffffu) << 8 | (K & 255u);
+            if (fr >= endFrame || i >= tg.liveList[-TB_LIVE_COUNT_WORDS]) return 3;
+            frame = fr; xy = tg.liveList[i];
+            return 1;
+        }
         const uint32_t x = ((uint32_t)e & 0x3ffu) * 16u + ((K >> 6) & 1u) * 8u + (K & 7u),
             y = (((uint32_t)e >> 10) & 0x3ffu) * 16u + ((K >> 7) & 1u) * 8u + ((K >> 3) & 7u);
         if (fr >= endFrame || x >= W || y >= H) return 3;
@@ -361,7 +381,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             float coin = rnd(p.seed, pf.Time);
             const size_t pix = PIX;
             TbFloat4 before{0, 0, 0, 0}; /* the adaptive launch: the sums before this sample (its LIVE_PIXELS AOV) */
-            if constexpr (ADAPTIVE && (F & FEAT_EXT) != 0) before = acc;
+            if constexpr (ADAPTIVE && !GROUPS && (F & FEAT_EXT) != 0) before = acc;
             if (GROUPS) tg.samples[(size_t)(frame - firstFrame) * W * H + pix] = TbFloat4{o0, o1, o2, coin < 0.5f ? -o3 : o3};
             else {
                 if (((F & FEAT_EXT) && pf.IsRealTime) || frame == 0) acc = TbFloat4{0, 0, 0, 0};
@@ -377,7 +397,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             if (tg.aovWorldPos1 && (frame % 2) == 1) tg.aovWorldPos1[pix] = TbFloat4{p.aovWorldPos.x, p.aovWorldPos.y, p.aovWorldPos.z, p.aovNeighbor};
             /* (the adaptive launch in LIVE_PIXELS mode: a sample that stored no primary albedo -- a camera ray that missed -- leaves the reference's
              * OutputLivePixels(false) tint of the sums before it, RayGenCommon.h:545-551) */
-            if (ADAPTIVE && tg.aovCustom && pf.OutputMode == TB_OUTPUT_TYPE_LIVE_PIXELS && !(p.flags & F_AOV_ALBEDO))
+            if (ADAPTIVE && !GROUPS && tg.aovCustom && pf.OutputMode == TB_OUTPUT_TYPE_LIVE_PIXELS && !(p.flags & F_AOV_ALBEDO))
                 tg.aovCustom[pix] = TbFloat4{before.x / before.w, 0.2f * (before.y / before.w), 0.2f * (before.z / before.w), before.w / before.w};
             else if (tg.aovCustom) tg.aovCustom[pix] = (p.flags & F_HEATMAP) ? TbFloat4{(float)p.lastTris, (float)p.lastBoxes, 0, 0} : TbFloat4{p.aovAlbedo.x,
                 p.aovAlbedo.y, p.aovAlbedo.z, 1.0f};
@@ -387,7 +407,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             if (COUNT) { cSamples++; cMats += p.nMat; cLights += p.nLight; }
             if (GROUPS) { const int r = next_sample(0, false); if (r == 2) { alive = false; break; } if (r == 0) { p.state = ST_WAIT; continue; } }
             else { frame++; if (frame >= endFrame) { alive = false; break; } }
-            if constexpr (ADAPTIVE) {
+            if constexpr (ADAPTIVE && !GROUPS) { /* (the list-driven frame-group form tests once per call: the list pass has) */
                 /* the skip test before every later frame, on the sums in the lane's registers (behind the cheap frame guard: seven divisions and a
                  * square root).  A pixel that skips keeps skipping -- its sums and the threshold no longer change -- so the lane retires: its sums
                  * go back unchanged below, and an AOV call leaves the reference's ClearAOVs + OutputLivePixels(true) of a skipped pixel */

@@ -132,9 +132,14 @@ struct TbDeviceTargets {
      * liveList[256 b + t]; before each later frame whose global index exceeds adaptiveMinFrames it applies the skip test again (tb_adaptive_skip,
      * pt_device.hpp) and retires if it holds.  The three share storage with frame-group members, which that launch does not have: a member
      * appended to this struct would move every kernel argument behind it (W, H, the frames, the tile map, the split-role kernel's parameters). */
+    /* The same launch tested once per call, through the frame-group kernels (pt_persistent GROUPS + ADAPTIVE): `samples`,
+     * frameGroup, workCounter and the slot log as in any frame-group launch, the list in regionOrder's place (such a launch has no order table) and
+     * its count where the kernel finds it from the list pointer: liveList[-TB_LIVE_COUNT_WORDS], the 16 bytes before the first entry.  A work item
+     * is one 256-entry block of the list x frameGroup frames. */
     uint32_t* regionCost;
     union { const uint32_t* regionOrder; const uint32_t* liveList; };
 };
+#define TB_LIVE_COUNT_WORDS 4
 
 /* Split-role kernel (pipeline 4, pt_split.inc): a workgroup is `travWaves` traversal waves followed by `shadeWaves` shading waves.
  * Shading waves own the paths (state in registers), write each pending ray -- origin, direction and the five quotients of

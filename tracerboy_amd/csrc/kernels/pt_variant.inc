@@ -58,6 +58,31 @@ extern "C" hipError_t PT_CAT(pt_launch_persistent_, PT_NAME)(hipStream_t stream,
 #else
 #define PT_PICK(L, C) do { if (pipeline != 0) return hipErrorInvalidValue; PT_LAUNCH(pt_persistent<PT_FEATURES, L, C, false>); } while (0)
 #endif
+    /* The list-driven frame-group launch (pt_launch.h PT_LAUNCH_LIVE_GROUPS in place of a pipeline number; TbDeviceTargets::liveList): this copy's
+     * frame-group kernel over the live list -- whole or split stack, scene in LDS or from memory, one or two levels; no counters, no hit records,
+     * layout B, equal groups.  The grid, the slot logs and the stash are the frame-group launch's, with the owned regions as the upper bound of
+     * the list's blocks (PT_LAUNCH). */
+    if (pipeline == PT_LAUNCH_LIVE_GROUPS) {
+        if (!tg->samples || !tg->liveList || countRays || tg->primaryHits || ds->nodesC || tg->fgGuided) return hipErrorInvalidValue;
+#define PT_LIVE(L, HY, TL) PT_LAUNCH(pt_persistent<PT_FEATURES, L, false, true, HY, false, TL, false, false, false, true>)
+#ifdef PT_ONLY_LDS_GROUPS
+        if (!sceneInLds || ds->numInstances || ds->stackOverflow) return hipErrorInvalidValue;
+        PT_LIVE(true, false, false);
+#elif defined(PT_ONLY_PERSISTENT)
+        if (ds->stackOverflow && ds->stackOverflowLanes < 2u * 8u * (uint32_t)numCUs * BLOCK) return hipErrorInvalidValue;
+        if (ds->numInstances) { if (sceneInLds) return hipErrorInvalidValue; if (ds->stackOverflow) PT_LIVE(false, true, true); else PT_LIVE(false, false, true); }
+        else if (ds->stackOverflow) { if (sceneInLds) PT_LIVE(true, true, false); else PT_LIVE(false, true, false); }
+        else if (sceneInLds) PT_LIVE(true, false, false); else PT_LIVE(false, false, false);
+#else
+        if (ds->stackOverflow) return hipErrorInvalidValue; /* a base copy: whole stack in LDS */
+#if !(PT_FEATURES & PT_FEAT_EXT)
+        if (ds->numInstances) return hipErrorInvalidValue; /* of the base copies only the full feature set walks two levels */
+#endif
+        if (sceneInLds) PT_LIVE(true, false, false); else PT_LIVE(false, false, false);
+#endif
+#undef PT_LIVE
+        return hipGetLastError();
+    }
     if (tg->samples && (countRays || pipeline != 0)) return hipErrorInvalidValue; /* frame groups: pt_persistent without counters only */
 #ifdef PT_ONLY_LDS_GROUPS
     /* a copy for scenes in LDS (pt_variant_matte6.hip): the frame-group kernels with the whole stack in LDS, nothing else */
