@@ -168,8 +168,9 @@ int tb_load_scene(tb_context* c, const char* path)
     return guarded(c, [&]() {
         if (!path) return fail(c, TB_E_INVALID, "tb_load_scene: null path");
         std::shared_ptr<PbrtScene> ps = importScene(path);
-        ConvertOptions co; auto it = c->options.find("flatten_instances"); if (it != c->options.end()) co.flattenInstances = it->second != 0;
-        it = c->options.find("flip_texture_uvs"); if (it != c->options.end()) co.flipTextureUVs = it->second != 0;
+        ConvertOptions co; /* whose defaults hold for an option nobody set */
+        if (const int64_t* v = c->options.ifSet<OPT_flatten_instances>()) co.flattenInstances = *v != 0;
+        if (const int64_t* v = c->options.ifSet<OPT_flip_texture_uvs>()) co.flipTextureUVs = *v != 0;
         c->hasScene = false;
         ConvertScene(*ps, c->scene, co);
         finalizeScene(c);
@@ -242,7 +243,7 @@ int tb_set_material(tb_context* c, int id, const TbMaterial* in)
 static int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* s, float t)
 {
     const uint32_t world = 1u + (uint32_t)c->peers.size();
-    if (c->options.count("aov") && c->options["aov"]) return fail(c, TB_E_UNSUPPORTED, "tb_render: AOV targets are not gathered across the devices of a group");
+    if (opt<OPT_aov>(c)) return fail(c, TB_E_UNSUPPORTED, "tb_render: AOV targets are not gathered across the devices of a group");
     std::vector<tb_context*> all; all.push_back(c); for (tb_context* p : c->peers) all.push_back(p);
     for (uint32_t i = 0; i < world; i++) if (all[i]->tiles.world != world || all[i]->tiles.rank != i) { all[i]->tiles = TbTileMap{i, world, 64, 64};
         all[i]->samplesRendered = 0; }
@@ -364,8 +365,8 @@ int tb_render_realtime(tb_context* c, uint32_t W, uint32_t H, const tb_output_se
         tb_output_settings s; if (settings) s = *settings; else DefaultOutputSettings(s);
         s.RenderModeRealTime = 1;
         tb_denoiser_settings dn; if (denoiser) dn = *denoiser; else tb_default_denoiser_settings(&dn);
-        const auto savedAov = c->options.find("aov") != c->options.end() ? c->options["aov"] : 0;
-        c->options["aov"] = 1;
+        const int64_t savedAov = c->options.value[OPT_aov]; const bool savedSet = c->options.isSet[OPT_aov];
+        c->options.value[OPT_aov] = 1; c->options.isSet[OPT_aov] = true;
         const size_t bytes = (size_t)W * H * sizeof(TbFloat4);
         if (c->rtWidth != W || c->rtHeight != H) {
             for (DevBuf* b : {&c->rtIndirect[0], &c->rtIndirect[1], &c->rtMoment[0], &c->rtMoment[1], &c->rtFinal[0], &c->rtFinal[1], &c->rtDenoise[0],
@@ -375,7 +376,7 @@ int tb_render_realtime(tb_context* c, uint32_t W, uint32_t H, const tb_output_se
             c->rtWidth = W; c->rtHeight = H; c->rtActive = 0; c->prevCamera = c->camera;
         }
         int rc = renderImpl(c, W, H, 1, &s, timeSeed, false);
-        c->options["aov"] = savedAov;
+        c->options.value[OPT_aov] = savedAov; c->options.isSet[OPT_aov] = savedSet;
         if (rc != TB_OK) return rc;
         const uint32_t cur = c->rtActive, prev = cur ^ 1u;
         /* AOVWorldPosition0SRV + GetPathTracerOutputIndex(), TracerBoy.cpp:3614-3622 */
@@ -542,8 +543,10 @@ void tb_plan_defaults(tb_plan_input* in)
 {
     if (!in) return;
     memset(in, 0, sizeof *in);
-    in->high_occupancy = 1; in->stack_overflow_max = 24; in->primary_prepass = 1; in->overlap_launches = 1; in->pooled_samples = 256ll << 20; in->costly_first = 1;
-    in->split_trav = 4; in->guided_groups = 1;
+    in->high_occupancy = OptionDefault(OPT_high_occupancy); in->stack_overflow_max = OptionDefault(OPT_stack_overflow_max);
+    in->primary_prepass = OptionDefault(OPT_primary_prepass); in->overlap_launches = OptionDefault(OPT_overlap_launches);
+    in->pooled_samples = OptionDefault(OPT_pooled_samples); in->costly_first = (uint32_t)OptionDefault(OPT_costly_first);
+    in->split_trav = OptionDefault(OPT_split_trav); in->guided_groups = OptionDefault(OPT_guided_groups);
 }
 int tb_variant_stash_entries(const char* name)
 {
@@ -663,22 +666,18 @@ int tb_unpack_gathered_host(uint32_t W, uint32_t H, uint32_t world, uint32_t tw,
 int tb_set_option(tb_context* c, const char* name, int64_t v)
 {
     if (!c || !name) return TB_E_INVALID;
-    static const char* known[] = {"costly_first", "costly_late_samples", "reinsertion_share", "reinsertion_passes", "presplit", "guided_groups", "compact_stamp_bits", "debug_profile_groups", "camera_constants", "texture_use_hint", "compact_hits", "first_bounce", "primary_prepass", "pipeline", "count_rays", "bvh_builder", "flatten_instances", "aov", "scene_in_lds", "lds_scene_budget",
-        "force_full_variant", "wavefront_paths", "wavefront_grid", "wavefront_segment", "pooled_paths", "pooled_samples", "pooled_profile", "park_min",
-        "alpha_test", "node_order", "node_order_top_levels", "frame_group", "overlap_launches", "high_occupancy", "stack_lds_cap", "stack_overflow_max",
-        "flip_texture_uvs", "wavefront_sort", "banded_items", "node_layout", "wavefront_refill",
-                                  "split_trav", "split_shade", "split_ready", "split_refill", "split_wi", "split_wl", "split_frame_group", "split_stack_cap",
-                                      "split_spin_limit", "split_profile", "split_trav_last", "split_shade_prio", "adaptive", "adaptive_min_frames", "adaptive_test"};
-    /* the adaptive launch has no counting copy; its frame threshold is a frame index */
-    auto on = [&](const char* k) { auto it = c->options.find(k); return it != c->options.end() && it->second != 0; };
-    if (!strcmp(name, "adaptive_min_frames") && v < 0) return fail(c, TB_E_INVALID, "tb_set_option: adaptive_min_frames must not be negative");
-    /* 0: the skip test runs before every frame (the reference's); 1: once per call, at its first frame */
-    if (!strcmp(name, "adaptive_test") && v != 0 && v != 1) return fail(c, TB_E_INVALID, "tb_set_option: adaptive_test is 0 (before every frame) or 1 (once per call)");
-    if ((!strcmp(name, "adaptive") && v && on("count_rays")) || (!strcmp(name, "count_rays") && v && on("adaptive")))
+    const int k = FindOption(name);
+    if (k < 0) return fail(c, TB_E_INVALID, std::string("unknown option '") + name + "'");
+    if ((kOptions[k].flags & OPT_NOT_NEGATIVE) && v < 0) return fail(c, TB_E_INVALID, std::string("tb_set_option: ") + name + " must not be negative");
+    /* adaptive_test 0: the skip test runs before every frame (the reference's); 1: once per call, at its first frame */
+    if ((kOptions[k].flags & OPT_ZERO_OR_ONE) && v != 0 && v != 1) return fail(c, TB_E_INVALID, std::string("tb_set_option: ") + name +
+        " is 0 (before every frame) or 1 (once per call)");
+    /* the adaptive launch has no counting copy */
+    if (v && ((k == OPT_adaptive && opt<OPT_count_rays>(c)) || (k == OPT_count_rays && opt<OPT_adaptive>(c))))
         return fail(c, TB_E_INVALID, "tb_set_option: options \"adaptive\" and \"count_rays\" exclude each other (the counting kernels have no adaptive copy)");
-    for (const char* k : known) if (!strcmp(k, name)) { c->options[name] = v; if (!strcmp(name, "count_rays") || !strcmp(name, "aov")) c->samplesRendered = 0;
-        return TB_OK; }
-    return fail(c, TB_E_INVALID, std::string("unknown option '") + name + "'");
+    c->options.value[k] = v; c->options.isSet[k] = true;
+    if (kOptions[k].flags & OPT_RESETS_HISTORY) c->samplesRendered = 0;
+    return TB_OK;
 }
 int64_t tb_get_option(tb_context* c, const char* name)
 {
@@ -720,7 +719,7 @@ int64_t tb_get_option(tb_context* c, const char* name)
     /* the adaptive launch: did the last call run it; the owned pixels that were live at its first frame (all owned pixels of a call that did not run
      * it) -- a device word: reading it waits for the call.  A group's owner counts its peers' too. */
     if (!strcmp(name, "last_adaptive")) return c->lastAdaptive ? 1 : 0;
-    if (!strcmp(name, "adaptive_min_frames")) { auto it = c->options.find(name); return it == c->options.end() ? 1024 : it->second; } /* the reference's */
+    if (!strcmp(name, "adaptive_min_frames")) return opt<OPT_adaptive_min_frames>(c);
     if (!strcmp(name, "last_live_pixels")) {
         int64_t sum = 0;
         std::vector<tb_context*> all(1, c); for (tb_context* p : c->peers) all.push_back(p);
@@ -734,7 +733,8 @@ int64_t tb_get_option(tb_context* c, const char* name)
     }
     /* 0 matte 1 env 2 surf 3 vol 4 full 5 sss */
     if (!strcmp(name, "last_variant")) { for (int i = 0; i < kNumVariants; i++) if (c->lastVariant == kVariants[i].name) return kVariants[i].id; return -1; }
-    auto it = c->options.find(name); return it == c->options.end() ? 0 : it->second;
+    /* an option: what it was set to, and 0 -- not its default -- if nobody set it (callers rely on it; reporting the default is a change of its own) */
+    const int k = FindOption(name); return k >= 0 && c->options.isSet[k] ? c->options.value[k] : 0;
 }
 
 static void fillView(const HostScene& s, TbSceneView* v);
@@ -770,9 +770,9 @@ int tb_trace_closest(tb_context* c, uint32_t n, const float* origins, const floa
         in(dO, origins, (size_t)n * 12); in(dD, dirs, (size_t)n * 12);
         ensure(dT.b, (size_t)n * 4); ensure(dM.b, (size_t)n * 4); ensure(dB.b, (size_t)n * 8); ensure(dP.b, (size_t)n * 4); ensure(dG.b, (size_t)n * 4);
         ensure(dN.b, (size_t)n * 12); ensure(dU.b, (size_t)n * 8); ensure(dBx.b, (size_t)n * 4); ensure(dTr.b, (size_t)n * 4);
-        { auto it = c->options.find("node_layout"); if (it != c->options.end() && it->second == 1) ensureCompactNodes(c); }
+        if (opt<OPT_node_layout>(c) == 1) ensureCompactNodes(c);
         TbDeviceScene dsTrace = c->ds; /* option "node_layout" = 1: the batch walks the compact nodes too (one-level scenes) */
-        { auto it = c->options.find("node_layout"); if (it == c->options.end() || it->second != 1 || dsTrace.numInstances) dsTrace.nodesC = nullptr; }
+        if (opt<OPT_node_layout>(c) != 1 || dsTrace.numInstances) dsTrace.nodesC = nullptr;
         HIP_TRY(pt_launch_trace_closest(c->stream, &dsTrace, n, (const float*)dO.b.p, (const float*)dD.b.p, (float*)dT.b.p, (int*)dM.b.p, (float*)dB.b.p,
             (uint32_t*)dP.b.p,
                                         (uint32_t*)dG.b.p, (float*)dN.b.p, (float*)dU.b.p, (uint32_t*)dBx.b.p, (uint32_t*)dTr.b.p));

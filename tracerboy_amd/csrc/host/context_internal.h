@@ -2,13 +2,16 @@
  * sets, struct tb_context (the role of `class TracerBoy`, /root/reference/TracerBoy/TracerBoy.h:158-398) and a few helpers.
  *   context.cpp         the C ABI (include/tracerboy_hip.h): create / destroy, scene loads, options, read-backs, output stage, real-time chain, groups
  *   context_scene.cpp   finalizeScene: BVH builds on the GPU, node orders, layout C, uploads, the LDS scene image
- *   context_render.cpp  renderImpl and the pipelines it dispatches to (the launch PLAN is launch_plan.h's)
+ *   context_render.cpp  renderImpl, a sequence of named steps, and the pipelines it dispatches to
+ *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
 #pragma once
 #include "host_scene.h"
 #include "../kernels/pt_launch.h"
 #include "../kernels/pt_device_features.h"
 #include "launch_plan.h"
+#include "launch_trials.h"
+#include "options.h"
 
 #include <hip/hip_runtime.h>
 
@@ -17,81 +20,41 @@
 #include <cstring>
 #include <limits>
 #include <cmath>
-#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 using namespace tbhost;
 
+/* the kernel launchers of the feature sets (pt_variant.inc, pt_split.inc, wf_*.hip): one prototype per kind */
+#define TB_LOCKSTEP_ARGS hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t, uint32_t, \
+    const TbTileMap*, int, int, int
+#define TB_SPLIT_ARGS hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t, uint32_t, \
+    uint32_t, uint32_t, const TbTileMap*, int, int*
+#define TB_LOCKSTEP(name) hipError_t name(TB_LOCKSTEP_ARGS);
+#define TB_SPLIT(name) hipError_t name(TB_SPLIT_ARGS);
 extern "C" {
-typedef hipError_t (*pt_variant_fn)(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t,
-                                    const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_matte(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_env(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_surf(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_matte5(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_matte6(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_env5(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_sss(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_sss4(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_vol4(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_vol(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_persistent_full(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
+typedef hipError_t (*pt_variant_fn)(TB_LOCKSTEP_ARGS);
+TB_LOCKSTEP(pt_launch_persistent_matte) TB_LOCKSTEP(pt_launch_persistent_env) TB_LOCKSTEP(pt_launch_persistent_surf) TB_LOCKSTEP(pt_launch_persistent_sss)
+TB_LOCKSTEP(pt_launch_persistent_vol) TB_LOCKSTEP(pt_launch_persistent_full)
+/* the copies held to an occupancy (fnHi, fnLds below) */
+TB_LOCKSTEP(pt_launch_persistent_matte5) TB_LOCKSTEP(pt_launch_persistent_matte6) TB_LOCKSTEP(pt_launch_persistent_env5) TB_LOCKSTEP(pt_launch_persistent_sss4)
+TB_LOCKSTEP(pt_launch_persistent_vol4)
 /* the adaptive launch of the six base copies (pt_variant.inc; option "adaptive") */
-hipError_t pt_launch_adaptive_matte(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_adaptive_env(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_adaptive_surf(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_adaptive_sss(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_adaptive_vol(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
-hipError_t pt_launch_adaptive_full(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t,
-    uint32_t, const TbTileMap*, int, int, int);
+TB_LOCKSTEP(pt_launch_adaptive_matte) TB_LOCKSTEP(pt_launch_adaptive_env) TB_LOCKSTEP(pt_launch_adaptive_surf) TB_LOCKSTEP(pt_launch_adaptive_sss)
+TB_LOCKSTEP(pt_launch_adaptive_vol) TB_LOCKSTEP(pt_launch_adaptive_full)
 /* pipeline 4, the split-role kernel (pt_split.inc): shading waves + traversal waves over an LDS ray queue */
-typedef hipError_t (*pt_split_fn)(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t,
-    uint32_t, uint32_t, uint32_t,
-                                  const TbTileMap*, int, int*);
-hipError_t pt_launch_split_matte(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t,
-    uint32_t, uint32_t, uint32_t, const TbTileMap*, int, int*);
-hipError_t pt_launch_split_env(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t, uint32_t,
-    uint32_t, uint32_t, const TbTileMap*, int, int*);
-hipError_t pt_launch_split_surf(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t,
-    uint32_t, uint32_t, uint32_t, const TbTileMap*, int, int*);
-hipError_t pt_launch_split_sss(hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t, uint32_t,
-    uint32_t, uint32_t, const TbTileMap*, int, int*);
+typedef hipError_t (*pt_split_fn)(TB_SPLIT_ARGS);
+TB_SPLIT(pt_launch_split_matte) TB_SPLIT(pt_launch_split_env) TB_SPLIT(pt_launch_split_surf) TB_SPLIT(pt_launch_split_sss)
 }
 
 #include "../kernels/wf_types.h"
+#define TB_WAVEFRONT_ARGS hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*, const WfQueue*, \
+    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t
+#define TB_WAVEFRONT(name) hipError_t name(TB_WAVEFRONT_ARGS);
 extern "C" {
-typedef hipError_t (*wf_variant_fn)(hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*,
-    const WfQueue*,
-                                    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t);
-hipError_t wf_launch_matte(hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*, const WfQueue*,
-    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t);
-hipError_t wf_launch_env(hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*, const WfQueue*,
-    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t);
-hipError_t wf_launch_surf(hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*, const WfQueue*,
-    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t);
-hipError_t wf_launch_sss(hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*, const WfQueue*,
-    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t);
-hipError_t wf_launch_vol(hipStream_t, int, const TbDeviceScene*, const TbPerFrameConstants*, const WfParams*, const WfQueue*, const WfQueue*, const WfQueue*,
-    const WfHits*, int, TbFloat4*, TbFloat4*, uint32_t);
+typedef hipError_t (*wf_variant_fn)(TB_WAVEFRONT_ARGS);
+TB_WAVEFRONT(wf_launch_matte) TB_WAVEFRONT(wf_launch_env) TB_WAVEFRONT(wf_launch_surf) TB_WAVEFRONT(wf_launch_sss) TB_WAVEFRONT(wf_launch_vol)
 }
 
 namespace tbctx {
@@ -189,21 +152,14 @@ struct tb_context {
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
     TbTileMap tiles{0, 1, 64, 64};
-    std::map<std::string, int64_t> options;
+    Options options; /* options.h; read with opt<OPT_name>(c) */
     float lastMs = 0.0f;
     std::string lastVariant;
     uint32_t lastCopyWaves = 0; /* waves per SIMD of the copy the last lock-step launch ran (option last_copy_waves; 0 = the base copy) */
     int lastNodeLayout = 0; /* 1: the last render walked the compact layout-C nodes */
     int lastSlotLogCap = 0;
     /* renderImpl */
-    struct PrepassTrial { uint64_t key = 0; int calls = 0, pending = 0, nWith = 0, nWithout = 0; float msWith = 0, msWithout = 0; bool keep = false;
-        uint64_t stamp = 0; } prepassTrial;
-    /* Do back-to-back calls gain from running on the two side streams at once?  Found by measurement where it is in doubt (renderImpl):
-     * the end of every render is marked by an event of a ring; the interval between two consecutive ends, when the later call was enqueued
-     * before the earlier one had finished (the device was never idle between them), is what a call costs in that mode. */
-    struct OverlapTrial { uint64_t key = 0; int phase = 0 /* 0 measuring overlapped, 1 measuring one at a time, 2 decided */; int n[2] = {0, 0};
-        float best[2] = {0, 0}; bool keep = true; } overlapTrial;
-    struct CallRec { uint64_t key = 0; int mode = -1; bool deviceBound = false, settled = false, used = true; } callRec[8];
+    PrepassTrial prepassTrial; OverlapTrial overlapTrial; CallRec callRec[8]; /* launch_trials.h */
     hipEvent_t evCallEnd[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; uint64_t callCount = 0; int lastOverlap = 0;
     tb_launch_plan lastPlan{}; /* what PlanLaunch decided for the last render (options last_plan_rule_*) */
     uint64_t kernelEventStamp = 0; /* counts the renders that have recorded evKernelStart / evKernel: a trial's sample belongs to the render it was asked of */
@@ -234,6 +190,7 @@ namespace tbctx {
     } while (0)
 
 int fail(tb_context* c, int code, const std::string& msg);
+template <Opt K> inline int64_t opt(const tb_context* c) { return c->options.get<K>(); }
 
 /* Every entry point runs on its context's device and hands the calling thread back the device it came with: a host that shares the
  * thread (torch in bench.py, an application's own hipMalloc) would otherwise go on allocating and launching on the last peer of a

@@ -248,8 +248,8 @@ void BuildTlasGpu(tb_context* c, HostScene& s, const std::vector<float>& blasBox
 /* TbDeviceScene::textureUse of the scene as it stands (finalizeScene, tb_set_material) */
 uint32_t sceneTextureUse(const tb_context* c)
 {
-    auto it = c->options.find("texture_use_hint");
-    if (it != c->options.end() && it->second == 0) return 3u; /* 0: fetch whole vertices whatever the materials say */
+    const int64_t* hint = c->options.ifSet<OPT_texture_use_hint>();
+    if (hint && *hint == 0) return 3u; /* 0: fetch whole vertices whatever the materials say */
     uint32_t use = 0;
     for (const TbMaterial& m : c->scene.materials) {
         if (m.albedoIndex != TB_INVALID_TEXTURE || m.emissiveIndex != TB_INVALID_TEXTURE || m.specularMapIndex != TB_INVALID_TEXTURE ||
@@ -276,11 +276,10 @@ void finalizeScene(tb_context* c, bool build)
         auto bitsFor = [](uint64_t maxValue) { uint32_t b = 1; while (b < 32 && (maxValue >> b)) b++; return b; };
         c->hitPrimBits = bitsFor(maxPrim); c->hitGeomBits = bitsFor(s.hitGroups.empty() ? 0 : s.hitGroups.size() - 1);
     }
-    auto opt = [&](const char* k, int64_t d) { auto it = c->options.find(k); return it == c->options.end() ? d : it->second; };
-    const int64_t builder = opt("bvh_builder", 0);
+    const int64_t builder = opt<OPT_bvh_builder>(c);
     const bool twoLevel = !s.instances.empty();
-    s.reinsertionPasses = (int)opt("reinsertion_passes", -1); s.reinsertionShare = (int)opt("reinsertion_share", 100);
-    s.presplitPercent = (int)std::max<int64_t>(0, std::min<int64_t>(400, opt("presplit", 0)));
+    s.reinsertionPasses = (int)opt<OPT_reinsertion_passes>(c); s.reinsertionShare = (int)opt<OPT_reinsertion_share>(c);
+    s.presplitPercent = (int)std::max<int64_t>(0, std::min<int64_t>(400, opt<OPT_presplit>(c)));
     if (build) {
     /* every bottom-level structure and the top level on the GPU (GpuBVH2Builder.cpp:498-501: the same passes, no treelets at the top) */
     if (twoLevel && (builder == 2 || builder == 4))
@@ -291,7 +290,7 @@ void finalizeScene(tb_context* c, bool build)
     else if (builder == 2 || builder == 4) BuildBvhGpu(c, s, builder == 4 ? 3u : 0u);
     else BuildBvh(s, (int)builder);
     /* measured on the 870 k scene: 0 -> 2258, 1 -> 2283, 2 (10 levels) -> 2300 Msamples/s */
-    if (!twoLevel) reorderNodes(s, (int)opt("node_order", 2), (uint32_t)opt("node_order_top_levels", 10));
+    if (!twoLevel) reorderNodes(s, (int)opt<OPT_node_order>(c), (uint32_t)opt<OPT_node_order_top_levels>(c));
     }
     c->camera = s.camera;
     releaseScene(c);
@@ -348,7 +347,7 @@ void finalizeScene(tb_context* c, bool build)
     /* a root-to-leaf path of bvhMaxDepth nodes has bvhMaxDepth - 1 inner nodes, each of which parks at most one far child: the
      * walk never holds more than bvhMaxDepth - 1 entries (one spare) */
     d.stackDepth = s.bvhMaxDepth < 2 ? 2 : s.bvhMaxDepth;
-    d.alphaTest = opt("alpha_test", 0) ? 1u : 0u;
+    d.alphaTest = opt<OPT_alpha_test>(c) ? 1u : 0u;
     d.textureUse = sceneTextureUse(c);
     /* LDS image of the walk: nodes and permuted triangles (pt_scene.h) */
     {
@@ -384,13 +383,14 @@ void finalizeScene(tb_context* c, bool build)
         auto r16 = [](size_t b) { return (b + 15) / 16 * 16; };
         const size_t shadingBytes = r16(devHit.size() * sizeof(TbDevHitGroup)) + r16(s.indexBuffer.size() * 4) + r16(s.vertexBuffer.size() * 4) +
             r16(devMat.size() * sizeof(TbDevMaterial)) + r16(devLight.size() * sizeof(TbDevLight));
-        size_t budget = (size_t)opt("lds_scene_budget", 40 * 1024);
-        c->sceneInLds = blob.size() + shadingBytes + (size_t)d.stackDepth * 256 * 4 <= budget && opt("scene_in_lds", 1) != 0 && !twoLevel;
+        size_t budget = (size_t)opt<OPT_lds_scene_budget>(c);
+        c->sceneInLds = blob.size() + shadingBytes + (size_t)d.stackDepth * 256 * 4 <= budget && opt<OPT_scene_in_lds>(c) != 0 && !twoLevel;
         if (c->sceneInLds) { d.ldsBlob = upload(c, blob); d.ldsBlobBytes = (uint32_t)blob.size(); }
         else { d.ldsBlob = nullptr; d.ldsBlobBytes = 0; }
         /* measured on MI355X: LDS-resident scenes are nearly insensitive (at five waves per SIMD 1-2 is best: 6 745 / 6 730 against
          * 6 680 at 4, 6 230 at 12), scenes fetched through the caches gain ~5 % from a late switch to the leaf phase (16-24) */
-        d.parkMin = (uint32_t)std::max<int64_t>(1, opt("park_min", c->sceneInLds ? 2 : 24));
+        const int64_t* parkMin = c->options.ifSet<OPT_park_min>();
+        d.parkMin = (uint32_t)std::max<int64_t>(1, parkMin ? *parkMin : (c->sceneInLds ? 2 : 24));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->sceneFeatures = sceneFeatureMask(s);

@@ -1,5 +1,5 @@
 /* launch_plan.h -- WHICH kernels a render call launches and how, as a pure function of what is known before anything is enqueued:
- * statistics of the loaded scene, the size of the call, the options.  renderImpl (context.cpp) executes the plan; tests/test_launch_plan.py
+ * statistics of the loaded scene, the size of the call, the options.  renderImpl (context_render.cpp) executes the plan; tests/test_launch_plan.py
  * walks every branch on the CPU through tb_plan_launch (include/tracerboy_hip.h).  The thresholds are measurements; each carries the
  * numbers it came from (DESIGN.md section 6 has the tables). */
 #pragma once
