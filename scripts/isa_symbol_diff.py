@@ -39,6 +39,7 @@ def split(path):
         funcs[m.group(1)] = m.group(2)
     meta = {}
     md = txt[txt.find('amdhsa.kernels:'):] if 'amdhsa.kernels:' in txt else ''
+    md = re.split(r'\n(?=amdhsa\.\w+:)', md)[0]   # the block ends at the next top-level key: whichever entry comes last would otherwise carry the file's trailer
     for blk in re.split(r'\n  - ', md)[1:]:
         n = re.search(r'\.name:\s+(\S+)', blk)
         if n: meta[n.group(1)] = blk

@@ -11,23 +11,34 @@ from test_isa_walk_loops import _listing
 
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-# unit -> the forms the launcher can pick (pt_variant.inc PT_LIVE): (SCENE_LDS, HYBRID, TWOLEVEL)
-ALL_FORMS = [(l, h, t) for l in ("false", "true") for h in ("false", "true") for t in ("false", "true") if not (l == "true" and t == "true")]
-UNITS = {"matte5": ALL_FORMS, "env5": ALL_FORMS, "sss4": ALL_FORMS, "vol4": ALL_FORMS, "matte6": [("true", "false", "false")]}
+from test_launch_forms import LIVE_GROUPS, picker_table
+
+UNITS = ["env5", "matte5", "matte6", "sss4", "vol4"]     # the copies that are not a base copy (pt_copies.h)
+
+
+def list_driven_forms(unit):
+    """the forms the unit's launcher can pick for a list-driven frame-group launch (pt_pick_form through tests/forms/forms_driver.cpp):
+    (SCENE_LDS, HYBRID, TWOLEVEL)"""
+    copies, picks = picker_table()
+    assert sorted(n for n, c in copies.items() if c.role != 0) == UNITS
+    text = ("false", "true")
+    return sorted({(text[k[0][1]], text[k[0][4]], text[k[0][6]]) for (n, s), k in picks.items() if n == unit and k and s.mode == LIVE_GROUPS})
 
 
 def template_args(name):
     return name[name.index("<") + 1:].rstrip(">").split(", ")
 
 
-@pytest.mark.parametrize("unit", sorted(UNITS))
+@pytest.mark.parametrize("unit", UNITS)
 def test_list_driven_kernels_of_the_occupancy_copies(tmp_path, built, unit):
     from isa_spill_map import spill_map
     from tracerboy_amd import build as b
     text = _listing(tmp_path, unit)
     kernels = {tuple(template_args(k["name"])[1:]): k for k in spill_map(text) if "pt_persistent<" in k["name"]}
     lib = open(b.LIB, "rb").read()
-    for lds, hybrid, two in UNITS[unit]:
+    forms = list_driven_forms(unit)
+    assert len(forms) == (1 if unit == "matte6" else 6), forms
+    for lds, hybrid, two in forms:
         # <F, SCENE_LDS, COUNT, GROUPS, HYBRID, NODEC, TWOLEVEL, PRIMARY, FIRST, GUIDED, ADAPTIVE>
         args = (lds, "false", "true", hybrid, "false", two, "false", "false", "false", "true")
         assert args in kernels, (unit, args)

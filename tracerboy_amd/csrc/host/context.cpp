@@ -15,18 +15,24 @@ namespace tbctx {
 std::string g_createError;
 std::atomic<int64_t> g_liveDeviceBytes{0};
 #ifndef __HIP_DEVICE_COMPILE__ /* host data: the file goes through hipcc's device pass too, which has no use for a table of host functions */
+#define TB_COPY(copy) {&kPtCopies[PT_COPY_INDEX_##copy], pt_launch_persistent_##copy},
+#define TB_COPY_INDEX(copy) PT_COPY_INDEX_##copy,
+enum { PT_COPY_LIST(TB_COPY_INDEX) };
+static const Copy kCopies[] = { PT_COPY_LIST(TB_COPY) };
+static constexpr bool sameName(const char* a, const char* b) { for (; *a == *b; a++, b++) if (!*a) return true; return false; }
+static const Copy* copyOf(const char* set, int role) /* the set's copy in that role, if it has one */
+{
+    for (const Copy& k : kCopies) if (k.row->role == role && sameName(k.row->set, set)) return &k;
+    return nullptr;
+}
+#define TB_SET(set) .name = #set, .base = copyOf(#set, PT_ROLE_BASE), .hi = copyOf(#set, PT_ROLE_OCCUPANCY), .lds = copyOf(#set, PT_ROLE_LDS_GROUPS)
 const Variant kVariants[] = {
-    {0u, pt_launch_persistent_matte, "matte", pt_launch_persistent_matte5, TB_MATTE_WAVES, 0, wf_launch_matte, true, pt_launch_split_matte, 0u,
-        pt_launch_persistent_matte6, TB_MATTE_LDS_WAVES, pt_launch_adaptive_matte},
-        {PT_FEAT_ENV, pt_launch_persistent_env, "env", pt_launch_persistent_env5, TB_ENV_WAVES, 1, wf_launch_env, true, pt_launch_split_env, TB_ENV_STASH,
-            nullptr, 0u, pt_launch_adaptive_env},
-    {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES, pt_launch_persistent_surf, "surf", nullptr, 0, 2, wf_launch_surf, true, pt_launch_split_surf, 0u,
-        nullptr, 0u, pt_launch_adaptive_surf},
-        {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS, pt_launch_persistent_sss, "sss", pt_launch_persistent_sss4, TB_SSS_WAVES, 5,
-            wf_launch_sss, false, pt_launch_split_sss, TB_SSS_STASH, nullptr, 0u, pt_launch_adaptive_sss},
-    {PT_FEAT_ENV | PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS | PT_FEAT_MIX, pt_launch_persistent_vol, "vol", pt_launch_persistent_vol4, TB_VOL_WAVES,
-        3, wf_launch_vol, false, nullptr, TB_VOL_STASH, nullptr, 0u, pt_launch_adaptive_vol},
-        {PT_FEAT_ALL, pt_launch_persistent_full, "full", nullptr, 0, 4, nullptr, false, nullptr, 0u, nullptr, 0u, pt_launch_adaptive_full},
+    {TB_SET(matte), .id = 0, .wf = wf_launch_matte, .pooled = true, .split = pt_launch_split_matte},
+    {TB_SET(env), .id = 1, .wf = wf_launch_env, .pooled = true, .split = pt_launch_split_env},
+    {TB_SET(surf), .id = 2, .wf = wf_launch_surf, .pooled = true, .split = pt_launch_split_surf},
+    {TB_SET(sss), .id = 5, .wf = wf_launch_sss, .pooled = false, .split = pt_launch_split_sss},
+    {TB_SET(vol), .id = 3, .wf = wf_launch_vol, .pooled = false, .split = nullptr},
+    {TB_SET(full), .id = 4, .wf = nullptr, .pooled = false, .split = nullptr},
 };
 const int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 #endif
@@ -551,20 +557,19 @@ void tb_plan_defaults(tb_plan_input* in)
 int tb_variant_stash_entries(const char* name)
 {
     if (!name) return -1;
-    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return tbctx::kVariants[i].fnHi ? (int)tbctx::kVariants[i].stashHi : 0;
+    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return (int)tbctx::kVariants[i].stashHi();
     return -1;
 }
 int tb_variant_waves_hi(const char* name)
 {
     if (!name) return -1;
-    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name,
-        name)) return tbctx::kVariants[i].fnHi ? (int)tbctx::kVariants[i].wavesHi : 0;
+    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return (int)tbctx::kVariants[i].wavesHi();
     return -1;
 }
 int tb_variant_waves_lds(const char* name)
 {
     if (!name) return -1;
-    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return tbctx::kVariants[i].fnLds ? (int)tbctx::kVariants[i].wavesLds : 0;
+    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return (int)tbctx::kVariants[i].wavesLds();
     return -1;
 }
 uint32_t tb_frame_groups(uint32_t frames, uint32_t frameGroup, uint32_t guided, uint32_t group, uint32_t* firstFrame, uint32_t* numFrames)

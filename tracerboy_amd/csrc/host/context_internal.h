@@ -26,24 +26,12 @@
 
 using namespace tbhost;
 
-/* the kernel launchers of the feature sets (pt_variant.inc, pt_split.inc, wf_*.hip): one prototype per kind */
-#define TB_LOCKSTEP_ARGS hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, uint32_t, uint32_t, uint32_t, uint32_t, \
-    const TbTileMap*, int, int, int
+/* the kernel launchers of the feature sets: the lock-step copies' come with pt_launch.h (one per row of pt_copies.h); pipeline 4, the
+ * split-role kernel (pt_split.inc): shading waves + traversal waves over an LDS ray queue */
 #define TB_SPLIT_ARGS hipStream_t, const TbDeviceScene*, const TbPerFrameConstants*, const TbDeviceTargets*, const TbSplitParams*, uint32_t, uint32_t, \
     uint32_t, uint32_t, const TbTileMap*, int, int*
-#define TB_LOCKSTEP(name) hipError_t name(TB_LOCKSTEP_ARGS);
 #define TB_SPLIT(name) hipError_t name(TB_SPLIT_ARGS);
 extern "C" {
-typedef hipError_t (*pt_variant_fn)(TB_LOCKSTEP_ARGS);
-TB_LOCKSTEP(pt_launch_persistent_matte) TB_LOCKSTEP(pt_launch_persistent_env) TB_LOCKSTEP(pt_launch_persistent_surf) TB_LOCKSTEP(pt_launch_persistent_sss)
-TB_LOCKSTEP(pt_launch_persistent_vol) TB_LOCKSTEP(pt_launch_persistent_full)
-/* the copies held to an occupancy (fnHi, fnLds below) */
-TB_LOCKSTEP(pt_launch_persistent_matte5) TB_LOCKSTEP(pt_launch_persistent_matte6) TB_LOCKSTEP(pt_launch_persistent_env5) TB_LOCKSTEP(pt_launch_persistent_sss4)
-TB_LOCKSTEP(pt_launch_persistent_vol4)
-/* the adaptive launch of the six base copies (pt_variant.inc; option "adaptive") */
-TB_LOCKSTEP(pt_launch_adaptive_matte) TB_LOCKSTEP(pt_launch_adaptive_env) TB_LOCKSTEP(pt_launch_adaptive_surf) TB_LOCKSTEP(pt_launch_adaptive_sss)
-TB_LOCKSTEP(pt_launch_adaptive_vol) TB_LOCKSTEP(pt_launch_adaptive_full)
-/* pipeline 4, the split-role kernel (pt_split.inc): shading waves + traversal waves over an LDS ray queue */
 typedef hipError_t (*pt_split_fn)(TB_SPLIT_ARGS);
 TB_SPLIT(pt_launch_split_matte) TB_SPLIT(pt_launch_split_env) TB_SPLIT(pt_launch_split_surf) TB_SPLIT(pt_launch_split_sss)
 }
@@ -61,40 +49,19 @@ namespace tbctx {
 using namespace tbhost;
 
 extern std::string g_createError;
-/* fnHi: the same feature set compiled to `wavesHi` waves per SIMD (fewer VGPRs, more scratch; pipeline 0 only), used when LDS
- * has room for that many workgroups per CU -- otherwise its spills would buy no residency.  Searched in order: the first feature
- * set that covers what scene + settings need.  id: what option "last_variant" reports (stable across insertions).
+/* A lock-step copy: its row of pt_copies.h and its launcher. */
+struct Copy { const PtCopy* row; pt_variant_fn launch; };
+/* A feature set.  Searched in order: the first one that covers what scene + settings need.  id: what option "last_variant" reports (stable across
+ * insertions).  base / hi / lds: its copies by role (pt_copies.h) -- hi is used when LDS has room for hi->row->waves workgroups per CU (otherwise
+ * its spills would buy no residency), lds in place of hi where the plan picks hi for a frame-group launch of a scene in LDS and lds->row->waves
+ * workgroups fit (launch_plan.h LdsCopyFits); null for the sets without one.
  * wf: the wavefront pipeline's launcher of the feature set (pipeline 2; none for the full set); pooled: pipeline 3 exists. */
-#ifndef TB_MATTE_WAVES
-#define TB_MATTE_WAVES 5
-#endif
-#ifndef TB_MATTE_LDS_WAVES
-#define TB_MATTE_LDS_WAVES 6 /* pt_variant_matte6.hip */
-#endif
-#ifndef TB_ENV_WAVES
-#define TB_ENV_WAVES 6
-#endif
-#ifndef TB_SSS_WAVES
-#define TB_SSS_WAVES 6
-#endif
-#ifndef TB_VOL_WAVES
-#define TB_VOL_WAVES 4
-#endif
-#ifndef TB_ENV_STASH
-#define TB_ENV_STASH 7 /* pt_variant_env5.hip: LDS entries per lane its frame-group kernels keep behind the stacks for a path's cold state */
-#endif
-#ifndef TB_VOL_STASH
-#define TB_VOL_STASH 0
-#endif
-#ifndef TB_SSS_STASH
-#define TB_SSS_STASH 0
-#endif
-/* stashHi: LDS entries per lane the frame-group kernels of the fnHi copy keep behind the stacks (scenes fetched from memory, one level)
- * fnLds: a copy at `wavesLds` waves per SIMD with the frame-group kernels of scenes in LDS only (whole stack in LDS), used in place of fnHi where the
- * plan picks fnHi for such a launch and wavesLds workgroups per CU fit (launch_plan.h LdsCopyFits); null for the sets without one */
-/* fnAdaptive: the base copy's adaptive launch (pt_variant.inc pt_launch_adaptive_*) */
-struct Variant { uint32_t features; pt_variant_fn fn; const char* name; pt_variant_fn fnHi; uint32_t wavesHi; int id; wf_variant_fn wf; bool pooled;
-    pt_split_fn split; uint32_t stashHi; pt_variant_fn fnLds; uint32_t wavesLds; pt_variant_fn fnAdaptive; };
+struct Variant { const char* name; const Copy* base; const Copy* hi; const Copy* lds; int id; wf_variant_fn wf; bool pooled; pt_split_fn split;
+    uint32_t features() const { return base->row->features; }
+    uint32_t wavesHi() const { return hi ? hi->row->waves : 0u; }
+    uint32_t wavesLds() const { return lds ? lds->row->waves : 0u; }
+    uint32_t stashHi() const { return hi ? hi->row->stash : 0u; } /* LDS entries per lane behind the stacks: frame groups, scenes from memory, one level */
+};
 extern const Variant kVariants[];
 extern const int kNumVariants;
 

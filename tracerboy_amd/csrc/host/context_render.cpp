@@ -42,7 +42,7 @@ void renderWavefront(tb_context* c, int variant, uint32_t W, uint32_t H, uint32_
         if (16 + (size_t)c->ds.stackDepth * 1024 + blobBytes > ldsLimit) throw std::runtime_error("wavefront pipeline: traversal stack of depth " +
             std::to_string(c->ds.stackDepth) + " does not fit LDS; unsupported");
     }
-    const bool sss = (kVariants[variant].features & PT_FEAT_SSS) != 0; /* entries may be steps of the interior walk: two more columns per queue */
+    const bool sss = (kVariants[variant].features() & PT_FEAT_SSS) != 0; /* entries may be steps of the interior walk: two more columns per queue */
     {
         for (int q = 0; q < 2; q++) for (int k = 0; k < (sss ? 6 : 4); k++) ensure(c->wfCols[q][k], capacity * 16);
         for (int k = 0; k < (sss ? 12 : 11); k++) if (sss || k != 8) ensure(c->wfShadowCols[k], capacity * 16); /* column i (8) and l (11): FEAT_SSS only */
@@ -182,12 +182,14 @@ struct RenderCall {
     TbPerFrameConstants pf; TbDeviceTargets tg;
     const Variant* v; int variantIndex; bool twoLevel; tb_plan_input pin; tb_launch_plan plan;
     bool wavefront, pooled, split, groups; /* of the first plan (a plan made again for layout C changes none of them) */
-    pt_variant_fn launch; TbDeviceScene dsLaunch; size_t overflowHalf; /* the copy of the feature set, the scene as it sees it, words per half of the split stack */
+    const Copy* copy; int mode; TbDeviceScene dsLaunch; size_t overflowHalf; /* the copy of the feature set and how it is asked to run (PtMode), the scene as it sees it, words per half of the split stack */
     bool prepass, firstBounce, compactHits, overlap; uint32_t hitPrimBits, stampBits; size_t hitRecordBytes;
     /* The stamp of compact hit records is cyclic: with s = 32 - hitIndexBits bits it repeats every 2^s - 1 launches (15 at the 4-bit minimum; a buffer
      * sees every second launch, so a record as a launch 30 launches ago left it on the same buffer would pass -- every launch in between has rewritten
      * every record of the buffer, and what was actually observed, a line of the launch before last, differs in its stamp at any width).  There is no
      * check word: a 16-B piece is written and read whole. */
+    /* a key per (copy, mode) for the trials and the warm-ups: the launcher's address, and a bit for the adaptive launch, whose kernels are others */
+    uintptr_t launchKey() const { return (uintptr_t)copy->launch ^ (mode == PT_MODE_ADAPTIVE ? ~(~(uintptr_t)0 >> 1) : 0); }
     uint32_t hitStampOf(uint32_t epoch) const { return compactHits ? 1u + epoch % ((1u << stampBits) - 1u) : 0u; }
 };
 
@@ -333,7 +335,7 @@ static void renderSplit(const RenderCall& r)
 static void renderFrameGroups(RenderCall& r)
 {
     tb_context* c = r.c; const uint32_t W = r.W, H = r.H; const TbPerFrameConstants& pf = r.pf; TbDeviceTargets& tg = r.tg;
-    const tb_launch_plan& plan = r.plan; const pt_variant_fn launch = r.launch; const int lds = c->sceneInLds ? 1 : 0, numCUs = deviceCUs(c);
+    const tb_launch_plan& plan = r.plan; const pt_variant_fn launch = r.copy->launch; const int lds = c->sceneInLds ? 1 : 0, numCUs = deviceCUs(c);
     const uint64_t pixels = (uint64_t)W * H;
     const uint32_t batch = plan.batch_frames;
     const uint64_t regions = std::max<uint64_t>(1, tb_persistent_grid(W, H, c->tiles));
@@ -360,19 +362,19 @@ static void renderFrameGroups(RenderCall& r)
         warm.primaryHits = withHits ? (unsigned long long*)c->fgHits[par].p : nullptr; warm.firstBounce = withHits && r.firstBounce ? 1u : 0u;
         warm.hitStamp = withHits ? r.hitStampOf(warm.launchEpoch) : 0u; warm.hitPrimBits = r.hitPrimBits; warm.hitGeomBits = c->hitGeomBits;
         const TbDeviceScene dsPar = sceneOfSide(r.dsLaunch, par, r.overflowHalf);
-        HIP_TRY(launch(ex.launchStream(par), &dsPar, &pf, &warm, W, H, c->samplesRendered, 0, &c->tiles, withHits ? 0 : lds, 0, 0));
+        HIP_TRY(launch(ex.launchStream(par), &dsPar, &pf, &warm, W, H, c->samplesRendered, 0, &c->tiles, withHits ? 0 : lds, 0, PT_MODE_LOCKSTEP));
         HIP_TRY(hipStreamSynchronize(ex.launchStream(par)));
     };
     /* The kernel copies held to an occupancy keep a few registers in scratch: the first render with a given kernel sends a zero-frame launch
      * of its one-pixel-per-lane form (same feature set, at least as much scratch, a full grid of workgroups that exit at once; nobody waits for
      * it) down both side streams.  Two-level scenes in the tuned copies have no one-pixel-per-lane form (pt_variant.inc refuses it: the first
      * render of an instanced scene in a fresh context used to fail here and then for good): they are warmed with the frame-group form
-     * itself, and so is a copy for scenes in LDS (fnLds), which has no other form. */
-    if (ex.overlap) ex.warmOnce((const void*)launch, [&](uint32_t par) {
-        if (r.twoLevel || launch == r.v->fnLds) return warmFrameGroupForm(par, false);
+     * itself, and so is a copy for scenes in LDS, which has no other form. */
+    if (ex.overlap) ex.warmOnce((const void*)r.launchKey(), [&](uint32_t par) {
+        if (r.twoLevel || r.copy->row->role == PT_ROLE_LDS_GROUPS) return warmFrameGroupForm(par, false);
         TbDeviceTargets none = tg; none.samples = nullptr;
         TbDeviceScene dsWarm = c->ds; dsWarm.nodesC = nullptr; /* the one-pixel-per-lane twin fetches layout B */
-        HIP_TRY(launch(c->side[par], &dsWarm, &pf, &none, W, H, c->samplesRendered, 0, &c->tiles, lds, 0, 0));
+        HIP_TRY(launch(c->side[par], &dsWarm, &pf, &none, W, H, c->samplesRendered, 0, &c->tiles, lds, 0, PT_MODE_LOCKSTEP));
     });
     if (r.prepass) {
         /* the hit records: sized and touched once like the sample buffers; and the kernels that take their first hits from them
@@ -381,7 +383,7 @@ static void renderFrameGroups(RenderCall& r)
          * that follows another kernel closely gave one wrong 16x16 region in the first render of 1 process in ~3 000 */
         for (uint32_t par = 0; par < 2u; par++) ex.grow(c->fgHits[par], par, pixels * batch * r.hitRecordBytes, true);
         /* one kernel per (split stack, node layout) */
-        const void* key = (const void*)((uintptr_t)launch ^ (1u | (r.dsLaunch.stackOverflow ? 2u : 0u) | (r.dsLaunch.nodesC ? 4u : 0u) | (r.firstBounce ? 8u : 0u)));
+        const void* key = (const void*)(r.launchKey() ^ (1u | (r.dsLaunch.stackOverflow ? 2u : 0u) | (r.dsLaunch.nodesC ? 4u : 0u) | (r.firstBounce ? 8u : 0u)));
         ex.warmOnce(key, [&](uint32_t par) { warmFrameGroupForm(par, true); });
     }
     ex.run(r.n, batch, r.clearStats,
@@ -412,7 +414,7 @@ static void renderFrameGroups(RenderCall& r)
         },
         /* (the adaptive launch tested per call: the same copy's kernel over the live list, and the fold over the list) */
         [&](uint32_t f0, uint32_t nf, uint32_t par, hipStream_t ptStream) { const TbDeviceScene dsPar = sceneOfSide(r.dsLaunch, par, r.overflowHalf);
-            HIP_TRY(launch(ptStream, &dsPar, &pf, &tg, W, H, c->samplesRendered + f0, nf, &c->tiles, lds, 0, r.adaptive ? PT_LAUNCH_LIVE_GROUPS : 0)); },
+            HIP_TRY(launch(ptStream, &dsPar, &pf, &tg, W, H, c->samplesRendered + f0, nf, &c->tiles, lds, 0, r.mode)); },
         [&](uint32_t f0, uint32_t nf) {
             if (r.adaptive) HIP_TRY(pt_launch_accumulate_live(c->stream, tg.samples, W, H, c->samplesRendered + f0, nf, liveList, c->lastOwnedPixels, tg.output,
                 tg.jittered));
@@ -497,9 +499,8 @@ static void fillPlanInput(const RenderCall& r, tb_plan_input& in)
 {
     tb_context* c = r.c; const Variant* v = r.v;
     memset(&in, 0, sizeof in);
-    /* surf: compiled into its only copy */
-    in.variant_features = v->features; in.variant_waves_hi = v->fnHi ? v->wavesHi : 0u; in.variant_prepass_in_base = (!v->fnHi && v->id == 2) ? 1u : 0u;
-    in.variant_stash_entries = v->fnHi ? v->stashHi : 0u;
+    in.variant_features = v->features(); in.variant_waves_hi = v->wavesHi(); in.variant_prepass_in_base = !v->hi && v->base->row->prepassInBase ? 1u : 0u;
+    in.variant_stash_entries = v->stashHi();
     in.variant_has_wavefront = v->wf ? 1u : 0u; in.variant_has_pooled = v->pooled ? 1u : 0u; in.variant_has_split = v->split ? 1u : 0u;
     in.scene_in_lds = c->sceneInLds ? 1u : 0u; in.lds_blob_bytes = c->ds.ldsBlobBytes; in.stack_depth = c->ds.stackDepth;
     in.two_level = c->ds.numInstances ? 1u : 0u;
@@ -524,7 +525,7 @@ static int pickVariantAndPlan(RenderCall& r)
     uint32_t need = c->sceneFeatures | settingsFeatureMask(c, r.s, r.aov);
     if (r.count || opt<OPT_force_full_variant>(c)) need = PT_FEAT_ALL;
     r.v = &kVariants[kNumVariants - 1];
-    for (int i = 0; i < kNumVariants; i++) if ((need & ~kVariants[i].features) == 0) { r.v = &kVariants[i]; break; }
+    for (int i = 0; i < kNumVariants; i++) if ((need & ~kVariants[i].features()) == 0) { r.v = &kVariants[i]; break; }
     c->lastVariant = r.v->name;
     r.variantIndex = (int)(r.v - kVariants);
     r.twoLevel = c->ds.numInstances != 0; /* instanced scene (flatten_instances = 0): pipeline 0 only */
@@ -536,7 +537,7 @@ static int pickVariantAndPlan(RenderCall& r)
         r.pin.pipeline = 0; PlanLaunch(r.pin, r.plan); r.plan.rule_pipeline = TB_PLAN_RULE_SPLIT_NO_ROOM;
     }
     r.wavefront = r.plan.pipeline == 2; r.pooled = r.plan.pipeline == 3; r.split = r.plan.pipeline == 4; r.groups = r.plan.groups != 0;
-    r.launch = r.plan.high_occupancy_copy ? r.v->fnHi : r.v->fn;
+    r.copy = r.plan.high_occupancy_copy ? r.v->hi : r.v->base;
     return TB_OK;
 }
 
@@ -558,14 +559,19 @@ static void sizeSplitStack(RenderCall& r)
 static void pickCopy(RenderCall& r)
 {
     tb_context* c = r.c; const Variant*& v = r.v; tb_launch_plan& plan = r.plan;
-    if (plan.full_variant && v != &kVariants[kNumVariants - 1]) { v = &kVariants[kNumVariants - 1]; r.launch = v->fn; c->lastVariant = v->name; }
-    /* the set's copy for scenes in LDS (fnLds) in place of fnHi where its workgroups fit with the whole stack: the frame-group kernels of a
-     * one-level scene in LDS without counters (the launcher refuses anything else) */
-    c->lastCopyWaves = r.launch == v->fnHi ? v->wavesHi : 0u;
-    if (r.launch == v->fnHi && v->fnLds && r.groups && c->sceneInLds && !r.twoLevel && !r.count && !plan.stack_overflow_entries && !plan.prepass &&
-        LdsCopyFits(v->wavesLds, c->ds.stackDepth, c->ds.ldsBlobBytes)) { r.launch = v->fnLds; c->lastCopyWaves = v->wavesLds; }
-    /* the base copy's adaptive form (pt_variant.inc); the list-driven frame-group launch (rule TB_PLAN_RULE_ADAPTIVE_GROUPS) keeps the copy chosen above */
-    if (r.adaptive && !r.groups) r.launch = v->fnAdaptive;
+    if (plan.full_variant && v != &kVariants[kNumVariants - 1]) { v = &kVariants[kNumVariants - 1]; r.copy = v->base; c->lastVariant = v->name; }
+    c->lastCopyWaves = r.copy == v->hi ? v->wavesHi() : 0u;
+    r.mode = r.adaptive ? (r.groups ? PT_MODE_LIVE_GROUPS : PT_MODE_ADAPTIVE) : r.pipe == 1 ? PT_MODE_STREAM : PT_MODE_LOCKSTEP;
+    /* the set's copy for scenes in LDS in place of the occupancy copy where its workgroups fit with the whole stack and it has a kernel for the call
+     * as planned (pt_pick_form: the frame-group kernels of a one-level scene in LDS without counters; a pre-pass, even one left to the trial, keeps
+     * the occupancy copy) */
+    const PtShape planned{r.mode, r.groups, r.adaptive, r.count, c->sceneInLds, r.twoLevel, plan.compact_nodes != 0, plan.stack_overflow_entries != 0, true,
+        plan.prepass != TB_PLAN_PREPASS_OFF, false, plan.guided_groups != 0};
+    if (r.copy == v->hi && v->lds && pt_pick_form(*v->lds->row, planned).ok && LdsCopyFits(v->wavesLds(), c->ds.stackDepth, c->ds.ldsBlobBytes)) {
+        r.copy = v->lds; c->lastCopyWaves = v->wavesLds(); }
+    /* the adaptive launch, one pixel per lane, is the base copy's; the list-driven frame-group launch (rule TB_PLAN_RULE_ADAPTIVE_GROUPS) keeps the copy
+     * chosen above */
+    if (r.mode == PT_MODE_ADAPTIVE) r.copy = v->base;
     /* layout C on first demand */
     if (opt<OPT_node_layout>(c) == 1 && !r.twoLevel && !c->sceneInLds && !c->ds.nodesC && !c->compactTried) {
         ensureCompactNodes(c); r.dsLaunch.nodesC = c->ds.nodesC; r.dsLaunch.quant = c->ds.quant;
@@ -578,7 +584,7 @@ static void pickCopy(RenderCall& r)
 static uint64_t kindOfCall(const RenderCall& r) /* same scene, frame, frames per call, depth and kernel: the key of a trial */
 {
     return ((uint64_t)r.W << 48) ^ ((uint64_t)r.H << 32) ^ ((uint64_t)r.n << 12) ^ ((uint64_t)r.s.MaxBounces << 4) ^ ((uint64_t)r.c->sceneGeneration << 24) ^
-        (uint64_t)(uintptr_t)r.launch;
+        (uint64_t)r.launchKey();
 }
 
 /* the pre-pass where the plan leaves it to the trial (launch_trials.h): the sample is the first launch of the call before this one, if it has
@@ -629,7 +635,7 @@ static void tryOverlap(RenderCall& r)
     tb_context* c = r.c;
     r.overlap = r.plan.overlap_launches != 0;
     const uint64_t callKey = kindOfCall(r) ^ (r.prepass ? 1u : 0u);
-    const bool trial = r.overlap && opt<OPT_overlap_launches>(c) == 1 && (r.v->features & (PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS | PT_FEAT_MIX)) != 0;
+    const bool trial = r.overlap && opt<OPT_overlap_launches>(c) == 1 && (r.v->features() & (PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS | PT_FEAT_MIX)) != 0;
     hipEvent_t* ends = c->evCallEnd;
     if (trial) r.overlap = OverlapTrialStep(c->overlapTrial, c->callRec, c->callCount, callKey,
         [&](uint64_t i) { return ends[i & 7u] && ends[(i - 2) & 7u] && hipEventQuery(ends[i & 7u]) == hipSuccess; },
@@ -668,8 +674,8 @@ static void dispatch(RenderCall& r)
     else if (r.wavefront) renderWavefront(c, r.variantIndex, r.W, r.H, c->samplesRendered, r.n, r.pf);
     else if (r.pooled) renderPooled(c, r.variantIndex, r.W, r.H, c->samplesRendered, r.n, r.pf);
     else if (r.groups) renderFrameGroups(r);
-    else HIP_TRY(r.launch(c->stream, &r.dsLaunch, &r.pf, &r.tg, r.W, r.H, c->samplesRendered, r.n, &c->tiles, c->sceneInLds ? 1 : 0, r.count ? 1 : 0,
-        r.adaptive ? 0 : (int)r.pipe));
+    else HIP_TRY(r.copy->launch(c->stream, &r.dsLaunch, &r.pf, &r.tg, r.W, r.H, c->samplesRendered, r.n, &c->tiles, c->sceneInLds ? 1 : 0, r.count ? 1 : 0,
+        r.mode));
     /* one launch (or one pipeline) for the whole call */
     if (!c->lastKernelFrames) { HIP_TRY(hipEventRecord(c->evKernel, c->stream)); c->lastKernelFrames = r.n; }
 }

@@ -12,7 +12,7 @@ namespace tbhost {
 
 /* Does a copy held to `waves` per SIMD keep `waves` workgroups per CU resident with the whole stack and the scene's LDS image in LDS?  The plan's
  * arithmetic below: a workgroup's share of 160 KB and its need, in 512-B granules, with 128 B of static LDS.  renderImpl asks it of the copies
- * for scenes in LDS (Variant::fnLds, context_internal.h). */
+ * for scenes in LDS (Variant::lds, context_internal.h). */
 inline bool LdsCopyFits(uint32_t waves, uint32_t stackDepth, uint32_t ldsBlobBytes)
 {
     if (!waves) return false;
@@ -33,7 +33,7 @@ inline void PlanLaunch(const tb_plan_input& in, tb_launch_plan& p)
     if (in.adaptive && !listGroups) {
         /* The adaptive launch (option "adaptive"): converged pixels are left out and the live ones packed 256 to a workgroup.
          * A pixel's samples must run in frame order -- the skip test before each frame reads the sums of the frames before it -- so: the lock-step
-         * kernel's one-pixel-per-lane form in the base copy of the feature set (pt_variant.inc pt_launch_adaptive_*), no frame groups, no pre-pass,
+         * kernel's one-pixel-per-lane form in the base copy of the feature set (PT_MODE_ADAPTIVE, pt_copies.h), no frame groups, no pre-pass,
          * no overlapping launches; two-level scenes in the full feature set, whose kernels walk two levels in every form. */
         p.pipeline = 0; p.rule_pipeline = TB_PLAN_RULE_ADAPTIVE; p.stack_lds_entries = in.stack_depth;
         p.rule_copy = TB_PLAN_RULE_COPY_NONE; p.prepass = TB_PLAN_PREPASS_OFF; p.rule_prepass = TB_PLAN_RULE_PREPASS_NO_KERNEL;

@@ -2,12 +2,27 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include "pt_scene.h"
+#include "pt_copies.h"
 
-#ifdef __cplusplus
+/* compute units of the CURRENT device (a process may drive several: tb_create_multi), cached per device ordinal */
+static inline hipError_t pt_device_cus(int* numCUs)
+{
+    static int cuCache[64] = {0};
+    int dev = 0; hipError_t e = hipGetDevice(&dev); if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64 && cuCache[dev]) { *numCUs = cuCache[dev]; return hipSuccess; }
+    e = hipDeviceGetAttribute(numCUs, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess && dev >= 0 && dev < 64) cuCache[dev] = *numCUs;
+    return e;
+}
+
 extern "C" {
-#endif
-hipError_t pt_launch_persistent(hipStream_t stream, const TbDeviceScene* ds, const TbPerFrameConstants* pf, const TbDeviceTargets* tg, uint32_t W, uint32_t H,
-                                uint32_t firstFrame, uint32_t numFrames, const TbTileMap* tiles, int sceneInLds, int countRays);
+/* the lock-step kernels: one launcher per copy (pt_copies.h PT_COPY_LIST, pt_variant.inc); mode: PtMode -- what it launches, or that it refuses
+ * (hipErrorInvalidValue), is pt_pick_form's answer */
+#define PT_LOCKSTEP_ARGS hipStream_t stream, const TbDeviceScene* ds, const TbPerFrameConstants* pf, const TbDeviceTargets* tg, uint32_t W, uint32_t H, \
+    uint32_t firstFrame, uint32_t numFrames, const TbTileMap* tiles, int sceneInLds, int countRays, int mode
+typedef hipError_t (*pt_variant_fn)(PT_LOCKSTEP_ARGS);
+#define PT_LAUNCHER(copy) hipError_t pt_launch_persistent_##copy(PT_LOCKSTEP_ARGS);
+PT_COPY_LIST(PT_LAUNCHER)
 hipError_t pt_launch_trace_closest(hipStream_t stream, const TbDeviceScene* ds, uint32_t n, const float* origins, const float* dirs, float* outT, int* outMat,
                                    float* outBary, uint32_t* outPrim, uint32_t* outGeom, float* outNormal, float* outUV, uint32_t* outBoxes, uint32_t* outTris);
 /* TbDeviceTargets::regionOrder (1 + regions x numGroups words) from TbDeviceTargets::regionCost; keys: regions words of scratch; lateFrom: the first
@@ -22,11 +37,9 @@ hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const
 hipError_t pt_launch_accumulate_samples(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
     const TbTileMap* tiles,
                                         TbFloat4* output, TbFloat4* jittered);
-/* The list-driven frame-group launch (pt_scene.h TB_LIVE_COUNT_WORDS): the last argument of pt_launch_persistent_* in place of a pipeline number --
- * the frame-group kernels over the live list (tg->samples and tg->liveList set, the count in the 16 bytes before the list) -- and the fold over the
- * same list: accumulate_samples_kernel's sums for the listed pixels only (the other pixels' samples were never written).  maxEntries: an upper
- * bound of the count, the owned pixels; the count itself stays on the device. */
-#define PT_LAUNCH_LIVE_GROUPS (-2)
+/* The fold of the list-driven frame-group launch (PT_MODE_LIVE_GROUPS; pt_scene.h TB_LIVE_COUNT_WORDS: tg->samples and tg->liveList set, the count in
+ * the 16 bytes before the list): accumulate_samples_kernel's sums for the listed pixels only (the other pixels' samples were never written).
+ * maxEntries: an upper bound of the count, the owned pixels; the count itself stays on the device. */
 hipError_t pt_launch_accumulate_live(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
                                      const uint32_t* list, uint64_t maxEntries, TbFloat4* output, TbFloat4* jittered);
 hipError_t pt_launch_device_math(hipStream_t stream, int fn, uint32_t n, const float* a, const float* b, float* out);
@@ -56,6 +69,4 @@ hipError_t rt_launch_composite(hipStream_t stream, uint32_t W, uint32_t H, const
 /* output stage (post_kernels.hip): optional histogram + average (auto exposure), then PostProcessCS */
 hipError_t post_launch(hipStream_t stream, const TbPostConstants* pc, const TbFloat4* in, const float* inR32, const TbFloat4* aux,
                        uint32_t* histogram, float* averaged, TbFloat4* out, uint32_t* outRgba8);
-#ifdef __cplusplus
 }
-#endif

@@ -8,9 +8,6 @@ namespace {
 #include "pt_split.inc"
 }
 
-#define PT_CAT2(a, b) a##b
-#define PT_CAT(a, b) PT_CAT2(a, b)
-
 /* LDS of one workgroup: traversal stacks + scene image + 48-B ray slots (two per shading lane) + the queue + control words */
 static size_t split_lds_bytes(const TbDeviceScene* ds, const TbSplitParams* sp, int sceneInLds)
 {
@@ -35,13 +32,7 @@ extern "C" hipError_t PT_CAT(pt_launch_split_, PT_NAME)(hipStream_t stream, cons
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const uint32_t threads = (sp->travWaves + sp->shadeWaves) * 64;
     int numCUs = 0;
-    {
-        static int cuCache[64] = {0};
-        int dev = 0; hipError_t e = hipGetDevice(&dev); if (e != hipSuccess) return e;
-        if (dev < 0 || dev >= 64 || !cuCache[dev]) { e = hipDeviceGetAttribute(&numCUs, hipDeviceAttributeMultiprocessorCount, dev);
-            if (e != hipSuccess) return e; if (dev >= 0 && dev < 64) cuCache[dev] = numCUs; }
-        else numCUs = cuCache[dev];
-    }
+    { const hipError_t e = pt_device_cus(&numCUs); if (e != hipSuccess) return e; }
 #define SPLIT_LAUNCH(...) do { \
         hipError_t e = hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; \
         int perCU = 0; e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, __VA_ARGS__, (int)threads, lds); if (e != hipSuccess) return e; \

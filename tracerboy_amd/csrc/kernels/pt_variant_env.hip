@@ -1,8 +1,4 @@
-/* pt_variant_env.hip -- persistent path-tracing kernel compiled for feature set "env" (pt_device_features.h):
- * 4 waves per SIMD.  pt_variant_env5.hip is the copy at 5 waves per SIMD the host prefers when LDS has room. */
-#include "pt_device_features.h"
-#define PT_FEATURES (PT_FEAT_ENV)
-#define PT_NAME env
-#define PT_COUNT 0
-#define PT_PERSISTENT_ATTR __attribute__((amdgpu_waves_per_eu(4)))
+/* pt_variant_env.hip -- copy "env" of pt_copies.h: the base copy of feature set "env" (pt_device_features.h),
+ * 4 waves per SIMD.  pt_variant_env5.hip is the copy at a higher occupancy the host prefers when LDS has room. */
+#define PT_COPY env
 #include "pt_variant.inc"
