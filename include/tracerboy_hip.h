@@ -213,6 +213,59 @@ int tb_unpack_gathered_device(tb_context* ctx, void* stream, const void* gathere
 int tb_unpack_gathered_host(uint32_t width, uint32_t height, uint32_t world, uint32_t tile_w, uint32_t tile_h,
                             const float* const* per_rank_packed, float* full_rgba);
 
+/* ---- render states (no reference counterpart: the reference's accumulation dies with its process) ----------
+ * A render state is what a progressive render IS: the two accumulation surfaces and the range [first_frame, next_frame) of the frames
+ * whose samples they hold, together with everything a later process must agree on to go on with the same bits.  Seeds depend on
+ * (x, y, frame) only, so a render that is saved, loaded into a new context and continued is bit-identical to the uninterrupted one; states
+ * of adjacent frame ranges add up (TB_STATE_ADD) to the fp32 sum of the partial sums.  AOVs, the real-time history, ray counters and region
+ * costs are not part of a state: none of them changes a bit of the picture.
+ * File: TB_STATE_HEADER_BYTES of header ("TBSTATE1", tb_state_info, zeros), then the output surface, then the jittered one, each
+ * width x height RGBA32F, row 0 = top.  The digests (include/tb_state.h) are taken on the device from the surfaces as they lie in HBM. */
+#define TB_STATE_VERSION 1u
+#define TB_STATE_HEADER_BYTES 256u
+typedef struct tb_state_info {
+    uint32_t version;                         /* TB_STATE_VERSION */
+    uint32_t width, height;
+    uint32_t first_frame, next_frame;         /* the surfaces hold the samples of frames [first_frame, next_frame) */
+    float time_seed;                          /* as passed to tb_render */
+    tb_output_settings settings;              /* the settings the surfaces were accumulated under */
+    tb_camera camera;
+    uint32_t tile_rank, tile_world, tile_w, tile_h; /* tb_set_tile_assignment; tile_world == 1: a complete frame */
+    uint32_t alpha_test, adaptive, adaptive_test;   /* the options that change the result, with adaptive_min_frames below */
+    int64_t adaptive_min_frames;
+    uint64_t scene_digest;                    /* tb_scene_digest of the scene the frames were rendered of */
+    uint64_t output_digest, jittered_digest;  /* tb_accum_digest at the time of the save */
+} tb_state_info;
+enum { TB_STATE_REPLACE = 0, TB_STATE_ADD = 1, TB_STATE_ANY_SCENE = 16 };
+/* The context holds the empty state [first_frame, first_frame): surfaces sized and zeroed.  A following tb_render with the same size,
+ * time seed and history-relevant settings renders frames first_frame, first_frame + 1, ...; whatever resets the history (a change of any
+ * of those, tb_set_camera, tb_set_material, tb_invalidate_history, tb_set_tile_assignment, an option that resets it) returns to frame 0. */
+int tb_state_begin(tb_context* ctx, uint32_t width, uint32_t height, const tb_output_settings* settings, float time_seed, uint32_t first_frame);
+/* Waits for the context's stream like tb_read_accum.  Atomic: the file is written beside `path` and renamed.  Refused (TB_E_INVALID) when
+ * nothing is rendered or the last render was tb_render_realtime. */
+int tb_state_save(tb_context* ctx, const char* path);
+/* flags: TB_STATE_REPLACE or TB_STATE_ADD, optionally | TB_STATE_ANY_SCENE (do not compare the scene digests).  A scene must be loaded.
+ * REPLACE: the context adopts size, settings, time seed, camera (without a history reset) and frame range; the options alpha_test, adaptive,
+ * adaptive_min_frames and adaptive_test must have the file's values.  A complete frame (tile_world == 1) loads into any context -- every device
+ * of a tb_create_multi group receives it --, a rank's partial frame only into a context with the same tile assignment.
+ * ADD: context += file, per float, on the device; size, history-relevant settings, time seed, camera (by bits), scene and completeness must be
+ * equal and the frame ranges adjacent (the file's appends or prepends).  The result is the fp32 sum of the two partial sums, NOT the bits of
+ * one straight render.
+ * TB_E_IO: the file cannot be read; TB_E_PARSE: bad magic, version, sizes, length or digest; TB_E_INVALID: a mismatch (the message names it). */
+int tb_state_load(tb_context* ctx, const char* path, uint32_t flags);
+/* digests of the output / jittered surface, computed on the device from HBM (waits for the context's stream) */
+int tb_accum_digest(tb_context* ctx, uint64_t out2[2]);
+/* digest of the loaded scene: every array of TbSceneView, each prefixed by its length (layout-A BVH, hit groups, indices, vertices,
+ * materials, texture data, lights, images + texels, environment map, config constants without the camera's lens height, top level) */
+int tb_scene_digest(tb_context* ctx, uint64_t* out);
+/* host only, no device, no context.  tb_state_info_read validates the header and the file's length; tb_state_read_host also returns the
+ * surfaces (each width x height x 4 floats; either may be NULL) and checks them against the stored digests; tb_state_write_host computes
+ * the surface digests itself (the two digest fields and the version of `in` are ignored). */
+int tb_state_info_read(const char* path, tb_state_info* out, char* err, uint32_t err_len);
+int tb_state_read_host(const char* path, tb_state_info* out, float* output, float* jittered, char* err, uint32_t err_len);
+int tb_state_write_host(const char* path, const tb_state_info* in, const float* output, const float* jittered);
+uint64_t tb_state_digest_host(const void* words, uint64_t n_words);
+
 /* Tunables / instrumentation: "pipeline" (0 = lock-step-bounce persistent kernel [default, fastest measured],
  * 1 = streaming persistent kernel with a resumable BVH walk),
  * "count_rays" (0/1), "bvh_builder" (0 = LBVH, 1 = binned SAH + reinsertion passes, 2 = LBVH built on the GPU, 3 = LBVH + the fallback layer's
@@ -227,7 +280,9 @@ int tb_unpack_gathered_host(uint32_t width, uint32_t height, uint32_t world, uin
  * An unknown name is an error. */
 int tb_set_option(tb_context* ctx, const char* name, int64_t value);
 /* tb_get_option also reads what the last render did ("last_*") and "debug_live_device_bytes": the device bytes the library holds for all
- * contexts of the process together (a context that is destroyed gives back all it took). */
+ * contexts of the process together (a context that is destroyed gives back all it took).  Render states: "state_first_frame" (the first
+ * frame the surfaces hold; tb_samples_rendered is the one after the last), "last_state_digest_us" / "last_state_add_us" (GPU microseconds of
+ * the last surface digest / TB_STATE_ADD sum, HIP events). */
 int64_t tb_get_option(tb_context* ctx, const char* name);
 
 /* The launch policy of tb_render as a pure function (no device, no context): which pipeline, which copy of the feature set (and how
@@ -341,6 +396,7 @@ void tb_host_scene_free(tb_host_scene* s);
 int tb_host_scene_view_get(tb_host_scene* s, TbSceneView* view);          /* pointers owned by s */
 int tb_host_scene_camera(tb_host_scene* s, tb_camera* cam);
 int tb_host_scene_info(tb_host_scene* s, tb_scene_info* info);
+int tb_host_scene_digest(tb_host_scene* s, uint64_t* out);                /* what tb_scene_digest gives for the same scene and builder */
 int tb_host_scene_frame_constants(tb_host_scene* s, const tb_output_settings* settings, uint32_t frame, float time_seed, TbPerFrameConstants* out);
 /* layout-B arrays (what the kernels fetch) and the per-triangle builder inputs */
 int tb_host_scene_layout_b(tb_host_scene* s, const TbNodeB** nodes, uint32_t* num_nodes, const TbTriB** tris, uint32_t* num_tris, uint32_t* root_ref);

@@ -160,6 +160,15 @@ class tb_scene_info(C.Structure):
                 ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3)]
 
 
+class tb_state_info(C.Structure):
+    """include/tracerboy_hip.h tb_state_info: the header of a render-state file."""
+    _fields_ = [("version", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("first_frame", C.c_uint32), ("next_frame", C.c_uint32),
+                ("time_seed", C.c_float), ("settings", tb_output_settings), ("camera", tb_camera),
+                ("tile_rank", C.c_uint32), ("tile_world", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("alpha_test", C.c_uint32), ("adaptive", C.c_uint32), ("adaptive_test", C.c_uint32),
+                ("adaptive_min_frames", C.c_int64), ("scene_digest", C.c_uint64), ("output_digest", C.c_uint64), ("jittered_digest", C.c_uint64)]
+
+
 class tb_plan_input(C.Structure):
     """include/tracerboy_hip.h tb_plan_input: what the launch policy is told (scene statistics, the call, the options)."""
     _fields_ = [("variant_features", C.c_uint32), ("variant_waves_hi", C.c_uint32), ("variant_prepass_in_base", C.c_uint32),
@@ -181,6 +190,7 @@ class tb_launch_plan(C.Structure):
                 ("rule_pipeline", C.c_uint32), ("rule_copy", C.c_uint32), ("rule_prepass", C.c_uint32), ("guided_groups", C.c_uint32), ("costly_first", C.c_uint32)]
 
 
+assert C.sizeof(tb_state_info) == 208
 assert C.sizeof(TbPostConstants) == 36
 assert C.sizeof(TbTemporalConstants) == 144
 assert C.sizeof(TbDenoiserConstants) == 28

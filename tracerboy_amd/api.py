@@ -97,6 +97,16 @@ def lib():
         "tb_device_math": (C.c_int, [vp, C.c_int, C.c_uint32, vp, vp, vp]),
         "tb_variant_stash_entries": (C.c_int, [C.c_char_p]),
         "tb_frame_groups": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
+        "tb_state_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), C.c_float, C.c_uint32]),
+        "tb_state_save": (C.c_int, [vp, C.c_char_p]),
+        "tb_state_load": (C.c_int, [vp, C.c_char_p, C.c_uint32]),
+        "tb_accum_digest": (C.c_int, [vp, P(C.c_uint64)]),
+        "tb_scene_digest": (C.c_int, [vp, P(C.c_uint64)]),
+        "tb_state_info_read": (C.c_int, [C.c_char_p, P(abi.tb_state_info), C.c_char_p, C.c_uint32]),
+        "tb_state_read_host": (C.c_int, [C.c_char_p, P(abi.tb_state_info), vp, vp, C.c_char_p, C.c_uint32]),
+        "tb_state_write_host": (C.c_int, [C.c_char_p, P(abi.tb_state_info), vp, vp]),
+        "tb_state_digest_host": (C.c_uint64, [vp, C.c_uint64]),
+        "tb_host_scene_digest": (C.c_int, [vp, P(C.c_uint64)]),
         "tb_host_scene_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, P(vp), C.c_char_p, C.c_uint32]),
         "tb_host_scene_procedural": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_int, P(vp), C.c_char_p, C.c_uint32]),
         "tb_host_scene_free": (None, [vp]),
@@ -196,6 +206,49 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# -- render-state files, host only: no device, no context ----------------
+TB_STATE_REPLACE, TB_STATE_ADD, TB_STATE_ANY_SCENE = 0, 1, 16
+STATE_HEADER_BYTES = 256
+
+
+def StateDigest(words):
+    """The digest of include/tb_state.h over the array's bytes as 32-bit words (tb_state_digest_host)."""
+    a = np.ascontiguousarray(words)
+    assert a.nbytes % 4 == 0, "the digest is defined over 32-bit words"
+    return int(lib().tb_state_digest_host(_np_ptr(a), a.nbytes // 4))
+
+
+def StateInfo(path):
+    """The header of a state file (tb_state_info), validated together with the file's length; reads no surface."""
+    info, err = abi.tb_state_info(), C.create_string_buffer(512)
+    rc = lib().tb_state_info_read(os.fsencode(path), C.byref(info), err, 512)
+    if rc != 0:
+        raise TracerBoyError(rc, err.value.decode(errors="replace"))
+    return info
+
+
+def ReadStateFile(path):
+    """(tb_state_info, output, jittered): the header and the two (H, W, 4) float32 surfaces, checked against the stored digests."""
+    info = StateInfo(path)
+    out = np.empty((info.height, info.width, 4), np.float32); jit = np.empty_like(out)
+    err = C.create_string_buffer(512)
+    rc = lib().tb_state_read_host(os.fsencode(path), C.byref(info), _np_ptr(out), _np_ptr(jit), err, 512)
+    if rc != 0:
+        raise TracerBoyError(rc, err.value.decode(errors="replace"))
+    return info, out, jit
+
+
+def WriteStateFile(path, info, output, jittered):
+    """Write a state file from host arrays (tb_state_write_host): width, height and the two digests are taken from the arrays."""
+    out = np.ascontiguousarray(output, np.float32); jit = np.ascontiguousarray(jittered, np.float32)
+    assert out.ndim == 3 and out.shape[2] == 4 and jit.shape == out.shape
+    h = abi.tb_state_info.from_buffer_copy(info)
+    h.height, h.width = out.shape[:2]
+    rc = lib().tb_state_write_host(os.fsencode(path), C.byref(h), _np_ptr(out), _np_ptr(jit))
+    if rc != 0:
+        raise TracerBoyError(rc, "could not write state file %s" % path)
+
+
 class HostScene:
     """Host-only LoadScene (parse + convert + BVH build): no GPU needed, renders nothing."""
 
@@ -248,6 +301,14 @@ class HostScene:
         pf = abi.TbPerFrameConstants()
         lib().tb_host_scene_frame_constants(self._h, C.byref(settings) if settings is not None else None, frame, time_seed, C.byref(pf))
         return pf
+
+    def digest(self):
+        """The scene digest a context reports for this scene and builder (tb_host_scene_digest)."""
+        d = C.c_uint64()
+        rc = lib().tb_host_scene_digest(self._h, C.byref(d))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_digest")
+        return d.value
 
     def bvh_bytes(self):
         v = self.view()
@@ -386,6 +447,37 @@ class TracerBoy:
         jit = np.empty_like(out) if jittered else None
         self._check(self._L.tb_read_accum(self._ctx, _np_ptr(out), _np_ptr(jit) if jittered else None))
         return (out, jit) if jittered else out
+
+    # -- render states ----------------------------------------------------
+    def BeginAccumulation(self, width, height, outputSettings=None, time_seed=0.0, first_frame=0):
+        """The context holds the empty state [first_frame, first_frame): the next Render with the same size, settings and time seed renders
+        frames first_frame, first_frame + 1, ... onto zeroed surfaces (tb_state_begin)."""
+        self._check(self._L.tb_state_begin(self._ctx, width, height, C.byref(outputSettings) if outputSettings is not None else None, time_seed, first_frame))
+        self.width, self.height = width, height
+
+    def SaveState(self, path):
+        """Surfaces, frame range, settings, camera, tile assignment and digests into one file, atomically (tb_state_save)."""
+        self._check(self._L.tb_state_save(self._ctx, os.fsencode(path)))
+
+    def LoadState(self, path, add=False, any_scene=False):
+        """add=False: the context becomes the file's state and a following Render continues it bit for bit.  add=True: the file's sums are added
+        to the context's (adjacent frame ranges; the fp32 sum of the partial sums).  any_scene: do not compare the scene digests."""
+        flags = (TB_STATE_ADD if add else TB_STATE_REPLACE) | (TB_STATE_ANY_SCENE if any_scene else 0)
+        self._check(self._L.tb_state_load(self._ctx, os.fsencode(path), flags))
+        if not add:
+            info = StateInfo(path)
+            self.width, self.height = info.width, info.height
+
+    def AccumDigest(self):
+        """(output digest, jittered digest) computed on the device from the surfaces as they lie in HBM (tb_accum_digest)."""
+        d = (C.c_uint64 * 2)()
+        self._check(self._L.tb_accum_digest(self._ctx, d))
+        return int(d[0]), int(d[1])
+
+    def SceneDigest(self):
+        d = C.c_uint64()
+        self._check(self._L.tb_scene_digest(self._ctx, C.byref(d)))
+        return d.value
 
     def RenderRealTime(self, width, height, outputSettings=None, denoiserSettings=None, time_seed=0.0):
         """One displayed frame of RenderMode::RealTime: 1 spp + TAA + a-trous denoiser + albedo composite + TAA (TracerBoy.cpp:2677-3160)."""

@@ -3,6 +3,7 @@
  *                 [--builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu] [--blue-noise 0|1] [--tonemap 0..7] [--exposure E|auto]
  *                 [--out frame.png|frame.pfm|frame.exr]
  *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C] [--adaptive-test frame|call]]
+ *                 [--save-state f.tbs] [--resume f.tbs] [--add g.tbs]... [--frames A:B] [--checkpoint-every N]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -23,7 +24,15 @@
  * 64) until N frames are rendered or no pixel is live; one line per call: frames so far, live pixels at the call's start, milliseconds.  With
  * --ranks every rank runs the schedule over its own tiles.  --adaptive-test call (option "adaptive_test" = 1; default frame): a pixel is tested once
  * per call, at the call's first frame, and the live ones get all C frames at the frame-group kernels' speed -- the form to prefer for scenes that
- * are fetched from memory. */
+ * are fetched from memory.
+ *
+ * Render states (tb_state_begin / tb_state_save / tb_state_load): --save-state f writes the accumulation after the render;
+ * --resume f loads one and renders on to --spp frames in all -- bit-identical to the render that was never interrupted -- or, without --spp or with
+ * no more than the file holds, renders nothing and just writes the picture; --add g (repeatable, applied in order after --resume) adds states of
+ * adjacent frame ranges: the merge tool of an spp split; --frames A:B renders the frames [A, B) instead of --spp frames from 0, for one job of
+ * such a split; --checkpoint-every N renders in calls of N frames (with --adaptive: after every call of its schedule) and saves to the
+ * --save-state path after each.  A resumed render takes size, settings and time seed from the file; flags that contradict it are refused.
+ * Not together with --ranks N > 1 (exit status 2): the gather moves the output surface only, rank 0 would not hold a complete state. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -121,15 +130,17 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
     float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
+    std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
+    bool sppSet = false, timeSet = false;
     for (int i = 2; i + 1 < argc; i += 2) {
         std::string k = argv[i]; const char* v = argv[i + 1];
-        if (k == "--width") W = (uint32_t)atoi(v); else if (k == "--height") H = (uint32_t)atoi(v); else if (k == "--spp") spp = (uint32_t)atoi(v);
-        else if (k == "--depth") depth = atoi(v); else if (k == "--seed-time") t = (float)atof(v); else if (k == "--device") device = atoi(v);
+        if (k == "--width") W = (uint32_t)atoi(v); else if (k == "--height") H = (uint32_t)atoi(v); else if (k == "--spp") { spp = (uint32_t)atoi(v); sppSet = true; }
+        else if (k == "--depth") depth = atoi(v); else if (k == "--seed-time") { t = (float)atof(v); timeSet = true; } else if (k == "--device") device = atoi(v);
         else if (k == "--builder") builder = !strcmp(v, "sah") ? 1 : !strcmp(v, "lbvh-gpu") ? 2 : !strcmp(v, "treelets") ? 3 : !strcmp(v,
             "treelets-gpu") ? 4 : 0; /* tb_set_option "bvh_builder" */ else if (k == "--blue-noise") blue = atoi(v); else if (k == "--out") out = v;
             else if (k == "--ranks") ranks = atoi(v);
@@ -137,6 +148,10 @@ int main(int argc, char** argv)
         else if (k == "--adaptive-chunk") adaptiveChunk = atoll(v);
         else if (k == "--adaptive-test") { if (!strcmp(v, "call")) adaptiveTest = 1; else if (!strcmp(v, "frame")) adaptiveTest = 0;
             else { fprintf(stderr, "--adaptive-test is frame or call\n"); return 2; } }
+        else if (k == "--save-state") saveState = v; else if (k == "--resume") resume = v; else if (k == "--add") adds.push_back(v);
+        else if (k == "--checkpoint-every") checkpointEvery = atoll(v);
+        else if (k == "--frames") { char* end = nullptr; frameA = strtoll(v, &end, 10); frameB = end && *end == ':' ? strtoll(end + 1, &end, 10) : -1;
+            if (frameA < 0 || frameB < frameA || frameB > 0xffffffffll || !end || *end) { fprintf(stderr, "--frames is A:B with 0 <= A <= B\n"); return 2; } }
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -147,6 +162,12 @@ int main(int argc, char** argv)
     const bool forceRccl = getenv("TB_CLI_FORCE_RCCL") && atoi(getenv("TB_CLI_FORCE_RCCL")) != 0;
     if (ranks < 1) { fprintf(stderr, "--ranks must be at least 1\n"); return 2; }
     if (adaptiveAfter < 0 || adaptiveChunk < 1) { fprintf(stderr, "--adaptive-after must not be negative, --adaptive-chunk must be at least 1\n"); return 2; }
+    const bool states = !saveState.empty() || !resume.empty() || !adds.empty() || frameA >= 0 || checkpointEvery != 0;
+    if (states && ranks > 1) { fprintf(stderr,
+        "--save-state, --resume, --add, --frames and --checkpoint-every do not go with --ranks: the gather moves the output surface only\n"); return 2; }
+    if (checkpointEvery < 0 || (checkpointEvery > 0 && saveState.empty())) { fprintf(stderr, "--checkpoint-every N needs N >= 1 and --save-state\n"); return 2; }
+    if (frameA >= 0 && (sppSet || !resume.empty())) { fprintf(stderr, "--frames A:B stands in place of --spp and starts its own accumulation (no --resume)\n"); return 2; }
+    if (!adds.empty() && resume.empty()) { fprintf(stderr, "--add merges into the state --resume loads\n"); return 2; }
     if (ranks > 1 && !envRank) return spawnRanks(argc, argv, ranks);
     if (envRank && (!getenv("TB_CLI_WORLD") || atoi(getenv("TB_CLI_WORLD")) < 1 || atoi(envRank) < 0 || atoi(envRank) >= atoi(getenv("TB_CLI_WORLD")) ||
                     (atoi(getenv("TB_CLI_WORLD")) > 1 && !getenv("TB_CLI_ID_FILE")))) {
@@ -163,6 +184,7 @@ int main(int argc, char** argv)
     if ((rc = tb_load_scene(ctx, scene.c_str()))) return fail(ctx, "tb_load_scene", rc);
     double loadS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     tb_scene_info info; tb_scene_info_get(ctx, &info);
+    const uint32_t argWidth = W, argHeight = H;
     if (!W) W = info.filmWidth ? info.filmWidth : 1920;
     if (!H) H = info.filmHeight ? info.filmHeight : 1080;
     tb_output_settings s; tb_default_output_settings(&s);
@@ -172,28 +194,68 @@ int main(int argc, char** argv)
     if (world > 1 && (rc = tb_set_tile_assignment(ctx, (uint32_t)rank, (uint32_t)world, TILE, TILE))) return fail(ctx, "tb_set_tile_assignment", rc);
     auto r0 = std::chrono::steady_clock::now();
     float ms = 0.0f;
-    if (adaptive < 0.0f) {
-        if ((rc = tb_render(ctx, W, H, spp, &s, t))) return fail(ctx, "tb_render", rc);
-        ms = tb_last_render_ms(ctx);
-    } else {
+    if (adaptive >= 0.0f) { /* before a state is loaded: the file's values of these options must be the context's */
         s.ConvergencePercentage = adaptive;
         if ((rc = tb_set_option(ctx, "adaptive", 1)) || (rc = tb_set_option(ctx, "adaptive_min_frames", adaptiveAfter)) ||
             (rc = tb_set_option(ctx, "adaptive_test", adaptiveTest))) return fail(ctx, "tb_set_option", rc);
-        uint32_t done = (uint32_t)std::min<long long>(adaptiveAfter + 1, spp); /* the plain call: no pixel can skip before frame F + 1 */
-        if ((rc = tb_render(ctx, W, H, done, &s, t))) return fail(ctx, "tb_render", rc);
-        ms = tb_last_render_ms(ctx);
-        while (done < spp) {
-            const uint32_t n = (uint32_t)std::min<long long>(adaptiveChunk, (long long)spp - done);
+    }
+    /* `done`: the index of the next frame; the render goes on to frame `target` */
+    uint32_t done = 0, target = spp;
+    if (!resume.empty()) {
+        if ((rc = tb_state_load(ctx, resume.c_str(), TB_STATE_REPLACE))) return fail(ctx, "tb_state_load", rc);
+        for (const std::string& a : adds) if ((rc = tb_state_load(ctx, a.c_str(), TB_STATE_ADD))) return fail(ctx, ("tb_state_load (--add " + a + ")").c_str(), rc);
+        tb_state_info held; char err[256] = "";
+        if ((rc = tb_state_info_read(resume.c_str(), &held, err, sizeof err))) { fprintf(stderr, "tracerboy-hip: %s\n", err); tb_destroy(ctx); return 1; }
+        /* the state decides size, settings and time seed: a flag that contradicts it would make tb_render start over at frame 0 */
+        if ((argWidth && argWidth != held.width) || (argHeight && argHeight != held.height) || (depth >= 0 && depth != held.settings.MaxBounces) ||
+            (blue >= 0 && (uint32_t)blue != held.settings.EnableBlueNoise) || (timeSet && t != held.time_seed)) {
+            fprintf(stderr, "tracerboy-hip: --width / --height / --depth / --blue-noise / --seed-time contradict the state in %s\n", resume.c_str());
+            tb_destroy(ctx); return 2; }
+        W = held.width; H = held.height; t = held.time_seed;
+        const float convergence = s.ConvergencePercentage; s = held.settings; if (adaptive >= 0.0f) s.ConvergencePercentage = convergence;
+        done = tb_samples_rendered(ctx); /* after the --add files */
+        target = sppSet ? std::max(spp, done) : done;
+    } else if (frameA >= 0) {
+        if ((rc = tb_state_begin(ctx, W, H, &s, t, (uint32_t)frameA))) return fail(ctx, "tb_state_begin", rc);
+        done = (uint32_t)frameA; target = (uint32_t)frameB;
+    }
+    const uint32_t start = done;
+    auto checkpoint = [&]() { return checkpointEvery > 0 ? tb_state_save(ctx, saveState.c_str()) : 0; };
+    if (adaptive < 0.0f) {
+        if (!states) { /* the plain render: one call */
+            if ((rc = tb_render(ctx, W, H, spp, &s, t))) return fail(ctx, "tb_render", rc);
+            ms = tb_last_render_ms(ctx); done = spp;
+        }
+        while (states && done < target) {
+            const uint32_t n = (uint32_t)std::min<long long>(checkpointEvery > 0 ? checkpointEvery : (long long)target - done, (long long)target - done);
+            if ((rc = tb_render(ctx, W, H, n, &s, t))) return fail(ctx, "tb_render", rc);
+            ms += tb_last_render_ms(ctx); done += n;
+            if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+        }
+    } else {
+        /* the plain call: no pixel can skip before frame F + 1; a resumed state that is past it goes straight on with the adaptive calls */
+        const uint32_t plainEnd = (uint32_t)std::min<long long>(adaptiveAfter + 1, target);
+        if (done < plainEnd || !states) {
+            if ((rc = tb_render(ctx, W, H, plainEnd - done, &s, t))) return fail(ctx, "tb_render", rc);
+            ms = tb_last_render_ms(ctx); done = plainEnd;
+            if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+        }
+        while (done < target) {
+            /* the calls keep the grid of an uninterrupted schedule: with --adaptive-test call the pixels are tested at those frames */
+            const long long toBoundary = adaptiveChunk - ((long long)(done - plainEnd) % adaptiveChunk);
+            const uint32_t n = (uint32_t)std::min<long long>(toBoundary, (long long)target - done);
             if ((rc = tb_render(ctx, W, H, n, &s, t))) return fail(ctx, "tb_render", rc);
             const float callMs = tb_last_render_ms(ctx);
             const long long live = (long long)tb_get_option(ctx, "last_live_pixels");
             done += n; ms += callMs;
             if (world > 1) printf("adaptive rank %d: %u frames, %lld live pixels, %.3f ms\n", rank, done, live, callMs);
             else printf("adaptive: %u frames, %lld live pixels, %.3f ms\n", done, live, callMs);
+            if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
             if (live == 0) break;
         }
-        spp = done;
     }
+    spp = done;
+    if (!saveState.empty() && (rc = tb_state_save(ctx, saveState.c_str()))) return fail(ctx, "tb_state_save", rc);
     if (world > 1 || forceRccl) {
         /* ---- the gather: packed tiles of every rank -> rank 0's accumulation surface ---- */
         Rccl nccl; if (!nccl.load()) { tb_destroy(ctx); return 1; }
@@ -266,7 +328,7 @@ int main(int argc, char** argv)
     }
     printf("%s: %u triangles, %ux%u x %u spp, depth %d, %d GPU%s: %.2f ms (%.1f Msamples/s), scene load + BVH %.2f s -> %s\n",
            scene.c_str(), info.numTriangles, W, H, spp, s.MaxBounces, world, world > 1 ? "s (tiles gathered over RCCL)" : "", ms,
-               (double)W * H * spp / (ms * 1e3), loadS, out.c_str());
+               ms > 0.0f ? (double)W * H * (spp - start) / (ms * 1e3) : 0.0, loadS, out.c_str());
     tb_destroy(ctx);
     return 0;
 }

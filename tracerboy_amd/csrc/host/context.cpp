@@ -6,6 +6,7 @@
  * launches a HIP kernel, and tb_create fails when no HIP device is usable.
  */
 #include "context_internal.h"
+#include "tb_state.h"
 
 using namespace tbhost;
 using namespace tbctx;
@@ -126,7 +127,7 @@ void tb_destroy(tb_context* c)
         c->fgSamples[1].release(); c->fgHits[0].release(); c->fgHits[1].release(); c->fgSlotLog[0].release(); c->fgSlotLog[1].release();
         c->stackOverflow.release();
     c->regionCost.release(); c->regionOrder[0].release(); c->regionOrder[1].release(); c->regionCostKey = ~0ull;
-    c->liveList.release();
+    c->liveList.release(); releaseStateBuffers(c);
     c->postOut.release(); c->postRgba8.release(); c->postHistogram.release(); c->postAverage.release();
     for (int i = 0; i < 2; i++) { c->rtIndirect[i].release(); c->rtMoment[i].release(); c->rtFinal[i].release(); c->rtDenoise[i].release(); }
     c->rtComposited.release();
@@ -165,8 +166,6 @@ static int shareSceneWithPeers(tb_context* c)
     }
     return TB_OK;
 }
-#define TB_REFUSE_PEER(c) do { if ((c) && (c)->groupOwner) return fail((c), TB_E_INVALID, \
-    "this context is a member of a multi-device group: call the group's context"); } while (0)
 
 int tb_load_scene(tb_context* c, const char* path)
 {
@@ -217,7 +216,7 @@ int tb_set_camera(tb_context* c, const tb_camera* cam)
 {
     if (!c || !cam) return TB_E_INVALID;
     if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-    c->camera = *cam; c->ds.config.CameraLensHeight = cam->LensHeight; c->scene.config.CameraLensHeight = cam->LensHeight; c->samplesRendered = 0;
+    c->camera = *cam; c->ds.config.CameraLensHeight = cam->LensHeight; c->scene.config.CameraLensHeight = cam->LensHeight; resetHistory(c);
     for (tb_context* p : c->peers) { const int rc = tb_set_camera(p, cam); if (rc != TB_OK) return rc; }
     return TB_OK;
 }
@@ -237,7 +236,7 @@ int tb_set_material(tb_context* c, int id, const TbMaterial* in)
         HIP_TRY(hipMemcpy((void*)&c->ds.materials[id].m, in, sizeof *in, hipMemcpyHostToDevice));
         c->sceneFeatures = sceneFeatureMask(c->scene);
         c->ds.textureUse = sceneTextureUse(c); /* the edit may be the scene's first texture or normal map */
-        c->samplesRendered = 0;
+        resetHistory(c); c->materialEdits++;
         for (tb_context* p : c->peers) { const int rc = tb_set_material(p, id, in); if (rc != TB_OK) return rc; }
         return TB_OK;
     });
@@ -252,7 +251,7 @@ static int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const 
     if (opt<OPT_aov>(c)) return fail(c, TB_E_UNSUPPORTED, "tb_render: AOV targets are not gathered across the devices of a group");
     std::vector<tb_context*> all; all.push_back(c); for (tb_context* p : c->peers) all.push_back(p);
     for (uint32_t i = 0; i < world; i++) if (all[i]->tiles.world != world || all[i]->tiles.rank != i) { all[i]->tiles = TbTileMap{i, world, 64, 64};
-        all[i]->samplesRendered = 0; }
+        resetHistory(all[i]); }
     for (uint32_t i = world; i-- > 0;) { /* the peers first: their launches are in flight while the owner's are enqueued */
         tb_context* x = all[i];
         const int rc = guarded(x, [&]() { x->options = c->options; x->selX = c->selX; x->selY = c->selY; x->lastRenderRealtime = false; return renderImpl(x, W,
@@ -599,7 +598,7 @@ int tb_read_split_profile(tb_context* c, uint64_t* out16)
     });
 }
 
-void tb_invalidate_history(tb_context* c) { if (c) { c->samplesRendered = 0; for (tb_context* p : c->peers) p->samplesRendered = 0; } }
+void tb_invalidate_history(tb_context* c) { if (c) { resetHistory(c); for (tb_context* p : c->peers) resetHistory(p); } }
 uint32_t tb_samples_rendered(tb_context* c) { return c ? c->samplesRendered : 0; }
 /* (a group renders the selection on the device that owns the pixel's tile; ReadbackStats reads the owner's buffer) */
 int tb_select_pixel(tb_context* c, uint32_t x, uint32_t y) { if (!c) return TB_E_INVALID; c->selX = x; c->selY = y; return TB_OK; }
@@ -610,7 +609,7 @@ int tb_set_tile_assignment(tb_context* c, uint32_t rank, uint32_t world, uint32_
     if (!c || world == 0 || rank >= world || tw == 0 || th == 0) return c ? fail(c, TB_E_INVALID, "tb_set_tile_assignment: bad arguments") : TB_E_INVALID;
     if (world > 1 && (tw % 16 || th % 16)) return fail(c, TB_E_INVALID,
         "tb_set_tile_assignment: tile width and height must be multiples of 16 (a workgroup renders 16x16 pixels)");
-    c->tiles = TbTileMap{rank, world, tw, th}; c->samplesRendered = 0;
+    c->tiles = TbTileMap{rank, world, tw, th}; resetHistory(c);
     return TB_OK;
 }
 
@@ -681,7 +680,7 @@ int tb_set_option(tb_context* c, const char* name, int64_t v)
     if (v && ((k == OPT_adaptive && opt<OPT_count_rays>(c)) || (k == OPT_count_rays && opt<OPT_adaptive>(c))))
         return fail(c, TB_E_INVALID, "tb_set_option: options \"adaptive\" and \"count_rays\" exclude each other (the counting kernels have no adaptive copy)");
     c->options.value[k] = v; c->options.isSet[k] = true;
-    if (kOptions[k].flags & OPT_RESETS_HISTORY) c->samplesRendered = 0;
+    if (kOptions[k].flags & OPT_RESETS_HISTORY) resetHistory(c);
     return TB_OK;
 }
 int64_t tb_get_option(tb_context* c, const char* name)
@@ -720,6 +719,10 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "last_split_waves")) return c->lastSplitWaves; /* traversal waves * 100 + shading waves per workgroup of the last pipeline-4 launch */
     /* the pipeline the last render actually ran (2 / 3 fall back to 0 for feature sets they lack) */
     if (!strcmp(name, "last_pipeline")) return c->lastPipeline;
+    /* render states: GPU microseconds (HIP events) of the last digest of the two surfaces / of the last TB_STATE_ADD's sum; the first frame held */
+    if (!strcmp(name, "last_state_digest_us")) return (int64_t)(c->lastStateDigestMs * 1000.0f + 0.5f);
+    if (!strcmp(name, "last_state_add_us")) return (int64_t)(c->lastStateAddMs * 1000.0f + 0.5f);
+    if (!strcmp(name, "state_first_frame")) return c->firstFrame;
     if (!strcmp(name, "last_copy_waves")) return c->lastCopyWaves;
     /* the adaptive launch: did the last call run it; the owned pixels that were live at its first frame (all owned pixels of a call that did not run
      * it) -- a device word: reading it waits for the call.  A group's owner counts its peers' too. */
@@ -743,6 +746,30 @@ int64_t tb_get_option(tb_context* c, const char* name)
 }
 
 static void fillView(const HostScene& s, TbSceneView* v);
+} // extern "C"
+/* The scene digest (include/tb_state.h): every array of the kernel seam, each prefixed by its length.  The camera's lens height, which
+ * tb_set_camera writes into the config constants, is left out: the camera travels with a render state on its own. */
+uint64_t tbctx::sceneDigestOf(const HostScene& s)
+{
+    TbSceneView v; fillView(s, &v);
+    TbStateDigest d{0, 0};
+    tb_state_digest_array(&d, v.bvh, v.bvhBytes);
+    tb_state_digest_array(&d, v.hitGroups, (uint64_t)v.numHitGroups * sizeof(TbHitGroupRecord));
+    tb_state_digest_array(&d, v.indexBuffer, (uint64_t)v.numIndices * 4u);
+    tb_state_digest_array(&d, v.vertexBuffer, (uint64_t)v.numVertexFloats * 4u);
+    tb_state_digest_array(&d, v.materials, (uint64_t)v.numMaterials * sizeof(TbMaterial));
+    tb_state_digest_array(&d, v.textureData, (uint64_t)v.numTextureData * sizeof(TbTextureData));
+    tb_state_digest_array(&d, v.lights, (uint64_t)v.numLights * sizeof(TbLight));
+    tb_state_digest_array(&d, v.images, (uint64_t)v.numImages * sizeof(TbImageDesc));
+    tb_state_digest_array(&d, v.texelPool, (uint64_t)s.texelPool.size() * sizeof(TbFloat4));
+    tb_state_digest_array(&d, v.envMap, (uint64_t)v.envWidth * v.envHeight * sizeof(TbFloat4));
+    TbConfigConstants config = v.config; config.CameraLensHeight = 0.0f;
+    tb_state_digest_array(&d, &config, sizeof config);
+    tb_state_digest_array(&d, v.tlas, v.tlasBytes);
+    tb_state_digest_array(&d, v.blasOffsets, v.blasOffsets ? ((uint64_t)v.numBlas + 1u) * 4u : 0u);
+    return d.sum;
+}
+extern "C" {
 int tb_host_scene_view(tb_context* c, TbSceneView* v)
 {
     if (!c || !v) return TB_E_INVALID;
@@ -876,6 +903,7 @@ static void fillView(const HostScene& s, TbSceneView* v)
 }
 
 int tb_host_scene_view_get(tb_host_scene* s, TbSceneView* v) { if (!s || !v) return TB_E_INVALID; fillView(s->scene, v); return TB_OK; }
+int tb_host_scene_digest(tb_host_scene* s, uint64_t* out) { if (!s || !out) return TB_E_INVALID; *out = sceneDigestOf(s->scene); return TB_OK; }
 int tb_host_scene_camera(tb_host_scene* s, tb_camera* cam) { if (!s || !cam) return TB_E_INVALID; *cam = s->scene.camera; return TB_OK; }
 int tb_host_scene_info(tb_host_scene* h, tb_scene_info* o)
 {

@@ -3,6 +3,7 @@
  *   context.cpp         the C ABI (include/tracerboy_hip.h): create / destroy, scene loads, options, read-backs, output stage, real-time chain, groups
  *   context_scene.cpp   finalizeScene: BVH builds on the GPU, node orders, layout C, uploads, the LDS scene image
  *   context_render.cpp  renderImpl, a sequence of named steps, and the pipelines it dispatches to
+ *   render_state.cpp    render states: begin at a frame, save, load, merge
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
 #pragma once
@@ -115,6 +116,11 @@ struct tb_context {
     uint64_t wfCapacity = 0, wfSampleCapacity = 0;
     int lastPipeline = 0;
     uint32_t samplesRendered = 0;
+    /* render states (render_state.cpp): the surfaces hold the samples of frames [firstFrame, samplesRendered) */
+    uint32_t firstFrame = 0;
+    DevBuf stateScratch; /* the digest's per-workgroup partials and its two results (state_launch.h) */
+    hipEvent_t evState[2] = {nullptr, nullptr}; float lastStateDigestMs = 0.0f, lastStateAddMs = 0.0f; /* options last_state_digest_us / last_state_add_us */
+    uint64_t sceneDigest = 0, sceneDigestKey = ~0ull; uint32_t materialEdits = 0; /* tb_scene_digest, cached per (sceneGeneration, materialEdits) */
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -157,6 +163,11 @@ namespace tbctx {
     } while (0)
 
 int fail(tb_context* c, int code, const std::string& msg);
+/* forget the accumulated frames: the next render starts at frame 0 (where the kernels overwrite the surfaces instead of adding to them) */
+inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; }
+/* an entry point that only a group's own context may be asked */
+#define TB_REFUSE_PEER(c) do { if ((c) && (c)->groupOwner) return fail((c), TB_E_INVALID, \
+    "this context is a member of a multi-device group: call the group's context"); } while (0)
 template <Opt K> inline int64_t opt(const tb_context* c) { return c->options.get<K>(); }
 
 /* Every entry point runs on its context's device and hands the calling thread back the device it came with: a host that shares the
@@ -203,7 +214,10 @@ uint32_t sceneTextureUse(const tb_context* c);
 uint32_t settingsFeatureMask(const tb_context* c, const tb_output_settings& s, bool aov);
 void ensureCompactNodes(tb_context* c);
 void finalizeScene(tb_context* c, bool build = true); /* build = false: c->scene already holds a built, reordered tree (a peer of a multi-device group) */
+uint64_t sceneDigestOf(const HostScene& s); /* context.cpp */
+void releaseStateBuffers(tb_context* c);    /* render_state.cpp */
 /* context_render.cpp */
+bool historyRelevantChange(const tb_output_settings& a, const tb_output_settings& b);
 int deviceCUs(tb_context* c);
 std::string splitAbortMessage(tb_context* c, bool clear = true);
 int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* settings, float timeSeed, bool sync);

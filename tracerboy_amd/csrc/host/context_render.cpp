@@ -437,9 +437,9 @@ static int beginCall(RenderCall& r, const tb_output_settings* settings)
         ensure(c->output, bytes); ensure(c->jittered, bytes);
         HIP_TRY(hipMemsetAsync(c->output.p, 0, bytes, c->stream)); HIP_TRY(hipMemsetAsync(c->jittered.p, 0, bytes, c->stream));
         for (DevBuf& b : c->aov) b.release();
-        c->width = W; c->height = H; c->samplesRendered = 0;
+        c->width = W; c->height = H; resetHistory(c);
     }
-    if (c->haveLastSettings && (historyRelevantChange(r.s, c->lastSettings) || r.timeSeed != c->lastTime)) c->samplesRendered = 0;
+    if (c->haveLastSettings && (historyRelevantChange(r.s, c->lastSettings) || r.timeSeed != c->lastTime)) resetHistory(c);
     c->lastSettings = r.s; c->haveLastSettings = true; c->lastTime = r.timeSeed;
     return TB_OK;
 }

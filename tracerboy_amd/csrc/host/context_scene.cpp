@@ -395,7 +395,7 @@ void finalizeScene(tb_context* c, bool build)
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->sceneFeatures = sceneFeatureMask(s);
     c->hasScene = true;
-    c->samplesRendered = 0;
+    resetHistory(c);
 }
 
 } // namespace tbctx
