@@ -676,21 +676,25 @@ def _read_device_u32(ptr, n):
     return buf
 
 
+# (520, 520, 1500): 33 x 33 = 1089 regions -- more than the 1024 threads of region_order_kernel, so its key loop takes a second pass -- and with 3 groups
+# 3267 items: three whole chunks of 1024 and a partial one, base[0] / base[1] carried across them; lateFrom = 3267 - 1500 = 1767 lies inside the
+# second chunk and is no multiple of 1024.  (328, 200, 300): 273 regions, 819 items, one chunk, one pass.
+@pytest.mark.parametrize("W,H,late", [(328, 200, 300), (520, 520, 1500)])
 @pytest.mark.parametrize("world,rank", [(1, 0), (3, 1)])
-def test_costly_regions_first_is_a_permutation_and_changes_no_bit(gpu_tb, settings, world, rank):
+def test_costly_regions_first_is_a_permutation_and_changes_no_bit(gpu_tb, settings, world, rank, W, H, late):
     """Costly regions first (pt_scene.h TbDeviceTargets::regionOrder, option costly_first): the kernels with interior walks count long walks per region
     and the next launch hands those regions out first.  The table every launch reads must be a permutation of its regions whatever the counts are
     (a region handed out twice or never is a wrong picture), counted regions in front; and the picture is the one-pixel-per-lane kernel's bits with
     the table empty, filled, and filled under back-to-back asynchronous launches that count while the next table is built."""
     gpu_tb.LoadProcedural(1, 20000, 5)               # glass blobs: feature set with interior walks, fetched from memory
-    W, H, F = 328, 200, 6                            # last region row half outside the frame
+    F = 6                                            # last region row half outside the frame
     s = copy.copy(settings); s.MaxBounces = 6
     gpu_tb.SetTileAssignment(rank, world, 64, 64)
     try:
         gpu_tb.SetOption("frame_group", -1); gpu_tb.InvalidateHistory(); gpu_tb.Render(W, H, F, s, 0.0); ref = gpu_tb.ReadAccumulation(jittered=True)
         gpu_tb.SetOption("frame_group", 2)
         for rnd in range(3):
-            if rnd == 2: gpu_tb.SetOption("costly_late_samples", 256 * 2 * 300)   # only the last 300 items of the usual list count as late
+            if rnd == 2: gpu_tb.SetOption("costly_late_samples", 256 * 2 * late)   # only the last `late` items of the usual list count as late
             gpu_tb.InvalidateHistory(); gpu_tb.Render(W, H, F, s, 0.0)
             assert gpu_tb.GetOption("last_plan_costly_first") == 1
             got = gpu_tb.ReadAccumulation(jittered=True)
@@ -702,13 +706,15 @@ def test_costly_regions_first_is_a_permutation_and_changes_no_bit(gpu_tb, settin
                 usual = [(g << 20) | r for g in range(groups) for r in range(regions)]
                 assert sorted(order[1:].tolist()) == usual                              # every item once
                 moved = int(order[0])
+                print("costly regions first %dx%d, round %d: %d of %d items moved to the front" % (W, H, rnd, moved, len(usual)))
                 assert (rnd == 0) == (moved == 0)                                       # the first launch found no counts; it left some
                 pos = {v: i for i, v in enumerate(usual)}
                 for part in (order[1:1 + moved], order[1 + moved:]):                    # both parts in their usual order
                     assert np.all(np.diff(np.array([pos[int(v)] for v in part], np.int64)) > 0)
                 bx = (W + 15) // 16
                 c_of = lambda r: int(cost[(r // bx) << 10 | (r % bx)])
-                assert all(pos[int(v)] >= (len(usual) - 300 if rnd == 2 else 0) for v in order[1:1 + moved])
+                assert len(usual) == regions * groups > late
+                assert all(pos[int(v)] >= (len(usual) - late if rnd == 2 else 0) for v in order[1:1 + moved])
                 assert all(c_of(int(v) & 0xfffff) > 0 for v in order[1:1 + moved])      # (a count may have arrived after the table was built: no claim about the rest)
             assert world > 1 or int(cost.sum()) > 0
         for _ in range(4):

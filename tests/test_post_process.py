@@ -169,6 +169,120 @@ def test_image_writers_round_trip(built, tmp_path):
     assert np.array_equal(rows[::-1], f[..., :3])
 
 
+# ---- synthetic accumulation surfaces: what a render of cornell-box never holds ---------------------------------------
+SW, SH = 70, 50                                                 # ragged against the 16x16 groups: the last column of groups has 6 x 16 pixels
+F32 = np.float32
+EPSILON = F32(0.00001)                                          # GenerateHistogramCS.hlsl:21
+
+
+def luma32(c):
+    """ColorToLuma in float32, operation for operation."""
+    c = np.asarray(c, F32)
+    return (c[..., 0] * F32(0.212671) + c[..., 1] * F32(0.715160)) + c[..., 2] * F32(0.072169)
+
+
+def ulps(x, ks):
+    """float32 x moved by k units in the last place, for each k (x > 0)."""
+    return [(F32(x).view(np.uint32) + np.uint32(k)).view(F32) if k >= 0 else (F32(x).view(np.uint32) - np.uint32(-k)).view(F32) for k in ks]
+
+
+def bin_centre(b):
+    """A luminance in the middle of histogram bin b (1 .. 254): log2 L = -10 + (b - 0.5) / 254 * 16."""
+    return np.exp2(-10.0 + (np.asarray(b, np.float64) - 0.5) / 254.0 * 16.0)
+
+
+def special_pixels():
+    """(r, g, b, w) sums: the values on which a host compiler and the device may part.  Fewer than 2 % of the frame."""
+    inf, nan, den = F32(np.inf), F32(np.nan), F32(1e-41)
+    px = [(0, 0, 0, 0), (1.5, 0.25, 3.0, 0), (0.5, -0.25, 0.125, 0),                       # w = 0: 0 / 0, x / 0 of either sign
+          (-1.2, 2.0, 0.8, 4), (0.4, 0.4, -0.004, 4),                                       # a negative component
+          (inf, 1.0, 1.0, 4), (1.0, 1.0, inf, 4), (2.0, inf, inf, 4),
+          (nan, 1.0, 1.0, 4), (0.5, 0.5, nan, 4), (nan, nan, nan, 4),
+          (den, den, den, 4), (den, 2.0, 2.0, 4), (F32(4e-41), F32(8e-41), 0, 4)]          # sums and quotients that are denormal
+    grey = [v for v in ulps(EPSILON, range(-40, 41)) if luma32([v, v, v]) == EPSILON]      # luminance exactly the cut, and the values next to it
+    assert grey, "no grey whose float32 luminance is exactly float32(0.00001)"
+    for v in (ulps(grey[0], [-3])[0], grey[0], ulps(grey[-1], [3])[0]):
+        px.append((v * F32(4), v * F32(4), v * F32(4), 4))
+    sc = F32(0.8) - F32(0.04)                                                               # khronos: min component against 0.08, peak against 0.8 - 0.04
+    for v in ulps(F32(0.08), [-1, 0, 1]):
+        px.append((v * 4, 1.2, 2.0, 4))
+    for v in ulps(sc, [-1, 0, 1]):
+        px.append((v * 4, 0, 0, 4))                                                         # offset 0: the peak is the component itself
+    for v in ulps(sc + F32(0.04), [-2, -1, 0, 1, 2]):
+        px.append((v * 4, 2.0, 1.6, 4))                                                     # offset 0.04
+    m, l = F32(0.22), F32(0.4)                                                              # GT: x / m reaches 1 at m, w2 switches at m + l
+    for v in ulps(m, [-1, 0, 1]) + ulps(m + l, [-1, 0, 1]):
+        px.append((v * 4, v * 4, v * 4, 4))
+    for ev in (-12.47393, 4.026069):                                                        # AgX: log2 of the transformed colour against minEv / maxEv
+        for k in (0.5, 0.999, 1.001, 2.0):
+            v = F32(2.0 ** ev * k)
+            px.append((v * 4, v * 4, v * 4, 4))
+    return np.array(px, F32)
+
+
+def surface_p1():
+    """Luminance log-uniform over 2^-20 .. 2^10 (stratified, so that each of the 256 bins gets pixels: some under the 1e-5 cut, some past the last
+    bin's edge 2^6), random chroma, w = 4; rows 16 .. 19: each wave's 64 pixels (16 x 4 of a group) equal; rows 32 .. 35: 64 distinct bins in
+    each wave; the special pixels at random places."""
+    rng = np.random.default_rng(20)
+    a = np.zeros((SH, SW, 4), F32)
+    free = np.ones((SH, SW), bool)
+    y, x = np.meshgrid(np.arange(SH), np.arange(SW), indexing="ij")
+    one = (y >= 16) & (y < 20)
+    a[one, :3] = bin_centre(20 + 50 * (x[one] // 16))[:, None]
+    many = (y >= 32) & (y < 36)
+    a[many, :3] = bin_centre(1 + (37 * (x[many] // 16) + 16 * (y[many] - 32) + x[many] % 16) % 254)[:, None]
+    free &= ~one & ~many
+    sp = special_pixels()
+    assert len(sp) < 0.02 * SW * SH
+    at = rng.permutation(np.flatnonzero(free))[:len(sp)]
+    free.ravel()[at] = False
+    n = int(free.sum())
+    lum = np.exp2(-20.0 + 30.0 * (rng.permutation(n) + rng.uniform(0, 1, n)) / n)
+    chroma = rng.uniform(0.2, 1.0, (n, 3))
+    a[free, :3] = chroma * (lum / (chroma @ np.array([0.212671, 0.715160, 0.072169])))[:, None]
+    a[..., :3] *= F32(4); a[..., 3] = 4
+    a.reshape(-1, 4)[at] = sp
+    return a
+
+
+def surface_p2():
+    """Every pixel under the cut -- small, zero, negative -- so the mean's divisor W * H - bin 0 is 0."""
+    rng = np.random.default_rng(21)
+    a = np.empty((SH, SW, 4), F32)
+    a[..., :3] = np.exp2(rng.uniform(-40, -17.5, (SH, SW, 3))); a[..., 3] = 1
+    a[::7, ::5, :3] = 0; a[3::7, 1::5, :3] *= -1
+    return a * F32(3)
+
+
+def surface_p3():
+    return np.array([[[0.9, 0.3, 0.6, 2.0]]], F32)
+
+
+SURFACES = {"p1": surface_p1, "p2": surface_p2, "p3": surface_p3}
+
+
+def test_synthetic_surfaces_are_what_they_claim(built):
+    """By construction, checked with the oracle's own histogram before anything goes to a GPU: P1 leaves no bin empty, P2 leaves every bin but 0 empty."""
+    ps = post(TONEMAPS["clamp"], auto=1)
+    p1 = surface_p1()
+    h = ol.post_process(p1, ps)["histogram"]
+    print("P1: smallest bin count %d (bin %d), bin 0 %d, bin 255 %d" % (int(h.min()), int(h.argmin()), int(h[0]), int(h[255])))
+    assert h.sum() == SW * SH and h.min() > 0
+    with np.errstate(all="ignore"):
+        lum = luma32(p1[..., :3] / p1[..., 3:4])
+    assert (lum == EPSILON).any() and (lum < EPSILON).sum() == h[0] and np.isnan(lum).any() and np.isinf(lum).any()
+    # rows 16 .. 19: one bin in each wave; rows 32 .. 35: 64 bins in each whole wave
+    for y0, want in ((16, 1), (32, 64)):
+        for x0 in range(0, 64, 16):
+            one_wave = np.zeros_like(p1); one_wave[..., 3] = 1             # bin 0 everywhere else
+            one_wave[y0:y0 + 4, x0:x0 + 16] = p1[y0:y0 + 4, x0:x0 + 16]
+            assert np.count_nonzero(ol.post_process(one_wave, ps)["histogram"][1:]) == want
+    r = ol.post_process(surface_p2(), ps)
+    assert r["histogram"][0] == SW * SH and r["histogram"][1:].sum() == 0
+    assert r["averaged"] == np.inf                                          # q = 0xffffffff: exp2 of 2^32 / 254 * 16 - 10
+
+
 # ---- GPU: post_kernels.hip against the oracle -----------------------------------------------------------------------
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
@@ -210,6 +324,55 @@ def test_gpu_post_process_aov_output_types(gpu_tb, settings):
             gpu_tb.PostProcess(ps, outputType=4)   # motion vectors: surface of the real-time chain, not built
     finally:
         gpu_tb.SetOption("aov", 0)
+
+
+@pytest.fixture(scope="module")
+def synthetic(built, settings, tmp_path_factory):
+    """A context of its own (a loaded state brings its camera along) and one state file per synthetic surface."""
+    from tracerboy_amd import api
+    from test_render_state_host import default_info
+    d = tmp_path_factory.mktemp("post_surfaces")
+    tb = api.TracerBoy(0)
+    try:
+        tb.LoadScene(CORNELL)
+        info = default_info(first=0, next_frame=4, scene_digest=tb.SceneDigest(), settings=settings, camera=tb.GetCamera())
+        made = {}
+        for name, make in SURFACES.items():
+            a = make()
+            api.WriteStateFile(str(d / (name + ".tbs")), info, a, a)
+            made[name] = (str(d / (name + ".tbs")), a)
+        yield tb, made
+    finally:
+        tb.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(TONEMAPS))
+@pytest.mark.parametrize("surface", sorted(SURFACES))
+def test_gpu_post_process_synthetic_surfaces(synthetic, surface, name):
+    """post_kernels.hip on the surfaces above, loaded through a state file: every bin of the wave-ballot histogram, the zero divisor of the mean,
+    the float -> uint conversions and the 8-bit store on NaN, infinities, negatives and denormals, the tonemappers at their branch points, one
+    pixel.  rgba in bits (a NaN for a NaN: a host and a device NaN may differ in sign and payload, as in tests/test_math.py), rgba8 and the
+    averaged luminance exactly.  Exposure 1 without auto exposure, so that the branch points arrive at the tonemappers as they were written."""
+    tb, made = synthetic
+    path, a = made[surface]
+    tb.LoadState(path)
+    assert np.array_equal(bits(tb.ReadAccumulation()), bits(a))
+    for out_type in (0, 5):                                     # LIT, LUMINANCE
+        for auto in (0, 1):
+            for gam in (0, 1):
+                ps = post(TONEMAPS[name], exposure=1.0, auto=auto, gamma=gam)
+                what = "%s %s type %d auto %d gamma %d" % (surface, name, out_type, auto, gam)
+                f, b = tb.PostProcess(ps, outputType=out_type)
+                ref = ol.post_process(a, ps, output_type=out_type, frames_rendered=4)
+                same = (bits(f) == bits(ref["rgba"])) | (np.isnan(f) & np.isnan(ref["rgba"]))
+                assert same.all(), "%s: rgba differs in %d pixels, first at %s: sums %s" % (
+                    what, int((~same).any(-1).sum()), np.argwhere(~same)[0], a[tuple(np.argwhere(~same)[0][:2])])
+                assert np.array_equal(b, ref["rgba8"]), "%s: rgba8 differs in %d pixels, first at %s" % (
+                    what, int((b != ref["rgba8"]).any(-1).sum()), np.argwhere(b != ref["rgba8"])[0])
+                if auto and out_type == 0:
+                    got, want = F32(tb.AveragedLuminance()), F32(ref["averaged"])
+                    assert got.view(np.uint32) == want.view(np.uint32), "%s: averaged luminance %r, oracle %r" % (what, got, want)
 
 
 def test_exr_writer_layout(built, tmp_path):

@@ -82,7 +82,9 @@ def addends(n_words, seed):
 
 
 # ---- device digest = host digest, and state_add -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("w,h", [(1, 1), (3, 1), (17, 1), (64, 1), (65, 1), (70, 50)])
+# (1024, 513): 525 312 vectors, 1024 over the kernels' grid of 2048 workgroups x 256 lanes = 524 288 -- the digest's remainder loop takes a second
+# turn for 1024 lanes, state_add_kernel's paired loop runs for those and leaves a single add to every other lane.  The condition: w * h > 524 288.
+@pytest.mark.parametrize("w,h", [(1, 1), (3, 1), (17, 1), (64, 1), (65, 1), (70, 50), (1024, 513)])
 def test_device_digest_is_the_host_digest_and_add_is_float32_addition(built, settings, tmp_path, w, h):
     from tracerboy_amd import api
     with context() as tb:
@@ -106,6 +108,22 @@ def test_device_digest_is_the_host_digest_and_add_is_float32_addition(built, set
         assert same_state(state(tb), want)
         assert tb.AccumDigest() == (np_digest(want[0]), np_digest(want[1]))
         assert (tb.GetOption("state_first_frame"), tb.GetNumberOfSamplesSinceLastInvalidate()) == ((2, 9) if append else (0, 5))
+
+
+def test_device_digest_in_the_unrolled_loop(built, settings, tmp_path):
+    """state_digest_partials keeps four loads in flight while v + 3 * stride < nVec, stride = 524 288 vectors: the condition on the frame is
+    w * h > 3 * 524 288 = 1 572 864.  2048 x 769 = 1 574 912 is 2048 over it: the first 2048 lanes take one turn of the unrolled loop, every other
+    lane three turns of the remainder loop.  Digest only (one file of 50 MB); the sums of this size are the test above's."""
+    from tracerboy_amd import api
+    w, h = 2048, 769
+    assert w * h > 3 * 2048 * 256
+    with context() as tb:
+        info = default_info(first=2, next_frame=5, scene_digest=tb.SceneDigest(), settings=settings, camera=tb.GetCamera())
+        out, jit = payload(w * h * 4, 41).reshape(h, w, 4), payload(w * h * 4, 42).reshape(h, w, 4)
+        api.WriteStateFile(str(tmp_path / "big.tbs"), info, out, jit)
+        tb.LoadState(str(tmp_path / "big.tbs"))
+        assert tb.AccumDigest() == (np_digest(out), np_digest(jit)) == (api.StateDigest(out), api.StateDigest(jit))
+        assert same_state(state(tb), (out, jit))
 
 
 # ---- resume exactness -------------------------------------------------------------------------------------------------------------------
