@@ -1,5 +1,5 @@
 """-m gpu: a context gives back every device byte it took.  Option "debug_live_device_bytes" reads the library's own count of the device
-memory it holds (added where it allocates, taken back in DevBuf::release; every context of the process together).  It is exact and does not
+memory it holds (added where it allocates, taken back where DevBuf frees; every context of the process together).  It is exact and does not
 depend on other processes, which hipMemGetInfo on a shared device would.  Each test makes a fresh context beside the session's, runs one path
 through it, destroys it and asks for the count it found -- to the byte."""
 import copy
@@ -17,11 +17,11 @@ def live(tb):
     return tb.GetOption("debug_live_device_bytes")
 
 
-def _fresh_context_round_trip(gpu_tb, exercise):
-    """The count before a fresh context is made, the most it held while alive, and the count after it is destroyed."""
+def _fresh_context_round_trip(gpu_tb, exercise, devices=None):
+    """The count before a fresh context (or group, over `devices`) is made, the most it held while alive, and the count after it is destroyed."""
     from tracerboy_amd import api
     before = live(gpu_tb)
-    tb = api.TracerBoy(0)
+    tb = api.TracerBoy(0) if devices is None else api.TracerBoy(devices=devices)
     try:
         exercise(tb)
         held = live(gpu_tb) - before
@@ -30,8 +30,8 @@ def _fresh_context_round_trip(gpu_tb, exercise):
     return before, held, live(gpu_tb)
 
 
-def _assert_given_back(gpu_tb, exercise, what):
-    before, held, after = _fresh_context_round_trip(gpu_tb, exercise)
+def _assert_given_back(gpu_tb, exercise, what, devices=None):
+    before, held, after = _fresh_context_round_trip(gpu_tb, exercise, devices)
     assert held > 0, "%s: the counter saw no allocation (%d B)" % (what, held)
     assert after == before, "%s: %d B of device memory outlive the context (it held %d B)" % (what, after - before, held)
 
@@ -122,6 +122,72 @@ def test_tile_assignment_and_device_pack_give_back_everything(gpu_tb, settings):
         tb.PackOwnedTo(buf.data_ptr())
         assert float(buf[:, 3].max()) == 2.0
     _assert_given_back(gpu_tb, exercise, "tile assignment + PackOwnedTo")
+
+
+def test_group_on_one_device_gives_back_everything(gpu_tb, settings):
+    """(f) a group of two members on one device, 4 x 2 tiles of 64 x 64 so that both own tiles: the packed and gathered tiles, the events
+    between the members (the second asynchronous call waits for the first one's un-permute) and the peer's whole context."""
+    W, H = 200, 120
+
+    def exercise(tb):
+        assert tb._L.tb_group_size(tb._ctx) == 2
+        tb.LoadScene(CORNELL)
+        tb.Render(W, H, 2, settings, 0.0)
+        tb.Render(W, H, 2, settings, 0.0, sync=False); tb.Render(W, H, 2, settings, 0.0, sync=False); tb.Sync()
+        assert tb.GetNumberOfSamplesSinceLastInvalidate() == 6
+    _assert_given_back(gpu_tb, exercise, "group of two on one device", devices=[0, 0])
+
+
+def test_prepass_records_and_split_stack_give_back_everything(gpu_tb, settings):
+    """(g) cornell fetched from memory in frame groups: sample buffers and slot logs, the pre-pass's hit records, the first-bounce pass's
+    larger ones, then the split stack's overflow columns (forced as tests/test_primary_prepass.py forces them)."""
+    s = copy.copy(settings); s.MaxBounces = 5
+    W, H = 120, 72
+
+    def render(tb):
+        tb.InvalidateHistory(); tb.Render(W, H, 4, s, 0.0)
+
+    def exercise(tb):
+        tb.SetOption("scene_in_lds", 0); tb.SetOption("frame_group", 2)
+        tb.LoadScene(CORNELL)
+        tb.SetOption("primary_prepass", 1); render(tb)
+        assert tb.GetOption("scene_in_lds_active") == 0 and tb.GetOption("last_primary_prepass") == 0     # the default policy: not for a call this small
+        tb.SetOption("primary_prepass", 2); render(tb)
+        assert tb.GetOption("last_primary_prepass") == 1 and tb.GetOption("last_first_bounce") == 0
+        tb.SetOption("first_bounce", 1); render(tb)
+        assert tb.GetOption("last_primary_prepass") == 1 and tb.GetOption("last_first_bounce") == 1
+        tb.SetOption("stack_lds_cap", 4); tb.SetOption("stack_overflow_max", 64); render(tb)
+        assert tb.GetOption("last_primary_prepass") == 1 and tb.GetOption("last_plan_stack_overflow") > 0
+    _assert_given_back(gpu_tb, exercise, "pre-pass records + split stack")
+
+
+def test_layout_c_gives_back_everything(gpu_tb, settings):
+    """(h) the compact nodes, built at the first render that asks for them, lie among the scene's buffers."""
+    def exercise(tb):
+        tb.SetOption("scene_in_lds", 0); tb.SetOption("node_layout", 1)
+        tb.LoadScene(CORNELL)
+        tb.Render(64, 48, 4, settings, 0.0)                     # frame groups of a scene fetched from memory: the kernels that walk layout C
+        assert tb.GetOption("last_node_layout") == 1
+    _assert_given_back(gpu_tb, exercise, "layout C")
+
+
+def test_batch_entry_points_hold_nothing_after_they_return(gpu_tb):
+    """(i) TraceClosest and DeviceMath work in buffers of their own: gone when the call returns, while the context lives."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    n = 1000
+
+    def exercise(tb):
+        tb.LoadScene(CORNELL)
+        loaded = live(gpu_tb)
+        d = rng.normal(size=(n, 3)).astype(np.float32); d /= np.linalg.norm(d, axis=1, keepdims=True)
+        info = tb.SceneInfo()
+        centre = (np.float32(info.sceneMin[:]) + np.float32(info.sceneMax[:])) / 2
+        hits = tb.TraceClosest(np.tile(centre, (n, 1)), d)
+        assert (hits["t"] > 0).any() and live(gpu_tb) == loaded
+        x = rng.uniform(0.5, 2.0, n).astype(np.float32)
+        assert np.array_equal(tb.DeviceMath(11, x, x), np.ones(n, np.float32)) and live(gpu_tb) == loaded      # 11: a / b
+    _assert_given_back(gpu_tb, exercise, "TraceClosest + DeviceMath")
 
 
 def test_failed_load_gives_back_everything(gpu_tb, settings, tmp_path):

@@ -1,6 +1,6 @@
 /* context.cpp -- implementation of the C ABI (include/tracerboy_hip.h) on top of the host scene
  * code and the HIP kernels.  tb_context plays the role of `class TracerBoy`
- * (/root/reference/TracerBoy/TracerBoy.h:158-398): it owns every device resource, the accumulation
+ * (the reference's TracerBoy.h:158-398): it owns every device resource, the accumulation
  * surfaces (OutputTexture / JitteredOutputTexture) and the sample counter (m_SamplesRendered).
  * There is no CPU rendering path in this library: every entry point that produces pixels or hits
  * launches a HIP kernel, and tb_create fails when no HIP device is usable.
@@ -66,13 +66,10 @@ int tb_create(tb_context** out, int device_id)
     c->device = device_id;
     try {
         HIP_TRY(hipSetDevice(device_id));
-        HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&c->ev0)); HIP_TRY(hipEventCreate(&c->ev1)); HIP_TRY(hipEventCreate(&c->evKernel)); HIP_TRY(hipEventCreate(&c->evKernelStart));
-        HIP_TRY(hipEventCreateWithFlags(&c->evMain, hipEventDisableTiming));
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&c->evPt[i], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&c->evFold[i], hipEventDisableTiming));
-        }
+        c->stream.create();
+        c->ev0.create(); c->ev1.create(); c->evKernel.create(); c->evKernelStart.create();
+        c->evMain.create(hipEventDisableTiming);
+        for (int i = 0; i < 2; i++) { c->side[i].create(); c->evPt[i].create(hipEventDisableTiming); c->evFold[i].create(hipEventDisableTiming); }
     } catch (const std::exception& ex) { g_createError = ex.what(); delete c; return TB_E_DEVICE; }
     *out = c;
     return TB_OK;
@@ -89,8 +86,6 @@ int tb_create_multi(tb_context** out, const int* device_ids, int n_devices)
     for (int i = 1; i < n_devices; i++) {
         tb_context* p = nullptr;
         rc = tb_create(&p, device_ids[i]);
-        if (rc == TB_OK && hipEventCreateWithFlags(&p->evGroup,
-            hipEventDisableTiming) != hipSuccess) { g_createError = "tb_create_multi: hipEventCreate failed"; rc = TB_E_DEVICE; }
         if (rc != TB_OK) { if (p) tb_destroy(p); tb_destroy(owner); return rc; }
         p->groupOwner = owner; owner->peers.push_back(p);
         if (device_ids[i] != device_ids[0]) { /* direct peer copies over xGMI where the devices allow it; the copy works (staged) without */
@@ -108,44 +103,15 @@ int tb_create_multi(tb_context** out, const int* device_ids, int n_devices)
 
 int tb_group_size(tb_context* c) { return c ? 1 + (int)c->peers.size() : 0; }
 
+/* What only this function knows: the peers go first, the context's device is current for every free (and stays the calling thread's device, as it
+ * always has), nothing is in flight.  The members give their resources back themselves (context_internal.h). */
 void tb_destroy(tb_context* c)
 {
     if (!c) return;
     for (tb_context* p : c->peers) { p->groupOwner = nullptr; tb_destroy(p); }
     c->peers.clear();
     (void)hipSetDevice(c->device);
-    for (int k = 0; k < 2; k++) { c->groupPacked[k].release(); c->groupGathered[k].release(); }
-    if (c->evGroup) (void)hipEventDestroy(c->evGroup);
-    if (c->evGroupDone) (void)hipEventDestroy(c->evGroupDone);
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    releaseScene(c);
-    c->output.release(); c->jittered.release(); c->stats.release(); c->rayStats.release(); c->packed.release();
-    for (int q = 0; q < 2; q++) for (DevBuf& b : c->wfCols[q]) b.release();
-    for (DevBuf& b : c->wfShadowCols) b.release();
-    c->wfHitA.release(); c->wfHitG.release(); c->wfSamples.release(); c->wfCounts.release(); c->workCounter.release(); c->fgSamples[0].release();
-        c->fgSamples[1].release(); c->fgHits[0].release(); c->fgHits[1].release(); c->fgSlotLog[0].release(); c->fgSlotLog[1].release();
-        c->stackOverflow.release();
-    c->regionCost.release(); c->regionOrder[0].release(); c->regionOrder[1].release(); c->regionCostKey = ~0ull;
-    c->liveList.release(); releaseStateBuffers(c);
-    c->postOut.release(); c->postRgba8.release(); c->postHistogram.release(); c->postAverage.release();
-    for (int i = 0; i < 2; i++) { c->rtIndirect[i].release(); c->rtMoment[i].release(); c->rtFinal[i].release(); c->rtDenoise[i].release(); }
-    c->rtComposited.release();
-    for (DevBuf& b : c->aov) b.release();
-    for (hipEvent_t& e : c->evCallEnd) if (e) (void)hipEventDestroy(e);
-    if (c->splitAbort) (void)hipHostFree(c->splitAbort);
-    c->splitProf.release(); c->debugCounters.release();
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->evKernel) (void)hipEventDestroy(c->evKernel);
-    if (c->evKernelStart) (void)hipEventDestroy(c->evKernelStart);
-    if (c->evMain) (void)hipEventDestroy(c->evMain);
-    for (int i = 0; i < 2; i++) {
-        if (c->evPt[i]) (void)hipEventDestroy(c->evPt[i]);
-        if (c->evFold[i]) (void)hipEventDestroy(c->evFold[i]);
-        if (c->side[i]) { (void)hipStreamSynchronize(c->side[i]); (void)hipStreamDestroy(c->side[i]); }
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (hipStream_t s : {(hipStream_t)c->stream, (hipStream_t)c->side[0], (hipStream_t)c->side[1]}) if (s) (void)hipStreamSynchronize(s);
     delete c;
 }
 
@@ -194,17 +160,21 @@ int tb_load_procedural(tb_context* c, int kind, uint32_t targetTriangles, uint32
     });
 }
 
-int tb_scene_info_get(tb_context* c, tb_scene_info* o)
+static void fillSceneInfo(const HostScene& s, tb_scene_info* o)
 {
-    if (!c || !o) return TB_E_INVALID;
-    if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-    const HostScene& s = c->scene;
     memset(o, 0, sizeof *o);
     o->numTriangles = (uint32_t)s.triGeometry.size(); o->numVertices = (uint32_t)(s.positions.size() / 3); o->numMaterials = (uint32_t)s.materials.size();
     o->numLights = (uint32_t)s.lights.size(); o->numGeometries = (uint32_t)s.hitGroups.size(); o->numTextures = (uint32_t)s.textureData.size();
     o->bvhBytesA = (uint32_t)s.bvhA.size(); o->bvhNodesB = (uint32_t)s.nodesB.size(); o->bvhMaxDepth = s.bvhMaxDepth;
     o->filmWidth = (uint32_t)s.filmWidth; o->filmHeight = (uint32_t)s.filmHeight;
     memcpy(o->sceneMin, s.sceneMin, 12); memcpy(o->sceneMax, s.sceneMax, 12);
+}
+
+int tb_scene_info_get(tb_context* c, tb_scene_info* o)
+{
+    if (!c || !o) return TB_E_INVALID;
+    if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
+    fillSceneInfo(c->scene, o);
     return TB_OK;
 }
 
@@ -249,7 +219,7 @@ static int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const 
 {
     const uint32_t world = 1u + (uint32_t)c->peers.size();
     if (opt<OPT_aov>(c)) return fail(c, TB_E_UNSUPPORTED, "tb_render: AOV targets are not gathered across the devices of a group");
-    std::vector<tb_context*> all; all.push_back(c); for (tb_context* p : c->peers) all.push_back(p);
+    const std::vector<tb_context*> all = members(c);
     for (uint32_t i = 0; i < world; i++) if (all[i]->tiles.world != world || all[i]->tiles.rank != i) { all[i]->tiles = TbTileMap{i, world, 64, 64};
         resetHistory(all[i]); }
     for (uint32_t i = world; i-- > 0;) { /* the peers first: their launches are in flight while the owner's are enqueued */
@@ -276,7 +246,7 @@ static int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const 
                 HIP_TRY(pt_launch_pack_owned(p->stream, surface, (TbFloat4*)p->groupPacked[k].p, W, H, &p->tiles, ownedTiles(W, H, p->tiles)));
                 HIP_TRY(hipMemcpyPeerAsync((uint8_t*)c->groupGathered[k].p + bytes * i, c->device, p->groupPacked[k].p, p->device, bytes, p->stream));
             }
-            HIP_TRY(hipEventRecord(p->evGroup, p->stream));
+            HIP_TRY(hipEventRecord(p->evGroup.create(hipEventDisableTiming), p->stream));
             HIP_TRY(hipSetDevice(c->device));
             HIP_TRY(hipStreamWaitEvent(c->stream, p->evGroup, 0));
         }
@@ -287,8 +257,7 @@ static int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const 
             HIP_TRY(pt_launch_unpack_gathered(c->stream, (const TbFloat4*)c->groupGathered[k].p, (size_t)capacity, surface, W, H, world, 64, 64));
         }
         HIP_TRY(hipEventRecord(c->ev1, c->stream)); /* tb_last_render_ms of a group: render + gather + un-permute on the owner's stream */
-        if (!c->evGroupDone) HIP_TRY(hipEventCreateWithFlags(&c->evGroupDone, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->evGroupDone, c->stream));
+        HIP_TRY(hipEventRecord(c->evGroupDone.create(hipEventDisableTiming), c->stream));
         return TB_OK;
     });
 }
@@ -553,24 +522,14 @@ void tb_plan_defaults(tb_plan_input* in)
     in->pooled_samples = OptionDefault(OPT_pooled_samples); in->costly_first = (uint32_t)OptionDefault(OPT_costly_first);
     in->split_trav = OptionDefault(OPT_split_trav); in->guided_groups = OptionDefault(OPT_guided_groups);
 }
-int tb_variant_stash_entries(const char* name)
+static const Variant* variantNamed(const char* name)
 {
-    if (!name) return -1;
-    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return (int)tbctx::kVariants[i].stashHi();
-    return -1;
+    if (name) for (int i = 0; i < kNumVariants; i++) if (!strcmp(kVariants[i].name, name)) return &kVariants[i];
+    return nullptr;
 }
-int tb_variant_waves_hi(const char* name)
-{
-    if (!name) return -1;
-    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return (int)tbctx::kVariants[i].wavesHi();
-    return -1;
-}
-int tb_variant_waves_lds(const char* name)
-{
-    if (!name) return -1;
-    for (int i = 0; i < tbctx::kNumVariants; i++) if (!strcmp(tbctx::kVariants[i].name, name)) return (int)tbctx::kVariants[i].wavesLds();
-    return -1;
-}
+int tb_variant_stash_entries(const char* name) { const Variant* v = variantNamed(name); return v ? (int)v->stashHi() : -1; }
+int tb_variant_waves_hi(const char* name) { const Variant* v = variantNamed(name); return v ? (int)v->wavesHi() : -1; }
+int tb_variant_waves_lds(const char* name) { const Variant* v = variantNamed(name); return v ? (int)v->wavesLds() : -1; }
 uint32_t tb_frame_groups(uint32_t frames, uint32_t frameGroup, uint32_t guided, uint32_t group, uint32_t* firstFrame, uint32_t* numFrames)
 {
     uint32_t lg = 0; while ((2u << lg) <= frameGroup) lg++;
@@ -616,28 +575,20 @@ int tb_set_tile_assignment(tb_context* c, uint32_t rank, uint32_t world, uint32_
 
 uint64_t tb_owned_pixels(tb_context* c, uint32_t W, uint32_t H) { return c ? (uint64_t)ownedTiles(W, H, c->tiles) * c->tiles.tileW * c->tiles.tileH : 0; }
 
-int tb_pack_owned_device(tb_context* c, void* dst)
+static int packOwned(tb_context* c, void* dst, const char* who, bool sync)
 {
     return guarded(c, [&]() {
-        if (!dst || !c->output.p) return fail(c, TB_E_INVALID, "tb_pack_owned_device: nothing rendered / null destination");
+        if (!dst || !c->output.p) return fail(c, TB_E_INVALID, std::string(who) + ": nothing rendered / null destination");
         HIP_TRY(pt_launch_pack_owned(c->stream, (const TbFloat4*)c->output.p, (TbFloat4*)dst, c->width, c->height, &c->tiles, ownedTiles(c->width, c->height,
             c->tiles)));
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
         return TB_OK;
     });
 }
+int tb_pack_owned_device_async(tb_context* c, void* dst) { return packOwned(c, dst, "tb_pack_owned_device_async", false); }
+int tb_pack_owned_device(tb_context* c, void* dst) { return packOwned(c, dst, "tb_pack_owned_device", true); } /* ... and the wait */
 
-int tb_pack_owned_device_async(tb_context* c, void* dst)
-{
-    return guarded(c, [&]() {
-        if (!dst || !c->output.p) return fail(c, TB_E_INVALID, "tb_pack_owned_device_async: nothing rendered / null destination");
-        HIP_TRY(pt_launch_pack_owned(c->stream, (const TbFloat4*)c->output.p, (TbFloat4*)dst, c->width, c->height, &c->tiles, ownedTiles(c->width, c->height,
-            c->tiles)));
-        return TB_OK;
-    });
-}
-
-void* tb_stream(tb_context* c) { return c ? (void*)c->stream : nullptr; }
+void* tb_stream(tb_context* c) { return c ? (void*)c->stream.s : nullptr; }
 
 int tb_unpack_gathered_device(tb_context* c, void* stream, const void* gathered, uint64_t capacityPixels, uint32_t W, uint32_t H, uint32_t world, uint32_t tw,
     uint32_t th, void* full)
@@ -730,8 +681,7 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "adaptive_min_frames")) return opt<OPT_adaptive_min_frames>(c);
     if (!strcmp(name, "last_live_pixels")) {
         int64_t sum = 0;
-        std::vector<tb_context*> all(1, c); for (tb_context* p : c->peers) all.push_back(p);
-        for (tb_context* x : all) {
+        for (tb_context* x : members(c)) {
             if (!x->lastAdaptive || !x->liveList.p) { sum += (int64_t)x->lastOwnedPixels; continue; }
             uint32_t v = 0; DeviceScope scope(x->device);
             if (hipStreamSynchronize(x->stream) != hipSuccess || hipMemcpy(&v, (const uint8_t*)x->liveList.p + x->liveCountOffset, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -796,20 +746,18 @@ int tb_trace_closest(tb_context* c, uint32_t n, const float* origins, const floa
         if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
         if (n == 0) return TB_OK;
         if (!origins || !dirs || !outT) return fail(c, TB_E_INVALID, "tb_trace_closest: null array");
-        struct Tmp { DevBuf b; ~Tmp() { b.release(); } };
-        Tmp dO, dD, dT, dM, dB, dP, dG, dN, dU, dBx, dTr;
-        auto in = [&](Tmp& t, const void* h, size_t bytes) { ensure(t.b, bytes); HIP_TRY(hipMemcpy(t.b.p, h, bytes, hipMemcpyHostToDevice)); };
+        DevBuf dO, dD, dT, dM, dB, dP, dG, dN, dU, dBx, dTr;
+        auto in = [&](DevBuf& d, const void* h, size_t bytes) { ensure(d, bytes); HIP_TRY(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice)); };
         in(dO, origins, (size_t)n * 12); in(dD, dirs, (size_t)n * 12);
-        ensure(dT.b, (size_t)n * 4); ensure(dM.b, (size_t)n * 4); ensure(dB.b, (size_t)n * 8); ensure(dP.b, (size_t)n * 4); ensure(dG.b, (size_t)n * 4);
-        ensure(dN.b, (size_t)n * 12); ensure(dU.b, (size_t)n * 8); ensure(dBx.b, (size_t)n * 4); ensure(dTr.b, (size_t)n * 4);
+        ensure(dT, (size_t)n * 4); ensure(dM, (size_t)n * 4); ensure(dB, (size_t)n * 8); ensure(dP, (size_t)n * 4); ensure(dG, (size_t)n * 4);
+        ensure(dN, (size_t)n * 12); ensure(dU, (size_t)n * 8); ensure(dBx, (size_t)n * 4); ensure(dTr, (size_t)n * 4);
         if (opt<OPT_node_layout>(c) == 1) ensureCompactNodes(c);
         TbDeviceScene dsTrace = c->ds; /* option "node_layout" = 1: the batch walks the compact nodes too (one-level scenes) */
         if (opt<OPT_node_layout>(c) != 1 || dsTrace.numInstances) dsTrace.nodesC = nullptr;
-        HIP_TRY(pt_launch_trace_closest(c->stream, &dsTrace, n, (const float*)dO.b.p, (const float*)dD.b.p, (float*)dT.b.p, (int*)dM.b.p, (float*)dB.b.p,
-            (uint32_t*)dP.b.p,
-                                        (uint32_t*)dG.b.p, (float*)dN.b.p, (float*)dU.b.p, (uint32_t*)dBx.b.p, (uint32_t*)dTr.b.p));
+        HIP_TRY(pt_launch_trace_closest(c->stream, &dsTrace, n, (const float*)dO.p, (const float*)dD.p, (float*)dT.p, (int*)dM.p, (float*)dB.p, (uint32_t*)dP.p,
+                                        (uint32_t*)dG.p, (float*)dN.p, (float*)dU.p, (uint32_t*)dBx.p, (uint32_t*)dTr.p));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        auto outc = [&](void* h, Tmp& t, size_t bytes) { if (h) HIP_TRY(hipMemcpy(h, t.b.p, bytes, hipMemcpyDeviceToHost)); };
+        auto outc = [&](void* h, const DevBuf& d, size_t bytes) { if (h) HIP_TRY(hipMemcpy(h, d.p, bytes, hipMemcpyDeviceToHost)); };
         outc(outT, dT, (size_t)n * 4); outc(outMat, dM, (size_t)n * 4); outc(outBary, dB, (size_t)n * 8); outc(outPrim, dP, (size_t)n * 4);
             outc(outGeom, dG, (size_t)n * 4);
         outc(outNormal, dN, (size_t)n * 12); outc(outUV, dU, (size_t)n * 8); outc(outBoxes, dBx, (size_t)n * 4); outc(outTris, dTr, (size_t)n * 4);
@@ -823,15 +771,12 @@ int tb_device_math(tb_context* c, int fn, uint32_t n, const float* a, const floa
         if (!a || !out) return fail(c, TB_E_INVALID, "tb_device_math: null array");
         if (n == 0) return TB_OK;
         DevBuf dA, dB, dO;
-        try {
-            ensure(dA, (size_t)n * 4); ensure(dO, (size_t)n * 4);
-            HIP_TRY(hipMemcpy(dA.p, a, (size_t)n * 4, hipMemcpyHostToDevice));
-            if (b) { ensure(dB, (size_t)n * 4); HIP_TRY(hipMemcpy(dB.p, b, (size_t)n * 4, hipMemcpyHostToDevice)); }
-            HIP_TRY(pt_launch_device_math(c->stream, fn, n, (const float*)dA.p, (const float*)dB.p, (float*)dO.p));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            HIP_TRY(hipMemcpy(out, dO.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        } catch (...) { dA.release(); dB.release(); dO.release(); throw; }
-        dA.release(); dB.release(); dO.release();
+        ensure(dA, (size_t)n * 4); ensure(dO, (size_t)n * 4);
+        HIP_TRY(hipMemcpy(dA.p, a, (size_t)n * 4, hipMemcpyHostToDevice));
+        if (b) { ensure(dB, (size_t)n * 4); HIP_TRY(hipMemcpy(dB.p, b, (size_t)n * 4, hipMemcpyHostToDevice)); }
+        HIP_TRY(pt_launch_device_math(c->stream, fn, n, (const float*)dA.p, (const float*)dB.p, (float*)dO.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(out, dO.p, (size_t)n * 4, hipMemcpyDeviceToHost));
         return TB_OK;
     });
 }
@@ -908,13 +853,7 @@ int tb_host_scene_camera(tb_host_scene* s, tb_camera* cam) { if (!s || !cam) ret
 int tb_host_scene_info(tb_host_scene* h, tb_scene_info* o)
 {
     if (!h || !o) return TB_E_INVALID;
-    const HostScene& s = h->scene;
-    memset(o, 0, sizeof *o);
-    o->numTriangles = (uint32_t)s.triGeometry.size(); o->numVertices = (uint32_t)(s.positions.size() / 3); o->numMaterials = (uint32_t)s.materials.size();
-    o->numLights = (uint32_t)s.lights.size(); o->numGeometries = (uint32_t)s.hitGroups.size(); o->numTextures = (uint32_t)s.textureData.size();
-    o->bvhBytesA = (uint32_t)s.bvhA.size(); o->bvhNodesB = (uint32_t)s.nodesB.size(); o->bvhMaxDepth = s.bvhMaxDepth;
-    o->filmWidth = (uint32_t)s.filmWidth; o->filmHeight = (uint32_t)s.filmHeight;
-    memcpy(o->sceneMin, s.sceneMin, 12); memcpy(o->sceneMax, s.sceneMax, 12);
+    fillSceneInfo(h->scene, o);
     return TB_OK;
 }
 int tb_host_scene_frame_constants(tb_host_scene* h, const tb_output_settings* settings, uint32_t frame, float t, TbPerFrameConstants* out)

@@ -1,5 +1,5 @@
-/* context_internal.h -- what the three translation units of the context share: the kernel launchers' C interface, the table of feature
- * sets, struct tb_context (the role of `class TracerBoy`, /root/reference/TracerBoy/TracerBoy.h:158-398) and a few helpers.
+/* context_internal.h -- what the translation units of the context share: the kernel launchers' C interface, the table of feature
+ * sets, the owners of device resources, struct tb_context (the role of the reference's `class TracerBoy`, TracerBoy.h:158-398) and a few helpers.
  *   context.cpp         the C ABI (include/tracerboy_hip.h): create / destroy, scene loads, options, read-backs, output stage, real-time chain, groups
  *   context_scene.cpp   finalizeScene: BVH builds on the GPU, node orders, layout C, uploads, the LDS scene image
  *   context_render.cpp  renderImpl, a sequence of named steps, and the pipelines it dispatches to
@@ -66,25 +66,61 @@ struct Variant { const char* name; const Copy* base; const Copy* hi; const Copy*
 extern const Variant kVariants[];
 extern const int kNumVariants;
 
-/* device bytes the library holds, all contexts of the process together (option "debug_live_device_bytes"): added at the two hipMalloc sites
- * (ensure, upload), taken back in DevBuf::release -- a context that is destroyed must leave it where it found it */
+#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+/* Owners of what the library takes from HIP: device memory, streams, events, host-mapped words.  None can be copied; each destructor gives its
+ * handle back, on the device that is current then -- a context's members go in tb_destroy, after its hipSetDevice; a function's locals go inside
+ * guarded()'s DeviceScope.  Nothing else in the host code frees or destroys.
+ * g_liveDeviceBytes: device bytes the library holds, all contexts of the process together (option "debug_live_device_bytes"): added where ensure
+ * allocates, subtracted where DevBuf::release frees -- a context that is destroyed leaves the count where it found it. */
 extern std::atomic<int64_t> g_liveDeviceBytes;
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
-    void release() { if (p) { (void)hipFree(p); g_liveDeviceBytes -= (int64_t)bytes; } p = nullptr; bytes = 0; }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DevBuf() { release(); }
+    void release() { if (p) { (void)hipFree(p); g_liveDeviceBytes -= (int64_t)bytes; } p = nullptr; bytes = 0; } /* early, on purpose: a resize drops the AOVs, a load the old scene */
+};
+struct DevStream {
+    hipStream_t s = nullptr;
+    DevStream() = default;
+    DevStream(const DevStream&) = delete; DevStream& operator=(const DevStream&) = delete;
+    ~DevStream() { if (s) (void)hipStreamDestroy(s); }
+    void create() { HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    operator hipStream_t() const { return s; }
+};
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent&) = delete; DevEvent& operator=(const DevEvent&) = delete;
+    ~DevEvent() { if (e) (void)hipEventDestroy(e); }
+    hipEvent_t create(unsigned flags = hipEventDefault) { if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags)); return e; } /* the event, made at its first use */
+    operator hipEvent_t() const { return e; }
+};
+struct MappedWords { /* zeroed host memory the device writes and the host polls */
+    uint32_t* p = nullptr;
+    MappedWords() = default;
+    MappedWords(const MappedWords&) = delete; MappedWords& operator=(const MappedWords&) = delete;
+    ~MappedWords() { if (p) (void)hipHostFree(p); }
+    uint32_t* create(size_t bytes) { if (!p) { HIP_TRY(hipHostMalloc((void**)&p, bytes, hipHostMallocMapped)); memset(p, 0, bytes); } return p; }
+    operator uint32_t*() const { return p; }
 };
 
 } // namespace tbctx
 using tbctx::DevBuf;
 
 struct tb_context {
+    tb_context() = default;
+    tb_context(const tb_context&) = delete; tb_context& operator=(const tb_context&) = delete;
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evKernelStart = nullptr, evKernel = nullptr; /* evKernelStart..evKernel: the render's first path-tracing launch */
     /* frame-group launches alternate between two side streams and two sample buffers: launch k+1 starts while the last paths
-     * of launch k drain; the folds stay on `stream`, in order (renderImpl) */
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t evPt[2] = {nullptr, nullptr}, evFold[2] = {nullptr, nullptr}, evMain = nullptr;
+     * of launch k drain; the folds stay on `stream`, in order (renderImpl).  The streams stand before every buffer and event: they go last */
+    tbctx::DevStream stream, side[2];
+    tbctx::DevEvent ev0, ev1, evKernelStart, evKernel; /* evKernelStart..evKernel: the render's first path-tracing launch */
+    tbctx::DevEvent evPt[2], evFold[2], evMain;
     DevBuf fgSamples[2];
     int numCUs = 0;           /* of `device` (deviceCUs) */
     uint32_t launchEpoch = 0; /* TbDeviceTargets::launchEpoch of the last frame-group launch */
@@ -119,7 +155,7 @@ struct tb_context {
     /* render states (render_state.cpp): the surfaces hold the samples of frames [firstFrame, samplesRendered) */
     uint32_t firstFrame = 0;
     DevBuf stateScratch; /* the digest's per-workgroup partials and its two results (state_launch.h) */
-    hipEvent_t evState[2] = {nullptr, nullptr}; float lastStateDigestMs = 0.0f, lastStateAddMs = 0.0f; /* options last_state_digest_us / last_state_add_us */
+    tbctx::DevEvent evState[2]; float lastStateDigestMs = 0.0f, lastStateAddMs = 0.0f; /* options last_state_digest_us / last_state_add_us */
     uint64_t sceneDigest = 0, sceneDigestKey = ~0ull; uint32_t materialEdits = 0; /* tb_scene_digest, cached per (sceneGeneration, materialEdits) */
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
@@ -133,7 +169,7 @@ struct tb_context {
     int lastSlotLogCap = 0;
     /* renderImpl */
     PrepassTrial prepassTrial; OverlapTrial overlapTrial; CallRec callRec[8]; /* launch_trials.h */
-    hipEvent_t evCallEnd[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; uint64_t callCount = 0; int lastOverlap = 0;
+    tbctx::DevEvent evCallEnd[8]; uint64_t callCount = 0; int lastOverlap = 0;
     tb_launch_plan lastPlan{}; /* what PlanLaunch decided for the last render (options last_plan_rule_*) */
     uint64_t kernelEventStamp = 0; /* counts the renders that have recorded evKernelStart / evKernel: a trial's sample belongs to the render it was asked of */
     uint32_t sceneGeneration = 0; /* counts finalizeScene calls */
@@ -142,7 +178,7 @@ struct tb_context {
     int lastCompactHits = 0;
     DevBuf debugCounters; /* TbDeviceTargets::debugCounters (16 words, zeroed once) */
     /* pipeline 4: host-mapped abort word of the split-role kernel (renderSplit); travWaves * 100 + shadeWaves of the last launch */
-    DevBuf splitProf; uint32_t* splitAbort = nullptr; int lastSplitWaves = 0;
+    DevBuf splitProf; tbctx::MappedWords splitAbort; int lastSplitWaves = 0;
     int lastFgPar = 0;          /* which of the two sample buffers the last frame-group launch wrote (debug query) */
     int lastPrimaryPrepass = 0; /* 1: the last render took its first hits from the primary-visibility pre-pass */
     int lastFirstBounce = 0;    /* 1: ... its paths' state after the first bounce from the first-bounce pass */
@@ -153,14 +189,11 @@ struct tb_context {
     std::vector<tb_context*> peers;
     tb_context* groupOwner = nullptr;          /* set on a peer: API calls on a peer handle are refused */
     DevBuf groupPacked[2], groupGathered[2];   /* [0] output, [1] jittered: this device's packed tiles; (owner) world x capacity gathered tiles */
-    hipEvent_t evGroup = nullptr, evGroupDone = nullptr; /* evGroupDone (owner): the un-permute of the last group render has read groupGathered */
+    tbctx::DevEvent evGroup, evGroupDone; /* evGroup (peer): its packed tiles are on their way; evGroupDone (owner): the un-permute of the last group render has read groupGathered */
     bool compactTried = false; /* layout C was asked for and built -- or could not be built -- for the loaded scene (ensureCompactNodes) */
 };
 
 namespace tbctx {
-
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 int fail(tb_context* c, int code, const std::string& msg);
 /* forget the accumulated frames: the next render starts at frame 0 (where the kernels overwrite the surfaces instead of adding to them) */
@@ -194,19 +227,18 @@ template <class F> int guarded(tb_context* c, F f)
     }
 }
 
+void ensure(DevBuf& b, size_t bytes); /* b holds exactly `bytes`: as it is if it does already, else freed and allocated */
 template <class T> const T* upload(tb_context* c, const std::vector<T>& v)
 {
-    DevBuf b;
-    b.bytes = v.size() * sizeof(T);
-    if (b.bytes == 0) return nullptr;
-    HIP_TRY(hipMalloc(&b.p, b.bytes));
-    g_liveDeviceBytes += (int64_t)b.bytes;
-    c->sceneBufs.push_back(b);
+    if (v.empty()) return nullptr;
+    DevBuf b; ensure(b, v.size() * sizeof(T));
     HIP_TRY(hipMemcpyAsync(b.p, v.data(), b.bytes, hipMemcpyHostToDevice, c->stream));
-    return (const T*)b.p;
+    c->sceneBufs.push_back(std::move(b));
+    return (const T*)c->sceneBufs.back().p;
 }
+/* a context and the peers of its group */
+inline std::vector<tb_context*> members(tb_context* c) { std::vector<tb_context*> all(1, c); all.insert(all.end(), c->peers.begin(), c->peers.end()); return all; }
 
-void ensure(DevBuf& b, size_t bytes);
 /* context_scene.cpp */
 void releaseScene(tb_context* c);
 uint32_t sceneFeatureMask(const HostScene& s);
@@ -215,7 +247,6 @@ uint32_t settingsFeatureMask(const tb_context* c, const tb_output_settings& s, b
 void ensureCompactNodes(tb_context* c);
 void finalizeScene(tb_context* c, bool build = true); /* build = false: c->scene already holds a built, reordered tree (a peer of a multi-device group) */
 uint64_t sceneDigestOf(const HostScene& s); /* context.cpp */
-void releaseStateBuffers(tb_context* c);    /* render_state.cpp */
 /* context_render.cpp */
 bool historyRelevantChange(const tb_output_settings& a, const tb_output_settings& b);
 int deviceCUs(tb_context* c);

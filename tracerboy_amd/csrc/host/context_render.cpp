@@ -1,4 +1,4 @@
-/* context_render.cpp -- TracerBoy::Render x n frames (/root/reference/TracerBoy/TracerBoy.cpp:2677-2946) as launches of the path-tracing
+/* context_render.cpp -- TracerBoy::Render x n frames (the reference's TracerBoy.cpp:2677-2946) as launches of the path-tracing
  * kernels: renderImpl, at the end of the file, is the list of a call's steps.  They execute the plan launch_plan.h makes (pipeline, copy of
  * the feature set, split stack, pre-pass, batches and frame groups), ask the two trials no rule could replace (launch_trials.h) and dispatch to
  * the pipelines; frame-group mode and the split-role pipeline share one executor (FrameGroupExec). */
@@ -289,8 +289,7 @@ static void renderSplit(const RenderCall& r)
     batch = (n + (n + batch - 1) / batch - 1) / ((n + batch - 1) / batch); /* equal batches */
     const int lds = c->sceneInLds ? 1 : 0;
     TbSplitParams sp; splitParamsFromOptions(c, sp);
-    if (!c->splitAbort) { HIP_TRY(hipHostMalloc((void**)&c->splitAbort, 64, hipHostMallocMapped)); memset(c->splitAbort, 0, 64); }
-    HIP_TRY(hipHostGetDevicePointer((void**)&sp.abortFlag, c->splitAbort, 0));
+    HIP_TRY(hipHostGetDevicePointer((void**)&sp.abortFlag, c->splitAbort.create(64), 0));
     if (opt<OPT_split_profile>(c)) { /* counting copy: 16 counters, cleared with the history, read back with tb_read_split_profile */
         ensure(c->splitProf, 16 * 8);
         if (c->samplesRendered == 0) HIP_TRY(hipMemsetAsync(c->splitProf.p, 0, 16 * 8, c->stream));
@@ -636,12 +635,12 @@ static void tryOverlap(RenderCall& r)
     r.overlap = r.plan.overlap_launches != 0;
     const uint64_t callKey = kindOfCall(r) ^ (r.prepass ? 1u : 0u);
     const bool trial = r.overlap && opt<OPT_overlap_launches>(c) == 1 && (r.v->features() & (PT_FEAT_SPECULAR | PT_FEAT_TEXTURES | PT_FEAT_SSS | PT_FEAT_MIX)) != 0;
-    hipEvent_t* ends = c->evCallEnd;
+    const DevEvent* ends = c->evCallEnd;
     if (trial) r.overlap = OverlapTrialStep(c->overlapTrial, c->callRec, c->callCount, callKey,
         [&](uint64_t i) { return ends[i & 7u] && ends[(i - 2) & 7u] && hipEventQuery(ends[i & 7u]) == hipSuccess; },
         [&](uint64_t i) { float ms = 0; return hipEventElapsedTime(&ms, ends[(i - 2) & 7u], ends[i & 7u]) == hipSuccess ? ms : 0.0f; });
     c->lastOverlap = r.overlap ? 1 : 0;
-    hipEvent_t prevEnd = c->callCount ? ends[(c->callCount - 1) & 7u] : nullptr;
+    hipEvent_t prevEnd = c->callCount ? ends[(c->callCount - 1) & 7u].e : nullptr;
     RecordCall(c->callRec, c->callCount, callKey, trial, r.overlap, prevEnd && hipEventQuery(prevEnd) == hipErrorNotReady);
 }
 
@@ -685,8 +684,7 @@ static int closeCall(RenderCall& r)
 {
     tb_context* c = r.c;
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    if (!c->evCallEnd[c->callCount & 7u]) HIP_TRY(hipEventCreate(&c->evCallEnd[c->callCount & 7u]));
-    HIP_TRY(hipEventRecord(c->evCallEnd[c->callCount & 7u], c->stream)); c->callCount++;
+    HIP_TRY(hipEventRecord(c->evCallEnd[c->callCount & 7u].create(), c->stream)); c->callCount++;
     c->samplesRendered += r.n;
     if (r.sync) {
         HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipEventElapsedTime(&c->lastMs, c->ev0, c->ev1));

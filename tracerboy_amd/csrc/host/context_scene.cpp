@@ -1,4 +1,4 @@
-/* context_scene.cpp -- the device half of LoadScene (/root/reference/TracerBoy/TracerBoy.cpp:1065-2161): BVH builds on the GPU, storage
+/* context_scene.cpp -- the device half of LoadScene (the reference's TracerBoy.cpp:1065-2161): BVH builds on the GPU, storage
  * order of the nodes, the compact node layout, uploads in the kernels' 16-B aligned device forms, the whole-scene-in-LDS image. */
 #include "context_internal.h"
 
@@ -6,7 +6,6 @@ namespace tbctx {
 
 void releaseScene(tb_context* c)
 {
-    for (DevBuf& b : c->sceneBufs) b.release();
     c->sceneBufs.clear();
     memset(&c->ds, 0, sizeof c->ds);
 }
@@ -129,26 +128,20 @@ void BuildBvhGpu(tb_context* c, HostScene& s, uint32_t treeletPasses)
     if (total > 0xffffffffull) throw std::runtime_error("BuildBvh: BVH image exceeds 4 GiB");
     DevBuf dPos, dIdx, dGeo, dPrim, dFlag, dA, dNodes, dTris, dScratch, dHeight;
     auto up = [&](DevBuf& b, const void* p, size_t bytes) { ensure(b, bytes); HIP_TRY(hipMemcpyAsync(b.p, p, bytes, hipMemcpyHostToDevice, c->stream)); };
-    try {
-        up(dPos, s.positions.data(), s.positions.size() * 4); up(dIdx, s.triVertexIndex.data(), s.triVertexIndex.size() * 4);
-        up(dGeo, s.triGeometry.data(), 4ull * N); up(dPrim, s.triPrimitive.data(), 4ull * N); up(dFlag, s.triFlags.data(), 4ull * N);
-        const size_t nB = N > 1 ? N - 1 : 1, scratchBytes = bvh_gpu_scratch_bytes(N);
-        ensure(dA, total); ensure(dNodes, nB * sizeof(TbNodeB)); ensure(dTris, (size_t)N * sizeof(TbTriB)); ensure(dScratch, scratchBytes); ensure(dHeight, 4);
-        HIP_TRY(hipMemsetAsync(dNodes.p, 0, nB * sizeof(TbNodeB), c->stream));
-        HIP_TRY(bvh_gpu_build(c->stream, (const float*)dPos.p, (const uint32_t*)dIdx.p, (const uint32_t*)dGeo.p, (const uint32_t*)dPrim.p,
-            (const uint32_t*)dFlag.p, N,
-                              treeletPasses, (uint8_t*)dScratch.p, scratchBytes, (uint8_t*)dA.p, (TbNodeB*)dNodes.p, (TbTriB*)dTris.p, (uint32_t*)dHeight.p));
-        s.bvhA.resize((size_t)total); s.nodesB.resize(nB); s.trisB.resize(N);
-        HIP_TRY(hipMemcpy(s.bvhA.data(), dA.p, total, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(s.nodesB.data(), dNodes.p, nB * sizeof(TbNodeB), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(s.trisB.data(), dTris.p, (size_t)N * sizeof(TbTriB), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&s.bvhMaxDepth, dHeight.p, 4, hipMemcpyDeviceToHost));
-        s.rootRefB = N == 1 ? TB_BVH_LEAF_FLAG : 0u;
-    } catch (...) {
-        for (DevBuf* b : {&dPos, &dIdx, &dGeo, &dPrim, &dFlag, &dA, &dNodes, &dTris, &dScratch, &dHeight}) b->release();
-        throw;
-    }
-    for (DevBuf* b : {&dPos, &dIdx, &dGeo, &dPrim, &dFlag, &dA, &dNodes, &dTris, &dScratch, &dHeight}) b->release();
+    up(dPos, s.positions.data(), s.positions.size() * 4); up(dIdx, s.triVertexIndex.data(), s.triVertexIndex.size() * 4);
+    up(dGeo, s.triGeometry.data(), 4ull * N); up(dPrim, s.triPrimitive.data(), 4ull * N); up(dFlag, s.triFlags.data(), 4ull * N);
+    const size_t nB = N > 1 ? N - 1 : 1, scratchBytes = bvh_gpu_scratch_bytes(N);
+    ensure(dA, total); ensure(dNodes, nB * sizeof(TbNodeB)); ensure(dTris, (size_t)N * sizeof(TbTriB)); ensure(dScratch, scratchBytes); ensure(dHeight, 4);
+    HIP_TRY(hipMemsetAsync(dNodes.p, 0, nB * sizeof(TbNodeB), c->stream));
+    HIP_TRY(bvh_gpu_build(c->stream, (const float*)dPos.p, (const uint32_t*)dIdx.p, (const uint32_t*)dGeo.p, (const uint32_t*)dPrim.p,
+        (const uint32_t*)dFlag.p, N,
+                          treeletPasses, (uint8_t*)dScratch.p, scratchBytes, (uint8_t*)dA.p, (TbNodeB*)dNodes.p, (TbTriB*)dTris.p, (uint32_t*)dHeight.p));
+    s.bvhA.resize((size_t)total); s.nodesB.resize(nB); s.trisB.resize(N);
+    HIP_TRY(hipMemcpy(s.bvhA.data(), dA.p, total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s.nodesB.data(), dNodes.p, nB * sizeof(TbNodeB), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s.trisB.data(), dTris.p, (size_t)N * sizeof(TbTriB), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&s.bvhMaxDepth, dHeight.p, 4, hipMemcpyDeviceToHost));
+    s.rootRefB = N == 1 ? TB_BVH_LEAF_FLAG : 0u;
 }
 
 /* Layout C (tb_abi.h TbNodeC): the layout-B nodes, same order, boxes rounded outward onto a 16-bit grid over the root box.
@@ -224,25 +217,19 @@ void BuildTlasGpu(tb_context* c, HostScene& s, const std::vector<float>& blasBox
     const size_t total = 16 + 32 * (2ull * M - 1) + 116ull * M, scratchBytes = bvh_gpu_tlas_scratch_bytes(M);
     DevBuf dO, dW, dB, dH, dBox, dScratch, dA, dTop, dWords;
     auto up = [&](DevBuf& b, const void* p, size_t bytes) { ensure(b, bytes); HIP_TRY(hipMemcpyAsync(b.p, p, bytes, hipMemcpyHostToDevice, c->stream)); };
-    try {
-        up(dO, o2w.data(), o2w.size() * 4); up(dW, w2o.data(), w2o.size() * 4); up(dB, blas.data(), 4ull * M); up(dH, base.data(), 4ull * M);
-            up(dBox, blasBoxes.data(), blasBoxes.size() * 4);
-        ensure(dScratch, scratchBytes); ensure(dA, total); ensure(dTop, std::max<size_t>(1, M - 1) * sizeof(TbNodeB)); ensure(dWords, 8);
-        HIP_TRY(hipMemsetAsync(dA.p, 0, total, c->stream));
-        HIP_TRY(bvh_gpu_build_tlas(c->stream, M, (const float*)dO.p, (const float*)dW.p, (const uint32_t*)dB.p, (const uint32_t*)dH.p, (const float*)dBox.p,
-            (uint8_t*)dScratch.p, scratchBytes,
-                                   (uint8_t*)dA.p, (TbNodeB*)dTop.p, (uint32_t*)dWords.p, (uint32_t*)dWords.p + 1));
-        s.tlasA.resize(total); top.assign(M > 1 ? M - 1 : 0, TbNodeB{});
-        uint32_t words[2];
-        HIP_TRY(hipMemcpy(s.tlasA.data(), dA.p, total, hipMemcpyDeviceToHost));
-        if (M > 1) HIP_TRY(hipMemcpy(top.data(), dTop.p, (size_t)(M - 1) * sizeof(TbNodeB), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(words, dWords.p, 8, hipMemcpyDeviceToHost));
-        rootRef = words[0]; depth = words[1];
-    } catch (...) {
-        for (DevBuf* b : {&dO, &dW, &dB, &dH, &dBox, &dScratch, &dA, &dTop, &dWords}) b->release();
-        throw;
-    }
-    for (DevBuf* b : {&dO, &dW, &dB, &dH, &dBox, &dScratch, &dA, &dTop, &dWords}) b->release();
+    up(dO, o2w.data(), o2w.size() * 4); up(dW, w2o.data(), w2o.size() * 4); up(dB, blas.data(), 4ull * M); up(dH, base.data(), 4ull * M);
+        up(dBox, blasBoxes.data(), blasBoxes.size() * 4);
+    ensure(dScratch, scratchBytes); ensure(dA, total); ensure(dTop, std::max<size_t>(1, M - 1) * sizeof(TbNodeB)); ensure(dWords, 8);
+    HIP_TRY(hipMemsetAsync(dA.p, 0, total, c->stream));
+    HIP_TRY(bvh_gpu_build_tlas(c->stream, M, (const float*)dO.p, (const float*)dW.p, (const uint32_t*)dB.p, (const uint32_t*)dH.p, (const float*)dBox.p,
+        (uint8_t*)dScratch.p, scratchBytes,
+                               (uint8_t*)dA.p, (TbNodeB*)dTop.p, (uint32_t*)dWords.p, (uint32_t*)dWords.p + 1));
+    s.tlasA.resize(total); top.assign(M > 1 ? M - 1 : 0, TbNodeB{});
+    uint32_t words[2];
+    HIP_TRY(hipMemcpy(s.tlasA.data(), dA.p, total, hipMemcpyDeviceToHost));
+    if (M > 1) HIP_TRY(hipMemcpy(top.data(), dTop.p, (size_t)(M - 1) * sizeof(TbNodeB), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(words, dWords.p, 8, hipMemcpyDeviceToHost));
+    rootRef = words[0]; depth = words[1];
 }
 
 /* TbDeviceScene::textureUse of the scene as it stands (finalizeScene, tb_set_material) */

@@ -96,7 +96,6 @@ int writeState(const char* path, const tb_state_info& h, const float* output, co
 int hostFail(char* err, uint32_t n, int code, const std::string& m) { if (err && n) { strncpy(err, m.c_str(), n - 1); err[n - 1] = 0; } return code; }
 
 /* ---- the context's side ---- */
-std::vector<tb_context*> members(tb_context* c) { std::vector<tb_context*> all(1, c); for (tb_context* p : c->peers) all.push_back(p); return all; }
 bool sameBits(const void* a, const void* b, size_t n) { return memcmp(a, b, n) == 0; }
 bool sameTiles(const TbTileMap& t, const tb_state_info& h) { return t.rank == h.tile_rank && t.world == h.tile_world && t.tileW == h.tile_w && t.tileH == h.tile_h; }
 
@@ -107,17 +106,14 @@ uint64_t sceneDigestCached(tb_context* c)
     return c->sceneDigest;
 }
 
-void ensureStateEvents(tb_context* x) { for (hipEvent_t& e : x->evState) if (!e) HIP_TRY(hipEventCreate(&e)); }
-
 /* digests of two surfaces of nWords words each, on x's device and stream; waits */
 void deviceDigest(tb_context* x, const void* a, const void* b, uint64_t nWords, uint64_t out[2])
 {
     ensure(x->stateScratch, (size_t)TB_STATE_DIGEST_SCRATCH_WORDS * 8u);
-    ensureStateEvents(x);
     uint64_t* scratch = (uint64_t*)x->stateScratch.p;
-    HIP_TRY(hipEventRecord(x->evState[0], x->stream));
+    HIP_TRY(hipEventRecord(x->evState[0].create(), x->stream));
     HIP_TRY(state_launch_digest(x->stream, (const uint32_t*)a, (const uint32_t*)b, nWords, scratch));
-    HIP_TRY(hipEventRecord(x->evState[1], x->stream));
+    HIP_TRY(hipEventRecord(x->evState[1].create(), x->stream));
     HIP_TRY(hipMemcpyAsync(out, scratch + 2u * TB_STATE_DIGEST_MAX_GROUPS, 16, hipMemcpyDeviceToHost, x->stream));
     HIP_TRY(hipStreamSynchronize(x->stream));
     if (hipEventElapsedTime(&x->lastStateDigestMs, x->evState[0], x->evState[1]) != hipSuccess) x->lastStateDigestMs = 0.0f;
@@ -145,15 +141,6 @@ void setGroupTiles(const std::vector<tb_context*>& all)
 }
 
 } // namespace
-
-namespace tbctx {
-void releaseStateBuffers(tb_context* c)
-{
-    c->stateScratch.release();
-    for (hipEvent_t& e : c->evState) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-}
-} // namespace tbctx
-
 
 extern "C" {
 
@@ -308,13 +295,12 @@ int tb_state_load(tb_context* c, const char* path, uint32_t flags)
 
         const std::vector<tb_context*> all = members(c);
         auto forget = [&]() { for (tb_context* x : all) resetHistory(x); };
-        struct Tmp { DevBuf b; ~Tmp() { b.release(); } };
         for (tb_context* x : all) {
             DeviceScope scope(x->device);
             HIP_TRY(hipStreamSynchronize(x->stream));
-            Tmp fileOut, fileJit;
+            DevBuf fileOut, fileJit; /* the file's copies of an addition: released at the end of the member's turn */
             void *dstOut = nullptr, *dstJit = nullptr;
-            if (add) { ensure(fileOut.b, bytes); ensure(fileJit.b, bytes); dstOut = fileOut.b.p; dstJit = fileJit.b.p; }
+            if (add) { ensure(fileOut, bytes); ensure(fileJit, bytes); dstOut = fileOut.p; dstJit = fileJit.p; }
             else { adopt(x, h.width, h.height, h.settings, h.time_seed, h.first_frame, h.next_frame); dstOut = x->output.p; dstJit = x->jittered.p; }
             uint64_t dev[2] = {0, 0};
             try {
@@ -327,10 +313,9 @@ int tb_state_load(tb_context* c, const char* path, uint32_t flags)
             if (add) {
                 if (x->samplesRendered == x->firstFrame) { /* an empty range: whatever an earlier history left in the surfaces does not count */
                     HIP_TRY(hipMemsetAsync(x->output.p, 0, bytes, x->stream)); HIP_TRY(hipMemsetAsync(x->jittered.p, 0, bytes, x->stream)); }
-                ensureStateEvents(x);
-                HIP_TRY(hipEventRecord(x->evState[0], x->stream));
+                HIP_TRY(hipEventRecord(x->evState[0].create(), x->stream));
                 HIP_TRY(state_launch_add(x->stream, (float*)x->output.p, (const float*)dstOut, (float*)x->jittered.p, (const float*)dstJit, words));
-                HIP_TRY(hipEventRecord(x->evState[1], x->stream));
+                HIP_TRY(hipEventRecord(x->evState[1].create(), x->stream));
                 HIP_TRY(hipStreamSynchronize(x->stream)); /* the file's copies are released below */
                 if (hipEventElapsedTime(&x->lastStateAddMs, x->evState[0], x->evState[1]) != hipSuccess) x->lastStateAddMs = 0.0f;
             }
