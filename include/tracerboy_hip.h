@@ -175,6 +175,33 @@ int tb_render_realtime(tb_context* ctx, uint32_t width, uint32_t height, const t
     float time_seed);
 int tb_read_realtime(tb_context* ctx, int stage, float* rgba);
 
+/* ---- denoised stills ---------------------------------------------------------
+ * The reference denoises a still with OIDN on DirectML (out of scope); here the progressive render's own two surfaces
+ * feed the real-time chain's a-trous filter.  The jittered surface holds an independent half of every pixel's samples (RayGenCommon.h:721-727),
+ * so the difference of the two halves' mean luminances estimates the variance of the mean's luminance.  The chain, all IEEE fp32:
+ *   prepare    (sum rgb / sum w, that variance; 0 where a half is empty or the estimate is not finite)
+ *   prefilter  3x3 Gaussian over the variance, coordinates clamped to the frame
+ *   filter     WaveletIterations passes of DenoiserCS (OffsetMultiplier 1 << i) guided by the normals (TB_AOV_NORMALS) and the world positions
+ *              of the last rendered frame L = tb_samples_rendered - 1 (TB_AOV_WORLD_POSITION0 + L % 2): render with option "aov", from the
+ *              first frame on (setting the option resets the history)
+ *   finish     (rgb, 1)
+ * Pixels whose normal AOV is zero -- camera rays that missed, pixels the adaptive launch retired -- keep their mean and weigh nothing as a
+ * neighbour's tap.  dn_or_null: NULL = tb_default_denoiser_settings; Enabled == 0 or WaveletIterations == 0: no filter pass, final is the mean
+ * and no AOV is needed; more than 10 iterations: TB_E_INVALID.  rgba_or_null receives final (W*H*4 floats, row 0 = top).  Synchronous.
+ * TB_E_INVALID (the message names the cause): nothing rendered; the last render was tb_render_realtime; filter passes asked for without the AOVs
+ * of frame L (option "aov" off, or nothing rendered since tb_state_load / tb_state_begin: AOVs are not part of a state).  TB_E_UNSUPPORTED: a
+ * context of a tb_create_multi group (AOVs are not gathered).
+ * Writes neither the accumulation surfaces nor the AOVs, the frame counter or the history: tb_accum_digest is the same before and after, and a
+ * render continued after the call is the uninterrupted render, bit for bit.  Whatever changes the accumulation surfaces (a render, tb_state_load,
+ * tb_state_begin, a history reset) invalidates the denoised surfaces.
+ * Option "post_denoised" = 1: tb_post_process(TB_OUTPUT_TYPE_LIT) and its auto exposure read final instead of the accumulated output
+ * (TB_E_INVALID while no valid denoised surface exists); other output types ignore it.  tb_get_option "last_denoise_us": GPU microseconds of the
+ * last chain, prepare to finish (HIP events).
+ * tb_read_denoise_stage: 0 prepared, 1 filtered (both rgb, variance), 2 the last filter pass's output (rgb, variance; unavailable when no pass
+ * ran), 3 final. */
+int tb_denoise(tb_context* ctx, const tb_denoiser_settings* dn_or_null, float* rgba_or_null);
+int tb_read_denoise_stage(tb_context* ctx, int stage, float* rgba);
+
 /* <-> ReadbackStats copy (TracerBoy.cpp:2946, D3D12App.cpp:195-201) */
 int tb_read_stats(tb_context* ctx, tb_readback_stats* out);
 /* Wave-occupancy profile of the last counting render (option "count_rays"): 7 pairs (active lane-executions,

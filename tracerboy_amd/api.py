@@ -64,6 +64,8 @@ def lib():
         "tb_default_denoiser_settings": (None, [P(abi.tb_denoiser_settings)]),
         "tb_render_realtime": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), P(abi.tb_denoiser_settings), C.c_float]),
         "tb_read_realtime": (C.c_int, [vp, C.c_int, vp]),
+        "tb_denoise": (C.c_int, [vp, P(abi.tb_denoiser_settings), vp]),
+        "tb_read_denoise_stage": (C.c_int, [vp, C.c_int, vp]),
         "tb_post_process": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, vp, vp]),
         "tb_read_averaged_luminance": (C.c_int, [vp, P(C.c_float)]),
         "tb_write_image_rgba8": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, vp]),
@@ -489,6 +491,20 @@ class TracerBoy:
         """0 first TAA output (rgb, variance), 1 moments, 2 denoised, 3 composited, 4 final TAA output."""
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._L.tb_read_realtime(self._ctx, stage, _np_ptr(out)))
+        return out
+
+    def Denoise(self, denoiserSettings=None, read=True):
+        """Denoise the progressive render the context holds (tb_denoise): dual-buffer variance, 3x3 prefilter,
+        WaveletIterations a-trous passes guided by the AOVs of the last frame (render with option "aov"), (rgb, 1).  Leaves the accumulation as
+        it is.  Returns the (H, W, 4) float32 result, or None with read=False (ReadDenoiseStage(3), or option "post_denoised" + PostProcess)."""
+        out = np.empty((self.height, self.width, 4), np.float32) if read else None
+        self._check(self._L.tb_denoise(self._ctx, C.byref(denoiserSettings) if denoiserSettings is not None else None, _np_ptr(out) if read else None))
+        return out
+
+    def ReadDenoiseStage(self, stage):
+        """0 prepared (mean rgb, variance), 1 filtered (variance after the 3x3 Gaussian), 2 the last filter pass's output, 3 final (rgb, 1)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(self._L.tb_read_denoise_stage(self._ctx, stage, _np_ptr(out)))
         return out
 
     def PostProcess(self, postSettings=None, outputType=0, rgba8=True):

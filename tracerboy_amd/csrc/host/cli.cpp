@@ -4,6 +4,7 @@
  *                 [--out frame.png|frame.pfm|frame.exr]
  *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C] [--adaptive-test frame|call]]
  *                 [--save-state f.tbs] [--resume f.tbs] [--add g.tbs]... [--frames A:B] [--checkpoint-every N]
+ *                 [--denoise] [--denoise-iterations N]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -32,7 +33,13 @@
  * adjacent frame ranges: the merge tool of an spp split; --frames A:B renders the frames [A, B) instead of --spp frames from 0, for one job of
  * such a split; --checkpoint-every N renders in calls of N frames (with --adaptive: after every call of its schedule) and saves to the
  * --save-state path after each.  A resumed render takes size, settings and time seed from the file; flags that contradict it are refused.
- * Not together with --ranks N > 1 (exit status 2): the gather moves the output surface only, rank 0 would not hold a complete state. */
+ * Not together with --ranks N > 1 (exit status 2): the gather moves the output surface only, rank 0 would not hold a complete state.
+ *
+ * --denoise (tb_denoise; takes no value): the render runs with option "aov" from its first frame on (the option resets the
+ * history), the picture is denoised after the last frame -- --denoise-iterations N a-trous passes, default 5, 0 = the mean itself -- and --out
+ * is written from the result: .pfm / .exr directly, .png through option "post_denoised".  --save-state still saves the raw accumulation.  With
+ * --resume at least one more frame must be rendered (AOVs are not part of a state).  Not together with --ranks N > 1 (exit status 2): the ranks'
+ * AOVs are not gathered. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -130,15 +137,18 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
     float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
     std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
-    bool sppSet = false, timeSet = false;
-    for (int i = 2; i + 1 < argc; i += 2) {
-        std::string k = argv[i]; const char* v = argv[i + 1];
+    bool sppSet = false, timeSet = false, denoise = false; long long denoiseIterations = -1;
+    for (int i = 2; i < argc; i += 2) {
+        std::string k = argv[i];
+        if (k == "--denoise") { denoise = true; i--; continue; } /* the one flag without a value */
+        if (i + 1 >= argc) break;
+        const char* v = argv[i + 1];
         if (k == "--width") W = (uint32_t)atoi(v); else if (k == "--height") H = (uint32_t)atoi(v); else if (k == "--spp") { spp = (uint32_t)atoi(v); sppSet = true; }
         else if (k == "--depth") depth = atoi(v); else if (k == "--seed-time") { t = (float)atof(v); timeSet = true; } else if (k == "--device") device = atoi(v);
         else if (k == "--builder") builder = !strcmp(v, "sah") ? 1 : !strcmp(v, "lbvh-gpu") ? 2 : !strcmp(v, "treelets") ? 3 : !strcmp(v,
@@ -150,6 +160,8 @@ int main(int argc, char** argv)
             else { fprintf(stderr, "--adaptive-test is frame or call\n"); return 2; } }
         else if (k == "--save-state") saveState = v; else if (k == "--resume") resume = v; else if (k == "--add") adds.push_back(v);
         else if (k == "--checkpoint-every") checkpointEvery = atoll(v);
+        else if (k == "--denoise-iterations") { denoiseIterations = atoll(v);
+            if (denoiseIterations < 0 || denoiseIterations > 10) { fprintf(stderr, "--denoise-iterations is 0 to 10\n"); return 2; } }
         else if (k == "--frames") { char* end = nullptr; frameA = strtoll(v, &end, 10); frameB = end && *end == ':' ? strtoll(end + 1, &end, 10) : -1;
             if (frameA < 0 || frameB < frameA || frameB > 0xffffffffll || !end || *end) { fprintf(stderr, "--frames is A:B with 0 <= A <= B\n"); return 2; } }
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
@@ -165,6 +177,8 @@ int main(int argc, char** argv)
     const bool states = !saveState.empty() || !resume.empty() || !adds.empty() || frameA >= 0 || checkpointEvery != 0;
     if (states && ranks > 1) { fprintf(stderr,
         "--save-state, --resume, --add, --frames and --checkpoint-every do not go with --ranks: the gather moves the output surface only\n"); return 2; }
+    if (denoise && ranks > 1) { fprintf(stderr, "--denoise does not go with --ranks: the ranks' AOVs are not gathered\n"); return 2; }
+    if (denoiseIterations >= 0 && !denoise) { fprintf(stderr, "--denoise-iterations needs --denoise\n"); return 2; }
     if (checkpointEvery < 0 || (checkpointEvery > 0 && saveState.empty())) { fprintf(stderr, "--checkpoint-every N needs N >= 1 and --save-state\n"); return 2; }
     if (frameA >= 0 && (sppSet || !resume.empty())) { fprintf(stderr, "--frames A:B stands in place of --spp and starts its own accumulation (no --resume)\n"); return 2; }
     if (!adds.empty() && resume.empty()) { fprintf(stderr, "--add merges into the state --resume loads\n"); return 2; }
@@ -180,6 +194,7 @@ int main(int argc, char** argv)
     int rc = tb_create(&ctx, device);
     if (rc) return fail(nullptr, "tb_create", rc);
     tb_set_option(ctx, "bvh_builder", builder);
+    if (denoise && (rc = tb_set_option(ctx, "aov", 1))) return fail(ctx, "tb_set_option", rc); /* before the first frame: the option resets the history */
     auto t0 = std::chrono::steady_clock::now();
     if ((rc = tb_load_scene(ctx, scene.c_str()))) return fail(ctx, "tb_load_scene", rc);
     double loadS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -215,6 +230,9 @@ int main(int argc, char** argv)
         const float convergence = s.ConvergencePercentage; s = held.settings; if (adaptive >= 0.0f) s.ConvergencePercentage = convergence;
         done = tb_samples_rendered(ctx); /* after the --add files */
         target = sppSet ? std::max(spp, done) : done;
+        if (denoise && target <= done) { fprintf(stderr,
+            "tracerboy-hip: --resume with --denoise: render at least one more frame (--spp above the %u the state holds): the filter is guided by the "
+            "last frame's normals and positions, and AOVs are not part of a state\n", done); tb_destroy(ctx); return 1; }
     } else if (frameA >= 0) {
         if ((rc = tb_state_begin(ctx, W, H, &s, t, (uint32_t)frameA))) return fail(ctx, "tb_state_begin", rc);
         done = (uint32_t)frameA; target = (uint32_t)frameB;
@@ -315,10 +333,21 @@ int main(int argc, char** argv)
 #undef HIP_OK
     }
     const bool png = out.size() >= 4 && out.compare(out.size() - 4, 4, ".png") == 0;
+    std::vector<float> denoised;
+    if (denoise) { /* after --save-state: a state is the raw accumulation */
+        tb_denoiser_settings dn; tb_default_denoiser_settings(&dn);
+        if (denoiseIterations >= 0) dn.WaveletIterations = (uint32_t)denoiseIterations;
+        if (!png) denoised.resize((size_t)W * H * 4);
+        if ((rc = tb_denoise(ctx, &dn, png ? nullptr : denoised.data()))) return fail(ctx, "tb_denoise", rc);
+        printf("denoise: %u a-trous passes, %.3f ms on the GPU\n", dn.WaveletIterations, (double)tb_get_option(ctx, "last_denoise_us") / 1e3);
+        if (png && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
+    }
     if (png) {
         std::vector<uint8_t> img((size_t)W * H * 4);
         if ((rc = tb_post_process(ctx, &post, TB_OUTPUT_TYPE_LIT, nullptr, img.data()))) return fail(ctx, "tb_post_process", rc);
         if ((rc = tb_write_image_rgba8(out.c_str(), W, H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc);
+    } else if (denoise) {
+        if ((rc = tb_write_image_f32(out.c_str(), W, H, denoised.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
     } else {
         std::vector<float> acc((size_t)W * H * 4);
         if ((rc = tb_read_accum(ctx, acc.data(), nullptr))) return fail(ctx, "tb_read_accum", rc);

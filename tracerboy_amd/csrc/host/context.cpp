@@ -224,7 +224,7 @@ static int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const 
         resetHistory(all[i]); }
     for (uint32_t i = world; i-- > 0;) { /* the peers first: their launches are in flight while the owner's are enqueued */
         tb_context* x = all[i];
-        const int rc = guarded(x, [&]() { x->options = c->options; x->selX = c->selX; x->selY = c->selY; x->lastRenderRealtime = false; return renderImpl(x, W,
+        const int rc = guarded(x, [&]() { x->options = c->options; x->selX = c->selX; x->selY = c->selY; x->lastRenderRealtime = false; touchAccumulation(x); return renderImpl(x, W,
             H, n, s, t, false); });
         if (rc != TB_OK) return x == c ? rc : fail(c, rc, "peer device " + std::to_string(x->device) + ": " + x->err);
     }
@@ -266,13 +266,13 @@ int tb_render(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output
 {
     TB_REFUSE_PEER(c);
     if (c && !c->peers.empty()) { const int rc = renderGroup(c, W, H, n, s, t); return rc != TB_OK ? rc : tb_sync(c); }
-    return guarded(c, [&]() { c->lastRenderRealtime = false; return renderImpl(c, W, H, n, s, t, true); });
+    return guarded(c, [&]() { c->lastRenderRealtime = false; touchAccumulation(c); return renderImpl(c, W, H, n, s, t, true); });
 }
 int tb_render_async(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* s, float t)
 {
     TB_REFUSE_PEER(c);
     if (c && !c->peers.empty()) return renderGroup(c, W, H, n, s, t);
-    return guarded(c, [&]() { c->lastRenderRealtime = false; return renderImpl(c, W, H, n, s, t, false); });
+    return guarded(c, [&]() { c->lastRenderRealtime = false; touchAccumulation(c); return renderImpl(c, W, H, n, s, t, false); });
 }
 int tb_sync(tb_context* c)
 {
@@ -349,6 +349,7 @@ int tb_render_realtime(tb_context* c, uint32_t W, uint32_t H, const tb_output_se
             }
             c->rtWidth = W; c->rtHeight = H; c->rtActive = 0; c->prevCamera = c->camera;
         }
+        touchAccumulation(c);
         int rc = renderImpl(c, W, H, 1, &s, timeSeed, false);
         c->options.value[OPT_aov] = savedAov; c->options.isSet[OPT_aov] = savedSet;
         if (rc != TB_OK) return rc;
@@ -427,7 +428,13 @@ int tb_post_process(tb_context* c, const tb_post_settings* post, uint32_t output
         const TbFloat4* in = nullptr; const float* inR32 = nullptr;
         switch (outputType) { /* GetOutputSRV, TracerBoy.cpp:2354-2383 */
         /* PostProcessInput after the real-time chain, TracerBoy.cpp:3144-3160 */
-        case TB_OUTPUT_TYPE_LIT: in = (const TbFloat4*)(c->lastRenderRealtime ? c->rtFinal[c->rtLast[4]].p : c->output.p); break;
+        case TB_OUTPUT_TYPE_LIT:
+            if (opt<OPT_post_denoised>(c)) { /* the denoised still (tb_denoise): (rgb, 1), so that ProcessLit's division by .w is the identity */
+                if (!c->dnValid) return fail(c, TB_E_INVALID,
+                    "tb_post_process: option \"post_denoised\" is set and there is no valid denoised surface: call tb_denoise after the last change of the accumulation");
+                in = (const TbFloat4*)c->dnFinal.p; break;
+            }
+            in = (const TbFloat4*)(c->lastRenderRealtime ? c->rtFinal[c->rtLast[4]].p : c->output.p); break;
         case TB_OUTPUT_TYPE_LUMINANCE: in = (const TbFloat4*)c->output.p; break;
         case TB_OUTPUT_TYPE_ALBEDO: case TB_OUTPUT_TYPE_LIVE_PIXELS: case TB_OUTPUT_TYPE_HEATMAP: in = (const TbFloat4*)c->aov[TB_AOV_CUSTOM].p; break;
         case TB_OUTPUT_TYPE_NORMAL: in = (const TbFloat4*)c->aov[TB_AOV_NORMALS].p; break;
@@ -674,6 +681,7 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "last_state_digest_us")) return (int64_t)(c->lastStateDigestMs * 1000.0f + 0.5f);
     if (!strcmp(name, "last_state_add_us")) return (int64_t)(c->lastStateAddMs * 1000.0f + 0.5f);
     if (!strcmp(name, "state_first_frame")) return c->firstFrame;
+    if (!strcmp(name, "last_denoise_us")) return (int64_t)(c->lastDenoiseMs * 1000.0f + 0.5f); /* the last tb_denoise, prepare to finish (HIP events) */
     if (!strcmp(name, "last_copy_waves")) return c->lastCopyWaves;
     /* the adaptive launch: did the last call run it; the owned pixels that were live at its first frame (all owned pixels of a call that did not run
      * it) -- a device word: reading it waits for the call.  A group's owner counts its peers' too. */

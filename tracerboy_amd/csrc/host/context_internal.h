@@ -4,6 +4,7 @@
  *   context_scene.cpp   finalizeScene: BVH builds on the GPU, node orders, layout C, uploads, the LDS scene image
  *   context_render.cpp  renderImpl, a sequence of named steps, and the pipelines it dispatches to
  *   render_state.cpp    render states: begin at a frame, save, load, merge
+ *   context_denoise.cpp the denoise of a progressive render: dual-buffer variance + the a-trous filter
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
 #pragma once
@@ -157,6 +158,12 @@ struct tb_context {
     DevBuf stateScratch; /* the digest's per-workgroup partials and its two results (state_launch.h) */
     tbctx::DevEvent evState[2]; float lastStateDigestMs = 0.0f, lastStateAddMs = 0.0f; /* options last_state_digest_us / last_state_add_us */
     uint64_t sceneDigest = 0, sceneDigestKey = ~0ull; uint32_t materialEdits = 0; /* tb_scene_digest, cached per (sceneGeneration, materialEdits) */
+    /* the denoise of a progressive render (context_denoise.cpp): prepared, filtered, the filter passes' ping-pong, final.
+     * dnValid: they belong to the accumulation surfaces as they are now -- whatever writes those clears it (touchAccumulation); dnLastPass: which
+     * dnPass holds the last filter pass's output, -1 = no pass ran.  aovStaleUntilCall: the AOVs hold the first hits of frame samplesRendered - 1
+     * once callCount has reached it (a state that was begun or loaded brings frames without AOVs) */
+    DevBuf dnPrepared, dnFiltered, dnPass[2], dnFinal; bool dnValid = false; int dnLastPass = -1; uint64_t aovStaleUntilCall = 0;
+    tbctx::DevEvent evDn[2]; float lastDenoiseMs = 0.0f; /* option last_denoise_us */
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -197,7 +204,9 @@ namespace tbctx {
 
 int fail(tb_context* c, int code, const std::string& msg);
 /* forget the accumulated frames: the next render starts at frame 0 (where the kernels overwrite the surfaces instead of adding to them) */
-inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; }
+inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dnValid = false; }
+/* the accumulation surfaces are about to change (a render, a state that is begun, loaded or added): the denoised surfaces no longer belong to them */
+inline void touchAccumulation(tb_context* c) { c->dnValid = false; }
 /* an entry point that only a group's own context may be asked */
 #define TB_REFUSE_PEER(c) do { if ((c) && (c)->groupOwner) return fail((c), TB_E_INVALID, \
     "this context is a member of a multi-device group: call the group's context"); } while (0)

@@ -131,6 +131,7 @@ void adopt(tb_context* x, uint32_t W, uint32_t H, const tb_output_settings& s, f
     if (x->rayStats.p) HIP_TRY(hipMemsetAsync(x->rayStats.p, 0, x->rayStats.bytes, x->stream));
     x->width = W; x->height = H; x->lastSettings = s; x->haveLastSettings = true; x->lastTime = timeSeed;
     x->firstFrame = first; x->samplesRendered = next; x->lastRenderRealtime = false;
+    touchAccumulation(x); x->aovStaleUntilCall = x->callCount + 1; /* the state's frames come without AOVs (context_denoise.cpp) */
 }
 
 /* a group deals 64x64 tiles round-robin (renderGroup): with the map in place already the group's first render keeps the frames */
@@ -311,6 +312,7 @@ int tb_state_load(tb_context* c, const char* path, uint32_t flags)
             if (dev[0] != h.output_digest || dev[1] != h.jittered_digest) { if (!add) forget(); return fail(c, TB_E_DEVICE,
                 "tb_state_load: output_digest / jittered_digest: the uploaded surfaces do not have the file's digests on device " + std::to_string(x->device)); }
             if (add) {
+                touchAccumulation(x); x->aovStaleUntilCall = x->callCount + 1;
                 if (x->samplesRendered == x->firstFrame) { /* an empty range: whatever an earlier history left in the surfaces does not count */
                     HIP_TRY(hipMemsetAsync(x->output.p, 0, bytes, x->stream)); HIP_TRY(hipMemsetAsync(x->jittered.p, 0, bytes, x->stream)); }
                 HIP_TRY(hipEventRecord(x->evState[0].create(), x->stream));

@@ -1,0 +1,16 @@
+/* dn_launch.h -- the launchers of dn_kernels.hip: the three passes a still's denoise adds around the a-trous filter of rt_kernels.hip
+ * (DESIGN.md section 12).  Each streams RGBA32F surfaces of nPixels = W x H pixels once; none knows about frames, options or contexts.
+ * Every surface 16-B aligned; a launcher refuses (hipErrorInvalidValue) a null or misaligned surface and a zero-sized frame. */
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "tb_abi.h"
+
+extern "C" {
+/* prepared[i] = (mean colour of output[i], variance of the luminance of that mean estimated from the two halves output / jittered hold) */
+hipError_t dn_launch_prepare(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, TbFloat4* prepared, uint32_t W, uint32_t H);
+/* filtered[i] = (prepared[i].xyz, 3x3 Gaussian of prepared.w, coordinates clamped to the frame) */
+hipError_t dn_launch_prefilter(hipStream_t stream, const TbFloat4* prepared, TbFloat4* filtered, uint32_t W, uint32_t H);
+/* final[i] = (in[i].xyz, 1) */
+hipError_t dn_launch_finish(hipStream_t stream, const TbFloat4* in, TbFloat4* final, uint32_t W, uint32_t H);
+}
