@@ -202,6 +202,42 @@ int tb_read_realtime(tb_context* ctx, int stage, float* rgba);
 int tb_denoise(tb_context* ctx, const tb_denoiser_settings* dn_or_null, float* rgba_or_null);
 int tb_read_denoise_stage(tb_context* ctx, int stage, float* rgba);
 
+/* ---- the guide pass of a denoised still ---------------------------------------
+ * Seeds depend on (x, y, frame) only, so the first hits of any frames can be traced again at any time -- after a render that ran with option "aov"
+ * off, at full speed, or after tb_state_load / tb_state_begin.  tb_render_guides traces the first bounce of the frames [first_frame, first_frame +
+ * n_frames) with the context's current size, settings, time seed and camera (those of the last tb_render, tb_state_load or tb_state_begin; any
+ * frame range, inside the rendered one or not; 1 <= n_frames <= 256; every pixel, adaptive retirement is ignored) and replaces the three guide
+ * surfaces, RGBA32F, W x H, fp32 sums acc = acc + v from 0 in frame order:
+ *   0 albedo    (sum of e_f, frames)                   e_f = the frame's albedo AOV, or (1, 1, 1) where it is all zero (a miss, a light, a path
+ *                                                      that ended before it stored one): a pixel half on a light blends towards "not demodulated"
+ *   1 normal    (sum of the normal AOV over the frames that hit, their number)      a frame hits where its normal AOV is not all zero
+ *   2 position  (sum of the world position over the frames that hit, sum of the distance to the neighbour's hit over them)
+ * With n_frames = 1 these are the AOVs a render with option "aov" leaves of that frame (TB_AOV_CUSTOM with zeros as ones, TB_AOV_NORMALS,
+ * TB_AOV_WORLD_POSITION0 + frame % 2).  Synchronous.  Writes nothing else: accumulation, AOVs, frame counter, history and tb_accum_digest are what
+ * they were, and a render continued afterwards is the uninterrupted one, bit for bit.
+ * TB_E_INVALID (the message names the cause): no scene; no size yet; the last render was tb_render_realtime; an OutputType whose custom AOV is not
+ * the albedo (heat map, live pixels); n_frames out of range.  TB_E_UNSUPPORTED: a tb_create_multi group; a tile assignment with world > 1.
+ * The guides stay valid while scene, camera, size, history-relevant settings, time seed and option "alpha_test" are those they were traced with:
+ * whatever resets the history, a resize or a scene load invalidates them; further rendering, tb_state_load(TB_STATE_ADD) and a TB_STATE_REPLACE
+ * that leaves all of those equal do not.  tb_read_guide reads surface `which` (0..2; W*H*4 floats, row 0 = top; TB_E_INVALID without valid
+ * guides).  tb_get_option "last_guides_us": GPU microseconds of the last pass's kernel (HIP events).
+ * "last_guides_stack_overflow": stack entries per lane that pass kept in global memory (0: the whole traversal stack in LDS).
+ * Option "denoise_guides" (does not reset the history) selects what tb_denoise reads:
+ *   0 (default)  section 12 as it stands, bit for bit
+ *   1            the filter's normals = sum / hits (brought back to length 1 where hits > 1: a mean of unequal normals is shorter than 1 and the
+ *                filter raises dot products to NormalWeightingExponential), (0, 0, 0) where no frame hit; positions = sum / hits, all four
+ *                components.  No AOV is needed: neither option "aov" nor a frame rendered since a state was loaded.  With guides of the one frame
+ *                tb_samples_rendered - 1 the result is mode 0's of a render with option "aov", bit for bit.
+ *   2            mode 1, and the chain runs on demodulated colour: d = max(albedo.xyz / albedo.w, 0.01) per channel, prepare divides the mean and
+ *                both halves' means by d (the variance is that of the demodulated luminance), finish multiplies by d.  tb_read_denoise_stage
+ *                0-2 are in the demodulated domain, 3 is remodulated.
+ * With 1 or 2 and no valid guides tb_denoise returns TB_E_INVALID and says to call tb_render_guides. */
+#define TB_GUIDE_ALBEDO 0
+#define TB_GUIDE_NORMAL 1
+#define TB_GUIDE_POSITION 2
+int tb_render_guides(tb_context* ctx, uint32_t first_frame, uint32_t n_frames);
+int tb_read_guide(tb_context* ctx, int which, float* rgba);
+
 /* <-> ReadbackStats copy (TracerBoy.cpp:2946, D3D12App.cpp:195-201) */
 int tb_read_stats(tb_context* ctx, tb_readback_stats* out);
 /* Wave-occupancy profile of the last counting render (option "count_rays"): 7 pairs (active lane-executions,

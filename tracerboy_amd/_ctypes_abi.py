@@ -1,6 +1,9 @@
 """ctypes mirrors of include/tb_abi.h and include/tracerboy_hip.h (POD layouts only, no logic)."""
 import ctypes as C
 
+# tb_read_guide selectors (include/tracerboy_hip.h, the guide pass)
+TB_GUIDE_ALBEDO, TB_GUIDE_NORMAL, TB_GUIDE_POSITION = 0, 1, 2
+
 
 class TbFloat2(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float)]

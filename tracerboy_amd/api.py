@@ -66,6 +66,8 @@ def lib():
         "tb_read_realtime": (C.c_int, [vp, C.c_int, vp]),
         "tb_denoise": (C.c_int, [vp, P(abi.tb_denoiser_settings), vp]),
         "tb_read_denoise_stage": (C.c_int, [vp, C.c_int, vp]),
+        "tb_render_guides": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
+        "tb_read_guide": (C.c_int, [vp, C.c_int, vp]),
         "tb_post_process": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, vp, vp]),
         "tb_read_averaged_luminance": (C.c_int, [vp, P(C.c_float)]),
         "tb_write_image_rgba8": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, vp]),
@@ -505,6 +507,19 @@ class TracerBoy:
         """0 prepared (mean rgb, variance), 1 filtered (variance after the 3x3 Gaussian), 2 the last filter pass's output, 3 final (rgb, 1)."""
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._L.tb_read_denoise_stage(self._ctx, stage, _np_ptr(out)))
+        return out
+
+    def RenderGuides(self, first_frame, n_frames):
+        """The guide pass (tb_render_guides): the first hits of frames [first_frame, first_frame + n_frames) traced again with
+        the context's current size, settings, time seed and camera, summed into the three guide surfaces.  Leaves everything else as it is.
+        Option "denoise_guides" = 1 / 2 makes Denoise read them."""
+        self._check(self._L.tb_render_guides(self._ctx, first_frame, n_frames))
+
+    def ReadGuide(self, which):
+        """0 albedo (sum of the effective albedo, frames), 1 normal (sum over the frames that hit, their number), 2 position (sum of world
+        positions, sum of neighbour distances): (H, W, 4) float32."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(self._L.tb_read_guide(self._ctx, which, _np_ptr(out)))
         return out
 
     def PostProcess(self, postSettings=None, outputType=0, rgba8=True):

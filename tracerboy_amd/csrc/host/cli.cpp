@@ -4,7 +4,7 @@
  *                 [--out frame.png|frame.pfm|frame.exr]
  *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C] [--adaptive-test frame|call]]
  *                 [--save-state f.tbs] [--resume f.tbs] [--add g.tbs]... [--frames A:B] [--checkpoint-every N]
- *                 [--denoise] [--denoise-iterations N]
+ *                 [--denoise] [--denoise-iterations N] [--denoise-guides K [--denoise-demodulate]]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -39,7 +39,13 @@
  * history), the picture is denoised after the last frame -- --denoise-iterations N a-trous passes, default 5, 0 = the mean itself -- and --out
  * is written from the result: .pfm / .exr directly, .png through option "post_denoised".  --save-state still saves the raw accumulation.  With
  * --resume at least one more frame must be rendered (AOVs are not part of a state).  Not together with --ranks N > 1 (exit status 2): the ranks'
- * AOVs are not gathered. */
+ * AOVs are not gathered.
+ *
+ * --denoise-guides K (tb_render_guides; implies --denoise): the render runs WITHOUT option "aov", at full speed; after the last
+ * frame the first hits of the last min(K, frames held) frames of the state's range are traced again and summed, and the filter is guided by their
+ * means (option "denoise_guides" = 1).  Guides are not part of a state either, but they can be traced at any time: --resume s.tbs --denoise-guides 8
+ * with no frame left to render works.  --denoise-demodulate (takes no value; needs --denoise-guides): the chain runs on colour divided by the mean
+ * albedo of those frames and multiplies it back at the end (option "denoise_guides" = 2).  K is 1 to 256. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -137,16 +143,17 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
     float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
     std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
-    bool sppSet = false, timeSet = false, denoise = false; long long denoiseIterations = -1;
+    bool sppSet = false, timeSet = false, denoise = false, demodulate = false; long long denoiseIterations = -1, denoiseGuides = 0;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
-        if (k == "--denoise") { denoise = true; i--; continue; } /* the one flag without a value */
+        if (k == "--denoise") { denoise = true; i--; continue; } /* the flags without a value */
+        if (k == "--denoise-demodulate") { demodulate = true; i--; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[i + 1];
         if (k == "--width") W = (uint32_t)atoi(v); else if (k == "--height") H = (uint32_t)atoi(v); else if (k == "--spp") { spp = (uint32_t)atoi(v); sppSet = true; }
@@ -162,6 +169,8 @@ int main(int argc, char** argv)
         else if (k == "--checkpoint-every") checkpointEvery = atoll(v);
         else if (k == "--denoise-iterations") { denoiseIterations = atoll(v);
             if (denoiseIterations < 0 || denoiseIterations > 10) { fprintf(stderr, "--denoise-iterations is 0 to 10\n"); return 2; } }
+        else if (k == "--denoise-guides") { denoiseGuides = atoll(v); denoise = true;
+            if (denoiseGuides < 1 || denoiseGuides > 256) { fprintf(stderr, "--denoise-guides is 1 to 256\n"); return 2; } }
         else if (k == "--frames") { char* end = nullptr; frameA = strtoll(v, &end, 10); frameB = end && *end == ':' ? strtoll(end + 1, &end, 10) : -1;
             if (frameA < 0 || frameB < frameA || frameB > 0xffffffffll || !end || *end) { fprintf(stderr, "--frames is A:B with 0 <= A <= B\n"); return 2; } }
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
@@ -178,6 +187,7 @@ int main(int argc, char** argv)
     if (states && ranks > 1) { fprintf(stderr,
         "--save-state, --resume, --add, --frames and --checkpoint-every do not go with --ranks: the gather moves the output surface only\n"); return 2; }
     if (denoise && ranks > 1) { fprintf(stderr, "--denoise does not go with --ranks: the ranks' AOVs are not gathered\n"); return 2; }
+    if (demodulate && !denoiseGuides) { fprintf(stderr, "--denoise-demodulate needs --denoise-guides K\n"); return 2; }
     if (denoiseIterations >= 0 && !denoise) { fprintf(stderr, "--denoise-iterations needs --denoise\n"); return 2; }
     if (checkpointEvery < 0 || (checkpointEvery > 0 && saveState.empty())) { fprintf(stderr, "--checkpoint-every N needs N >= 1 and --save-state\n"); return 2; }
     if (frameA >= 0 && (sppSet || !resume.empty())) { fprintf(stderr, "--frames A:B stands in place of --spp and starts its own accumulation (no --resume)\n"); return 2; }
@@ -194,7 +204,7 @@ int main(int argc, char** argv)
     int rc = tb_create(&ctx, device);
     if (rc) return fail(nullptr, "tb_create", rc);
     tb_set_option(ctx, "bvh_builder", builder);
-    if (denoise && (rc = tb_set_option(ctx, "aov", 1))) return fail(ctx, "tb_set_option", rc); /* before the first frame: the option resets the history */
+    if (denoise && !denoiseGuides && (rc = tb_set_option(ctx, "aov", 1))) return fail(ctx, "tb_set_option", rc); /* before the first frame: the option resets the history */
     auto t0 = std::chrono::steady_clock::now();
     if ((rc = tb_load_scene(ctx, scene.c_str()))) return fail(ctx, "tb_load_scene", rc);
     double loadS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -230,7 +240,7 @@ int main(int argc, char** argv)
         const float convergence = s.ConvergencePercentage; s = held.settings; if (adaptive >= 0.0f) s.ConvergencePercentage = convergence;
         done = tb_samples_rendered(ctx); /* after the --add files */
         target = sppSet ? std::max(spp, done) : done;
-        if (denoise && target <= done) { fprintf(stderr,
+        if (denoise && !denoiseGuides && target <= done) { fprintf(stderr,
             "tracerboy-hip: --resume with --denoise: render at least one more frame (--spp above the %u the state holds): the filter is guided by the "
             "last frame's normals and positions, and AOVs are not part of a state\n", done); tb_destroy(ctx); return 1; }
     } else if (frameA >= 0) {
@@ -338,6 +348,13 @@ int main(int argc, char** argv)
         tb_denoiser_settings dn; tb_default_denoiser_settings(&dn);
         if (denoiseIterations >= 0) dn.WaveletIterations = (uint32_t)denoiseIterations;
         if (!png) denoised.resize((size_t)W * H * 4);
+        if (denoiseGuides) { /* the last min(K, frames held) frames of the state's range, traced again */
+            const uint32_t next = tb_samples_rendered(ctx), first = (uint32_t)tb_get_option(ctx, "state_first_frame");
+            const uint32_t k = (uint32_t)std::min<long long>(denoiseGuides, (long long)next - (long long)first);
+            if ((rc = tb_render_guides(ctx, next - k, k))) return fail(ctx, "tb_render_guides", rc);
+            printf("guides: first hits of frames [%u, %u), %.3f ms on the GPU\n", next - k, next, (double)tb_get_option(ctx, "last_guides_us") / 1e3);
+            if ((rc = tb_set_option(ctx, "denoise_guides", demodulate ? 2 : 1))) return fail(ctx, "tb_set_option", rc);
+        }
         if ((rc = tb_denoise(ctx, &dn, png ? nullptr : denoised.data()))) return fail(ctx, "tb_denoise", rc);
         printf("denoise: %u a-trous passes, %.3f ms on the GPU\n", dn.WaveletIterations, (double)tb_get_option(ctx, "last_denoise_us") / 1e3);
         if (png && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);

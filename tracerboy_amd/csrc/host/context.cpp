@@ -634,6 +634,8 @@ int tb_set_option(tb_context* c, const char* name, int64_t v)
     /* adaptive_test 0: the skip test runs before every frame (the reference's); 1: once per call, at its first frame */
     if ((kOptions[k].flags & OPT_ZERO_OR_ONE) && v != 0 && v != 1) return fail(c, TB_E_INVALID, std::string("tb_set_option: ") + name +
         " is 0 (before every frame) or 1 (once per call)");
+    if (k == OPT_denoise_guides && (v < 0 || v > 2)) return fail(c, TB_E_INVALID,
+        "tb_set_option: denoise_guides is 0 (the last frame's AOVs), 1 (the guide pass's normals and positions) or 2 (1 + albedo demodulation)");
     /* the adaptive launch has no counting copy */
     if (v && ((k == OPT_adaptive && opt<OPT_count_rays>(c)) || (k == OPT_count_rays && opt<OPT_adaptive>(c))))
         return fail(c, TB_E_INVALID, "tb_set_option: options \"adaptive\" and \"count_rays\" exclude each other (the counting kernels have no adaptive copy)");
@@ -682,6 +684,8 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "last_state_add_us")) return (int64_t)(c->lastStateAddMs * 1000.0f + 0.5f);
     if (!strcmp(name, "state_first_frame")) return c->firstFrame;
     if (!strcmp(name, "last_denoise_us")) return (int64_t)(c->lastDenoiseMs * 1000.0f + 0.5f); /* the last tb_denoise, prepare to finish (HIP events) */
+    if (!strcmp(name, "last_guides_us")) return (int64_t)(c->lastGuidesMs * 1000.0f + 0.5f); /* the last tb_render_guides, its kernel alone (HIP events) */
+    if (!strcmp(name, "last_guides_stack_overflow")) return c->lastGuidesOverflow; /* stack entries per lane the last pass kept in global memory (the HYBRID form) */
     if (!strcmp(name, "last_copy_waves")) return c->lastCopyWaves;
     /* the adaptive launch: did the last call run it; the owned pixels that were live at its first frame (all owned pixels of a call that did not run
      * it) -- a device word: reading it waits for the call.  A group's owner counts its peers' too. */

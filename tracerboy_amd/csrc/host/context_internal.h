@@ -5,6 +5,7 @@
  *   context_render.cpp  renderImpl, a sequence of named steps, and the pipelines it dispatches to
  *   render_state.cpp    render states: begin at a frame, save, load, merge
  *   context_denoise.cpp the denoise of a progressive render: dual-buffer variance + the a-trous filter
+ *   context_guides.cpp  the guide pass of that denoise: first hits traced again and summed over frames
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
 #pragma once
@@ -164,6 +165,12 @@ struct tb_context {
      * once callCount has reached it (a state that was begun or loaded brings frames without AOVs) */
     DevBuf dnPrepared, dnFiltered, dnPass[2], dnFinal; bool dnValid = false; int dnLastPass = -1; uint64_t aovStaleUntilCall = 0;
     tbctx::DevEvent evDn[2]; float lastDenoiseMs = 0.0f; /* option last_denoise_us */
+    /* the guide pass (context_guides.cpp): the sums over its frames (albedo, normal, position), its half of a split stack, and
+     * what the filter reads of them (dnNormals, dnPositions: resolved by tb_denoise).  guidesValid: they were traced of the scene, camera, size,
+     * settings and time seed in guideKey, and no history reset has come since (resetHistory clears it; guidesCurrent compares the key) */
+    DevBuf guide[3], guideOverflow, dnNormals, dnPositions; bool guidesValid = false; int dnMode = 0; /* option denoise_guides of the last tb_denoise */
+    struct GuideKey { uint32_t sceneGeneration, materialEdits, width, height, alphaTest; tb_camera camera; tb_output_settings settings; float time; } guideKey{};
+    tbctx::DevEvent evGuide[2]; float lastGuidesMs = 0.0f; uint32_t lastGuidesOverflow = 0; /* options last_guides_us, last_guides_stack_overflow */
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -204,7 +211,7 @@ namespace tbctx {
 
 int fail(tb_context* c, int code, const std::string& msg);
 /* forget the accumulated frames: the next render starts at frame 0 (where the kernels overwrite the surfaces instead of adding to them) */
-inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dnValid = false; }
+inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dnValid = false; c->guidesValid = false; }
 /* the accumulation surfaces are about to change (a render, a state that is begun, loaded or added): the denoised surfaces no longer belong to them */
 inline void touchAccumulation(tb_context* c) { c->dnValid = false; }
 /* an entry point that only a group's own context may be asked */
@@ -261,5 +268,8 @@ bool historyRelevantChange(const tb_output_settings& a, const tb_output_settings
 int deviceCUs(tb_context* c);
 std::string splitAbortMessage(tb_context* c, bool clear = true);
 int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* settings, float timeSeed, bool sync);
+void cameraConstants(const TbPerFrameConstants& pf, uint32_t W, uint32_t H, TbDeviceTargets& tg);
+/* context_guides.cpp: the guide surfaces belong to the context as it is now */
+bool guidesCurrent(const tb_context* c);
 
 } // namespace tbctx

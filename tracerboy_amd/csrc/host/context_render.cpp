@@ -460,6 +460,17 @@ static void decideAdaptive(RenderCall& r)
     r.pipe = opt<OPT_pipeline>(c) == 4 ? 0 : opt<OPT_pipeline>(c);
 }
 
+/* TbDeviceTargets::camPre: path_begin's own expressions (pt_device.hpp), evaluated once */
+void cameraConstants(const TbPerFrameConstants& pf, uint32_t W, uint32_t H, TbDeviceTargets& tg)
+{
+    const float resX = (float)W, resY = (float)H;
+    const tb3 camPos = tb3_make(pf.CameraPosition.x, pf.CameraPosition.y, pf.CameraPosition.z);
+    const tb3 lookAt = tb3_make(pf.CameraLookAt.x, pf.CameraLookAt.y, pf.CameraLookAt.z);
+    const tb3 focal = camPos - pf.FocalDistance * tb3_normalize(lookAt - camPos);
+    tg.camFocal[0] = focal.x; tg.camFocal[1] = focal.y; tg.camFocal[2] = focal.z;
+    tg.camInvResX = 1.0f / resX; tg.camInvResY = 1.0f / resY; tg.camAspect = resX / resY; tg.camPre = 1u;
+}
+
 /* TbDeviceTargets: surfaces, AOVs, counters (sized and cleared on the main stream), the frame constants and the camera's */
 static void fillTargets(RenderCall& r)
 {
@@ -483,14 +494,7 @@ static void fillTargets(RenderCall& r)
     if (r.count || opt<OPT_debug_profile_groups>(c)) { ensure(c->rayStats, 21 * 8); if (c->samplesRendered == 0) HIP_TRY(hipMemsetAsync(c->rayStats.p, 0, 21 * 8, c->stream));
         tg.rayStats = (unsigned long long*)c->rayStats.p; }
     MakeFrameConstants(c->scene, c->camera, r.s, c->samplesRendered, r.timeSeed, c->selX, c->selY, r.pf);
-    if (opt<OPT_camera_constants>(c) != 0) { /* TbDeviceTargets::camPre: path_begin's own expressions (pt_device.hpp), evaluated once */
-        const TbPerFrameConstants& pf = r.pf; const float resX = (float)W, resY = (float)H;
-        const tb3 camPos = tb3_make(pf.CameraPosition.x, pf.CameraPosition.y, pf.CameraPosition.z);
-        const tb3 lookAt = tb3_make(pf.CameraLookAt.x, pf.CameraLookAt.y, pf.CameraLookAt.z);
-        const tb3 focal = camPos - pf.FocalDistance * tb3_normalize(lookAt - camPos);
-        tg.camFocal[0] = focal.x; tg.camFocal[1] = focal.y; tg.camFocal[2] = focal.z;
-        tg.camInvResX = 1.0f / resX; tg.camInvResY = 1.0f / resY; tg.camAspect = resX / resY; tg.camPre = 1u;
-    }
+    if (opt<OPT_camera_constants>(c) != 0) cameraConstants(r.pf, W, H, tg);
 }
 
 /* what PlanLaunch (launch_plan.h) is told about this context's scene, the call and the options */

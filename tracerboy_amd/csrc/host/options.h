@@ -19,6 +19,7 @@ enum : uint32_t {
     X(guided_groups, 1, 0) X(costly_first, 1, 0) X(costly_late_samples, 1ll << 40, 0) X(banded_items, 0, 0) X(camera_constants, 1, 0) \
     X(count_rays, 0, OPT_RESETS_HISTORY) X(aov, 0, OPT_RESETS_HISTORY) X(force_full_variant, 0, 0) X(debug_profile_groups, 0, 0) X(alpha_test, 0, 0) \
     X(post_denoised, 0, 0) /* tb_post_process(LIT) reads the denoised still of tb_denoise */ \
+    X(denoise_guides, 0, 0) /* tb_denoise: 0 = the last frame's AOVs, 1 = the guide pass's normals and positions, 2 = 1 + albedo demodulation */ \
     X(adaptive, 0, 0) X(adaptive_min_frames, 1024 /* the reference's */, OPT_NOT_NEGATIVE) X(adaptive_test, 0, OPT_ZERO_OR_ONE) \
     X(wavefront_paths, 16ll << 20, 0) X(wavefront_grid, 256 * 8, 0) X(wavefront_segment, 4096, 0) X(wavefront_sort, 0, 0) X(wavefront_refill, 0, 0) \
     X(pooled_paths, 2, 0) X(pooled_samples, 256ll << 20, 0) X(pooled_profile, 0, 0) \

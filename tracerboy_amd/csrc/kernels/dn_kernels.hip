@@ -5,11 +5,16 @@
  *   dn_prepare_kernel     mean colour, and the variance of its luminance from the difference of the two halves' means
  *   dn_prefilter_kernel   3x3 Gaussian over that variance (a one-sample chi-square estimate per pixel), coordinates clamped to the frame
  *   dn_finish_kernel      (rgb, 1): a surface the output stage's division by .w leaves as it is
+ * and for the chain that takes its guides from the guide pass (guide_kernels.hip; DESIGN.md section 13, option "denoise_guides"):
+ *   dn_resolve_guides_kernel  the sums of the guide pass to the filter's normals and positions: sum / frames that hit, zero where none did
+ *   dn_prepare_demod_kernel   dn_prepare_kernel with the mean colour and both halves' means divided by d = max(mean effective albedo, 0.01)
+ *   dn_finish_remod_kernel    (rgb * d, 1)
  *
  * Memory-bound passes over RGBA32F surfaces: a pixel per lane in row-major order, 16-B accesses, so a wave instruction covers 1 KiB of
  * consecutive bytes; the prefilter's nine taps read the .w word of neighbouring rows and columns, which the caches hold.  Arithmetic is spelled
  * out per operation (IEEE fp32, no contraction) and mirrored by tests/still_denoise_ref.py, bit for bit. */
 #include "dn_launch.h"
+#include "tb_math.h"
 
 #define DN_THREADS 256u
 
@@ -63,6 +68,56 @@ __global__ __launch_bounds__(DN_THREADS) void dn_finish_kernel(const TbFloat4* _
     final[i] = p;
 }
 
+/* ---- the guide pass's chain ---- */
+__global__ __launch_bounds__(DN_THREADS) void dn_resolve_guides_kernel(const TbFloat4* __restrict__ gNormal, const TbFloat4* __restrict__ gPosition,
+    TbFloat4* __restrict__ normals, TbFloat4* __restrict__ positions, uint32_t nPixels)
+{
+    const uint32_t i = blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= nPixels) return;
+    const TbFloat4 n = gNormal[i], p = gPosition[i];
+    const float hits = n.w; /* one frame: a division by 1, the frame's AOVs bit for bit */
+    TbFloat4 on{0.0f, 0.0f, 0.0f, 1.0f}, op{0.0f, 0.0f, 0.0f, 0.0f};
+    if (hits > 0.0f) { on.x = n.x / hits; on.y = n.y / hits; on.z = n.z / hits; op.x = p.x / hits; op.y = p.y / hits; op.z = p.z / hits; op.w = p.w / hits; }
+    /* The mean of several frames' normals is shorter than 1 where they disagree (a silhouette inside the pixel), and DenoiserCS raises the dot
+     * product of two normals to NormalWeightingExponential: the centre tap's own weight |n|^(2 x 128) underflows to 0 from |n| = 0.5 down and
+     * the pass divides 0 by 0.  More than one frame: the mean's direction, or no normal at all (the pixel keeps its mean) where the sum cancels. */
+    if (hits > 1.0f) {
+        const float l = tb_sqrt((on.x * on.x + on.y * on.y) + on.z * on.z);
+        if (l > 0.0f) { on.x = on.x / l; on.y = on.y / l; on.z = on.z / l; } else { on.x = 0.0f; on.y = 0.0f; on.z = 0.0f; }
+    }
+    normals[i] = on; positions[i] = op;
+}
+
+/* d: the mean effective albedo per channel, held away from zero */
+__device__ __forceinline__ float dn_demod(float sum, float frames) { const float a = sum / frames; return a > 0.01f ? a : 0.01f; }
+
+__global__ __launch_bounds__(DN_THREADS) void dn_prepare_demod_kernel(const TbFloat4* __restrict__ output, const TbFloat4* __restrict__ jittered,
+    const TbFloat4* __restrict__ gAlbedo, TbFloat4* __restrict__ prepared, uint32_t nPixels)
+{
+    const uint32_t i = blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= nPixels) return;
+    const TbFloat4 o = output[i], q = jittered[i], a = gAlbedo[i];
+    const float dx = dn_demod(a.x, a.w), dy = dn_demod(a.y, a.w), dz = dn_demod(a.z, a.w);
+    const float n = o.w, m = q.w, r = n - m;
+    TbFloat4 p{0.0f, 0.0f, 0.0f, 0.0f};
+    if (n > 0.0f) { p.x = (o.x / n) / dx; p.y = (o.y / n) / dy; p.z = (o.z / n) / dz; }
+    if (m > 0.0f && r > 0.0f) {
+        const float d = dn_luma((q.x / m) / dx, (q.y / m) / dy, (q.z / m) / dz) - dn_luma(((o.x - q.x) / r) / dx, ((o.y - q.y) / r) / dy, ((o.z - q.z) / r) / dz);
+        const float v = (d * d) * ((m * r) / (n * n));
+        p.w = __builtin_fabsf(v) <= 3.402823466e+38f ? v : 0.0f;
+    }
+    prepared[i] = p;
+}
+
+__global__ __launch_bounds__(DN_THREADS) void dn_finish_remod_kernel(const TbFloat4* __restrict__ in, const TbFloat4* __restrict__ gAlbedo,
+    TbFloat4* __restrict__ final, uint32_t nPixels)
+{
+    const uint32_t i = blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= nPixels) return;
+    const TbFloat4 x = in[i], a = gAlbedo[i];
+    final[i] = TbFloat4{x.x * dn_demod(a.x, a.w), x.y * dn_demod(a.y, a.w), x.z * dn_demod(a.z, a.w), 1.0f};
+}
+
 /* a frame has at most 16384 pixels a side (tb_render): 2^28 pixels, 2^20 workgroups */
 bool dn_frame(uint32_t W, uint32_t H, uint32_t* nPixels, uint32_t* groups)
 {
@@ -95,5 +150,31 @@ extern "C" hipError_t dn_launch_finish(hipStream_t stream, const TbFloat4* in, T
     uint32_t nPixels, groups;
     if (!dn_frame(W, H, &nPixels, &groups) || !dn_surface(in) || !dn_surface(final)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dn_finish_kernel, dim3(groups), dim3(DN_THREADS), 0, stream, in, final, nPixels);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dn_launch_resolve_guides(hipStream_t stream, const TbFloat4* gNormal, const TbFloat4* gPosition, TbFloat4* normals, TbFloat4* positions,
+    uint32_t W, uint32_t H)
+{
+    uint32_t nPixels, groups;
+    if (!dn_frame(W, H, &nPixels, &groups) || !dn_surface(gNormal) || !dn_surface(gPosition) || !dn_surface(normals) || !dn_surface(positions)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dn_resolve_guides_kernel, dim3(groups), dim3(DN_THREADS), 0, stream, gNormal, gPosition, normals, positions, nPixels);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dn_launch_prepare_demod(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const TbFloat4* gAlbedo, TbFloat4* prepared,
+    uint32_t W, uint32_t H)
+{
+    uint32_t nPixels, groups;
+    if (!dn_frame(W, H, &nPixels, &groups) || !dn_surface(output) || !dn_surface(jittered) || !dn_surface(gAlbedo) || !dn_surface(prepared)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dn_prepare_demod_kernel, dim3(groups), dim3(DN_THREADS), 0, stream, output, jittered, gAlbedo, prepared, nPixels);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dn_launch_finish_remod(hipStream_t stream, const TbFloat4* in, const TbFloat4* gAlbedo, TbFloat4* final, uint32_t W, uint32_t H)
+{
+    uint32_t nPixels, groups;
+    if (!dn_frame(W, H, &nPixels, &groups) || !dn_surface(in) || !dn_surface(gAlbedo) || !dn_surface(final)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dn_finish_remod_kernel, dim3(groups), dim3(DN_THREADS), 0, stream, in, gAlbedo, final, nPixels);
     return hipGetLastError();
 }
