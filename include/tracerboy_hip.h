@@ -442,6 +442,17 @@ int tb_trace_closest(tb_context* ctx, uint32_t n, const float* origins, const fl
                      float* out_normal, float* out_uv, uint32_t* out_boxes, uint32_t* out_tris);
 /* Device-side evaluation of tb_math.h (fn codes as oracle tbo_math) for host/device bit-equality tests. */
 int tb_device_math(tb_context* ctx, int fn, uint32_t n, const float* a, const float* b, float* out);
+/* The three kernels of the real-time chain (rt_kernels.hip) on host surfaces of ResolutionX * ResolutionY * 4 floats (width * height * 4 for
+ * the composite), arguments as the oracle's tbo_temporal / tbo_denoise / tbo_composite: uploaded into temporary buffers, launched on the
+ * context's stream, waited for and copied back.  Need no scene; read and write nothing the context holds (no history, no ping-pong state, no
+ * accumulation, no denoised surface).  moment_history and out_moment may be null unless OutputMomentInformation is set.
+ * TB_E_INVALID (the message names the cause): a required array is null; a dimension is 0; more than 2^24 pixels; OffsetMultiplier 0;
+ * OutputMomentInformation set and one of the moment arrays null. */
+int tb_run_temporal(tb_context* ctx, const TbTemporalConstants* constants, const float* history, const float* current, const float* world_pos,
+                    const float* prev_world_pos, const float* moment_history, const float* normals, float* out, float* out_moment);
+int tb_run_denoise_pass(tb_context* ctx, const TbDenoiserConstants* constants, const float* input, const float* normals, const float* positions,
+                        const float* undenoised, float* out);
+int tb_run_composite(tb_context* ctx, uint32_t width, uint32_t height, const float* albedo, const float* lighting, const float* emissive, float* out);
 
 /* ---- host-only half of LoadScene (no device needed) ------------------------------------------------
  * The same parse / convert / BVH-build code tb_load_scene runs, exposed separately so that the

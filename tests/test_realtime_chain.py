@@ -110,56 +110,178 @@ def test_denoise_flat_region_and_edges(built):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
+MATERIAL_MAPS = os.path.join(GOLDEN, "scenes", "material-maps", "scene.pbrt")   # some camera rays leave the scene
+
+
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-@pytest.mark.gpu
-def test_gpu_realtime_chain_bit_exact(gpu_tb, settings):
+def same(got, want):
+    return np.array_equal(bits(got), bits(want))
+
+
+def replay(scene, size, settings, dn, action=None, frames=4, check_frame=None):
+    """tb_render_realtime on a fresh context, replayed frame by frame: every stage's device output against the oracle fed with the device's own
+    inputs (path-traced frame and AOVs) and the histories of the replay, bit for bit.  action(tb, frame), before the frame's render, may move
+    the camera or invalidate the history, and may return another (width, height) from that frame on: the context then starts over with zeroed
+    buffers, its first ping-pong half and the previous camera = the current one, and so does the replay.  check_frame(tb, frame, surfaces)
+    sees the frame's AOVs and replayed stages.  Returns the last frame's (composited, final)."""
     from tracerboy_amd import api
-    gpu_tb.LoadScene(CORNELL)
-    W, H = 104, 72
-    s = copy.copy(settings); s.MaxBounces = 3
-    dn = api.GetDefaultDenoiserSettings(); dn.WaveletIterations = 3
-    cam0 = gpu_tb.GetCamera()
-    zeros = np.zeros((H, W, 4), np.float32)
-    hist_ind, hist_mom, hist_fin = [zeros, zeros], [zeros, zeros], [zeros, zeros]
-    prev_cam = cam0
-    active = 0
-    try:
-        for frame in range(4):
-            cam = gpu_tb.GetCamera()
-            if frame == 2:      # move the camera: history must be reprojected (and the sample counter restarts like TracerBoy::Update)
-                cam.Position[0] += 0.15; cam.LookAt[0] += 0.15
-                gpu_tb.SetCamera(cam)
-            gpu_tb.RenderRealTime(W, H, s, dn, 0.0)
+    with api.TracerBoy(0) as tb:
+        tb.LoadScene(scene)
+        W = H = None
+        for frame in range(frames):
+            resized = action(tb, frame) if action is not None else None
+            if frame == 0 or (resized is not None and tuple(resized) != (W, H)):
+                W, H = resized if resized is not None else size
+                zeros = np.zeros((H, W, 4), np.float32)
+                hist_ind, hist_mom, hist_fin = [zeros, zeros], [zeros, zeros], [zeros, zeros]
+                wp = [zeros, zeros]
+                active = 0
+                prev_cam = tb.GetCamera()
+            cam = tb.GetCamera()
+            tb.RenderRealTime(W, H, settings, dn, 0.0)
             cur, prv = active, active ^ 1
-            frame_out = gpu_tb.ReadAccumulation()
-            wp = [gpu_tb.ReadAOV(3), gpu_tb.ReadAOV(4)]
-            normals, albedo, emissive = gpu_tb.ReadAOV(2), gpu_tb.ReadAOV(5), gpu_tb.ReadAOV(7)
+            frame_out = tb.ReadAccumulation()
+            wp_before, wp = wp, [tb.ReadAOV(3), tb.ReadAOV(4)]
+            # the frame's positions went to the half the chain reads as the current one, and the previous frame's are still in the other
+            assert np.array_equal(bits(wp[prv]), bits(wp_before[prv])), frame
+            assert not np.array_equal(bits(wp[cur]), bits(wp_before[cur])), frame
+            normals, albedo, emissive = tb.ReadAOV(2), tb.ReadAOV(5), tb.ReadAOV(7)
             k = camera_constants(W, H, cam, prev_cam, moments=True)
             taa1, mom = ol.temporal(k, hist_ind[prv], frame_out, wp[cur], wp[prv], hist_mom[prv], normals)
-            assert np.array_equal(bits(gpu_tb.ReadRealTimeStage(0)), bits(taa1)), frame
-            assert np.array_equal(bits(gpu_tb.ReadRealTimeStage(1)), bits(mom)), frame
-            x = taa1
-            for i in range(dn.WaveletIterations):
-                kd = abi.TbDenoiserConstants(W, H, 1 << i, dn.NormalWeightingExponential, dn.IntersectPositionWeightingMultiplier, dn.LuminanceWeightingMultiplier,
-                                             gpu_tb.GetNumberOfSamplesSinceLastInvalidate())
-                x = ol.denoise(kd, x, normals, wp[cur], taa1)
-            assert np.array_equal(bits(gpu_tb.ReadRealTimeStage(2)), bits(x)), frame
-            comp = ol.composite(albedo, x, emissive)
-            assert np.array_equal(bits(gpu_tb.ReadRealTimeStage(3)), bits(comp)), frame
+            assert same(tb.ReadRealTimeStage(0), taa1), frame
+            assert same(tb.ReadRealTimeStage(1), mom), frame
+            x = None
+            if dn.Enabled and settings.OutputType == 0:
+                for i in range(dn.WaveletIterations):
+                    kd = abi.TbDenoiserConstants(W, H, 1 << i, dn.NormalWeightingExponential, dn.IntersectPositionWeightingMultiplier, dn.LuminanceWeightingMultiplier,
+                                                 tb.GetNumberOfSamplesSinceLastInvalidate())
+                    x = ol.denoise(kd, taa1 if x is None else x, normals, wp[cur], taa1)
+            if x is not None:
+                assert same(tb.ReadRealTimeStage(2), x), frame
+            else:      # no filter pass ran: there is no stage 2, the composite reads the first temporal output
+                with pytest.raises(api.TracerBoyError) as refused:
+                    tb.ReadRealTimeStage(2)
+                assert refused.value.code == -1   # TB_E_INVALID
+            comp = ol.composite(albedo, taa1 if x is None else x, emissive)
+            assert same(tb.ReadRealTimeStage(3), comp), frame
             fin, _ = ol.temporal(camera_constants(W, H, cam, prev_cam, moments=False), hist_fin[prv], comp, wp[cur], wp[prv], None, normals)
-            assert np.array_equal(bits(gpu_tb.ReadRealTimeStage(4)), bits(fin)), frame
+            assert same(tb.ReadRealTimeStage(4), fin), frame
             # the post-process stage now reads the chain's output
             ps = api.GetDefaultPostProcessSettings()
-            f, b = gpu_tb.PostProcess(ps)
+            f, b = tb.PostProcess(ps)
             ref = ol.post_process(fin, ps)
-            assert np.array_equal(bits(f), bits(ref["rgba"])) and np.array_equal(b, ref["rgba8"])
+            assert same(f, ref["rgba"]) and np.array_equal(b, ref["rgba8"]), frame
+            if check_frame is not None:
+                check_frame(tb, frame, dict(normals=normals, taa1=taa1, moments=mom, filtered=x, composited=comp, final=fin, size=(W, H)))
             hist_ind[cur], hist_mom[cur], hist_fin[cur] = taa1, mom, fin
             prev_cam = cam
             active ^= 1
-        # after a few frames some history has been accepted: the final output differs from the composited frame
-        assert np.any(fin[..., :3] != comp[..., :3])
-    finally:
-        gpu_tb.SetCamera(cam0)
+        return comp, fin
+
+
+def move_at_frame_2(tb, frame):
+    if frame == 2:      # move the camera: history must be reprojected (and the sample counter restarts like TracerBoy::Update)
+        cam = tb.GetCamera()
+        cam.Position[0] += 0.15; cam.LookAt[0] += 0.15
+        tb.SetCamera(cam)
+
+
+def chain_settings(settings, passes, bounces=3):
+    from tracerboy_amd import api
+    s = copy.copy(settings); s.MaxBounces = bounces
+    dn = api.GetDefaultDenoiserSettings(); dn.WaveletIterations = passes
+    return s, dn
+
+
+@pytest.mark.gpu
+def test_gpu_realtime_chain_bit_exact(built, settings):
+    s, dn = chain_settings(settings, 3)
+    comp, fin = replay(CORNELL, (104, 72), s, dn, move_at_frame_2)
+    # after a few frames some history has been accepted: the final output differs from the composited frame
+    assert np.any(fin[..., :3] != comp[..., :3])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(100, 70), (13, 9)])
+def test_gpu_realtime_chain_ragged_frame_with_misses(built, settings, size):
+    """neither dimension a multiple of the 8 x 8 tile; 4 passes: the last one's taps at +-8 and +-16 leave the frame (all of them at 13 x 9);
+    pixels whose camera ray left the scene have no normal: the temporal passes and the filter pass them through"""
+    s, dn = chain_settings(settings, 4, bounces=2)
+    seen = []
+
+    def check(tb, frame, surf):
+        hit = (surf["normals"][..., :3] != 0).any(-1)
+        assert hit.any() and not hit.all()
+        assert np.array_equal(bits(surf["filtered"][~hit]), bits(surf["taa1"][~hit]))   # a miss is not filtered
+        seen.append(frame)
+    comp, fin = replay(MATERIAL_MAPS, size, s, dn, move_at_frame_2, check_frame=check)
+    assert seen == [0, 1, 2, 3] and np.any(fin[..., :3] != comp[..., :3])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("at_frame", [1, 2])
+def test_gpu_realtime_chain_look_at_change(built, settings, at_frame):
+    """the camera turns by about 25 degrees between two frames: much of the old frame reprojects outside, the rest far from where it was.
+    After an odd and after an even number of frames: the sample counter restarts at the turn, the ping-pong does not"""
+    s, dn = chain_settings(settings, 2)
+
+    def turn(tb, frame):
+        if frame == at_frame:
+            cam = tb.GetCamera()
+            pos, look, right = (np.array(v[:], np.float64) for v in (cam.Position, cam.LookAt, cam.Right))
+            d = look - pos
+            a = np.radians(25); up = np.array(cam.Up[:], np.float64); up /= np.linalg.norm(up)
+            rot = lambda v: v * np.cos(a) + np.cross(up, v) * np.sin(a) + up * (up @ v) * (1 - np.cos(a))   # about the camera's up axis
+            cam.LookAt[:] = list(pos + rot(d)); cam.Right[:] = list(rot(right))
+            tb.SetCamera(cam)
+    replay(CORNELL, (56, 40), s, dn, turn)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("at_frame", [1, 3])
+def test_gpu_realtime_chain_invalidated_history(built, settings, at_frame):
+    """tb_invalidate_history between two frames restarts the sample counter (the frame's random numbers, GlobalFrameCount); the chain's own
+    history, its ping-pong and the previous camera go on.  After an odd number of frames, where counter and ping-pong part ways (after an even
+    number, with the camera where it was, the frame repeats an earlier one's positions to the bit into the same half: nothing to tell apart)"""
+    s, dn = chain_settings(settings, 2)
+    counts = []
+
+    def invalidate(tb, frame):
+        if frame == at_frame:
+            tb.InvalidateHistory()
+
+    def check(tb, frame, surf):
+        counts.append(tb.GetNumberOfSamplesSinceLastInvalidate())
+    comp, fin = replay(CORNELL, (56, 40), s, dn, invalidate, check_frame=check)
+    assert counts == [1, 2, 3, 4][:at_frame] + [1, 2, 3][:4 - at_frame]
+    assert np.any(fin[..., :3] != comp[..., :3])   # history survived the call
+
+
+@pytest.mark.gpu
+def test_gpu_realtime_chain_resolution_change(built, settings):
+    """another size from the fourth frame on (an odd number of frames in): buffers zeroed, first ping-pong half, previous camera = current"""
+    s, dn = chain_settings(settings, 2)
+    sizes = []
+
+    def resize(tb, frame):
+        return (56, 40) if frame < 3 else (37, 23)
+
+    def check(tb, frame, surf):
+        sizes.append(surf["size"])
+    replay(CORNELL, None, s, dn, resize, frames=6, check_frame=check)
+    assert sizes == [(56, 40)] * 3 + [(37, 23)] * 3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("what", ["no iterations", "disabled", "albedo output"])
+def test_gpu_realtime_chain_without_filter_pass(built, settings, what):
+    """WaveletIterations = 0, Enabled = 0 or an OutputType other than LIT: no filter pass, stage 2 is refused, the composite reads stage 0"""
+    s, dn = chain_settings(settings, 0 if what == "no iterations" else 2)
+    if what == "disabled":
+        dn.Enabled = 0
+    if what == "albedo output":
+        s.OutputType = 1
+    replay(CORNELL, (56, 40), s, dn, move_at_frame_2, frames=3)

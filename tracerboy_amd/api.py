@@ -99,6 +99,9 @@ def lib():
         "tb_last_render_ms": (C.c_float, [vp]),
         "tb_trace_closest": (C.c_int, [vp, C.c_uint32] + [vp] * 11),
         "tb_device_math": (C.c_int, [vp, C.c_int, C.c_uint32, vp, vp, vp]),
+        "tb_run_temporal": (C.c_int, [vp, P(abi.TbTemporalConstants)] + [vp] * 8),
+        "tb_run_denoise_pass": (C.c_int, [vp, P(abi.TbDenoiserConstants)] + [vp] * 5),
+        "tb_run_composite": (C.c_int, [vp, C.c_uint32, C.c_uint32] + [vp] * 4),
         "tb_variant_stash_entries": (C.c_int, [C.c_char_p]),
         "tb_frame_groups": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "tb_state_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), C.c_float, C.c_uint32]),
@@ -611,6 +614,31 @@ class TracerBoy:
         b2 = np.ascontiguousarray(b, np.float32) if b is not None else None
         out = np.empty_like(a)
         self._check(self._L.tb_device_math(self._ctx, fn, a.size, _np_ptr(a), _np_ptr(b2) if b2 is not None else None, _np_ptr(out)))
+        return out
+
+    # the real-time kernels on host surfaces (tb_run_*): (H, W, 4) float32 arrays, no scene, nothing of the context read or written
+    def RunTemporal(self, constants, history, current, world_pos, prev_world_pos, moment_history, normals):
+        """rt_temporal_kernel; returns (out, moments), moments None unless constants.OutputMomentInformation."""
+        f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (history, current, world_pos, prev_world_pos, moment_history, normals)]
+        shape = (constants.ResolutionY, constants.ResolutionX, 4)
+        out = np.empty(shape, np.float32)
+        mom = np.empty(shape, np.float32) if constants.OutputMomentInformation and moment_history is not None else None
+        self._check(self._L.tb_run_temporal(self._ctx, C.byref(constants), *[None if a is None else _np_ptr(a) for a in f], _np_ptr(out),
+                                            None if mom is None else _np_ptr(mom)))
+        return out, mom
+
+    def RunDenoisePass(self, constants, inp, normals, positions, undenoised):
+        """rt_denoise_kernel: one a-trous pass."""
+        f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (inp, normals, positions, undenoised)]
+        out = np.empty((constants.ResolutionY, constants.ResolutionX, 4), np.float32)
+        self._check(self._L.tb_run_denoise_pass(self._ctx, C.byref(constants), *[None if a is None else _np_ptr(a) for a in f], _np_ptr(out)))
+        return out
+
+    def RunComposite(self, width, height, albedo, lighting, emissive):
+        """rt_composite_kernel."""
+        f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (albedo, lighting, emissive)]
+        out = np.empty((height, width, 4), np.float32)
+        self._check(self._L.tb_run_composite(self._ctx, width, height, *[None if a is None else _np_ptr(a) for a in f], _np_ptr(out)))
         return out
 
 

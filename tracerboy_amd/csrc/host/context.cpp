@@ -350,7 +350,9 @@ int tb_render_realtime(tb_context* c, uint32_t W, uint32_t H, const tb_output_se
             c->rtWidth = W; c->rtHeight = H; c->rtActive = 0; c->prevCamera = c->camera;
         }
         touchAccumulation(c);
-        int rc = renderImpl(c, W, H, 1, &s, timeSeed, false);
+        int rc;
+        { struct InChain { bool& f; explicit InChain(bool& b) : f(b) { f = true; } ~InChain() { f = false; } } inChain(c->rtChainFrame);
+            rc = renderImpl(c, W, H, 1, &s, timeSeed, false); }
         c->options.value[OPT_aov] = savedAov; c->options.isSet[OPT_aov] = savedSet;
         if (rc != TB_OK) return rc;
         const uint32_t cur = c->rtActive, prev = cur ^ 1u;
@@ -789,6 +791,72 @@ int tb_device_math(tb_context* c, int fn, uint32_t n, const float* a, const floa
         HIP_TRY(pt_launch_device_math(c->stream, fn, n, (const float*)dA.p, (const float*)dB.p, (float*)dO.p));
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(out, dO.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return TB_OK;
+    });
+}
+
+/* The real-time kernels on host surfaces: temporary buffers only, nothing of the context but its stream. */
+static const char* surfaceRefusal(uint32_t W, uint32_t H)
+{
+    if (W == 0 || H == 0) return "a dimension is 0";
+    if ((uint64_t)W * H > (1ull << 24)) return "more than 2^24 pixels";
+    return nullptr;
+}
+static void toDevice(DevBuf& d, const float* h, size_t bytes) { ensure(d, bytes); HIP_TRY(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice)); }
+
+int tb_run_temporal(tb_context* c, const TbTemporalConstants* k, const float* history, const float* current, const float* worldPos,
+                    const float* prevWorldPos, const float* momentHistory, const float* normals, float* out, float* outMoment)
+{
+    return guarded(c, [&]() {
+        if (!k || !history || !current || !worldPos || !prevWorldPos || !normals || !out) return fail(c, TB_E_INVALID, "tb_run_temporal: null array");
+        if (const char* why = surfaceRefusal(k->ResolutionX, k->ResolutionY)) return fail(c, TB_E_INVALID, std::string("tb_run_temporal: ") + why);
+        if (k->OutputMomentInformation && (!momentHistory || !outMoment)) return fail(c, TB_E_INVALID,
+            "tb_run_temporal: OutputMomentInformation is set and a moment array is null");
+        const size_t bytes = (size_t)k->ResolutionX * k->ResolutionY * sizeof(TbFloat4);
+        DevBuf dHist, dCur, dWp, dPrevWp, dMomHist, dNormals, dOut, dMom;
+        toDevice(dHist, history, bytes); toDevice(dCur, current, bytes); toDevice(dWp, worldPos, bytes); toDevice(dPrevWp, prevWorldPos, bytes);
+        toDevice(dNormals, normals, bytes); ensure(dOut, bytes);
+        if (k->OutputMomentInformation) { toDevice(dMomHist, momentHistory, bytes); ensure(dMom, bytes); }
+        HIP_TRY(rt_launch_temporal(c->stream, k, (const TbFloat4*)dHist.p, (const TbFloat4*)dCur.p, (const TbFloat4*)dWp.p, (const TbFloat4*)dPrevWp.p,
+                                   (const TbFloat4*)dMomHist.p, (const TbFloat4*)dNormals.p, (TbFloat4*)dOut.p, (TbFloat4*)dMom.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
+        if (k->OutputMomentInformation) HIP_TRY(hipMemcpy(outMoment, dMom.p, bytes, hipMemcpyDeviceToHost));
+        return TB_OK;
+    });
+}
+
+int tb_run_denoise_pass(tb_context* c, const TbDenoiserConstants* k, const float* input, const float* normals, const float* positions,
+                        const float* undenoised, float* out)
+{
+    return guarded(c, [&]() {
+        if (!k || !input || !normals || !positions || !undenoised || !out) return fail(c, TB_E_INVALID, "tb_run_denoise_pass: null array");
+        if (const char* why = surfaceRefusal(k->ResolutionX, k->ResolutionY)) return fail(c, TB_E_INVALID, std::string("tb_run_denoise_pass: ") + why);
+        if (k->OffsetMultiplier == 0) return fail(c, TB_E_INVALID, "tb_run_denoise_pass: OffsetMultiplier is 0");
+        const size_t bytes = (size_t)k->ResolutionX * k->ResolutionY * sizeof(TbFloat4);
+        DevBuf dIn, dNormals, dPos, dUnd, dOut;
+        toDevice(dIn, input, bytes); toDevice(dNormals, normals, bytes); toDevice(dPos, positions, bytes); toDevice(dUnd, undenoised, bytes);
+        ensure(dOut, bytes);
+        HIP_TRY(rt_launch_denoise(c->stream, k, (const TbFloat4*)dIn.p, (const TbFloat4*)dNormals.p, (const TbFloat4*)dPos.p, (const TbFloat4*)dUnd.p,
+                                  (TbFloat4*)dOut.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
+        return TB_OK;
+    });
+}
+
+int tb_run_composite(tb_context* c, uint32_t W, uint32_t H, const float* albedo, const float* lighting, const float* emissive, float* out)
+{
+    return guarded(c, [&]() {
+        if (!albedo || !lighting || !emissive || !out) return fail(c, TB_E_INVALID, "tb_run_composite: null array");
+        if (const char* why = surfaceRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_composite: ") + why);
+        const size_t bytes = (size_t)W * H * sizeof(TbFloat4);
+        DevBuf dAlbedo, dLighting, dEmissive, dOut;
+        toDevice(dAlbedo, albedo, bytes); toDevice(dLighting, lighting, bytes); toDevice(dEmissive, emissive, bytes); ensure(dOut, bytes);
+        HIP_TRY(rt_launch_composite(c->stream, W, H, (const TbFloat4*)dAlbedo.p, (const TbFloat4*)dLighting.p, (const TbFloat4*)dEmissive.p,
+            (TbFloat4*)dOut.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
         return TB_OK;
     });
 }

@@ -149,6 +149,7 @@ struct tb_context {
     DevBuf rtIndirect[2], rtMoment[2], rtFinal[2], rtDenoise[2], rtComposited;
     uint32_t rtActive = 0, rtWidth = 0, rtHeight = 0; int rtLast[5] = {-1, -1, -1, -1, -1}; /* which buffer holds each stage's last output */
     bool lastRenderRealtime = false; tb_camera prevCamera{};
+    bool rtChainFrame = false; /* renderImpl is rendering tb_render_realtime's frame: its positions go to world-position half rtActive (fillTargets) */
     /* wavefront pipeline: two ping-pong extend queues (4 columns), one shadow queue (11 columns), hits, samples, counters */
     DevBuf wfCols[2][6], wfShadowCols[12], wfHitA, wfHitG, wfSamples, wfCounts, workCounter;
     uint64_t wfCapacity = 0, wfSampleCapacity = 0;
