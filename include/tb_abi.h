@@ -131,6 +131,13 @@ typedef struct TbDenoiserConstants {
 } TbDenoiserConstants;
 TB_STATIC_ASSERT(sizeof(TbDenoiserConstants) == 28, "DenoiserConstants is 7 dwords");
 
+/* FSRConstants of both FSR 1 passes, FidelityFXSuperResolutionSharedShaderStructs.h: easu = const0..const3 of FsrEasuCon (ffx_fsr1.h:156-202),
+ * rcas = const0 of FsrRcasCon (:662-672).  Surface types of the two kernels (fsr_kernels.hip). */
+typedef struct TbFsrConstants { uint32_t easu[16]; uint32_t rcas[4]; } TbFsrConstants;
+TB_STATIC_ASSERT(sizeof(TbFsrConstants) == 80, "FSR constants are 20 dwords");
+#define TB_FSR_SURFACE_UNORM8 0u /* R8G8B8A8_UNORM in, between the passes and out: the reference's chain */
+#define TB_FSR_SURFACE_F32 1u    /* RGBA32F throughout, alpha 1, no clamp, no quantisation */
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

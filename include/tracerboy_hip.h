@@ -454,6 +454,37 @@ int tb_run_denoise_pass(tb_context* ctx, const TbDenoiserConstants* constants, c
                         const float* undenoised, float* out);
 int tb_run_composite(tb_context* ctx, uint32_t width, uint32_t height, const float* albedo, const float* lighting, const float* emissive, float* out);
 
+/* ---- FSR 1 upscaling -----------------------------------------------------------
+ * <-> the reference's display path below full size: m_downscaleFactor < 1 or PostProcessSettings::m_bEnableFSR shrink the render surfaces,
+ * GetSelectedUpscaler picks TAAUpscaler::FSR (TracerBoy.cpp:2520-2567) and the tail of Render runs FidelityFXSuperResolutionPass::Run
+ * (TracerBoy.cpp:3324-3336; FidelityFXSuperResolution.cpp:53-111): EASU on the post-processed image, then RCAS at 0.2 stops.
+ * Surface types (tb_abi.h): TB_FSR_SURFACE_UNORM8 -- input, intermediate and output are R8G8B8A8_UNORM as in the reference, so the picture
+ * is quantised between the passes; TB_FSR_SURFACE_F32 -- RGBA32F throughout, alpha 1, no clamp (values outside [0, 1] and non-finite values go
+ * through the same arithmetic).  All arithmetic is the fp32 contract of tb_math.h; tests/fsr_ref.py restates it in numpy.
+ *
+ * tb_fsr_constants: host only, no context.  easu = FsrEasuCon(in, in, out) (ffx_fsr1.h:156-202; all sixteen words, although the kernel reads
+ * the first four only), rcas = FsrRcasCon(sharpness_stops) (:662-672): rcas[0] = bits of exp2(-stops) by tb_math.h's exp2, rcas[1] = that value
+ * twice as truncated binary16.  TB_E_INVALID: a null pointer, a zero size, sharpness_stops not finite.
+ * tb_run_fsr_easu / tb_run_fsr_rcas: the kernel seam, like tb_run_denoise_pass: host surfaces (4 B or 16 B per texel by surface type, row 0 =
+ * top), temporary device buffers, no scene, nothing the context holds is read or written.  EASU: in is in_w x in_h, out is out_w x out_h.
+ * RCAS: both w x h.
+ * tb_upscale: the stage.  Runs exactly what tb_post_process(post, output_type) runs at the rendered size (option "post_denoised" included;
+ * after tb_render as well as after tb_render_realtime), then EASU -> RCAS to out_w x out_h: the UNORM8 chain on the 8-bit back-buffer value
+ * into rgba8_or_null (out_w * out_h * 4 bytes) when that is given, the F32 chain on the float image into rgba_f32_or_null (out_w * out_h * 4
+ * floats) when that is given, both when both are.  sharpness_stops < 0: the reference's 0.2.  Synchronous.  Like tb_denoise it writes neither
+ * the accumulation surfaces nor the AOVs, frame counter, history or denoised surfaces: tb_accum_digest is the same before and after.  Its
+ * scratch surfaces belong to the context.  tb_get_option "last_upscale_us" / "last_easu_us" / "last_rcas_us": GPU microseconds of the last call's
+ * FSR passes together / its EASU passes / its RCAS passes (HIP events; both chains when both ran).
+ * TB_E_INVALID (the message names the cause): a null required pointer or a zero size; out_w < in_w or out_h < in_h (FSR 1 only upscales; 1:1
+ * is allowed, as the reference allows it with m_bEnableFSR); more than 2^24 output pixels; an unknown surface type; sharpness_stops not finite;
+ * both output pointers null; whatever tb_post_process itself refuses. */
+int tb_fsr_constants(uint32_t in_w, uint32_t in_h, uint32_t out_w, uint32_t out_h, float sharpness_stops, TbFsrConstants* out);
+int tb_run_fsr_easu(tb_context* ctx, const TbFsrConstants* constants, uint32_t surface, uint32_t in_w, uint32_t in_h, uint32_t out_w, uint32_t out_h,
+                    const void* in, void* out);
+int tb_run_fsr_rcas(tb_context* ctx, const TbFsrConstants* constants, uint32_t surface, uint32_t w, uint32_t h, const void* in, void* out);
+int tb_upscale(tb_context* ctx, const tb_post_settings* post, uint32_t output_type, uint32_t out_w, uint32_t out_h, float sharpness_stops,
+               float* rgba_f32_or_null, uint8_t* rgba8_or_null);
+
 /* ---- host-only half of LoadScene (no device needed) ------------------------------------------------
  * The same parse / convert / BVH-build code tb_load_scene runs, exposed separately so that the
  * scene conversion and the BVH can be inspected and checked on machines without a GPU.  Nothing here

@@ -151,6 +151,15 @@ class TbDenoiserConstants(C.Structure):
                 ("IntersectionPositionWeightingMultiplier", C.c_float), ("LumaWeightingMultiplier", C.c_float), ("GlobalFrameCount", C.c_uint32)]
 
 
+class TbFsrConstants(C.Structure):
+    """FsrEasuCon's const0..const3 and FsrRcasCon's const0 (tb_abi.h)."""
+    _fields_ = [("easu", C.c_uint32 * 16), ("rcas", C.c_uint32 * 4)]
+
+
+TB_FSR_SURFACE_UNORM8 = 0
+TB_FSR_SURFACE_F32 = 1
+
+
 class tb_readback_stats(C.Structure):
     _fields_ = [("ActiveWaves", C.c_uint32), ("ActivePixels", C.c_uint32), ("SelectedPixelDistance", C.c_float), ("SelectedMaterialID", C.c_int32),
                 ("rays", TbRayStats)]
@@ -197,6 +206,7 @@ assert C.sizeof(tb_state_info) == 208
 assert C.sizeof(TbPostConstants) == 36
 assert C.sizeof(TbTemporalConstants) == 144
 assert C.sizeof(TbDenoiserConstants) == 28
+assert C.sizeof(TbFsrConstants) == 80
 assert C.sizeof(TbPerFrameConstants) == 148
 assert C.sizeof(TbConfigConstants) == 76
 assert C.sizeof(TbLight) == 104

@@ -102,6 +102,10 @@ def lib():
         "tb_run_temporal": (C.c_int, [vp, P(abi.TbTemporalConstants)] + [vp] * 8),
         "tb_run_denoise_pass": (C.c_int, [vp, P(abi.TbDenoiserConstants)] + [vp] * 5),
         "tb_run_composite": (C.c_int, [vp, C.c_uint32, C.c_uint32] + [vp] * 4),
+        "tb_fsr_constants": (C.c_int, [C.c_uint32] * 4 + [C.c_float, P(abi.TbFsrConstants)]),
+        "tb_run_fsr_easu": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 5 + [vp, vp]),
+        "tb_run_fsr_rcas": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 3 + [vp, vp]),
+        "tb_upscale": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp]),
         "tb_variant_stash_entries": (C.c_int, [C.c_char_p]),
         "tb_frame_groups": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "tb_state_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), C.c_float, C.c_uint32]),
@@ -153,6 +157,15 @@ def GetDefaultPostProcessSettings():
     s = abi.tb_post_settings()
     lib().tb_default_post_settings(C.byref(s))
     return s
+
+
+def FsrConstants(in_width, in_height, out_width, out_height, sharpness=0.2):
+    """FsrEasuCon(in, in, out) + FsrRcasCon(sharpness in stops) as the library computes them (tb_fsr_constants; host only, no device)."""
+    k = abi.TbFsrConstants()
+    rc = lib().tb_fsr_constants(in_width, in_height, out_width, out_height, sharpness, C.byref(k))
+    if rc != 0:
+        raise TracerBoyError(rc, "tb_fsr_constants: a size is 0 or the sharpness is not finite")
+    return k
 
 
 def VariantWavesHi(name):
@@ -533,6 +546,37 @@ class TracerBoy:
         b = np.empty((self.height, self.width, 4), np.uint8) if rgba8 else None
         self._check(self._L.tb_post_process(self._ctx, C.byref(ps), outputType, _np_ptr(f), _np_ptr(b) if rgba8 else None))
         return f, b
+
+    def Upscale(self, out_width, out_height, postSettings=None, outputType=0, sharpness=-1.0, rgba8=True):
+        """PostProcess at the rendered size, then FSR 1 (EASU -> RCAS) to out_width x out_height (tb_upscale); sharpness in
+        stops, negative = the reference's 0.2.  Returns (float32 image of the RGBA32F chain, uint8 image of the R8G8B8A8_UNORM chain or None),
+        both out_height x out_width x 4."""
+        ps = postSettings if postSettings is not None else GetDefaultPostProcessSettings()
+        f = np.empty((out_height, out_width, 4), np.float32)
+        b = np.empty((out_height, out_width, 4), np.uint8) if rgba8 else None
+        self._check(self._L.tb_upscale(self._ctx, C.byref(ps), outputType, out_width, out_height, sharpness, _np_ptr(f), _np_ptr(b) if rgba8 else None))
+        return f, b
+
+    @staticmethod
+    def _fsr_surface(image):
+        """(surface type, contiguous array) of an (H, W, 4) image: uint8 = R8G8B8A8_UNORM, anything else = RGBA32F."""
+        if np.asarray(image).dtype == np.uint8:
+            return abi.TB_FSR_SURFACE_UNORM8, np.ascontiguousarray(image, np.uint8)
+        return abi.TB_FSR_SURFACE_F32, np.ascontiguousarray(image, np.float32)
+
+    def RunFsrEasu(self, constants, image, out_width, out_height):
+        """fsr_easu_kernel on a host image (H, W, 4), uint8 or float32 (the surface type follows the dtype); nothing of the context read or written."""
+        surface, a = self._fsr_surface(image)
+        out = np.empty((out_height, out_width, 4), a.dtype)
+        self._check(self._L.tb_run_fsr_easu(self._ctx, C.byref(constants), surface, a.shape[1], a.shape[0], out_width, out_height, _np_ptr(a), _np_ptr(out)))
+        return out
+
+    def RunFsrRcas(self, constants, image):
+        """fsr_rcas_kernel on a host image (H, W, 4), uint8 or float32."""
+        surface, a = self._fsr_surface(image)
+        out = np.empty_like(a)
+        self._check(self._L.tb_run_fsr_rcas(self._ctx, C.byref(constants), surface, a.shape[1], a.shape[0], _np_ptr(a), _np_ptr(out)))
+        return out
 
     def AveragedLuminance(self):
         v = C.c_float()

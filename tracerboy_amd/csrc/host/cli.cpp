@@ -5,6 +5,7 @@
  *                 [--ranks N] [--adaptive P [--adaptive-after F] [--adaptive-chunk C] [--adaptive-test frame|call]]
  *                 [--save-state f.tbs] [--resume f.tbs] [--add g.tbs]... [--frames A:B] [--checkpoint-every N]
  *                 [--denoise] [--denoise-iterations N] [--denoise-guides K [--denoise-demodulate]]
+ *                 [--upscale WxH | --render-scale F] [--fsr-sharpness S]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -45,7 +46,15 @@
  * frame the first hits of the last min(K, frames held) frames of the state's range are traced again and summed, and the filter is guided by their
  * means (option "denoise_guides" = 1).  Guides are not part of a state either, but they can be traced at any time: --resume s.tbs --denoise-guides 8
  * with no frame left to render works.  --denoise-demodulate (takes no value; needs --denoise-guides): the chain runs on colour divided by the mean
- * albedo of those frames and multiplies it back at the end (option "denoise_guides" = 2).  K is 1 to 256. */
+ * albedo of those frames and multiplies it back at the end (option "denoise_guides" = 2).  K is 1 to 256.
+ *
+ * --upscale WxH (tb_upscale): the finished render is post-processed at its own size and upscaled to W x H with FSR 1 (EASU, then
+ * RCAS) before --out is written: .png through the R8G8B8A8_UNORM chain, the reference's; .pfm / .exr through the RGBA32F chain -- the POST-PROCESSED
+ * picture then, not the linear radiance these formats hold without --upscale.  W x H is at least the rendered size and at most 2^24 pixels.
+ * --render-scale F (0 < F <= 1; the reference's m_downscaleFactor): renders at max(1, (uint32_t)((float)W * F)) x the same of H -- the truncating
+ * `Width *= m_downscaleFactor` of TracerBoy.cpp:2750-2751 -- and upscales to --width x --height.  Not together with --upscale, nor with --resume (the
+ * state decides the rendered size).  --fsr-sharpness S: RCAS sharpness in stops, 0 = sharpest, default 0.2 (the reference's); needs one of the two.
+ * With --denoise the denoised picture is what is upscaled.  Mistakes in these three are reported before any device call (exit status 2). */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -143,13 +152,14 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
     float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
     std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
     bool sppSet = false, timeSet = false, denoise = false, demodulate = false; long long denoiseIterations = -1, denoiseGuides = 0;
+    uint32_t upW = 0, upH = 0; float renderScale = 0.0f, fsrSharpness = -1.0f; bool upscaleSet = false, renderScaleSet = false, sharpnessSet = false;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--denoise") { denoise = true; i--; continue; } /* the flags without a value */
@@ -173,6 +183,15 @@ int main(int argc, char** argv)
             if (denoiseGuides < 1 || denoiseGuides > 256) { fprintf(stderr, "--denoise-guides is 1 to 256\n"); return 2; } }
         else if (k == "--frames") { char* end = nullptr; frameA = strtoll(v, &end, 10); frameB = end && *end == ':' ? strtoll(end + 1, &end, 10) : -1;
             if (frameA < 0 || frameB < frameA || frameB > 0xffffffffll || !end || *end) { fprintf(stderr, "--frames is A:B with 0 <= A <= B\n"); return 2; } }
+        else if (k == "--upscale") { char* end = nullptr; const unsigned long long uw = strtoull(v, &end, 10);
+            const unsigned long long uh = end && end != v && *end == 'x' && end[1] >= '0' && end[1] <= '9' ? strtoull(end + 1, &end, 10) : 0;
+            if (!uw || !uh || !end || *end || uw > (1ull << 24) || uh > (1ull << 24) || uw * uh > (1ull << 24)) {
+                fprintf(stderr, "--upscale is WxH, both at least 1, at most 2^24 pixels\n"); return 2; }
+            upW = (uint32_t)uw; upH = (uint32_t)uh; upscaleSet = true; }
+        else if (k == "--render-scale") { char* end = nullptr; renderScale = strtof(v, &end); renderScaleSet = true;
+            if (end == v || *end || !(renderScale > 0.0f) || !(renderScale <= 1.0f)) { fprintf(stderr, "--render-scale is above 0 and at most 1\n"); return 2; } }
+        else if (k == "--fsr-sharpness") { char* end = nullptr; fsrSharpness = strtof(v, &end); sharpnessSet = true;
+            if (end == v || *end || !(fsrSharpness >= 0.0f) || !(fsrSharpness < 1e30f)) { fprintf(stderr, "--fsr-sharpness is a finite number of stops, 0 or more\n"); return 2; } }
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -192,6 +211,9 @@ int main(int argc, char** argv)
     if (checkpointEvery < 0 || (checkpointEvery > 0 && saveState.empty())) { fprintf(stderr, "--checkpoint-every N needs N >= 1 and --save-state\n"); return 2; }
     if (frameA >= 0 && (sppSet || !resume.empty())) { fprintf(stderr, "--frames A:B stands in place of --spp and starts its own accumulation (no --resume)\n"); return 2; }
     if (!adds.empty() && resume.empty()) { fprintf(stderr, "--add merges into the state --resume loads\n"); return 2; }
+    if (upscaleSet && renderScaleSet) { fprintf(stderr, "--upscale and --render-scale do not go together: --render-scale upscales to --width x --height\n"); return 2; }
+    if (sharpnessSet && !upscaleSet && !renderScaleSet) { fprintf(stderr, "--fsr-sharpness needs --upscale or --render-scale\n"); return 2; }
+    if (renderScaleSet && !resume.empty()) { fprintf(stderr, "--render-scale does not go with --resume: the state decides the rendered size\n"); return 2; }
     if (ranks > 1 && !envRank) return spawnRanks(argc, argv, ranks);
     if (envRank && (!getenv("TB_CLI_WORLD") || atoi(getenv("TB_CLI_WORLD")) < 1 || atoi(envRank) < 0 || atoi(envRank) >= atoi(getenv("TB_CLI_WORLD")) ||
                     (atoi(getenv("TB_CLI_WORLD")) > 1 && !getenv("TB_CLI_ID_FILE")))) {
@@ -212,6 +234,10 @@ int main(int argc, char** argv)
     const uint32_t argWidth = W, argHeight = H;
     if (!W) W = info.filmWidth ? info.filmWidth : 1920;
     if (!H) H = info.filmHeight ? info.filmHeight : 1080;
+    if (renderScaleSet) { /* m_downscaleFactor: the picture keeps its size, the render surfaces shrink (TracerBoy.cpp:2750-2751) */
+        upW = W; upH = H;
+        W = std::max(1u, (uint32_t)((float)W * renderScale)); H = std::max(1u, (uint32_t)((float)H * renderScale));
+    }
     tb_output_settings s; tb_default_output_settings(&s);
     if (depth >= 0) s.MaxBounces = depth;
     if (blue >= 0) s.EnableBlueNoise = (uint32_t)blue;
@@ -247,6 +273,9 @@ int main(int argc, char** argv)
         if ((rc = tb_state_begin(ctx, W, H, &s, t, (uint32_t)frameA))) return fail(ctx, "tb_state_begin", rc);
         done = (uint32_t)frameA; target = (uint32_t)frameB;
     }
+    if (upW && (upW < W || upH < H || (uint64_t)upW * upH > (1ull << 24))) { /* before the render, not after it */
+        fprintf(stderr, "tracerboy-hip: cannot upscale the %ux%u render to %ux%u: FSR 1 only upscales, to at most 2^24 pixels\n", W, H, upW, upH);
+        tb_destroy(ctx); return 2; }
     const uint32_t start = done;
     auto checkpoint = [&]() { return checkpointEvery > 0 ? tb_state_save(ctx, saveState.c_str()) : 0; };
     if (adaptive < 0.0f) {
@@ -347,7 +376,7 @@ int main(int argc, char** argv)
     if (denoise) { /* after --save-state: a state is the raw accumulation */
         tb_denoiser_settings dn; tb_default_denoiser_settings(&dn);
         if (denoiseIterations >= 0) dn.WaveletIterations = (uint32_t)denoiseIterations;
-        if (!png) denoised.resize((size_t)W * H * 4);
+        if (!png && !upW) denoised.resize((size_t)W * H * 4);
         if (denoiseGuides) { /* the last min(K, frames held) frames of the state's range, traced again */
             const uint32_t next = tb_samples_rendered(ctx), first = (uint32_t)tb_get_option(ctx, "state_first_frame");
             const uint32_t k = (uint32_t)std::min<long long>(denoiseGuides, (long long)next - (long long)first);
@@ -355,11 +384,19 @@ int main(int argc, char** argv)
             printf("guides: first hits of frames [%u, %u), %.3f ms on the GPU\n", next - k, next, (double)tb_get_option(ctx, "last_guides_us") / 1e3);
             if ((rc = tb_set_option(ctx, "denoise_guides", demodulate ? 2 : 1))) return fail(ctx, "tb_set_option", rc);
         }
-        if ((rc = tb_denoise(ctx, &dn, png ? nullptr : denoised.data()))) return fail(ctx, "tb_denoise", rc);
+        if ((rc = tb_denoise(ctx, &dn, denoised.empty() ? nullptr : denoised.data()))) return fail(ctx, "tb_denoise", rc);
         printf("denoise: %u a-trous passes, %.3f ms on the GPU\n", dn.WaveletIterations, (double)tb_get_option(ctx, "last_denoise_us") / 1e3);
-        if (png && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
+        if ((png || upW) && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
     }
-    if (png) {
+    if (upW) { /* the output stage at the rendered size, then FSR 1 to the picture's */
+        std::vector<uint8_t> img(png ? (size_t)upW * upH * 4 : 0); std::vector<float> imgF(png ? 0 : (size_t)upW * upH * 4);
+        if ((rc = tb_upscale(ctx, &post, TB_OUTPUT_TYPE_LIT, upW, upH, fsrSharpness, png ? nullptr : imgF.data(), png ? img.data() : nullptr)))
+            return fail(ctx, "tb_upscale", rc);
+        printf("upscale: %ux%u -> %ux%u, EASU %.3f ms + RCAS %.3f ms on the GPU\n", W, H, upW, upH, (double)tb_get_option(ctx, "last_easu_us") / 1e3,
+               (double)tb_get_option(ctx, "last_rcas_us") / 1e3);
+        if (png) { if ((rc = tb_write_image_rgba8(out.c_str(), upW, upH, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc); }
+        else if ((rc = tb_write_image_f32(out.c_str(), upW, upH, imgF.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
+    } else if (png) {
         std::vector<uint8_t> img((size_t)W * H * 4);
         if ((rc = tb_post_process(ctx, &post, TB_OUTPUT_TYPE_LIT, nullptr, img.data()))) return fail(ctx, "tb_post_process", rc);
         if ((rc = tb_write_image_rgba8(out.c_str(), W, H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc);

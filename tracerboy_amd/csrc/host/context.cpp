@@ -422,36 +422,48 @@ void tb_default_post_settings(tb_post_settings* o) /* TracerBoy.h:298,309-313 */
     o->ExposureMultiplier = 1.0f; o->EnableGammaCorrection = 1; o->EnableAutoExposure = 1; o->TonemapType = TB_TONEMAP_AGX_PUNCHY; o->VarianceMultiplier = 1.0f;
 }
 
+} // extern "C"
+
+/* The output stage on the context's stream, into postOut / postRgba8; not waited for.  tb_post_process and tb_upscale (context_upscale.cpp) run it. */
+int tbctx::launchPostProcess(tb_context* c, const tb_post_settings* post, uint32_t outputType)
+{
+    if (!c->output.p || c->width == 0) return fail(c, TB_E_INVALID, "tb_post_process: nothing rendered yet");
+    tb_post_settings ps; if (post) ps = *post; else tb_default_post_settings(&ps);
+    const TbFloat4* in = nullptr; const float* inR32 = nullptr;
+    switch (outputType) { /* GetOutputSRV, TracerBoy.cpp:2354-2383 */
+    /* PostProcessInput after the real-time chain, TracerBoy.cpp:3144-3160 */
+    case TB_OUTPUT_TYPE_LIT:
+        if (opt<OPT_post_denoised>(c)) { /* the denoised still (tb_denoise): (rgb, 1), so that ProcessLit's division by .w is the identity */
+            if (!c->dnValid) return fail(c, TB_E_INVALID,
+                "tb_post_process: option \"post_denoised\" is set and there is no valid denoised surface: call tb_denoise after the last change of the accumulation");
+            in = (const TbFloat4*)c->dnFinal.p; break;
+        }
+        in = (const TbFloat4*)(c->lastRenderRealtime ? c->rtFinal[c->rtLast[4]].p : c->output.p); break;
+    case TB_OUTPUT_TYPE_LUMINANCE: in = (const TbFloat4*)c->output.p; break;
+    case TB_OUTPUT_TYPE_ALBEDO: case TB_OUTPUT_TYPE_LIVE_PIXELS: case TB_OUTPUT_TYPE_HEATMAP: in = (const TbFloat4*)c->aov[TB_AOV_CUSTOM].p; break;
+    case TB_OUTPUT_TYPE_NORMAL: in = (const TbFloat4*)c->aov[TB_AOV_NORMALS].p; break;
+    case TB_OUTPUT_TYPE_DEPTH: inR32 = (const float*)c->aov[TB_AOV_DEPTH].p; break;
+    default: return fail(c, TB_E_UNSUPPORTED, "tb_post_process: this output type needs surfaces of the real-time chain (not built)");
+    }
+    if (!in && !inR32) return fail(c, TB_E_INVALID, "tb_post_process: the AOV for this output type was not rendered (set option \"aov\" before tb_render)");
+    const size_t px = (size_t)c->width * c->height;
+    ensure(c->postOut, px * 16); ensure(c->postRgba8, px * 4); ensure(c->postHistogram, 256 * 4); ensure(c->postAverage, 4);
+    TbPostConstants pc; memset(&pc, 0, sizeof pc);
+    pc.W = c->width; pc.H = c->height; pc.FramesRendered = c->samplesRendered; pc.ExposureMultiplier = ps.ExposureMultiplier;
+    pc.TonemapType = ps.TonemapType; pc.UseGammaCorrection = ps.EnableGammaCorrection; pc.UseAutoExposure = ps.EnableAutoExposure;
+    pc.OutputType = outputType; pc.VarianceMultiplier = ps.VarianceMultiplier;
+    HIP_TRY(post_launch(c->stream, &pc, in, inR32, (const TbFloat4*)c->aov[TB_AOV_CUSTOM].p, (uint32_t*)c->postHistogram.p, (float*)c->postAverage.p,
+                        (TbFloat4*)c->postOut.p, (uint32_t*)c->postRgba8.p));
+    return TB_OK;
+}
+
+extern "C" {
+
 int tb_post_process(tb_context* c, const tb_post_settings* post, uint32_t outputType, float* rgbaF32, uint8_t* rgba8)
 {
     return guarded(c, [&]() {
-        if (!c->output.p || c->width == 0) return fail(c, TB_E_INVALID, "tb_post_process: nothing rendered yet");
-        tb_post_settings ps; if (post) ps = *post; else tb_default_post_settings(&ps);
-        const TbFloat4* in = nullptr; const float* inR32 = nullptr;
-        switch (outputType) { /* GetOutputSRV, TracerBoy.cpp:2354-2383 */
-        /* PostProcessInput after the real-time chain, TracerBoy.cpp:3144-3160 */
-        case TB_OUTPUT_TYPE_LIT:
-            if (opt<OPT_post_denoised>(c)) { /* the denoised still (tb_denoise): (rgb, 1), so that ProcessLit's division by .w is the identity */
-                if (!c->dnValid) return fail(c, TB_E_INVALID,
-                    "tb_post_process: option \"post_denoised\" is set and there is no valid denoised surface: call tb_denoise after the last change of the accumulation");
-                in = (const TbFloat4*)c->dnFinal.p; break;
-            }
-            in = (const TbFloat4*)(c->lastRenderRealtime ? c->rtFinal[c->rtLast[4]].p : c->output.p); break;
-        case TB_OUTPUT_TYPE_LUMINANCE: in = (const TbFloat4*)c->output.p; break;
-        case TB_OUTPUT_TYPE_ALBEDO: case TB_OUTPUT_TYPE_LIVE_PIXELS: case TB_OUTPUT_TYPE_HEATMAP: in = (const TbFloat4*)c->aov[TB_AOV_CUSTOM].p; break;
-        case TB_OUTPUT_TYPE_NORMAL: in = (const TbFloat4*)c->aov[TB_AOV_NORMALS].p; break;
-        case TB_OUTPUT_TYPE_DEPTH: inR32 = (const float*)c->aov[TB_AOV_DEPTH].p; break;
-        default: return fail(c, TB_E_UNSUPPORTED, "tb_post_process: this output type needs surfaces of the real-time chain (not built)");
-        }
-        if (!in && !inR32) return fail(c, TB_E_INVALID, "tb_post_process: the AOV for this output type was not rendered (set option \"aov\" before tb_render)");
+        if (int rc = launchPostProcess(c, post, outputType)) return rc;
         const size_t px = (size_t)c->width * c->height;
-        ensure(c->postOut, px * 16); ensure(c->postRgba8, px * 4); ensure(c->postHistogram, 256 * 4); ensure(c->postAverage, 4);
-        TbPostConstants pc; memset(&pc, 0, sizeof pc);
-        pc.W = c->width; pc.H = c->height; pc.FramesRendered = c->samplesRendered; pc.ExposureMultiplier = ps.ExposureMultiplier;
-        pc.TonemapType = ps.TonemapType; pc.UseGammaCorrection = ps.EnableGammaCorrection; pc.UseAutoExposure = ps.EnableAutoExposure;
-        pc.OutputType = outputType; pc.VarianceMultiplier = ps.VarianceMultiplier;
-        HIP_TRY(post_launch(c->stream, &pc, in, inR32, (const TbFloat4*)c->aov[TB_AOV_CUSTOM].p, (uint32_t*)c->postHistogram.p, (float*)c->postAverage.p,
-                            (TbFloat4*)c->postOut.p, (uint32_t*)c->postRgba8.p));
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (rgbaF32) HIP_TRY(hipMemcpy(rgbaF32, c->postOut.p, px * 16, hipMemcpyDeviceToHost));
         if (rgba8) HIP_TRY(hipMemcpy(rgba8, c->postRgba8.p, px * 4, hipMemcpyDeviceToHost));
@@ -686,6 +698,10 @@ int64_t tb_get_option(tb_context* c, const char* name)
     if (!strcmp(name, "last_state_add_us")) return (int64_t)(c->lastStateAddMs * 1000.0f + 0.5f);
     if (!strcmp(name, "state_first_frame")) return c->firstFrame;
     if (!strcmp(name, "last_denoise_us")) return (int64_t)(c->lastDenoiseMs * 1000.0f + 0.5f); /* the last tb_denoise, prepare to finish (HIP events) */
+    /* the last tb_upscale: its FSR passes together, its EASU passes, its RCAS passes (HIP events; both chains when both ran) */
+    if (!strcmp(name, "last_upscale_us")) return (int64_t)(c->lastUpscaleMs * 1000.0f + 0.5f);
+    if (!strcmp(name, "last_easu_us")) return (int64_t)(c->lastEasuMs * 1000.0f + 0.5f);
+    if (!strcmp(name, "last_rcas_us")) return (int64_t)(c->lastRcasMs * 1000.0f + 0.5f);
     if (!strcmp(name, "last_guides_us")) return (int64_t)(c->lastGuidesMs * 1000.0f + 0.5f); /* the last tb_render_guides, its kernel alone (HIP events) */
     if (!strcmp(name, "last_guides_stack_overflow")) return c->lastGuidesOverflow; /* stack entries per lane the last pass kept in global memory (the HYBRID form) */
     if (!strcmp(name, "last_copy_waves")) return c->lastCopyWaves;

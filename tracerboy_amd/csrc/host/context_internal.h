@@ -6,6 +6,7 @@
  *   render_state.cpp    render states: begin at a frame, save, load, merge
  *   context_denoise.cpp the denoise of a progressive render: dual-buffer variance + the a-trous filter
  *   context_guides.cpp  the guide pass of that denoise: first hits traced again and summed over frames
+ *   context_upscale.cpp FSR 1 upscaling of the post-processed picture: EASU + RCAS
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
 #pragma once
@@ -172,6 +173,9 @@ struct tb_context {
     DevBuf guide[3], guideOverflow, dnNormals, dnPositions; bool guidesValid = false; int dnMode = 0; /* option denoise_guides of the last tb_denoise */
     struct GuideKey { uint32_t sceneGeneration, materialEdits, width, height, alphaTest; tb_camera camera; tb_output_settings settings; float time; } guideKey{};
     tbctx::DevEvent evGuide[2]; float lastGuidesMs = 0.0f; uint32_t lastGuidesOverflow = 0; /* options last_guides_us, last_guides_stack_overflow */
+    /* FSR 1 upscaling (context_upscale.cpp): per surface type the EASU output and the RCAS output, at the size of the last
+     * tb_upscale that ran that chain; events around the passes: [2 t] before EASU, [2 t + 1] between the passes, [4 + t] after RCAS */
+    DevBuf fsrMid[2], fsrOut[2]; tbctx::DevEvent evFsr[6]; float lastUpscaleMs = 0.0f, lastEasuMs = 0.0f, lastRcasMs = 0.0f;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -270,6 +274,7 @@ int deviceCUs(tb_context* c);
 std::string splitAbortMessage(tb_context* c, bool clear = true);
 int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* settings, float timeSeed, bool sync);
 void cameraConstants(const TbPerFrameConstants& pf, uint32_t W, uint32_t H, TbDeviceTargets& tg);
+int launchPostProcess(tb_context* c, const tb_post_settings* post, uint32_t outputType); /* context.cpp */
 /* context_guides.cpp: the guide surfaces belong to the context as it is now */
 bool guidesCurrent(const tb_context* c);
 
