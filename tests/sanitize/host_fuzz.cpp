@@ -1,5 +1,5 @@
 /* host_fuzz.cpp -- AddressSanitizer / UBSan harness for the host-side file readers (CPU build only: GPU sanitizers are not available on
- * the pool).  Built by tests/test_host_sanitizers.py from the product's own host sources (everything but context.cpp, which needs HIP):
+ * the pool).  Built by tests/test_host_sanitizers.py from the product's own host sources (the readers and builders; not the context*.cpp files, which need HIP):
  *
  *   host_fuzz <seed> <mutations> file...
  *

@@ -2,6 +2,8 @@
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -78,3 +80,15 @@ def test_host_scene_errors_are_codes_not_aborts(built, tmp_path, monkeypatch):
     empty.write_text('Camera "perspective" "float fov" [30]\nWorldBegin\nWorldEnd\n')
     with pytest.raises(api.TracerBoyError):
         api.HostScene("empty.pbrt")
+
+
+def test_host_api_needs_no_hip():
+    """host_api.cpp holds the entry points that need no device: it compiles with a plain C++ compiler and includes neither a HIP header nor
+    the context's internal header."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    src = os.path.join(ROOT, "tracerboy_amd", "csrc", "host", "host_api.cpp")
+    text = open(src).read()
+    assert "hip/" not in text and "context_internal.h" not in text
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr

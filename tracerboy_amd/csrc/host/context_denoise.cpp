@@ -19,10 +19,10 @@ extern "C" {
 
 int tb_denoise(tb_context* c, const tb_denoiser_settings* denoiser, float* rgba)
 {
-    if (c && (!c->peers.empty() || c->groupOwner)) return fail(c, TB_E_UNSUPPORTED,
+    if (c && (!c->group.peers.empty() || c->group.owner)) return fail(c, TB_E_UNSUPPORTED,
         "tb_denoise: not supported for a multi-device group: AOV targets are not gathered across its devices");
     return guarded(c, [&]() {
-        if (c->lastRenderRealtime) return fail(c, TB_E_INVALID,
+        if (c->rt.lastRender) return fail(c, TB_E_INVALID,
             "tb_denoise: the last render was tb_render_realtime: its surface holds one frame, not an accumulation (the real-time chain denoises itself)");
         if (!c->output.p || !c->jittered.p || !c->width || c->samplesRendered == c->firstFrame) return fail(c, TB_E_INVALID,
             "tb_denoise: nothing rendered: the context holds no frames");
@@ -38,47 +38,40 @@ int tb_denoise(tb_context* c, const tb_denoiser_settings* denoiser, float* rgba)
         if (mode != 0 && !guidesCurrent(c)) return fail(c, TB_E_INVALID,
             "tb_denoise: option denoise_guides is set and the context holds no valid guide surfaces: call tb_render_guides (a history reset, a resize, "
             "a scene load or a change of camera, settings or time seed invalidates them)");
-        const DevBuf& normals = mode ? c->dnNormals : c->aov[TB_AOV_NORMALS];
-        const DevBuf& positions = mode ? c->dnPositions : c->aov[TB_AOV_WORLD_POSITION0 + (last % 2u)];
+        const DevBuf& normals = mode ? c->dn.normals : c->aov[TB_AOV_NORMALS];
+        const DevBuf& positions = mode ? c->dn.positions : c->aov[TB_AOV_WORLD_POSITION0 + (last % 2u)];
         if (iterations > 0 && mode == 0) {
-            if (c->callCount < c->aovStaleUntilCall) return fail(c, TB_E_INVALID,
+            if (c->callCount < c->dn.aovStaleUntilCall) return fail(c, TB_E_INVALID,
                 "tb_denoise: the filter passes need the normals and world positions of the last frame, and nothing was rendered since tb_state_load / "
                 "tb_state_begin (AOVs are not part of a state): render at least one more frame with option \"aov\"");
             if (!opt<OPT_aov>(c) || normals.bytes != bytes || positions.bytes != bytes) return fail(c, TB_E_INVALID,
                 "tb_denoise: the filter passes need the normals and world positions of the last frame: set option \"aov\" before tb_render");
         }
-        c->dnValid = false; c->dnLastPass = -1;
+        c->dn.valid = false; c->dn.lastPass = -1;
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->splitAbort && *c->splitAbort) return fail(c, TB_E_DEVICE, splitAbortMessage(c));
-        ensure(c->dnPrepared, bytes); ensure(c->dnFiltered, bytes); ensure(c->dnFinal, bytes);
-        if (iterations > 0) ensure(c->dnPass[0], bytes);
-        if (iterations > 1) ensure(c->dnPass[1], bytes);
-        if (mode != 0 && iterations > 0) { ensure(c->dnNormals, bytes); ensure(c->dnPositions, bytes); }
-        const TbFloat4* const albedo = (const TbFloat4*)c->guide[0].p; /* mode 2: (sum of the effective albedo, frames) */
-        HIP_TRY(hipEventRecord(c->evDn[0].create(), c->stream));
-        if (mode != 0 && iterations > 0) HIP_TRY(dn_launch_resolve_guides(c->stream, (const TbFloat4*)c->guide[1].p, (const TbFloat4*)c->guide[2].p,
-            (TbFloat4*)c->dnNormals.p, (TbFloat4*)c->dnPositions.p, W, H));
-        if (mode == 2) HIP_TRY(dn_launch_prepare_demod(c->stream, (const TbFloat4*)c->output.p, (const TbFloat4*)c->jittered.p, albedo, (TbFloat4*)c->dnPrepared.p, W, H));
+        ensure(c->dn.prepared, bytes); ensure(c->dn.filtered, bytes); ensure(c->dn.finalOut, bytes);
+        if (iterations > 0) ensure(c->dn.pass[0], bytes);
+        if (iterations > 1) ensure(c->dn.pass[1], bytes);
+        if (mode != 0 && iterations > 0) { ensure(c->dn.normals, bytes); ensure(c->dn.positions, bytes); }
+        const TbFloat4* const albedo = (const TbFloat4*)c->guides.sum[0].p; /* mode 2: (sum of the effective albedo, frames) */
+        HIP_TRY(hipEventRecord(c->dn.ev[0].create(), c->stream));
+        if (mode != 0 && iterations > 0) HIP_TRY(dn_launch_resolve_guides(c->stream, (const TbFloat4*)c->guides.sum[1].p, (const TbFloat4*)c->guides.sum[2].p,
+            (TbFloat4*)c->dn.normals.p, (TbFloat4*)c->dn.positions.p, W, H));
+        if (mode == 2) HIP_TRY(dn_launch_prepare_demod(c->stream, (const TbFloat4*)c->output.p, (const TbFloat4*)c->jittered.p, albedo, (TbFloat4*)c->dn.prepared.p, W, H));
         else
-        HIP_TRY(dn_launch_prepare(c->stream, (const TbFloat4*)c->output.p, (const TbFloat4*)c->jittered.p, (TbFloat4*)c->dnPrepared.p, W, H));
-        HIP_TRY(dn_launch_prefilter(c->stream, (const TbFloat4*)c->dnPrepared.p, (TbFloat4*)c->dnFiltered.p, W, H));
-        const TbFloat4* filtered = (const TbFloat4*)c->dnFiltered.p; const TbFloat4* in = filtered;
-        for (uint32_t i = 0; i < iterations; i++) { /* DenoiserPass.cpp:61-93, as tb_render_realtime runs it */
-            TbDenoiserConstants k; memset(&k, 0, sizeof k);
-            k.ResolutionX = W; k.ResolutionY = H; k.OffsetMultiplier = 1u << i; k.GlobalFrameCount = c->samplesRendered;
-            k.NormalWeightingExponential = dn.NormalWeightingExponential; k.IntersectionPositionWeightingMultiplier = dn.IntersectPositionWeightingMultiplier;
-            k.LumaWeightingMultiplier = dn.LuminanceWeightingMultiplier;
-            TbFloat4* out = (TbFloat4*)c->dnPass[i & 1u].p;
-            HIP_TRY(rt_launch_denoise(c->stream, &k, in, (const TbFloat4*)normals.p, (const TbFloat4*)positions.p, filtered, out));
-            in = out;
-        }
-        if (mode == 2) HIP_TRY(dn_launch_finish_remod(c->stream, in, albedo, (TbFloat4*)c->dnFinal.p, W, H));
-        else HIP_TRY(dn_launch_finish(c->stream, in, (TbFloat4*)c->dnFinal.p, W, H));
-        HIP_TRY(hipEventRecord(c->evDn[1].create(), c->stream));
+        HIP_TRY(dn_launch_prepare(c->stream, (const TbFloat4*)c->output.p, (const TbFloat4*)c->jittered.p, (TbFloat4*)c->dn.prepared.p, W, H));
+        HIP_TRY(dn_launch_prefilter(c->stream, (const TbFloat4*)c->dn.prepared.p, (TbFloat4*)c->dn.filtered.p, W, H));
+        const int lastPass = runAtrousPasses(c->stream, W, H, iterations, (const TbFloat4*)c->dn.filtered.p, (const TbFloat4*)normals.p,
+            (const TbFloat4*)positions.p, c->dn.pass, dn, c->samplesRendered); /* as tb_render_realtime runs them */
+        const TbFloat4* in = (const TbFloat4*)(lastPass < 0 ? c->dn.filtered.p : c->dn.pass[lastPass].p);
+        if (mode == 2) HIP_TRY(dn_launch_finish_remod(c->stream, in, albedo, (TbFloat4*)c->dn.finalOut.p, W, H));
+        else HIP_TRY(dn_launch_finish(c->stream, in, (TbFloat4*)c->dn.finalOut.p, W, H));
+        HIP_TRY(hipEventRecord(c->dn.ev[1].create(), c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hipEventElapsedTime(&c->lastDenoiseMs, c->evDn[0], c->evDn[1]) != hipSuccess) c->lastDenoiseMs = 0.0f;
-        c->dnLastPass = iterations ? (int)((iterations - 1u) & 1u) : -1; c->dnValid = true; c->dnMode = mode;
-        if (rgba) HIP_TRY(hipMemcpy(rgba, c->dnFinal.p, bytes, hipMemcpyDeviceToHost));
+        if (hipEventElapsedTime(&c->dn.lastMs, c->dn.ev[0], c->dn.ev[1]) != hipSuccess) c->dn.lastMs = 0.0f;
+        c->dn.lastPass = lastPass; c->dn.valid = true; c->dn.mode = mode;
+        if (rgba) HIP_TRY(hipMemcpy(rgba, c->dn.finalOut.p, bytes, hipMemcpyDeviceToHost));
         return TB_OK;
     });
 }
@@ -87,10 +80,10 @@ int tb_read_denoise_stage(tb_context* c, int stage, float* rgba)
 {
     return guarded(c, [&]() {
         if (!rgba || stage < 0 || stage > 3) return fail(c, TB_E_INVALID, "tb_read_denoise_stage: stage is 0 (prepared), 1 (filtered), 2 (last filter pass) or 3 (final)");
-        if (!c->dnValid) return fail(c, TB_E_INVALID,
+        if (!c->dn.valid) return fail(c, TB_E_INVALID,
             "tb_read_denoise_stage: no valid denoised surface: call tb_denoise after the last change of the accumulation");
-        if (stage == 2 && c->dnLastPass < 0) return fail(c, TB_E_INVALID, "tb_read_denoise_stage: stage 2: the last tb_denoise ran no filter pass");
-        const DevBuf& b = stage == 0 ? c->dnPrepared : stage == 1 ? c->dnFiltered : stage == 2 ? c->dnPass[c->dnLastPass] : c->dnFinal;
+        if (stage == 2 && c->dn.lastPass < 0) return fail(c, TB_E_INVALID, "tb_read_denoise_stage: stage 2: the last tb_denoise ran no filter pass");
+        const DevBuf& b = stage == 0 ? c->dn.prepared : stage == 1 ? c->dn.filtered : stage == 2 ? c->dn.pass[c->dn.lastPass] : c->dn.finalOut;
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(rgba, b.p, (size_t)c->width * c->height * sizeof(TbFloat4), hipMemcpyDeviceToHost));
         return TB_OK;

@@ -25,8 +25,8 @@ namespace tbctx {
 /* scene, camera (by bits), size, history-relevant settings, time seed (by bits) and option alpha_test are those the guides were traced with */
 bool guidesCurrent(const tb_context* c)
 {
-    if (!c->guidesValid || !c->haveLastSettings || !c->guide[0].p) return false;
-    const tb_context::GuideKey now = keyOf(c); const tb_context::GuideKey& k = c->guideKey;
+    if (!c->guides.valid || !c->haveLastSettings || !c->guides.sum[0].p) return false;
+    const tb_context::GuideKey now = keyOf(c); const tb_context::GuideKey& k = c->guides.key;
     return now.sceneGeneration == k.sceneGeneration && now.materialEdits == k.materialEdits && now.width == k.width && now.height == k.height &&
         now.alphaTest == k.alphaTest && !memcmp(&now.camera, &k.camera, sizeof k.camera) && !historyRelevantChange(now.settings, k.settings) &&
         !memcmp(&now.time, &k.time, sizeof k.time);
@@ -37,41 +37,41 @@ extern "C" {
 
 int tb_render_guides(tb_context* c, uint32_t firstFrame, uint32_t nFrames)
 {
-    if (c && (!c->peers.empty() || c->groupOwner)) return fail(c, TB_E_UNSUPPORTED,
+    if (c && (!c->group.peers.empty() || c->group.owner)) return fail(c, TB_E_UNSUPPORTED,
         "tb_render_guides: not supported for a multi-device group: guide surfaces are not gathered across its devices");
     return guarded(c, [&]() {
         if (c->tiles.world > 1) return fail(c, TB_E_UNSUPPORTED, "tb_render_guides: not supported with a tile assignment of world > 1: a rank holds a part of the frame");
         if (!c->hasScene) return fail(c, TB_E_INVALID, "tb_render_guides: no scene loaded");
         if (!c->width || !c->height || !c->haveLastSettings) return fail(c, TB_E_INVALID,
             "tb_render_guides: no size yet: the frame size, settings and time seed are those of the last tb_render, tb_state_load or tb_state_begin");
-        if (c->lastRenderRealtime || c->lastSettings.RenderModeRealTime) return fail(c, TB_E_INVALID,
+        if (c->rt.lastRender || c->lastSettings.RenderModeRealTime) return fail(c, TB_E_INVALID,
             "tb_render_guides: the last render was tb_render_realtime: its surface holds one frame, not an accumulation");
         if (c->lastSettings.OutputType == TB_OUTPUT_TYPE_HEATMAP || c->lastSettings.OutputType == TB_OUTPUT_TYPE_LIVE_PIXELS) return fail(c, TB_E_INVALID,
             "tb_render_guides: OutputType heat map / live pixels: the custom AOV of such a render is not the albedo");
         if (nFrames < 1 || nFrames > kMaxGuideFrames) return fail(c, TB_E_INVALID, "tb_render_guides: n_frames is 1 to " + std::to_string(kMaxGuideFrames));
         const uint32_t W = c->width, H = c->height;
         const size_t bytes = (size_t)W * H * sizeof(TbFloat4);
-        c->guidesValid = false;
+        c->guides.valid = false;
         GuidePlan plan = guide_stack_plan(c->ds.stackDepth, (uint32_t)std::max<int64_t>(0, opt<OPT_stack_overflow_max>(c)),
             (uint32_t)std::max<int64_t>(0, std::min<int64_t>(opt<OPT_stack_lds_cap>(c), 0xffff)));
         if (!plan.ok) return fail(c, TB_E_UNSUPPORTED, "tb_render_guides: traversal stack of depth " + std::to_string(c->ds.stackDepth) + " does not fit LDS; unsupported");
         HIP_TRY(guide_plan_grid(&plan, tb_persistent_grid(W, H, c->tiles)));
-        for (DevBuf& b : c->guide) ensure(b, bytes);
-        if (plan.overflowEntries) ensure(c->guideOverflow, (size_t)plan.overflowEntries * plan.lanes * 4);
+        for (DevBuf& b : c->guides.sum) ensure(b, bytes);
+        if (plan.overflowEntries) ensure(c->guides.overflow, (size_t)plan.overflowEntries * plan.lanes * 4);
         TbDeviceScene ds = c->ds; ds.alphaTest = opt<OPT_alpha_test>(c) ? 1u : 0u;
         TbPerFrameConstants pf;
         MakeFrameConstants(c->scene, c->camera, c->lastSettings, firstFrame, c->lastTime, 0xffffffffu, 0xffffffffu, pf);
         TbDeviceTargets tg; memset(&tg, 0, sizeof tg); /* the camera constants alone */
         if (opt<OPT_camera_constants>(c) != 0) cameraConstants(pf, W, H, tg);
-        HIP_TRY(hipEventRecord(c->evGuide[0].create(), c->stream));
-        HIP_TRY(guide_launch(c->stream, &ds, &pf, &tg, W, H, firstFrame, nFrames, &c->tiles, &plan, plan.overflowEntries ? (uint32_t*)c->guideOverflow.p : nullptr,
-            (TbFloat4*)c->guide[0].p, (TbFloat4*)c->guide[1].p, (TbFloat4*)c->guide[2].p));
-        HIP_TRY(hipEventRecord(c->evGuide[1].create(), c->stream));
+        HIP_TRY(hipEventRecord(c->guides.ev[0].create(), c->stream));
+        HIP_TRY(guide_launch(c->stream, &ds, &pf, &tg, W, H, firstFrame, nFrames, &c->tiles, &plan, plan.overflowEntries ? (uint32_t*)c->guides.overflow.p : nullptr,
+            (TbFloat4*)c->guides.sum[0].p, (TbFloat4*)c->guides.sum[1].p, (TbFloat4*)c->guides.sum[2].p));
+        HIP_TRY(hipEventRecord(c->guides.ev[1].create(), c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hipEventElapsedTime(&c->lastGuidesMs, c->evGuide[0], c->evGuide[1]) != hipSuccess) c->lastGuidesMs = 0.0f;
+        if (hipEventElapsedTime(&c->guides.lastMs, c->guides.ev[0], c->guides.ev[1]) != hipSuccess) c->guides.lastMs = 0.0f;
         if (c->splitAbort && *c->splitAbort) return fail(c, TB_E_DEVICE, splitAbortMessage(c));
-        c->guideKey = keyOf(c); c->guidesValid = true; c->lastGuidesOverflow = plan.overflowEntries;
-        if (c->dnMode != 0) c->dnValid = false; /* a denoised surface made of the guides before these */
+        c->guides.key = keyOf(c); c->guides.valid = true; c->guides.lastOverflow = plan.overflowEntries;
+        if (c->dn.mode != 0) c->dn.valid = false; /* a denoised surface made of the guides before these */
         return TB_OK;
     });
 }
@@ -82,7 +82,7 @@ int tb_read_guide(tb_context* c, int which, float* rgba)
         if (!rgba || which < 0 || which > 2) return fail(c, TB_E_INVALID, "tb_read_guide: which is 0 (albedo), 1 (normal) or 2 (position)");
         if (!guidesCurrent(c)) return fail(c, TB_E_INVALID, "tb_read_guide: no valid guide surfaces: call tb_render_guides");
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(rgba, c->guide[which].p, (size_t)c->width * c->height * sizeof(TbFloat4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rgba, c->guides.sum[which].p, (size_t)c->width * c->height * sizeof(TbFloat4), hipMemcpyDeviceToHost));
         return TB_OK;
     });
 }

@@ -1,16 +1,21 @@
 /* context_internal.h -- what the translation units of the context share: the kernel launchers' C interface, the table of feature
  * sets, the owners of device resources, struct tb_context (the role of the reference's `class TracerBoy`, TracerBoy.h:158-398) and a few helpers.
- *   context.cpp         the C ABI (include/tracerboy_hip.h): create / destroy, scene loads, options, read-backs, output stage, real-time chain, groups
+ *   context.cpp         the C ABI (include/tracerboy_hip.h): kVariants, create / destroy, scene loads, edits, tb_render / tb_sync, read-backs, tb_set_option
+ *   context_queries.cpp tb_get_option: the table of read-only names, then the options
  *   context_scene.cpp   finalizeScene: BVH builds on the GPU, node orders, layout C, uploads, the LDS scene image
  *   context_render.cpp  renderImpl, a sequence of named steps, and the pipelines it dispatches to
+ *   context_group.cpp   multi-device groups: tb_create_multi, the group's render and gather, tile assignments, pack / unpack of owned tiles
+ *   context_realtime.cpp the real-time chain (tb_render_realtime), the a-trous pass loop, the test hooks of rt_kernels.hip
+ *   context_post.cpp    the output stage: tb_post_process, launchPostProcess
  *   render_state.cpp    render states: begin at a frame, save, load, merge
  *   context_denoise.cpp the denoise of a progressive render: dual-buffer variance + the a-trous filter
  *   context_guides.cpp  the guide pass of that denoise: first hits traced again and summed over frames
  *   context_upscale.cpp FSR 1 upscaling of the post-processed picture: EASU + RCAS
+ *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
 #pragma once
-#include "host_scene.h"
+#include "host_shared.h"
 #include "../kernels/pt_launch.h"
 #include "../kernels/pt_device_features.h"
 #include "launch_plan.h"
@@ -52,7 +57,6 @@ TB_WAVEFRONT(wf_launch_matte) TB_WAVEFRONT(wf_launch_env) TB_WAVEFRONT(wf_launch
 namespace tbctx {
 using namespace tbhost;
 
-extern std::string g_createError;
 /* A lock-step copy: its row of pt_copies.h and its launcher. */
 struct Copy { const PtCopy* row; pt_variant_fn launch; };
 /* A feature set.  Searched in order: the first one that covers what scene + settings need.  id: what option "last_variant" reports (stable across
@@ -146,11 +150,14 @@ struct tb_context {
     uint32_t width = 0, height = 0;
     DevBuf output, jittered, aov[8], stats, rayStats, packed;
     DevBuf postOut, postRgba8, postHistogram, postAverage; /* output stage (post_kernels.hip) */
-    /* real-time chain (rt_kernels.hip): ping-pong histories like TracerBoy.h:513-518,747-749 */
-    DevBuf rtIndirect[2], rtMoment[2], rtFinal[2], rtDenoise[2], rtComposited;
-    uint32_t rtActive = 0, rtWidth = 0, rtHeight = 0; int rtLast[5] = {-1, -1, -1, -1, -1}; /* which buffer holds each stage's last output */
-    bool lastRenderRealtime = false; tb_camera prevCamera{};
-    bool rtChainFrame = false; /* renderImpl is rendering tb_render_realtime's frame: its positions go to world-position half rtActive (fillTargets) */
+    /* real-time chain (context_realtime.cpp, rt_kernels.hip): ping-pong histories like TracerBoy.h:513-518,747-749.  last: which buffer holds each
+     * stage's last output; lastRender: the last render was tb_render_realtime; chainFrame: renderImpl is rendering tb_render_realtime's frame: its
+     * positions go to world-position half `active` (fillTargets) */
+    struct Realtime {
+        DevBuf indirect[2], moment[2], finalOut[2], denoise[2], composited;
+        uint32_t active = 0, width = 0, height = 0; int last[5] = {-1, -1, -1, -1, -1};
+        bool lastRender = false, chainFrame = false; tb_camera prevCamera{};
+    } rt;
     /* wavefront pipeline: two ping-pong extend queues (4 columns), one shadow queue (11 columns), hits, samples, counters */
     DevBuf wfCols[2][6], wfShadowCols[12], wfHitA, wfHitG, wfSamples, wfCounts, workCounter;
     uint64_t wfCapacity = 0, wfSampleCapacity = 0;
@@ -161,21 +168,26 @@ struct tb_context {
     DevBuf stateScratch; /* the digest's per-workgroup partials and its two results (state_launch.h) */
     tbctx::DevEvent evState[2]; float lastStateDigestMs = 0.0f, lastStateAddMs = 0.0f; /* options last_state_digest_us / last_state_add_us */
     uint64_t sceneDigest = 0, sceneDigestKey = ~0ull; uint32_t materialEdits = 0; /* tb_scene_digest, cached per (sceneGeneration, materialEdits) */
-    /* the denoise of a progressive render (context_denoise.cpp): prepared, filtered, the filter passes' ping-pong, final.
-     * dnValid: they belong to the accumulation surfaces as they are now -- whatever writes those clears it (touchAccumulation); dnLastPass: which
-     * dnPass holds the last filter pass's output, -1 = no pass ran.  aovStaleUntilCall: the AOVs hold the first hits of frame samplesRendered - 1
-     * once callCount has reached it (a state that was begun or loaded brings frames without AOVs) */
-    DevBuf dnPrepared, dnFiltered, dnPass[2], dnFinal; bool dnValid = false; int dnLastPass = -1; uint64_t aovStaleUntilCall = 0;
-    tbctx::DevEvent evDn[2]; float lastDenoiseMs = 0.0f; /* option last_denoise_us */
-    /* the guide pass (context_guides.cpp): the sums over its frames (albedo, normal, position), its half of a split stack, and
-     * what the filter reads of them (dnNormals, dnPositions: resolved by tb_denoise).  guidesValid: they were traced of the scene, camera, size,
-     * settings and time seed in guideKey, and no history reset has come since (resetHistory clears it; guidesCurrent compares the key) */
-    DevBuf guide[3], guideOverflow, dnNormals, dnPositions; bool guidesValid = false; int dnMode = 0; /* option denoise_guides of the last tb_denoise */
-    struct GuideKey { uint32_t sceneGeneration, materialEdits, width, height, alphaTest; tb_camera camera; tb_output_settings settings; float time; } guideKey{};
-    tbctx::DevEvent evGuide[2]; float lastGuidesMs = 0.0f; uint32_t lastGuidesOverflow = 0; /* options last_guides_us, last_guides_stack_overflow */
+    /* the denoise of a progressive render (context_denoise.cpp): prepared, filtered, the filter passes' ping-pong, final, and
+     * what the filter reads of the guide pass (normals, positions: resolved by tb_denoise; mode: option denoise_guides of the last tb_denoise).
+     * valid: they belong to the accumulation surfaces as they are now -- whatever writes those clears it (touchAccumulation); lastPass: which
+     * pass[] holds the last filter pass's output, -1 = no pass ran.  aovStaleUntilCall: the AOVs hold the first hits of frame samplesRendered - 1
+     * once callCount has reached it (a state that was begun or loaded brings frames without AOVs).  lastMs: option last_denoise_us */
+    struct StillDenoise {
+        DevBuf prepared, filtered, pass[2], finalOut, normals, positions; bool valid = false; int lastPass = -1, mode = 0; uint64_t aovStaleUntilCall = 0;
+        tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+    } dn;
+    /* the guide pass (context_guides.cpp): the sums over its frames (albedo, normal, position) and its half of a split stack.
+     * valid: they were traced of the scene, camera, size, settings and time seed in key, and no history reset has come since (resetHistory clears
+     * it; guidesCurrent compares the key).  lastMs, lastOverflow: options last_guides_us, last_guides_stack_overflow */
+    struct GuideKey { uint32_t sceneGeneration, materialEdits, width, height, alphaTest; tb_camera camera; tb_output_settings settings; float time; };
+    struct Guides {
+        DevBuf sum[3], overflow; bool valid = false; GuideKey key{};
+        tbctx::DevEvent ev[2]; float lastMs = 0.0f; uint32_t lastOverflow = 0;
+    } guides;
     /* FSR 1 upscaling (context_upscale.cpp): per surface type the EASU output and the RCAS output, at the size of the last
      * tb_upscale that ran that chain; events around the passes: [2 t] before EASU, [2 t + 1] between the passes, [4 + t] after RCAS */
-    DevBuf fsrMid[2], fsrOut[2]; tbctx::DevEvent evFsr[6]; float lastUpscaleMs = 0.0f, lastEasuMs = 0.0f, lastRcasMs = 0.0f;
+    struct Fsr { DevBuf mid[2], out[2]; tbctx::DevEvent ev[6]; float lastUpscaleMs = 0.0f, lastEasuMs = 0.0f, lastRcasMs = 0.0f; } fsr;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -201,14 +213,16 @@ struct tb_context {
     int lastFgPar = 0;          /* which of the two sample buffers the last frame-group launch wrote (debug query) */
     int lastPrimaryPrepass = 0; /* 1: the last render took its first hits from the primary-visibility pre-pass */
     int lastFirstBounce = 0;    /* 1: ... its paths' state after the first bounce from the first-bounce pass */
-    /* Multi-device group (tb_create_multi): this context is device 0 of the group and owns the assembled frame; `peers` are the
+    /* Multi-device group (context_group.cpp, tb_create_multi): this context is device 0 of the group and owns the assembled frame; `peers` are the
      * contexts of the other devices.  A render splits the frame into 64x64 tiles dealt round-robin over the devices (DESIGN.md
      * section 7), every device renders its own, the peers' packed tiles come over with hipMemcpyPeerAsync (xGMI) and are un-permuted
      * into this context's accumulation surfaces.  One host thread drives all devices; nothing blocks until the final wait. */
-    std::vector<tb_context*> peers;
-    tb_context* groupOwner = nullptr;          /* set on a peer: API calls on a peer handle are refused */
-    DevBuf groupPacked[2], groupGathered[2];   /* [0] output, [1] jittered: this device's packed tiles; (owner) world x capacity gathered tiles */
-    tbctx::DevEvent evGroup, evGroupDone; /* evGroup (peer): its packed tiles are on their way; evGroupDone (owner): the un-permute of the last group render has read groupGathered */
+    struct Group {
+        std::vector<tb_context*> peers;
+        tb_context* owner = nullptr;     /* set on a peer: API calls on a peer handle are refused */
+        DevBuf packed[2], gathered[2];   /* [0] output, [1] jittered: this device's packed tiles; (owner) world x capacity gathered tiles */
+        tbctx::DevEvent evSent, evDone;  /* evSent (peer): its packed tiles are on their way; evDone (owner): the un-permute of the last group render has read `gathered` */
+    } group;
     bool compactTried = false; /* layout C was asked for and built -- or could not be built -- for the loaded scene (ensureCompactNodes) */
 };
 
@@ -216,11 +230,11 @@ namespace tbctx {
 
 int fail(tb_context* c, int code, const std::string& msg);
 /* forget the accumulated frames: the next render starts at frame 0 (where the kernels overwrite the surfaces instead of adding to them) */
-inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dnValid = false; c->guidesValid = false; }
+inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dn.valid = false; c->guides.valid = false; }
 /* the accumulation surfaces are about to change (a render, a state that is begun, loaded or added): the denoised surfaces no longer belong to them */
-inline void touchAccumulation(tb_context* c) { c->dnValid = false; }
+inline void touchAccumulation(tb_context* c) { c->dn.valid = false; }
 /* an entry point that only a group's own context may be asked */
-#define TB_REFUSE_PEER(c) do { if ((c) && (c)->groupOwner) return fail((c), TB_E_INVALID, \
+#define TB_REFUSE_PEER(c) do { if ((c) && (c)->group.owner) return fail((c), TB_E_INVALID, \
     "this context is a member of a multi-device group: call the group's context"); } while (0)
 template <Opt K> inline int64_t opt(const tb_context* c) { return c->options.get<K>(); }
 
@@ -257,8 +271,21 @@ template <class T> const T* upload(tb_context* c, const std::vector<T>& v)
     c->sceneBufs.push_back(std::move(b));
     return (const T*)c->sceneBufs.back().p;
 }
+/* The test hooks' staging (tb_trace_closest, tb_device_math, tb_run_*): temporary buffers only, nothing of the context but its stream.  staged: a
+ * buffer of its own holding a copy of a host array; scratch: one to write into; copyBack: all of it to the host, where the caller gave a pointer --
+ * d.bytes is what the hook asked for, since ensure makes a buffer hold exactly that */
+inline DevBuf scratch(size_t bytes) { DevBuf d; ensure(d, bytes); return d; }
+inline DevBuf staged(const void* host, size_t bytes) { DevBuf d = scratch(bytes); HIP_TRY(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice)); return d; }
+inline void copyBack(void* host, const DevBuf& d) { if (host) HIP_TRY(hipMemcpy(host, d.p, d.bytes, hipMemcpyDeviceToHost)); }
+/* why a hook or tb_upscale refuses a surface of that size; null: it does not */
+inline const char* surfaceRefusal(uint32_t W, uint32_t H)
+{
+    if (W == 0 || H == 0) return "a dimension is 0";
+    if ((uint64_t)W * H > (1ull << 24)) return "more than 2^24 pixels";
+    return nullptr;
+}
 /* a context and the peers of its group */
-inline std::vector<tb_context*> members(tb_context* c) { std::vector<tb_context*> all(1, c); all.insert(all.end(), c->peers.begin(), c->peers.end()); return all; }
+inline std::vector<tb_context*> members(tb_context* c) { std::vector<tb_context*> all(1, c); all.insert(all.end(), c->group.peers.begin(), c->group.peers.end()); return all; }
 
 /* context_scene.cpp */
 void releaseScene(tb_context* c);
@@ -267,14 +294,22 @@ uint32_t sceneTextureUse(const tb_context* c);
 uint32_t settingsFeatureMask(const tb_context* c, const tb_output_settings& s, bool aov);
 void ensureCompactNodes(tb_context* c);
 void finalizeScene(tb_context* c, bool build = true); /* build = false: c->scene already holds a built, reordered tree (a peer of a multi-device group) */
-uint64_t sceneDigestOf(const HostScene& s); /* context.cpp */
 /* context_render.cpp */
 bool historyRelevantChange(const tb_output_settings& a, const tb_output_settings& b);
 int deviceCUs(tb_context* c);
 std::string splitAbortMessage(tb_context* c, bool clear = true);
 int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* settings, float timeSeed, bool sync);
 void cameraConstants(const TbPerFrameConstants& pf, uint32_t W, uint32_t H, TbDeviceTargets& tg);
-int launchPostProcess(tb_context* c, const tb_post_settings* post, uint32_t outputType); /* context.cpp */
+/* context_post.cpp: the output stage on the context's stream, into postOut / postRgba8; not waited for */
+int launchPostProcess(tb_context* c, const tb_post_settings* post, uint32_t outputType);
+/* context_group.cpp */
+int shareSceneWithPeers(tb_context* c);
+int renderGroup(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* s, float t);
+/* context_realtime.cpp: n passes of the a-trous filter (DenoiserPass.cpp:61-93) enqueued on `stream`.  Pass i reads the output of pass i - 1 -- the
+ * first reads `first`, which every pass also gets as the undenoised surface -- and writes pingPong[i & 1], with OffsetMultiplier = 1 << i.
+ * Returns which of the two holds the last output, -1 when n is 0. */
+int runAtrousPasses(hipStream_t stream, uint32_t W, uint32_t H, uint32_t n, const TbFloat4* first, const TbFloat4* normals, const TbFloat4* positions,
+    DevBuf (&pingPong)[2], const tb_denoiser_settings& dn, uint32_t frameCount);
 /* context_guides.cpp: the guide surfaces belong to the context as it is now */
 bool guidesCurrent(const tb_context* c);
 

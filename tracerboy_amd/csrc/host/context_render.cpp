@@ -488,11 +488,11 @@ static void fillTargets(RenderCall& r)
             HIP_TRY(hipMemsetAsync(c->aov[i].p, 0, bytes, c->stream)); } }
         tg.aovNormals = (TbFloat4*)c->aov[2].p; tg.aovWorldPos0 = (TbFloat4*)c->aov[3].p; tg.aovWorldPos1 = (TbFloat4*)c->aov[4].p;
         tg.aovCustom = (TbFloat4*)c->aov[5].p; tg.aovDepth = (float*)c->aov[6].p; tg.aovEmissive = (TbFloat4*)c->aov[7].p;
-        /* a real-time frame's positions go to the half tb_render_realtime reads as the current one (rtActive), whichever of the two the
+        /* a real-time frame's positions go to the half tb_render_realtime reads as the current one (rt.active), whichever of the two the
          * kernels pick by the parity of the global frame number: the sample counter restarts with every camera move and tb_invalidate_history,
          * the chain's ping-pong does not -- left to the parity, a restart after an odd number of frames made the chain read the previous
          * frame's positions as the current ones and the current ones as the previous frame's */
-        if (c->rtChainFrame) tg.aovWorldPos0 = tg.aovWorldPos1 = (TbFloat4*)c->aov[TB_AOV_WORLD_POSITION0 + c->rtActive].p;
+        if (c->rt.chainFrame) tg.aovWorldPos0 = tg.aovWorldPos1 = (TbFloat4*)c->aov[TB_AOV_WORLD_POSITION0 + c->rt.active].p;
     }
     /* (debug_profile_groups: the counters' buffer handed to a frame-group launch -- only a library built with -DTB_EXP_PROFILE_GROUPS has a kernel
      * that writes them, scripts/c2_instruction_mix.py; the shipped frame-group kernels carry no counters and ignore the pointer) */

@@ -23,12 +23,6 @@ uint32_t halfTruncated(float f)
     return sign | ((e - 112u) << 10) | (m >> 13);
 }
 
-const char* sizeRefusal(uint32_t W, uint32_t H)
-{
-    if (W == 0 || H == 0) return "a dimension is 0";
-    if ((uint64_t)W * H > (1ull << 24)) return "more than 2^24 pixels";
-    return nullptr;
-}
 /* bytes per texel of a surface type; 0 = no such type */
 size_t texelBytes(uint32_t surface) { return surface == TB_FSR_SURFACE_UNORM8 ? 4u : surface == TB_FSR_SURFACE_F32 ? 16u : 0u; }
 
@@ -62,15 +56,13 @@ int tb_run_fsr_easu(tb_context* c, const TbFsrConstants* k, uint32_t surface, ui
         if (!k || !in || !out) return fail(c, TB_E_INVALID, "tb_run_fsr_easu: null pointer");
         const size_t texel = texelBytes(surface);
         if (!texel) return fail(c, TB_E_INVALID, "tb_run_fsr_easu: unknown surface type " + std::to_string(surface));
-        if (const char* why = sizeRefusal(inW, inH)) return fail(c, TB_E_INVALID, std::string("tb_run_fsr_easu: input: ") + why);
-        if (const char* why = sizeRefusal(outW, outH)) return fail(c, TB_E_INVALID, std::string("tb_run_fsr_easu: output: ") + why);
+        if (const char* why = surfaceRefusal(inW, inH)) return fail(c, TB_E_INVALID, std::string("tb_run_fsr_easu: input: ") + why);
+        if (const char* why = surfaceRefusal(outW, outH)) return fail(c, TB_E_INVALID, std::string("tb_run_fsr_easu: output: ") + why);
         if (outW < inW || outH < inH) return fail(c, TB_E_INVALID, "tb_run_fsr_easu: the output is smaller than the input: FSR 1 only upscales");
-        DevBuf dIn, dOut;
-        ensure(dIn, (size_t)inW * inH * texel); ensure(dOut, (size_t)outW * outH * texel);
-        HIP_TRY(hipMemcpy(dIn.p, in, dIn.bytes, hipMemcpyHostToDevice));
+        const DevBuf dIn = staged(in, (size_t)inW * inH * texel), dOut = scratch((size_t)outW * outH * texel);
         HIP_TRY(fsr_launch_easu(c->stream, surface, k->easu, inW, inH, outW, outH, dIn.p, dOut.p));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(out, dOut.p, dOut.bytes, hipMemcpyDeviceToHost));
+        copyBack(out, dOut);
         return TB_OK;
     });
 }
@@ -81,13 +73,11 @@ int tb_run_fsr_rcas(tb_context* c, const TbFsrConstants* k, uint32_t surface, ui
         if (!k || !in || !out) return fail(c, TB_E_INVALID, "tb_run_fsr_rcas: null pointer");
         const size_t texel = texelBytes(surface);
         if (!texel) return fail(c, TB_E_INVALID, "tb_run_fsr_rcas: unknown surface type " + std::to_string(surface));
-        if (const char* why = sizeRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_fsr_rcas: ") + why);
-        DevBuf dIn, dOut;
-        ensure(dIn, (size_t)W * H * texel); ensure(dOut, dIn.bytes);
-        HIP_TRY(hipMemcpy(dIn.p, in, dIn.bytes, hipMemcpyHostToDevice));
+        if (const char* why = surfaceRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_fsr_rcas: ") + why);
+        const DevBuf dIn = staged(in, (size_t)W * H * texel), dOut = scratch(dIn.bytes);
         HIP_TRY(fsr_launch_rcas(c->stream, surface, k->rcas[0], W, H, dIn.p, dOut.p));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpy(out, dOut.p, dOut.bytes, hipMemcpyDeviceToHost));
+        copyBack(out, dOut);
         return TB_OK;
     });
 }
@@ -97,7 +87,7 @@ int tb_upscale(tb_context* c, const tb_post_settings* post, uint32_t outputType,
 {
     return guarded(c, [&]() {
         if (!rgbaF32 && !rgba8) return fail(c, TB_E_INVALID, "tb_upscale: both output pointers are null");
-        if (const char* why = sizeRefusal(outW, outH)) return fail(c, TB_E_INVALID, std::string("tb_upscale: output: ") + why);
+        if (const char* why = surfaceRefusal(outW, outH)) return fail(c, TB_E_INVALID, std::string("tb_upscale: output: ") + why);
         if (!(tb_abs(sharpnessStops) < tb_u2f(0x7f800000u))) return fail(c, TB_E_INVALID, "tb_upscale: sharpness_stops is not finite");
         if (c->width && (outW < c->width || outH < c->height)) return fail(c, TB_E_INVALID, "tb_upscale: " + std::to_string(outW) + " x " +
             std::to_string(outH) + " is smaller than the rendered " + std::to_string(c->width) + " x " + std::to_string(c->height) + ": FSR 1 only upscales");
@@ -109,27 +99,27 @@ int tb_upscale(tb_context* c, const tb_post_settings* post, uint32_t outputType,
         const size_t outPx = (size_t)outW * outH;
         const bool run[2] = {rgba8 != nullptr, rgbaF32 != nullptr}; /* by surface type: TB_FSR_SURFACE_UNORM8, TB_FSR_SURFACE_F32 */
         const void* const src[2] = {c->postRgba8.p, c->postOut.p};
-        for (uint32_t t = 0; t < 2u; t++) if (run[t]) { ensure(c->fsrMid[t], outPx * texelBytes(t)); ensure(c->fsrOut[t], outPx * texelBytes(t)); }
+        for (uint32_t t = 0; t < 2u; t++) if (run[t]) { ensure(c->fsr.mid[t], outPx * texelBytes(t)); ensure(c->fsr.out[t], outPx * texelBytes(t)); }
         for (uint32_t t = 0; t < 2u; t++) {
             if (!run[t]) continue;
-            HIP_TRY(hipEventRecord(c->evFsr[2 * t].create(), c->stream));
-            HIP_TRY(fsr_launch_easu(c->stream, t, k.easu, inW, inH, outW, outH, src[t], c->fsrMid[t].p));
-            HIP_TRY(hipEventRecord(c->evFsr[2 * t + 1].create(), c->stream));
-            HIP_TRY(fsr_launch_rcas(c->stream, t, k.rcas[0], outW, outH, c->fsrMid[t].p, c->fsrOut[t].p));
-            HIP_TRY(hipEventRecord(c->evFsr[4 + t].create(), c->stream));
+            HIP_TRY(hipEventRecord(c->fsr.ev[2 * t].create(), c->stream));
+            HIP_TRY(fsr_launch_easu(c->stream, t, k.easu, inW, inH, outW, outH, src[t], c->fsr.mid[t].p));
+            HIP_TRY(hipEventRecord(c->fsr.ev[2 * t + 1].create(), c->stream));
+            HIP_TRY(fsr_launch_rcas(c->stream, t, k.rcas[0], outW, outH, c->fsr.mid[t].p, c->fsr.out[t].p));
+            HIP_TRY(hipEventRecord(c->fsr.ev[4 + t].create(), c->stream));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->lastEasuMs = 0.0f; c->lastRcasMs = 0.0f;
+        c->fsr.lastEasuMs = 0.0f; c->fsr.lastRcasMs = 0.0f;
         for (uint32_t t = 0; t < 2u; t++) {
             if (!run[t]) continue;
             float easu = 0.0f, rcas = 0.0f;
-            if (hipEventElapsedTime(&easu, c->evFsr[2 * t], c->evFsr[2 * t + 1]) != hipSuccess) easu = 0.0f;
-            if (hipEventElapsedTime(&rcas, c->evFsr[2 * t + 1], c->evFsr[4 + t]) != hipSuccess) rcas = 0.0f;
-            c->lastEasuMs += easu; c->lastRcasMs += rcas;
+            if (hipEventElapsedTime(&easu, c->fsr.ev[2 * t], c->fsr.ev[2 * t + 1]) != hipSuccess) easu = 0.0f;
+            if (hipEventElapsedTime(&rcas, c->fsr.ev[2 * t + 1], c->fsr.ev[4 + t]) != hipSuccess) rcas = 0.0f;
+            c->fsr.lastEasuMs += easu; c->fsr.lastRcasMs += rcas;
         }
-        c->lastUpscaleMs = c->lastEasuMs + c->lastRcasMs;
-        if (rgba8) HIP_TRY(hipMemcpy(rgba8, c->fsrOut[0].p, outPx * 4, hipMemcpyDeviceToHost));
-        if (rgbaF32) HIP_TRY(hipMemcpy(rgbaF32, c->fsrOut[1].p, outPx * 16, hipMemcpyDeviceToHost));
+        c->fsr.lastUpscaleMs = c->fsr.lastEasuMs + c->fsr.lastRcasMs;
+        if (rgba8) HIP_TRY(hipMemcpy(rgba8, c->fsr.out[0].p, outPx * 4, hipMemcpyDeviceToHost));
+        if (rgbaF32) HIP_TRY(hipMemcpy(rgbaF32, c->fsr.out[1].p, outPx * 16, hipMemcpyDeviceToHost));
         return TB_OK;
     });
 }

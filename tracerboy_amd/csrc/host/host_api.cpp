@@ -1,0 +1,220 @@
+/* host_api.cpp -- the entry points of include/tracerboy_hip.h that need no device: host scenes (tb_host_scene_*), the scene view and digest, image
+ * files, the launch plan as a pure function, frame groups, the host un-permute of gathered tiles.  Includes no HIP header and not the context's
+ * internal header: it compiles with a plain C++ compiler (tests/test_abi.py); what it shares with the context's files is in host_shared.h. */
+#include "host_shared.h"
+#include "launch_plan.h"
+#include "options.h"
+#include "tb_state.h"
+
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+
+using namespace tbhost;
+using namespace tbctx;
+
+void tbctx::fillSceneInfo(const HostScene& s, tb_scene_info* o)
+{
+    memset(o, 0, sizeof *o);
+    o->numTriangles = (uint32_t)s.triGeometry.size(); o->numVertices = (uint32_t)(s.positions.size() / 3); o->numMaterials = (uint32_t)s.materials.size();
+    o->numLights = (uint32_t)s.lights.size(); o->numGeometries = (uint32_t)s.hitGroups.size(); o->numTextures = (uint32_t)s.textureData.size();
+    o->bvhBytesA = (uint32_t)s.bvhA.size(); o->bvhNodesB = (uint32_t)s.nodesB.size(); o->bvhMaxDepth = s.bvhMaxDepth;
+    o->filmWidth = (uint32_t)s.filmWidth; o->filmHeight = (uint32_t)s.filmHeight;
+    memcpy(o->sceneMin, s.sceneMin, 12); memcpy(o->sceneMax, s.sceneMax, 12);
+}
+
+void tbctx::fillView(const HostScene& s, TbSceneView* v)
+{
+    memset(v, 0, sizeof *v);
+    v->bvh = s.bvhA.data(); v->bvhBytes = (uint32_t)s.bvhA.size(); v->numTriangles = (uint32_t)s.triGeometry.size();
+    v->hitGroups = s.hitGroups.data(); v->numHitGroups = (uint32_t)s.hitGroups.size();
+    v->indexBuffer = s.indexBuffer.data(); v->numIndices = (uint32_t)s.indexBuffer.size();
+    v->vertexBuffer = s.vertexBuffer.data(); v->numVertexFloats = (uint32_t)s.vertexBuffer.size();
+    v->materials = s.materials.data(); v->numMaterials = (uint32_t)s.materials.size();
+    v->textureData = s.textureData.empty() ? nullptr : s.textureData.data(); v->numTextureData = (uint32_t)s.textureData.size();
+    v->lights = s.lights.empty() ? nullptr : s.lights.data(); v->numLights = (uint32_t)s.lights.size();
+    v->images = s.images.empty() ? nullptr : s.images.data(); v->numImages = (uint32_t)s.images.size();
+    v->texelPool = s.texelPool.empty() ? nullptr : s.texelPool.data();
+    v->envMap = s.envMap.empty() ? nullptr : s.envMap.data(); v->envWidth = s.envWidth; v->envHeight = s.envHeight;
+    v->blueNoise0 = s.blueNoise0.empty() ? nullptr : s.blueNoise0.data(); v->blueNoise1 = s.blueNoise1.empty() ? nullptr : s.blueNoise1.data();
+    v->config = s.config;
+    if (!s.instances.empty()) { v->tlas = s.tlasA.data(); v->tlasBytes = (uint32_t)s.tlasA.size(); v->numInstances = (uint32_t)s.instances.size(); }
+    v->numBlas = s.blasOffsets.empty() ? 0u : (uint32_t)s.blasOffsets.size() - 1u; v->blasOffsets = s.blasOffsets.empty() ? nullptr : s.blasOffsets.data();
+}
+
+/* The scene digest (include/tb_state.h): every array of the kernel seam, each prefixed by its length.  The camera's lens height, which
+ * tb_set_camera writes into the config constants, is left out: the camera travels with a render state on its own. */
+uint64_t tbctx::sceneDigestOf(const HostScene& s)
+{
+    TbSceneView v; fillView(s, &v);
+    TbStateDigest d{0, 0};
+    tb_state_digest_array(&d, v.bvh, v.bvhBytes);
+    tb_state_digest_array(&d, v.hitGroups, (uint64_t)v.numHitGroups * sizeof(TbHitGroupRecord));
+    tb_state_digest_array(&d, v.indexBuffer, (uint64_t)v.numIndices * 4u);
+    tb_state_digest_array(&d, v.vertexBuffer, (uint64_t)v.numVertexFloats * 4u);
+    tb_state_digest_array(&d, v.materials, (uint64_t)v.numMaterials * sizeof(TbMaterial));
+    tb_state_digest_array(&d, v.textureData, (uint64_t)v.numTextureData * sizeof(TbTextureData));
+    tb_state_digest_array(&d, v.lights, (uint64_t)v.numLights * sizeof(TbLight));
+    tb_state_digest_array(&d, v.images, (uint64_t)v.numImages * sizeof(TbImageDesc));
+    tb_state_digest_array(&d, v.texelPool, (uint64_t)s.texelPool.size() * sizeof(TbFloat4));
+    tb_state_digest_array(&d, v.envMap, (uint64_t)v.envWidth * v.envHeight * sizeof(TbFloat4));
+    TbConfigConstants config = v.config; config.CameraLensHeight = 0.0f;
+    tb_state_digest_array(&d, &config, sizeof config);
+    tb_state_digest_array(&d, v.tlas, v.tlasBytes);
+    tb_state_digest_array(&d, v.blasOffsets, v.blasOffsets ? ((uint64_t)v.numBlas + 1u) * 4u : 0u);
+    return d.sum;
+}
+
+extern "C" {
+
+static bool hasSuffix(const char* path, const char* suf) { size_t n = strlen(path), m = strlen(suf); return n >= m && strcmp(path + n - m, suf) == 0; }
+int tb_write_image_rgba8(const char* path, uint32_t W, uint32_t H, const uint8_t* rgba8)
+{
+    if (!path || !rgba8 || !W || !H) return TB_E_INVALID;
+    if (!hasSuffix(path, ".png")) return TB_E_UNSUPPORTED;
+    std::string err;
+    return tbhost::WritePngRGBA8(path, W, H, rgba8, err) ? TB_OK : TB_E_IO;
+}
+int tb_write_image_f32(const char* path, uint32_t W, uint32_t H, const float* rgba)
+{
+    if (!path || !rgba || !W || !H) return TB_E_INVALID;
+    std::string err;
+    if (hasSuffix(path, ".exr")) return tbhost::WriteExrRGBA(path, W, H, rgba, err) ? TB_OK : TB_E_IO;
+    if (!hasSuffix(path, ".pfm")) return TB_E_UNSUPPORTED;
+    return tbhost::WritePfmRGB(path, W, H, rgba, err) ? TB_OK : TB_E_IO;
+}
+
+int tb_decode_image(const char* path, uint32_t* W, uint32_t* H, int* normalized, int* hasAlpha, float* rgba)
+{
+    if (!path || !W || !H) return TB_E_INVALID;
+    try {
+        std::vector<TbFloat4> texels; bool norm = false, alpha = false; std::string err;
+        if (!tbhost::LoadImageRGBA32F(path, texels, *W, *H, norm, err, &alpha)) { g_createError = err; return TB_E_IO; }
+        if (normalized) *normalized = norm; if (hasAlpha) *hasAlpha = alpha;
+        if (rgba) memcpy(rgba, texels.data(), texels.size() * sizeof(TbFloat4));
+        return TB_OK;
+    } catch (const std::exception& e) { g_createError = e.what(); return TB_E_IO; }
+}
+
+void tb_plan_defaults(tb_plan_input* in)
+{
+    if (!in) return;
+    memset(in, 0, sizeof *in);
+    in->high_occupancy = OptionDefault(OPT_high_occupancy); in->stack_overflow_max = OptionDefault(OPT_stack_overflow_max);
+    in->primary_prepass = OptionDefault(OPT_primary_prepass); in->overlap_launches = OptionDefault(OPT_overlap_launches);
+    in->pooled_samples = OptionDefault(OPT_pooled_samples); in->costly_first = (uint32_t)OptionDefault(OPT_costly_first);
+    in->split_trav = OptionDefault(OPT_split_trav); in->guided_groups = OptionDefault(OPT_guided_groups);
+}
+
+uint32_t tb_frame_groups(uint32_t frames, uint32_t frameGroup, uint32_t guided, uint32_t group, uint32_t* firstFrame, uint32_t* numFrames)
+{
+    uint32_t lg = 0; while ((2u << lg) <= frameGroup) lg++;
+    const uint32_t total = tb_fg_groups(frames, lg, guided ? 1u : 0u, 0xffffffffu, nullptr, nullptr);
+    if (group < total) { uint32_t f0 = 0, l = 0; (void)tb_fg_groups(frames, lg, guided ? 1u : 0u, group, &f0, &l);
+        if (firstFrame) *firstFrame = f0; if (numFrames) *numFrames = std::min(1u << l, frames - std::min(frames, f0)); }
+    return total;
+}
+
+int tb_plan_launch(const tb_plan_input* in, tb_launch_plan* out)
+{
+    if (!in || !out || !in->width || !in->height) return TB_E_INVALID;
+    PlanLaunch(*in, *out);
+    return TB_OK;
+}
+
+int tb_unpack_gathered_host(uint32_t W, uint32_t H, uint32_t world, uint32_t tw, uint32_t th, const float* const* perRank, float* full)
+{
+    if (!perRank || !full || world == 0 || tw == 0 || th == 0) return TB_E_INVALID;
+    uint32_t tilesX = (W + tw - 1) / tw, tilesY = (H + th - 1) / th;
+    for (uint32_t t = 0; t < tilesX * tilesY; t++) {
+        uint32_t rank = t % world, local = t / world;
+        const float* src = perRank[rank] + (size_t)local * tw * th * 4;
+        uint32_t x0 = (t % tilesX) * tw, y0 = (t / tilesX) * th;
+        uint32_t w = (W - x0 < tw) ? W - x0 : tw, h = (H - y0 < th) ? H - y0 : th;
+        for (uint32_t y = 0; y < h; y++) memcpy(full + ((size_t)(y0 + y) * W + x0) * 4, src + (size_t)y * w * 4, (size_t)w * 16);
+    }
+    return TB_OK;
+}
+
+/* ---- host-only scene API ---------------------------------------------------------------------- */
+struct tb_host_scene { HostScene scene; };
+
+static int hostFail(char* err, uint32_t n, int code, const std::string& m) { if (err && n) { strncpy(err, m.c_str(), n - 1); err[n - 1] = 0; } return code; }
+
+/* bvh_builder of the host-scene entry points: builder | (reinsertion passes + 1) << 8 | reinsertion share (percent) << 16 | presplit (percent, <= 127) << 24; a zero field =
+ * the library's own choice (options "reinsertion_passes" / "reinsertion_share" of a context) */
+static void applyBuilderWord(HostScene& s, int word)
+{
+    const int passes = (word >> 8) & 0xff, share = (word >> 16) & 0xff, presplit = (word >> 24) & 0x7f;
+    if (passes) s.reinsertionPasses = passes - 1;
+    if (share) s.reinsertionShare = share;
+    if (presplit) s.presplitPercent = presplit;
+}
+
+int tb_host_scene_load(const char* path, int builder, int loadFlags, tb_host_scene** out, char* err, uint32_t errLen)
+{
+    if (!path || !out) return TB_E_INVALID;
+    *out = nullptr;
+    try {
+        std::shared_ptr<PbrtScene> ps = importScene(path);
+        tb_host_scene* h = new tb_host_scene();
+        ConvertOptions co; co.flattenInstances = (loadFlags & 1) != 0; co.flipTextureUVs = (loadFlags & 2) == 0;
+        try { ConvertScene(*ps, h->scene, co); applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builder & 0xff); } catch (...) { delete h; throw; }
+        *out = h; return TB_OK;
+    } catch (const std::exception& e) {
+        std::string m = e.what();
+        int code = (m.find("open") != std::string::npos || m.find("Couldn't") != std::string::npos) ? TB_E_IO : TB_E_PARSE;
+        if (m.find("not supported") != std::string::npos || m.find("unsupported") != std::string::npos) code = TB_E_UNSUPPORTED;
+        return hostFail(err, errLen, code, m);
+    }
+}
+
+int tb_host_scene_procedural(int kind, uint32_t tris, uint32_t seed, int builder, tb_host_scene** out, char* err, uint32_t errLen)
+{
+    if (!out) return TB_E_INVALID;
+    *out = nullptr;
+    try {
+        tb_host_scene* h = new tb_host_scene();
+        try { MakeProceduralScene(h->scene, kind, tris, seed); applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builder & 0xff); } catch (...) { delete h; throw; }
+        *out = h; return TB_OK;
+    } catch (const std::exception& e) { return hostFail(err, errLen, TB_E_INVALID, e.what()); }
+}
+
+void tb_host_scene_free(tb_host_scene* s) { delete s; }
+
+int tb_host_scene_view_get(tb_host_scene* s, TbSceneView* v) { if (!s || !v) return TB_E_INVALID; fillView(s->scene, v); return TB_OK; }
+int tb_host_scene_digest(tb_host_scene* s, uint64_t* out) { if (!s || !out) return TB_E_INVALID; *out = sceneDigestOf(s->scene); return TB_OK; }
+int tb_host_scene_camera(tb_host_scene* s, tb_camera* cam) { if (!s || !cam) return TB_E_INVALID; *cam = s->scene.camera; return TB_OK; }
+int tb_host_scene_info(tb_host_scene* h, tb_scene_info* o)
+{
+    if (!h || !o) return TB_E_INVALID;
+    fillSceneInfo(h->scene, o);
+    return TB_OK;
+}
+int tb_host_scene_frame_constants(tb_host_scene* h, const tb_output_settings* settings, uint32_t frame, float t, TbPerFrameConstants* out)
+{
+    if (!h || !out) return TB_E_INVALID;
+    tb_output_settings s; if (settings) s = *settings; else DefaultOutputSettings(s);
+    MakeFrameConstants(h->scene, h->scene.camera, s, frame, t, 0xffffffffu, 0xffffffffu, *out);
+    return TB_OK;
+}
+int tb_host_scene_layout_b(tb_host_scene* h, const TbNodeB** nodes, uint32_t* nn, const TbTriB** tris, uint32_t* nt, uint32_t* root)
+{
+    if (!h) return TB_E_INVALID;
+    if (nodes) *nodes = h->scene.nodesB.data(); if (nn) *nn = (uint32_t)h->scene.nodesB.size();
+    if (tris) *tris = h->scene.trisB.data(); if (nt) *nt = (uint32_t)h->scene.trisB.size();
+    if (root) *root = h->scene.rootRefB;
+    return TB_OK;
+}
+int tb_host_scene_triangles(tb_host_scene* h, const float** pos, uint32_t* nv, const uint32_t** tvi, const uint32_t** tg, const uint32_t** tp,
+    const uint32_t** tf, uint32_t* nt)
+{
+    if (!h) return TB_E_INVALID;
+    const HostScene& s = h->scene;
+    if (pos) *pos = s.positions.data(); if (nv) *nv = (uint32_t)(s.positions.size() / 3);
+    if (tvi) *tvi = s.triVertexIndex.data(); if (tg) *tg = s.triGeometry.data(); if (tp) *tp = s.triPrimitive.data(); if (tf) *tf = s.triFlags.data();
+    if (nt) *nt = (uint32_t)s.triGeometry.size();
+    return TB_OK;
+}
+
+} // extern "C"

@@ -130,8 +130,8 @@ void adopt(tb_context* x, uint32_t W, uint32_t H, const tb_output_settings& s, f
     if (opt<OPT_count_rays>(x) || opt<OPT_debug_profile_groups>(x)) ensure(x->rayStats, 21 * 8);
     if (x->rayStats.p) HIP_TRY(hipMemsetAsync(x->rayStats.p, 0, x->rayStats.bytes, x->stream));
     x->width = W; x->height = H; x->lastSettings = s; x->haveLastSettings = true; x->lastTime = timeSeed;
-    x->firstFrame = first; x->samplesRendered = next; x->lastRenderRealtime = false;
-    touchAccumulation(x); x->aovStaleUntilCall = x->callCount + 1; /* the state's frames come without AOVs (context_denoise.cpp) */
+    x->firstFrame = first; x->samplesRendered = next; x->rt.lastRender = false;
+    touchAccumulation(x); x->dn.aovStaleUntilCall = x->callCount + 1; /* the state's frames come without AOVs (context_denoise.cpp) */
 }
 
 /* a group deals 64x64 tiles round-robin (renderGroup): with the map in place already the group's first render keeps the frames */
@@ -226,7 +226,7 @@ int tb_state_save(tb_context* c, const char* path)
     TB_REFUSE_PEER(c);
     return guarded(c, [&]() {
         if (!path) return fail(c, TB_E_INVALID, "tb_state_save: null path");
-        if (c->lastRenderRealtime) return fail(c, TB_E_INVALID, "tb_state_save: the last render was tb_render_realtime: its surface holds one frame, not an accumulation");
+        if (c->rt.lastRender) return fail(c, TB_E_INVALID, "tb_state_save: the last render was tb_render_realtime: its surface holds one frame, not an accumulation");
         if (!c->output.p || !c->width || !c->haveLastSettings || c->samplesRendered == c->firstFrame) return fail(c, TB_E_INVALID,
             "tb_state_save: nothing rendered: the context holds no frames");
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -234,7 +234,7 @@ int tb_state_save(tb_context* c, const char* path)
         tb_state_info h; memset(&h, 0, sizeof h);
         h.version = TB_STATE_VERSION; h.width = c->width; h.height = c->height; h.first_frame = c->firstFrame; h.next_frame = c->samplesRendered;
         h.time_seed = c->lastTime; h.settings = c->lastSettings; h.camera = c->camera;
-        const TbTileMap tiles = c->peers.empty() ? c->tiles : TbTileMap{0, 1, 64, 64}; /* a group's context holds the assembled frame */
+        const TbTileMap tiles = c->group.peers.empty() ? c->tiles : TbTileMap{0, 1, 64, 64}; /* a group's context holds the assembled frame */
         h.tile_rank = tiles.rank; h.tile_world = tiles.world; h.tile_w = tiles.tileW; h.tile_h = tiles.tileH;
         h.alpha_test = opt<OPT_alpha_test>(c) ? 1u : 0u; h.adaptive = opt<OPT_adaptive>(c) ? 1u : 0u; h.adaptive_test = (uint32_t)opt<OPT_adaptive_test>(c);
         h.adaptive_min_frames = opt<OPT_adaptive_min_frames>(c);
@@ -267,11 +267,11 @@ int tb_state_load(tb_context* c, const char* path, uint32_t flags)
         if (rc != TB_OK) return fail(c, rc, "tb_state_load: " + m);
         if (!(flags & TB_STATE_ANY_SCENE) && h.scene_digest != sceneDigestCached(c)) return fail(c, TB_E_INVALID,
             "tb_state_load: scene_digest: the state was rendered of another scene (other file, BVH builder or material edit; TB_STATE_ANY_SCENE overrides)");
-        const bool ctxComplete = !c->peers.empty() || c->tiles.world == 1, fileComplete = h.tile_world == 1;
-        const bool sameAssignment = c->peers.empty() && sameTiles(c->tiles, h);
+        const bool ctxComplete = !c->group.peers.empty() || c->tiles.world == 1, fileComplete = h.tile_world == 1;
+        const bool sameAssignment = c->group.peers.empty() && sameTiles(c->tiles, h);
         if (add) {
             if (!c->output.p || !c->width || !c->haveLastSettings) return fail(c, TB_E_INVALID, "tb_state_load: TB_STATE_ADD needs a context that holds a state");
-            if (c->lastRenderRealtime) return fail(c, TB_E_INVALID, "tb_state_load: TB_STATE_ADD after tb_render_realtime: the surface holds no accumulation");
+            if (c->rt.lastRender) return fail(c, TB_E_INVALID, "tb_state_load: TB_STATE_ADD after tb_render_realtime: the surface holds no accumulation");
             if (h.width != c->width || h.height != c->height) return fail(c, TB_E_INVALID, "tb_state_load: width / height differ from the context's");
             if (historyRelevantChange(h.settings, c->lastSettings)) return fail(c, TB_E_INVALID, "tb_state_load: settings differ from the context's in a history-relevant member");
             if (!sameBits(&h.time_seed, &c->lastTime, 4)) return fail(c, TB_E_INVALID, "tb_state_load: time_seed differs from the context's");
@@ -312,7 +312,7 @@ int tb_state_load(tb_context* c, const char* path, uint32_t flags)
             if (dev[0] != h.output_digest || dev[1] != h.jittered_digest) { if (!add) forget(); return fail(c, TB_E_DEVICE,
                 "tb_state_load: output_digest / jittered_digest: the uploaded surfaces do not have the file's digests on device " + std::to_string(x->device)); }
             if (add) {
-                touchAccumulation(x); x->aovStaleUntilCall = x->callCount + 1;
+                touchAccumulation(x); x->dn.aovStaleUntilCall = x->callCount + 1;
                 if (x->samplesRendered == x->firstFrame) { /* an empty range: whatever an earlier history left in the surfaces does not count */
                     HIP_TRY(hipMemsetAsync(x->output.p, 0, bytes, x->stream)); HIP_TRY(hipMemsetAsync(x->jittered.p, 0, bytes, x->stream)); }
                 HIP_TRY(hipEventRecord(x->evState[0].create(), x->stream));
