@@ -505,6 +505,13 @@ int tb_host_scene_digest(tb_host_scene* s, uint64_t* out);                /* wha
 int tb_host_scene_frame_constants(tb_host_scene* s, const tb_output_settings* settings, uint32_t frame, float time_seed, TbPerFrameConstants* out);
 /* layout-B arrays (what the kernels fetch) and the per-triangle builder inputs */
 int tb_host_scene_layout_b(tb_host_scene* s, const TbNodeB** nodes, uint32_t* num_nodes, const TbTriB** tris, uint32_t* num_tris, uint32_t* root_ref);
+/* The LDS image of the walk as a context uploads it for a scene that is LDS-resident (the same pure function builds both): node records
+ * node_stride bytes apart from off_nodes, tri_copies axis-permuted copies of every layout-B triangle from off_tris (copy = kz * 2 + (d[kz] < 0)).
+ * Child refs are offsets in 16-B units -- an inner ref from off_nodes, a leaf ref (leaf flag in the sign bit) from off_tris to the triangle's
+ * first copy; root_ref is 0 or LEAF | 0.  stack_depth: entries per lane of the traversal stack, one more than a walk can hold.  out = null: sizes only
+ * (off_nodes / off_tris are filled with the image). */
+typedef struct tb_lds_image_info { uint32_t bytes, off_nodes, off_tris, num_nodes, num_tris, node_stride, tri_copies, root_ref, stack_depth; } tb_lds_image_info;
+int tb_host_scene_lds_image(tb_host_scene* s, uint8_t* out, uint32_t capacity, tb_lds_image_info* info);
 /* Diagnostic: the build's own parse of a PBRT file in the record format of oracle/ref_dump.cpp. */
 int tb_host_pbrt_dump(const char* pbrt_path, const char* out_path, char* err, uint32_t err_len);
 int tb_host_scene_triangles(tb_host_scene* s, const float** positions, uint32_t* num_vertices, const uint32_t** tri_vertex_index,

@@ -172,6 +172,11 @@ class tb_scene_info(C.Structure):
                 ("sceneMin", C.c_float * 3), ("sceneMax", C.c_float * 3)]
 
 
+class tb_lds_image_info(C.Structure):
+    """include/tracerboy_hip.h tb_lds_image_info: the sections of the walk's LDS image (tb_host_scene_lds_image)."""
+    _fields_ = [(n, C.c_uint32) for n in ("bytes", "off_nodes", "off_tris", "num_nodes", "num_tris", "node_stride", "tri_copies", "root_ref", "stack_depth")]
+
+
 class tb_state_info(C.Structure):
     """include/tracerboy_hip.h tb_state_info: the header of a render-state file."""
     _fields_ = [("version", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("first_frame", C.c_uint32), ("next_frame", C.c_uint32),

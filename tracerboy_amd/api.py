@@ -127,6 +127,7 @@ def lib():
         "tb_host_scene_info": (C.c_int, [vp, P(abi.tb_scene_info)]),
         "tb_host_scene_frame_constants": (C.c_int, [vp, P(abi.tb_output_settings), C.c_uint32, C.c_float, P(abi.TbPerFrameConstants)]),
         "tb_host_scene_layout_b": (C.c_int, [vp, P(P(abi.TbNodeB)), P(C.c_uint32), P(P(abi.TbTriB)), P(C.c_uint32), P(C.c_uint32)]),
+        "tb_host_scene_lds_image": (C.c_int, [vp, P(C.c_uint8), C.c_uint32, P(abi.tb_lds_image_info)]),
         "tb_host_scene_triangles": (C.c_int, [vp, P(P(C.c_float)), P(C.c_uint32), P(P(C.c_uint32)), P(P(C.c_uint32)), P(P(C.c_uint32)), P(P(C.c_uint32)), P(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
@@ -349,6 +350,18 @@ class HostScene:
         nb = np.frombuffer(C.string_at(nodes, nn.value * 64), dtype=np.uint32).reshape(nn.value, 16).copy()
         tb = np.frombuffer(C.string_at(tris, nt.value * 48), dtype=np.uint32).reshape(nt.value, 12).copy()
         return nb, tb, root.value
+
+    def lds_image(self):
+        """(image bytes as uint8, tb_lds_image_info): the walk's LDS image as a context uploads it for an LDS-resident scene."""
+        info = abi.tb_lds_image_info()
+        rc = lib().tb_host_scene_lds_image(self._h, None, 0, C.byref(info))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_lds_image")
+        buf = np.zeros(info.bytes, dtype=np.uint8)
+        rc = lib().tb_host_scene_lds_image(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), info.bytes, C.byref(info))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_lds_image")
+        return buf, info
 
 
 class TracerBoy:

@@ -1,6 +1,7 @@
 /* context_scene.cpp -- the device half of LoadScene (the reference's TracerBoy.cpp:1065-2161): BVH builds on the GPU, storage
  * order of the nodes, the compact node layout, uploads in the kernels' 16-B aligned device forms, the whole-scene-in-LDS image. */
 #include "context_internal.h"
+#include "lds_image.h"
 
 namespace tbctx {
 
@@ -331,49 +332,23 @@ void finalizeScene(tb_context* c, bool build)
     d.envMap = upload(c, s.envMap); d.envWidth = s.envWidth; d.envHeight = s.envHeight;
     d.blueNoise0 = upload(c, s.blueNoise0); d.blueNoise1 = upload(c, s.blueNoise1);
     d.config = s.config;
-    /* a root-to-leaf path of bvhMaxDepth nodes has bvhMaxDepth - 1 inner nodes, each of which parks at most one far child: the
-     * walk never holds more than bvhMaxDepth - 1 entries (one spare) */
-    d.stackDepth = s.bvhMaxDepth < 2 ? 2 : s.bvhMaxDepth;
+    d.stackDepth = WalkStackDepth(s.bvhMaxDepth);
     d.alphaTest = opt<OPT_alpha_test>(c) ? 1u : 0u;
     d.textureUse = sceneTextureUse(c);
-    /* LDS image of the walk: nodes and permuted triangles (pt_scene.h) */
+    /* LDS image of the walk: nodes and permuted triangles (lds_image.h) */
     {
-        std::vector<uint8_t> blob;
-        auto put = [&](const void* p, size_t bytes) { while (blob.size() % 16) blob.push_back(0); uint32_t off = (uint32_t)blob.size();
-            const uint8_t* b = (const uint8_t*)p; blob.insert(blob.end(), b, b + bytes); return off; };
-        auto ldsRef = [](uint32_t ref) { return (ref & TB_BVH_LEAF_FLAG) ? (TB_BVH_LEAF_FLAG | ((ref & ~TB_BVH_LEAF_FLAG) * 3u * TB_LDS_TRI_COPIES)) : ref *
-            (TB_LDS_NODE_STRIDE / 16); };
-        {   /* nodes TB_LDS_NODE_STRIDE apart (pt_scene.h) */
-            std::vector<uint8_t> padded(s.nodesB.size() * TB_LDS_NODE_STRIDE, 0);
-            for (size_t i = 0; i < s.nodesB.size(); i++) {
-                TbNodeB nd = s.nodesB[i]; nd.left = ldsRef(nd.left); nd.right = ldsRef(nd.right);
-                memcpy(padded.data() + i * TB_LDS_NODE_STRIDE, &nd, sizeof nd);
-            }
-            d.offNodes = put(padded.data(), padded.size());
-        }
-        {   /* six axis-permuted copies per triangle (pt_scene.h): copy = kz * 2 + swapped, (kx, ky) = the two axes after kz, swapped when d[kz] < 0 */
-            std::vector<TbTriB> perm(s.trisB.size() * TB_LDS_TRI_COPIES);
-            for (size_t i = 0; i < s.trisB.size(); i++)
-                for (int kz = 0; kz < 3; kz++)
-                    for (int sw = 0; sw < 2; sw++) {
-                        int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-                        if (sw) std::swap(kx, ky);
-                        const TbTriB& t = s.trisB[i]; TbTriB q = t;
-                        const float* src[3] = {t.v0, t.v1, t.v2}; float* dst[3] = {q.v0, q.v1, q.v2};
-                        for (int v = 0; v < 3; v++) { dst[v][0] = src[v][kx]; dst[v][1] = src[v][ky]; dst[v][2] = src[v][kz]; }
-                        perm[i * TB_LDS_TRI_COPIES + (size_t)(kz * 2 + sw)] = q;
-                    }
-            d.offTris = put(perm.data(), perm.size() * sizeof(TbTriB));
-        }
-        while (blob.size() % 16) blob.push_back(0);
         /* the shading records stay in memory (pt_scene.h); the budget still counts them, so that which scenes are LDS-resident is as before */
         auto r16 = [](size_t b) { return (b + 15) / 16 * 16; };
         const size_t shadingBytes = r16(devHit.size() * sizeof(TbDevHitGroup)) + r16(s.indexBuffer.size() * 4) + r16(s.vertexBuffer.size() * 4) +
             r16(devMat.size() * sizeof(TbDevMaterial)) + r16(devLight.size() * sizeof(TbDevLight));
         size_t budget = (size_t)opt<OPT_lds_scene_budget>(c);
-        c->sceneInLds = blob.size() + shadingBytes + (size_t)d.stackDepth * 256 * 4 <= budget && opt<OPT_scene_in_lds>(c) != 0 && !twoLevel;
-        if (c->sceneInLds) { d.ldsBlob = upload(c, blob); d.ldsBlobBytes = (uint32_t)blob.size(); }
-        else { d.ldsBlob = nullptr; d.ldsBlobBytes = 0; }
+        c->sceneInLds = LdsImageBytes(s.nodesB.size(), s.trisB.size()) + shadingBytes + (size_t)d.stackDepth * 256 * 4 <= budget &&
+            opt<OPT_scene_in_lds>(c) != 0 && !twoLevel;
+        d.ldsBlob = nullptr; d.ldsBlobBytes = 0; d.offNodes = d.offTris = 0;
+        if (c->sceneInLds) {   /* (built only for the scenes that use it: six copies of every triangle of a large scene are gigabytes) */
+            const LdsImage image = BuildLdsImage(s.nodesB.data(), s.nodesB.size(), s.trisB.data(), s.trisB.size());
+            d.ldsBlob = upload(c, image.bytes); d.ldsBlobBytes = (uint32_t)image.bytes.size(); d.offNodes = image.offNodes; d.offTris = image.offTris;
+        }
         /* measured on MI355X: LDS-resident scenes are nearly insensitive (at five waves per SIMD 1-2 is best: 6 745 / 6 730 against
          * 6 680 at 4, 6 230 at 12), scenes fetched through the caches gain ~5 % from a late switch to the leaf phase (16-24) */
         const int64_t* parkMin = c->options.ifSet<OPT_park_min>();

@@ -3,6 +3,7 @@
  * internal header: it compiles with a plain C++ compiler (tests/test_abi.py); what it shares with the context's files is in host_shared.h. */
 #include "host_shared.h"
 #include "launch_plan.h"
+#include "lds_image.h"
 #include "options.h"
 #include "tb_state.h"
 
@@ -204,6 +205,23 @@ int tb_host_scene_layout_b(tb_host_scene* h, const TbNodeB** nodes, uint32_t* nn
     if (nodes) *nodes = h->scene.nodesB.data(); if (nn) *nn = (uint32_t)h->scene.nodesB.size();
     if (tris) *tris = h->scene.trisB.data(); if (nt) *nt = (uint32_t)h->scene.trisB.size();
     if (root) *root = h->scene.rootRefB;
+    return TB_OK;
+}
+int tb_host_scene_lds_image(tb_host_scene* h, uint8_t* out, uint32_t capacity, tb_lds_image_info* info)
+{
+    if (!h || !info) return TB_E_INVALID;
+    const HostScene& s = h->scene;
+    memset(info, 0, sizeof *info);
+    const size_t bytes = LdsImageBytes(s.nodesB.size(), s.trisB.size());
+    if (bytes > 0x7fffffffull) return TB_E_UNSUPPORTED;
+    info->bytes = (uint32_t)bytes; info->num_nodes = (uint32_t)s.nodesB.size(); info->num_tris = (uint32_t)s.trisB.size();
+    info->node_stride = TB_LDS_NODE_STRIDE; info->tri_copies = TB_LDS_TRI_COPIES; info->root_ref = s.rootRefB;
+    info->stack_depth = WalkStackDepth(s.bvhMaxDepth);
+    if (!out) return TB_OK;
+    if (capacity < bytes) return TB_E_INVALID;
+    const LdsImage im = BuildLdsImage(s.nodesB.data(), s.nodesB.size(), s.trisB.data(), s.trisB.size());
+    info->off_nodes = im.offNodes; info->off_tris = im.offTris;
+    memcpy(out, im.bytes.data(), im.bytes.size());
     return TB_OK;
 }
 int tb_host_scene_triangles(tb_host_scene* h, const float** pos, uint32_t* nv, const uint32_t** tvi, const uint32_t** tg, const uint32_t** tp,

@@ -326,7 +326,33 @@ TBD void walk_owns(tb3& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z));
  * compiled in (it still needs ds.alphaTest at run time); HYBRID: split stack; NODEC: fetch layout-C nodes (ds.nodesC) instead of layout B;
  * PROFILE: the wave-occupancy profile (counting launches only).  One flag per thing a kernel pays for: the first parameter used to stand
  * for "counters or the full feature set", one refactor away from changing who pays for what. */
-template <bool RAY_COUNTERS, bool ALPHA, bool HYBRID = false, bool NODEC = false, bool PROFILE = false, bool OWN_DIR = false>
+/* LDS_STEPS: the walk of a scene in LDS with the whole stack in LDS, without the bookkeeping the general step carries (docs/experiments/r8.md; the
+ * kernel is bound by VALU issue, and 15 of the general inner-node step's 35 VALU instructions are not the box test).  Same visits in the same
+ * order, same arithmetic, same `closest`; what differs is how a step finds its addresses:
+ *   - the kernel has rewritten the child refs of ITS copy of the image on their way into LDS (lds_steps_copy_in below; the image every other kernel
+ *     reads keeps refs in 16-B units, pt_scene.h): an inner ref is the node's LDS address, fetched as it is; a leaf ref is LEAF | the byte offset
+ *     of the triangle's first copy, and one add of a per-ray term (the copy, 2^31 whose carry takes the flag off, where the triangles lie) gives
+ *     the record's address;
+ *   - `stack` is entry 0 of the lane's column and holds DONE, written once per workgroup by the kernel, above it the parked far children; the lane
+ *     keeps the ADDRESS of its top entry.  A push is an add and a write, a pop a read and an add -- no count to compare with zero, no branch, no
+ *     address made from the count: the pop that finds nothing reads DONE.  A walk holds at most stackDepth - 1 entries (host/lds_image.h), so the
+ *     column's stackDepth entries hold them and the sentinel;
+ * (Carrying "is it an inner node" as one value for the parking ballot and the loop's mask removes a v_cmp and adds ten scalar mask instructions
+ * per step: -6 %, docs/experiments/r8_one_predicate.patch.) */
+typedef const __attribute__((address_space(3))) uint8_t* LdsBytes;
+TBD uint32_t lds_address(const void* p) { return (uint32_t)(uintptr_t)(LdsBytes)p; } /* of a pointer into LDS */
+TBD const uint8_t* lds_pointer(uint32_t a) { return (const uint8_t*)(LdsBytes)(uintptr_t)a; }
+/* one 16-B piece of the image on its way into LDS at `image`: piece 3 of a node record holds the two child refs */
+TBD uint4 lds_steps_copy_in(uint4 v, uint32_t piece, const TbDeviceScene& ds, const uint8_t* image)
+{
+    constexpr uint32_t PIECES = TB_LDS_NODE_STRIDE / 16u;
+    if (piece < ds.numNodes * PIECES && piece % PIECES == 3u) {
+        v.x = (v.x & TB_BVH_LEAF_FLAG) ? (v.x << 4 | TB_BVH_LEAF_FLAG) : (v.x << 4) + lds_address(image);
+        v.y = (v.y & TB_BVH_LEAF_FLAG) ? (v.y << 4 | TB_BVH_LEAF_FLAG) : (v.y << 4) + lds_address(image);
+    }
+    return v;
+}
+template <bool RAY_COUNTERS, bool ALPHA, bool HYBRID = false, bool NODEC = false, bool PROFILE = false, bool OWN_DIR = false, bool LDS_STEPS = false>
 TBD bool traverse(const SceneRefs& sc, const TbDeviceScene& ds, tb3 o, tb3 d, Hit& best, uint32_t* stack, uint32_t stride,
                   uint32_t& boxes, uint32_t& tris, WaveProf* prof = nullptr, uint32_t* overflow = nullptr)
 {
@@ -354,6 +380,40 @@ TBD bool traverse(const SceneRefs& sc, const TbDeviceScene& ds, tb3 o, tb3 d, Hi
      * sequence of box and triangle tests is unchanged. */
     constexpr uint32_t DONE = 0xffffffffu; /* has the leaf bit set, so it also leaves the inner loop */
     const int PARK_MIN = (int)ds.parkMin; /* option "park_min", default 8 */
+    if constexpr (LDS_STEPS) {
+        static_assert(!HYBRID && !NODEC, "the LDS steps: whole stack in LDS, layout B");
+        const uint32_t image = lds_address(sc.nodes);
+        const uint32_t leafAdd = (r.permUnits << 4) + (TB_BVH_LEAF_FLAG + image + ds.offTris);
+        const uint32_t* sp = stack; /* the lane's top entry */
+        uint32_t ref = (ds.rootRef & TB_BVH_LEAF_FLAG) ? ds.rootRef : ds.rootRef + image; /* 0 or LEAF | 0 */
+        while (ref != DONE) {
+            while ((int32_t)ref >= 0) {
+                if (PROFILE) prof_hit(prof, PROF_INNER);
+                float lt, rt; bool lh, rh;
+                const TbNodeB n = ((const NodeB16*)lds_pointer(ref))->n;
+                box_test2(lh, rh, lt, rt, best.t, r, n);
+                if (RAY_COUNTERS) boxes += 2;
+                if (lh && rh) {
+                    const bool rightFirst = rt < lt;
+                    sp += stride; *const_cast<uint32_t*>(sp) = rightFirst ? n.left : n.right;
+                    ref = rightFirst ? n.right : n.left;
+                } else if (lh || rh) {
+                    ref = rh ? n.right : n.left;
+                } else {
+                    ref = *sp; sp -= stride;
+                }
+                if (__popcll(__ballot((int32_t)ref >= 0)) < PARK_MIN) break;
+            }
+            if ((int32_t)ref < 0 && ref != DONE) {
+                if (PROFILE) prof_hit(prof, PROF_LEAF);
+                const TbTriB tri = ((const TriB16*)lds_pointer(ref + leafAdd))->t;
+                if (RAY_COUNTERS) tris++;
+                tri_test<ALPHA>(best, MIN_T, o, r, tri, true, sc, ds);
+                ref = *sp; sp -= stride;
+            }
+        }
+        return best.t < MAX_T;
+    }
     uint32_t top = 0;
     uint32_t ref = ds.rootRef;
     auto pop = [&]() -> uint32_t {

@@ -226,11 +226,19 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             bind_next();
         }
     }
+    /* the copies that walk with the LDS steps (traverse(), pt_device.hpp): inner child refs become LDS addresses on their way in, and every lane's
+     * stack column starts with the sentinel those steps pop last */
+#ifdef PT_LDS_WALK
+    constexpr bool LDS_STEPS = SCENE_LDS && !HYBRID && !NODEC && !TWOLEVEL && !(F & FEAT_EXT);
+#else
+    constexpr bool LDS_STEPS = false;
+#endif
     uint32_t* stackBase = (uint32_t*)smem;
     const uint8_t* blob = smem + (size_t)ds.stackDepth * BLOCK * 4;
     if (SCENE_LDS) {
         const uint4* src = (const uint4*)ds.ldsBlob; uint4* dst = (uint4*)(smem + (size_t)ds.stackDepth * BLOCK * 4);
-        for (uint32_t i = threadIdx.x; i < ds.ldsBlobBytes / 16; i += BLOCK) dst[i] = src[i];
+        for (uint32_t i = threadIdx.x; i < ds.ldsBlobBytes / 16; i += BLOCK) dst[i] = LDS_STEPS ? lds_steps_copy_in(src[i], i, ds, blob) : src[i];
+        if (LDS_STEPS) stackBase[threadIdx.x] = 0xffffffffu;
     }
     if (SCENE_LDS || GROUPS) __syncthreads();
     SceneRefs sc;
@@ -477,7 +485,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             if (TWOLEVEL) isHit = traverse_instanced<COUNT, ALPHA, HYBRID>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt, wa.overflow);
             /* two-level scenes */
             else if ((F & FEAT_EXT) && ds.numInstances) isHit = traverse_instanced<true, true>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt);
-            else isHit = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, COUNT, (F & FEAT_SSS) != 0>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt, prof,
+            else isHit = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, COUNT, (F & FEAT_SSS) != 0, LDS_STEPS>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt, prof,
                 wa.overflow);
 #ifdef PT_LDS_STASH
             if (STASH) { const uint32_t* st = stash_at();
@@ -486,7 +494,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
 #endif
 #if TB_EXP_DOUBLE == 2
             { Hit h2; uint32_t nb2 = 0, nt2 = 0; const tb3 o2 = tb3_make(exp_opaque(p.ro.x), exp_opaque(p.ro.y), exp_opaque(p.ro.z));
-              const bool hit2 = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, false, (F & FEAT_SSS) != 0>(sc, ds, o2, p.rd, h2, wa.stack, BLOCK, nb2, nt2, nullptr, wa.overflow);
+              const bool hit2 = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, false, (F & FEAT_SSS) != 0, LDS_STEPS>(sc, ds, o2, p.rd, h2, wa.stack, BLOCK, nb2, nt2, nullptr, wa.overflow);
               if (exp_never(h2.t, h2.u, h2.v, h2.t) && hit2 && h2.prim == 77u) p.flags |= 0x40000000u; }
 #endif
 #if TB_EXP_DOUBLE == 5
@@ -536,7 +544,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
                 const WalkAddr wa = walk_addr();
 #if TB_EXP_DOUBLE == 2
                 { Hit h2; uint32_t nb2 = 0, nt2 = 0; const tb3 o2 = tb3_make(exp_opaque(sro.x), exp_opaque(sro.y), exp_opaque(sro.z));
-                  const bool hit2 = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, false, (F & FEAT_SSS) != 0>(sc, ds, o2, srd, h2, wa.stack, BLOCK, nb2, nt2, nullptr, wa.overflow);
+                  const bool hit2 = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, false, (F & FEAT_SSS) != 0, LDS_STEPS>(sc, ds, o2, srd, h2, wa.stack, BLOCK, nb2, nt2, nullptr, wa.overflow);
                   if (exp_never(h2.t, h2.u, h2.v, h2.t) && hit2 && h2.prim == 77u) p.flags |= 0x40000000u; }
 #endif
 #ifdef PT_LDS_STASH
@@ -549,7 +557,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
                 /* instanced scenes, tuned copies */
                 if (TWOLEVEL) isHit = traverse_instanced<COUNT, ALPHA, HYBRID>(sc, ds, sro, srd, h, wa.stack, BLOCK, nb, nt, wa.overflow);
             else if ((F & FEAT_EXT) && ds.numInstances) isHit = traverse_instanced<true, true>(sc, ds, sro, srd, h, wa.stack, BLOCK, nb, nt);
-                else isHit = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, COUNT, (F & FEAT_SSS) != 0>(sc, ds, sro, srd, h, wa.stack, BLOCK, nb, nt, prof,
+                else isHit = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, COUNT, (F & FEAT_SSS) != 0, LDS_STEPS>(sc, ds, sro, srd, h, wa.stack, BLOCK, nb, nt, prof,
                     wa.overflow);
 #ifdef PT_LDS_STASH
                 if (STASH) { const uint32_t* st = stash_at();
@@ -575,7 +583,7 @@ __global__ __launch_bounds__(BLOCK) PT_PERSISTENT_ATTR void pt_persistent(TbDevi
             /* instanced scenes, tuned copies */
             if (TWOLEVEL) isHit = traverse_instanced<COUNT, ALPHA, HYBRID>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt, wa.overflow);
             else if ((F & FEAT_EXT) && ds.numInstances) isHit = traverse_instanced<true, true>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt);
-            else isHit = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, COUNT, (F & FEAT_SSS) != 0>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt, prof,
+            else isHit = traverse<RAY_COUNTERS, ALPHA, HYBRID, NODEC, COUNT, (F & FEAT_SSS) != 0, LDS_STEPS>(sc, ds, p.ro, p.rd, h, wa.stack, BLOCK, nb, nt, prof,
                 wa.overflow);
 #ifdef PT_LDS_STASH
             if (STASH) { const uint32_t* st = stash_at();

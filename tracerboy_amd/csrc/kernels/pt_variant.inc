@@ -9,6 +9,9 @@
 #define PT_FEATURES PT_FIELD(PT_F_FEATURES, PT_COPY)
 #define PT_NAME PT_COPY
 #define PT_PERSISTENT_ATTR __attribute__((amdgpu_waves_per_eu(PT_FIELD(PT_F_BOUND, PT_COPY))))
+#if PT_FIELD(PT_F_ROLE, PT_COPY) == PT_ROLE_LDS_GROUPS
+#define PT_LDS_WALK 1 /* this copy's kernels -- scenes in LDS, whole stack in LDS, nothing else -- walk with the LDS steps (pt_device.hpp traverse) */
+#endif
 #if PT_FIELD(PT_F_STASH, PT_COPY) > 0
 #define PT_LDS_STASH PT_FIELD(PT_F_STASH, PT_COPY) /* LDS entries per lane behind the stacks (pt_persistent.inc) */
 #endif
