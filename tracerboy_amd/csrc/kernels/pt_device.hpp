@@ -386,32 +386,48 @@ TBD bool traverse(const SceneRefs& sc, const TbDeviceScene& ds, tb3 o, tb3 d, Hi
         const uint32_t leafAdd = (r.permUnits << 4) + (TB_BVH_LEAF_FLAG + image + ds.offTris);
         const uint32_t* sp = stack; /* the lane's top entry */
         uint32_t ref = (ds.rootRef & TB_BVH_LEAF_FLAG) ? ds.rootRef : ds.rootRef + image; /* 0 or LEAF | 0 */
-        while (ref != DONE) {
-            while ((int32_t)ref >= 0) {
-                if (PROFILE) prof_hit(prof, PROF_INNER);
-                float lt, rt; bool lh, rh;
-                const TbNodeB n = ((const NodeB16*)lds_pointer(ref))->n;
-                box_test2(lh, rh, lt, rt, best.t, r, n);
-                if (RAY_COUNTERS) boxes += 2;
-                if (lh && rh) {
-                    const bool rightFirst = rt < lt;
-                    sp += stride; *const_cast<uint32_t*>(sp) = rightFirst ? n.left : n.right;
-                    ref = rightFirst ? n.right : n.left;
-                } else if (lh || rh) {
-                    ref = rh ? n.right : n.left;
-                } else {
-                    ref = *sp; sp -= stride;
-                }
-                if (__popcll(__ballot((int32_t)ref >= 0)) < PARK_MIN) break;
+        /* Both loops leave on wave-uniform conditions, and a lane's own condition only predicates a step (docs/experiments/r9.md).  As a per-lane
+         * `while` around the step with the parking test as a `break` inside it, the inner-node loop carried two "has left" masks per trip: 23
+         * scalar instructions, now 15, and the back edge is s_bcnt1 / s_cmp / s_cbranch_scc; +3.3 % on cornell-box.  Only the interleaving across
+         * lanes changes, as with parking itself.
+         * `busy` is taken BEFORE the leaf step, so a wave leaves on the pass that finds no lane descending and none at a leaf: one idle pass per
+         * walk, for a loop that is tested at its bottom and compares the ref twice per pass, not a third time with DONE (-0.35 % when priced).
+         * Tested at its top or in its middle, the loop carries the hit record through the leaf step as copies: 20 v_mov more per pass. */
+        const int parkMin = PARK_MIN > 1 ? PARK_MIN : 1; /* the inner loop goes on while at least this many descend: never on none */
+        unsigned long long inner = __ballot((int32_t)ref >= 0), busy;
+        do {
+            if (inner != 0ull) {
+                do {
+                    if ((int32_t)ref >= 0) {
+                        if (PROFILE) prof_hit(prof, PROF_INNER);
+                        float lt, rt; bool lh, rh;
+                        const TbNodeB n = ((const NodeB16*)lds_pointer(ref))->n;
+                        box_test2(lh, rh, lt, rt, best.t, r, n);
+                        if (RAY_COUNTERS) boxes += 2;
+                        if (lh && rh) {
+                            const bool rightFirst = rt < lt;
+                            sp += stride; *const_cast<uint32_t*>(sp) = rightFirst ? n.left : n.right;
+                            ref = rightFirst ? n.right : n.left;
+                        } else if (lh || rh) {
+                            ref = rh ? n.right : n.left;
+                        } else {
+                            ref = *sp; sp -= stride;
+                        }
+                    }
+                    inner = __ballot((int32_t)ref >= 0);
+                } while (__popcll(inner) >= parkMin);
             }
-            if ((int32_t)ref < 0 && ref != DONE) {
+            const bool atLeaf = (int32_t)ref < -1; /* has the leaf bit and is not DONE */
+            busy = inner | __ballot(atLeaf);
+            if (atLeaf) {
                 if (PROFILE) prof_hit(prof, PROF_LEAF);
                 const TbTriB tri = ((const TriB16*)lds_pointer(ref + leafAdd))->t;
                 if (RAY_COUNTERS) tris++;
                 tri_test<ALPHA>(best, MIN_T, o, r, tri, true, sc, ds);
                 ref = *sp; sp -= stride;
             }
-        }
+            inner = __ballot((int32_t)ref >= 0);
+        } while (busy != 0ull);
         return best.t < MAX_T;
     }
     uint32_t top = 0;
