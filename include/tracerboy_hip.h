@@ -176,7 +176,7 @@ int tb_render_realtime(tb_context* ctx, uint32_t width, uint32_t height, const t
 int tb_read_realtime(tb_context* ctx, int stage, float* rgba);
 
 /* ---- denoised stills ---------------------------------------------------------
- * The reference denoises a still with OIDN on DirectML (out of scope); here the progressive render's own two surfaces
+ * The reference denoises a still with OIDN on DirectML (the neural section below); here the progressive render's own two surfaces
  * feed the real-time chain's a-trous filter.  The jittered surface holds an independent half of every pixel's samples (RayGenCommon.h:721-727),
  * so the difference of the two halves' mean luminances estimates the variance of the mean's luminance.  The chain, all IEEE fp32:
  *   prepare    (sum rgb / sum w, that variance; 0 where a half is empty or the estimate is not finite)
@@ -484,6 +484,55 @@ int tb_run_fsr_easu(tb_context* ctx, const TbFsrConstants* constants, uint32_t s
 int tb_run_fsr_rcas(tb_context* ctx, const TbFsrConstants* constants, uint32_t surface, uint32_t w, uint32_t h, const void* in, void* out);
 int tb_upscale(tb_context* ctx, const tb_post_settings* post, uint32_t output_type, uint32_t out_w, uint32_t out_h, float sharpness_stops,
                float* rgba_f32_or_null, uint8_t* rgba8_or_null);
+
+/* ---- neural still denoiser -----------------------------------------------------
+ * <-> the reference's TAAUpscaler::OIDN path (TracerBoy.cpp:3306-3322; OpenImageDenoise.cpp:855-1039): the OIDN U-Net -- 16 convolutions of 3 x 3,
+ * four 2 x 2 max-pools on the way down, four nearest upsamples x 2 on the way up, each concatenated in front of the skip tensor of its size, ReLU
+ * after every layer -- on the post-processed LDR picture, the mean albedo and the mean normals (9 input channels) or the picture alone (3).
+ * The library ships no weights: the caller names a TZA file (OIDN's rt_ldr_alb_nrm.tza / rt_ldr.tza, or any file of that graph).
+ * Layer arithmetic, the contract (tests/neural_ref.py restates it in torch): activations and weights are binary16; products are summed in fp32, in
+ * any order; then + bias, then max(., 0) where the layer has ReLU, then one rounding to binary16 (nearest even; overflow gives infinity, NaN is
+ * propagated).  Padding is zero; the max-pool takes the rounded values; the network runs on the picture zero-extended at the right and bottom to
+ * multiples of 16 and its result is cropped.
+ *
+ * tb_nn_weights_info: host only, no context.  Reads the file's tensors `<layer>.weight` (oihw, 3 x 3) and `<layer>.bias` (x) for the layers
+ * enc_conv0, enc_conv1, enc_conv2, enc_conv3, enc_conv4, enc_conv5a, enc_conv5b, dec_conv4a, dec_conv4b, dec_conv3a, dec_conv3b, dec_conv2a,
+ * dec_conv2b, dec_conv1a, dec_conv1b, dec_conv0 (the order of out_channels / in_channels_of); binary32 tensors are rounded to binary16.  Channel
+ * counts are the file's, each 1 ... 256, as long as the graph closes (3 or 9 inputs, 3 outputs).  weight_bytes: the binary16 bytes of all weights
+ * and biases.  TB_E_IO: the file cannot be read.  TB_E_PARSE (err names the tensor and the cause): bad magic or version, anything that runs past
+ * the end of the file, a missing tensor, a wrong layout or kernel size, a graph that does not close.
+ * tb_neural_load: the same read, then the repack for the kernel and the upload; replaces weights loaded before.
+ * tb_run_conv3x3: the layer seam, like tb_run_denoise_pass: host arrays of binary16 bits in unpadded NHWC order, temporary device buffers, no
+ * scene, no loaded weights, nothing the context holds is read or written.  in_a is width x height x c_a -- (width / 2) x (height / 2) x c_a with
+ * upsample_a, read nearest-upsampled -- in_b_or_null width x height x c_b, concatenated behind A; weight_oihw is c_out x (c_a + c_b) x 3 x 3, bias c_out;
+ * out is height x width x c_out, (height / 2) x (width / 2) x c_out with pool.  TB_E_INVALID (the message names the cause): a null required
+ * pointer, a zero size, an odd width or height with pool or upsample_a, more than 512 channels in a tensor, more than 2^24 pixels.
+ * tb_run_neural: the network on host surfaces (width x height RGBA32F, .xyz read; out gets (r, g, b, 1)).  Needs tb_neural_load; albedo and
+ * normal are given exactly when the weights have 9 inputs.  Bit for bit the chain of tb_run_conv3x3 calls on the packed input (channels colour,
+ * albedo, normal).  Reads and writes nothing else the context holds.  At most 2^24 pixels after the extension to multiples of 16.
+ * tb_denoise_neural: the stage. Colour is the float image tb_post_process(post, TB_OUTPUT_TYPE_LIT) writes at the rendered size (option
+ * "post_denoised" included); with 9-input weights albedo is sum.xyz / sum.w of guide surface TB_GUIDE_ALBEDO and the normals are those option
+ * "denoise_guides" = 1 gives the a-trous filter (the mean over the frames that hit, several brought to length 1, zero where nothing was hit), both of
+ * valid guide surfaces (tb_render_guides). The float result goes to rgba_f32_or_null (width * height * 4 floats), its 8-bit conversion as the output
+ * stage does it (clamp, scale, + 0.5, truncate) to rgba8_or_null. Synchronous. Like tb_denoise it writes neither the accumulation surfaces nor AOVs,
+ * frame counter, history, guides or denoised surfaces: tb_accum_digest is the same before and after. Its activation buffers belong to the context
+ * (sized at the first use, kept while the size holds, released by tb_destroy). TB_E_UNSUPPORTED: a tb_create_multi group. TB_E_INVALID: no weights,
+ * nothing rendered, both pointers null, no valid guides with 9-input weights (call tb_render_guides), whatever tb_post_process refuses. The picture
+ * goes in as the output stage wrote it: where that holds a NaN (the default AgX punchy tonemapper gives one for a black pixel) the network spreads it
+ * over its receptive field -- choose another tonemapper for scenes with black pixels. tb_get_option "last_neural_us": GPU microseconds of the last
+ * network, pack to unpack (HIP events); "neural_inputs": 0, 3 or 9. */
+typedef struct tb_nn_info { uint32_t in_channels; uint32_t out_channels[16]; uint32_t in_channels_of[16]; uint64_t weight_bytes; } tb_nn_info;
+typedef struct tb_conv3x3_desc { uint32_t width, height;      /* of the convolution's output before pooling */
+                                 uint32_t c_a, c_b, c_out;    /* channels of source A, source B (0 = none), output */
+                                 uint32_t upsample_a;         /* A is (width/2 x height/2), read nearest-upsampled */
+                                 uint32_t pool, relu; } tb_conv3x3_desc;
+int tb_nn_weights_info(const char* tza_path, tb_nn_info* out, char* err, uint32_t err_len);
+int tb_neural_load(tb_context* ctx, const char* tza_path);
+int tb_run_conv3x3(tb_context* ctx, const tb_conv3x3_desc* d, const uint16_t* in_a, const uint16_t* in_b_or_null,
+                   const uint16_t* weight_oihw, const uint16_t* bias, uint16_t* out);
+int tb_run_neural(tb_context* ctx, uint32_t width, uint32_t height, const float* color_rgba,
+                  const float* albedo_rgba_or_null, const float* normal_rgba_or_null, float* out_rgba);
+int tb_denoise_neural(tb_context* ctx, const tb_post_settings* post, float* rgba_f32_or_null, uint8_t* rgba8_or_null);
 
 /* ---- host-only half of LoadScene (no device needed) ------------------------------------------------
  * The same parse / convert / BVH-build code tb_load_scene runs, exposed separately so that the

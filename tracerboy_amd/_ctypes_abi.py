@@ -160,6 +160,16 @@ TB_FSR_SURFACE_UNORM8 = 0
 TB_FSR_SURFACE_F32 = 1
 
 
+class tb_nn_info(C.Structure):
+    """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
+    _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]
+
+
+class tb_conv3x3_desc(C.Structure):
+    """include/tracerboy_hip.h tb_conv3x3_desc: one layer of the neural denoiser at the layer seam (tb_run_conv3x3)."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "c_a", "c_b", "c_out", "upsample_a", "pool", "relu")]
+
+
 class tb_readback_stats(C.Structure):
     _fields_ = [("ActiveWaves", C.c_uint32), ("ActivePixels", C.c_uint32), ("SelectedPixelDistance", C.c_float), ("SelectedMaterialID", C.c_int32),
                 ("rays", TbRayStats)]

@@ -106,6 +106,11 @@ def lib():
         "tb_run_fsr_easu": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 5 + [vp, vp]),
         "tb_run_fsr_rcas": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 3 + [vp, vp]),
         "tb_upscale": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp]),
+        "tb_nn_weights_info": (C.c_int, [C.c_char_p, P(abi.tb_nn_info), C.c_char_p, C.c_uint32]),
+        "tb_neural_load": (C.c_int, [vp, C.c_char_p]),
+        "tb_run_conv3x3": (C.c_int, [vp, P(abi.tb_conv3x3_desc)] + [vp] * 5),
+        "tb_run_neural": (C.c_int, [vp, C.c_uint32, C.c_uint32] + [vp] * 4),
+        "tb_denoise_neural": (C.c_int, [vp, P(abi.tb_post_settings), vp, vp]),
         "tb_variant_stash_entries": (C.c_int, [C.c_char_p]),
         "tb_frame_groups": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "tb_state_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), C.c_float, C.c_uint32]),
@@ -167,6 +172,21 @@ def FsrConstants(in_width, in_height, out_width, out_height, sharpness=0.2):
     if rc != 0:
         raise TracerBoyError(rc, "tb_fsr_constants: a size is 0 or the sharpness is not finite")
     return k
+
+
+NEURAL_LAYERS = ("enc_conv0", "enc_conv1", "enc_conv2", "enc_conv3", "enc_conv4", "enc_conv5a", "enc_conv5b", "dec_conv4a", "dec_conv4b", "dec_conv3a",
+                 "dec_conv3b", "dec_conv2a", "dec_conv2b", "dec_conv1a", "dec_conv1b", "dec_conv0")
+
+
+def NeuralWeightsInfo(path):
+    """The channel counts of a TZA weights file of the neural still denoiser (tb_nn_weights_info; host only, no device): a tb_nn_info whose
+    out_channels / in_channels_of follow NEURAL_LAYERS.  Raises TracerBoyError with code -3 (unreadable) or -4 (the message names the tensor and
+    the cause)."""
+    info, err = abi.tb_nn_info(), C.create_string_buffer(512)
+    rc = lib().tb_nn_weights_info(os.fsencode(path), C.byref(info), err, 512)
+    if rc != 0:
+        raise TracerBoyError(rc, err.value.decode(errors="replace"))
+    return info
 
 
 def VariantWavesHi(name):
@@ -568,6 +588,44 @@ class TracerBoy:
         f = np.empty((out_height, out_width, 4), np.float32)
         b = np.empty((out_height, out_width, 4), np.uint8) if rgba8 else None
         self._check(self._L.tb_upscale(self._ctx, C.byref(ps), outputType, out_width, out_height, sharpness, _np_ptr(f), _np_ptr(b) if rgba8 else None))
+        return f, b
+
+    def LoadNeuralWeights(self, path):
+        """Read a TZA weights file of the neural still denoiser, repack it for the kernel and upload it (tb_neural_load, DESIGN.md section 15);
+        replaces weights loaded before.  Option "neural_inputs" tells 3 or 9 afterwards."""
+        self._check(self._L.tb_neural_load(self._ctx, os.fsencode(path)))
+
+    def RunConv3x3(self, in_a, weight, bias, in_b=None, upsample_a=False, pool=False, relu=True):
+        """One layer at the layer seam (tb_run_conv3x3): in_a (H, W, c_a) -- (H / 2, W / 2, c_a) with upsample_a -- and in_b (H, W, c_b) or None,
+        weight (c_out, c_a + c_b, 3, 3), bias (c_out,), all float16.  Returns (H, W, c_out) float16, (H / 2, W / 2, c_out) with pool."""
+        a = np.ascontiguousarray(in_a, np.float16); b = None if in_b is None else np.ascontiguousarray(in_b, np.float16)
+        w = np.ascontiguousarray(weight, np.float16); bi = np.ascontiguousarray(bias, np.float16)
+        H, W = (a.shape[0] * 2, a.shape[1] * 2) if upsample_a else a.shape[:2]
+        if b is not None: H, W = b.shape[:2]
+        c_b = 0 if b is None else b.shape[2]
+        assert w.shape == (w.shape[0], a.shape[2] + c_b, 3, 3) and bi.shape == (w.shape[0],), "weight is (c_out, c_a + c_b, 3, 3), bias (c_out,)"
+        d = abi.tb_conv3x3_desc(W, H, a.shape[2], c_b, w.shape[0], int(bool(upsample_a)), int(bool(pool)), int(bool(relu)))
+        out = np.empty((H // 2, W // 2, w.shape[0]) if pool else (H, W, w.shape[0]), np.float16)
+        self._check(self._L.tb_run_conv3x3(self._ctx, C.byref(d), _np_ptr(a), None if b is None else _np_ptr(b), _np_ptr(w), _np_ptr(bi), _np_ptr(out)))
+        return out
+
+    def RunNeural(self, color, albedo=None, normal=None):
+        """The network on host surfaces (tb_run_neural): (H, W, 4) float32 each, .xyz read; albedo and normal exactly when the loaded weights have
+        9 inputs.  Returns (H, W, 4) float32, alpha 1."""
+        f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (color, albedo, normal)]
+        h, w = f[0].shape[:2]
+        assert all(a is None or a.shape == (h, w, 4) for a in f), "surfaces are (H, W, 4)"
+        out = np.empty((h, w, 4), np.float32)
+        self._check(self._L.tb_run_neural(self._ctx, w, h, *[None if a is None else _np_ptr(a) for a in f], _np_ptr(out)))
+        return out
+
+    def DenoiseNeural(self, postSettings=None, rgba8=True):
+        """PostProcess at the rendered size, then the network on that picture and, with 9-input weights, on the albedo and normals of the guide
+        pass (tb_denoise_neural; RenderGuides first).  Returns (float32 HxWx4 picture, uint8 HxWx4 picture or None)."""
+        ps = postSettings if postSettings is not None else GetDefaultPostProcessSettings()
+        f = np.empty((self.height, self.width, 4), np.float32)
+        b = np.empty((self.height, self.width, 4), np.uint8) if rgba8 else None
+        self._check(self._L.tb_denoise_neural(self._ctx, C.byref(ps), _np_ptr(f), _np_ptr(b) if rgba8 else None))
         return f, b
 
     @staticmethod

@@ -6,6 +6,7 @@
  *                 [--save-state f.tbs] [--resume f.tbs] [--add g.tbs]... [--frames A:B] [--checkpoint-every N]
  *                 [--denoise] [--denoise-iterations N] [--denoise-guides K [--denoise-demodulate]]
  *                 [--upscale WxH | --render-scale F] [--fsr-sharpness S]
+ *                 [--denoise-neural FILE.tza [--denoise-guides K]]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -54,7 +55,17 @@
  * --render-scale F (0 < F <= 1; the reference's m_downscaleFactor): renders at max(1, (uint32_t)((float)W * F)) x the same of H -- the truncating
  * `Width *= m_downscaleFactor` of TracerBoy.cpp:2750-2751 -- and upscales to --width x --height.  Not together with --upscale, nor with --resume (the
  * state decides the rendered size).  --fsr-sharpness S: RCAS sharpness in stops, 0 = sharpest, default 0.2 (the reference's); needs one of the two.
- * With --denoise the denoised picture is what is upscaled.  Mistakes in these three are reported before any device call (exit status 2). */
+ * With --denoise the denoised picture is what is upscaled.  Mistakes in these three are reported before any device call (exit status 2).
+ *
+ * --denoise-neural FILE.tza (tb_neural_load / tb_denoise_neural): the finished render is post-processed and denoised by the OIDN
+ * U-Net whose weights FILE.tza holds (OIDN's rt_ldr_alb_nrm.tza or rt_ldr.tza; the tool ships none), and --out is the network's picture: .png its
+ * 8-bit conversion, .pfm / .exr the float LDR picture -- the POST-PROCESSED one, as with --upscale.  A file with 9 inputs also reads the mean albedo
+ * and normals of the guide pass: the first hits of the last min(K, frames held) frames are traced again after the last frame, as --denoise-guides
+ * does it, K = 8 unless --denoise-guides K says otherwise (which here does not imply --denoise); a file with 3 inputs takes no --denoise-guides.
+ * The network reads the float picture as the output stage wrote it, NaN included, and spreads one over its whole receptive field: the tool warns when
+ * the result holds values that are not finite (the default tonemapper gives NaN for a black pixel; --tonemap 0 does not).
+ * Not together with --denoise (and its --denoise-iterations / --denoise-demodulate), --upscale, --render-scale or --ranks N > 1.  Mistakes, an
+ * unreadable or malformed FILE.tza among them, are reported before any device call (exit status 2). */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -152,17 +163,18 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
     float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
     std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
     bool sppSet = false, timeSet = false, denoise = false, demodulate = false; long long denoiseIterations = -1, denoiseGuides = 0;
+    std::string neural; bool denoiseFlag = false; /* --denoise itself, not what --denoise-guides implies */
     uint32_t upW = 0, upH = 0; float renderScale = 0.0f, fsrSharpness = -1.0f; bool upscaleSet = false, renderScaleSet = false, sharpnessSet = false;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
-        if (k == "--denoise") { denoise = true; i--; continue; } /* the flags without a value */
+        if (k == "--denoise") { denoise = true; denoiseFlag = true; i--; continue; } /* the flags without a value */
         if (k == "--denoise-demodulate") { demodulate = true; i--; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[i + 1];
@@ -192,6 +204,7 @@ int main(int argc, char** argv)
             if (end == v || *end || !(renderScale > 0.0f) || !(renderScale <= 1.0f)) { fprintf(stderr, "--render-scale is above 0 and at most 1\n"); return 2; } }
         else if (k == "--fsr-sharpness") { char* end = nullptr; fsrSharpness = strtof(v, &end); sharpnessSet = true;
             if (end == v || *end || !(fsrSharpness >= 0.0f) || !(fsrSharpness < 1e30f)) { fprintf(stderr, "--fsr-sharpness is a finite number of stops, 0 or more\n"); return 2; } }
+        else if (k == "--denoise-neural") neural = v;
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -202,6 +215,18 @@ int main(int argc, char** argv)
     const bool forceRccl = getenv("TB_CLI_FORCE_RCCL") && atoi(getenv("TB_CLI_FORCE_RCCL")) != 0;
     if (ranks < 1) { fprintf(stderr, "--ranks must be at least 1\n"); return 2; }
     if (adaptiveAfter < 0 || adaptiveChunk < 1) { fprintf(stderr, "--adaptive-after must not be negative, --adaptive-chunk must be at least 1\n"); return 2; }
+    if (!neural.empty()) {
+        if (denoiseFlag || denoiseIterations >= 0 || demodulate) { fprintf(stderr,
+            "--denoise-neural does not go with --denoise, --denoise-iterations or --denoise-demodulate: the network stands in place of the a-trous filter\n"); return 2; }
+        if (upscaleSet || renderScaleSet) { fprintf(stderr, "--denoise-neural does not go with --upscale or --render-scale\n"); return 2; }
+        if (ranks > 1) { fprintf(stderr, "--denoise-neural does not go with --ranks: the ranks' guide surfaces are not gathered\n"); return 2; }
+        tb_nn_info nn; char err[512] = "";
+        if (tb_nn_weights_info(neural.c_str(), &nn, err, sizeof err)) { fprintf(stderr, "--denoise-neural %s: %s\n", neural.c_str(), err); return 2; }
+        if (nn.in_channels == 3u && denoiseGuides) { fprintf(stderr, "--denoise-neural %s: its weights have 3 inputs and read no guides: leave --denoise-guides out\n",
+            neural.c_str()); return 2; }
+        if (nn.in_channels == 9u && !denoiseGuides) denoiseGuides = 8;
+        denoise = false; /* --denoise-guides K: the network's guides, not the filter's */
+    }
     const bool states = !saveState.empty() || !resume.empty() || !adds.empty() || frameA >= 0 || checkpointEvery != 0;
     if (states && ranks > 1) { fprintf(stderr,
         "--save-state, --resume, --add, --frames and --checkpoint-every do not go with --ranks: the gather moves the output surface only\n"); return 2; }
@@ -388,7 +413,25 @@ int main(int argc, char** argv)
         printf("denoise: %u a-trous passes, %.3f ms on the GPU\n", dn.WaveletIterations, (double)tb_get_option(ctx, "last_denoise_us") / 1e3);
         if ((png || upW) && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
     }
-    if (upW) { /* the output stage at the rendered size, then FSR 1 to the picture's */
+    if (!neural.empty()) { /* the output stage, then the network; after --save-state: a state is the raw accumulation */
+        if ((rc = tb_neural_load(ctx, neural.c_str()))) return fail(ctx, "tb_neural_load", rc);
+        if (denoiseGuides) { /* the last min(K, frames held) frames of the state's range, traced again */
+            const uint32_t next = tb_samples_rendered(ctx), first = (uint32_t)tb_get_option(ctx, "state_first_frame");
+            const uint32_t k = (uint32_t)std::min<long long>(denoiseGuides, (long long)next - (long long)first);
+            if ((rc = tb_render_guides(ctx, next - k, k))) return fail(ctx, "tb_render_guides", rc);
+            printf("guides: first hits of frames [%u, %u), %.3f ms on the GPU\n", next - k, next, (double)tb_get_option(ctx, "last_guides_us") / 1e3);
+        }
+        std::vector<uint8_t> img(png ? (size_t)W * H * 4 : 0); std::vector<float> imgF((size_t)W * H * 4);
+        if ((rc = tb_denoise_neural(ctx, &post, imgF.data(), png ? img.data() : nullptr))) return fail(ctx, "tb_denoise_neural", rc);
+        printf("neural denoise: %lld input channels, %.3f ms on the GPU\n", (long long)tb_get_option(ctx, "neural_inputs"),
+               (double)tb_get_option(ctx, "last_neural_us") / 1e3);
+        size_t notFinite = 0; /* a NaN of the post-processed picture spreads over the network's whole receptive field */
+        for (float v : imgF) notFinite += !(v - v == 0.0f);
+        if (notFinite) fprintf(stderr, "tracerboy-hip: warning: %zu values of the network's picture are not finite: the post-processed picture held some "
+            "(the AgX tonemappers, 5 and the default 6, give NaN for a black pixel); try --tonemap 0\n", notFinite);
+        if (png) { if ((rc = tb_write_image_rgba8(out.c_str(), W, H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc); }
+        else if ((rc = tb_write_image_f32(out.c_str(), W, H, imgF.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
+    } else if (upW) { /* the output stage at the rendered size, then FSR 1 to the picture's */
         std::vector<uint8_t> img(png ? (size_t)upW * upH * 4 : 0); std::vector<float> imgF(png ? 0 : (size_t)upW * upH * 4);
         if ((rc = tb_upscale(ctx, &post, TB_OUTPUT_TYPE_LIT, upW, upH, fsrSharpness, png ? nullptr : imgF.data(), png ? img.data() : nullptr)))
             return fail(ctx, "tb_upscale", rc);

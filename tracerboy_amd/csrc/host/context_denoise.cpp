@@ -1,7 +1,7 @@
 /* context_denoise.cpp -- the denoise of a progressive render (include/tracerboy_hip.h tb_denoise / tb_read_denoise_stage):
  * prepare (mean + dual-buffer variance of its luminance), prefilter (3x3 Gaussian over the variance), WaveletIterations passes of the real-time
  * chain's a-trous filter guided by the first-hit normals and world positions of the last rendered frame, finish ((rgb, 1) for the output stage).
- * The reference denoises stills with OIDN on DirectML (out of scope); what is kept from it is DenoiserCS itself, run
+ * The reference denoises stills with OIDN on DirectML (context_neural.cpp builds that); what is kept from it is DenoiserCS itself, run
  * unchanged.  Reads the accumulation surfaces and the AOVs, writes surfaces of its own: a render continued afterwards is the uninterrupted one.
  * Option "denoise_guides" (DESIGN.md section 13): the guides come from the guide pass (context_guides.cpp) instead of the last frame's AOVs, and with
  * 2 the chain runs on colour divided by the mean effective albedo and multiplies it back at the end. */

@@ -11,6 +11,7 @@
  *   context_denoise.cpp the denoise of a progressive render: dual-buffer variance + the a-trous filter
  *   context_guides.cpp  the guide pass of that denoise: first hits traced again and summed over frames
  *   context_upscale.cpp FSR 1 upscaling of the post-processed picture: EASU + RCAS
+ *   context_neural.cpp  the neural still denoiser: the OIDN U-Net on the matrix cores, its layer seam and its stage
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -188,6 +189,16 @@ struct tb_context {
     /* FSR 1 upscaling (context_upscale.cpp): per surface type the EASU output and the RCAS output, at the size of the last
      * tb_upscale that ran that chain; events around the passes: [2 t] before EASU, [2 t + 1] between the passes, [4 + t] after RCAS */
     struct Fsr { DevBuf mid[2], out[2]; tbctx::DevEvent ev[6]; float lastUpscaleMs = 0.0f, lastEasuMs = 0.0f, lastRcasMs = 0.0f; } fsr;
+    /* the neural still denoiser (context_neural.cpp).  inputs: 0 = no weights loaded, else enc_conv0's input channels (3 or 9);
+     * in / out: the layers' channel counts; splitA: how many of a layer's input channels come from its first source (all of them, except where a
+     * decoder reads an upsampled tensor in front of a skip tensor); weight / bias: the layers repacked for nn_conv3x3.  Activations, sized at
+     * the first use and kept while the size holds: the packed input, two tensors the layers alternate between, the three pooled skip tensors.
+     * aux, result, rgba8: tb_denoise_neural's resolved albedo and normals, its float picture and its 8-bit one.  lastMs: option last_neural_us */
+    struct Neural {
+        uint32_t inputs = 0, in[16] = {}, out[16] = {}, splitA[16] = {};
+        DevBuf weight[16], bias[16], input, pingPong[2], skip[3], aux[2], result, rgba8;
+        tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+    } nn;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;

@@ -69,6 +69,8 @@ const Query kQueries[] = {
     /* the last tb_upscale: its FSR passes together, its EASU passes, its RCAS passes (HIP events; both chains when both ran) */
     Q("last_upscale_us", microseconds(c->fsr.lastUpscaleMs)) Q("last_easu_us", microseconds(c->fsr.lastEasuMs))
     Q("last_rcas_us", microseconds(c->fsr.lastRcasMs))
+    /* the neural still denoiser: the last network, pack to unpack (HIP events); the input channels of the loaded weights, 0 = none */
+    Q("last_neural_us", microseconds(c->nn.lastMs)) Q("neural_inputs", c->nn.inputs)
     Q("last_guides_us", microseconds(c->guides.lastMs)) /* the last tb_render_guides, its kernel alone (HIP events) */
     Q("last_guides_stack_overflow", c->guides.lastOverflow) /* stack entries per lane the last pass kept in global memory (the HYBRID form) */
     Q("last_copy_waves", c->lastCopyWaves)

@@ -1,0 +1,222 @@
+/* nn_kernels.hip -- the layers of the still denoiser's U-Net (launchers in nn_launch.h):
+ *   nn_conv3x3_kernel        3 x 3 convolution + bias (+ ReLU) as an implicit GEMM on v_mfma_f32_16x16x32_f16; reads up to two source tensors in
+ *                            channel order, the first optionally nearest-upsampled x 2 as it is gathered (upsample and concat cost no pass)
+ *   nn_maxpool2x2_kernel     2 x 2 max-pool, stride 2, on the rounded values
+ *   nn_pack_input_kernel     three RGBA32F surfaces -> the network's zero-extended NHWC binary16 input
+ *   nn_unpack_output_kernel  the 3-channel result -> RGBA32F (r, g, b, 1), cropped
+ *   nn_resolve_aux_kernel    the guide sums -> the albedo and normals the network reads
+ *   nn_to_rgba8_kernel       the output stage's 8-bit store
+ *
+ * The layer arithmetic: binary16 activations and weights, fp32 accumulation (in the matrix core's order), + bias, max(., 0) where the layer has
+ * ReLU, then one rounding to binary16 (nearest even; overflow gives infinity, NaN stays NaN).  Padding is zero.
+ *
+ * The GEMM of one wave: D[output channel][pixel] += W[output channel][k] * X[k][pixel] over k = 32 channels of one tap, for 16 consecutive x of one
+ * output row and NB x 16 output channels.  Lane l holds, as the instruction wants them (cdna_hip_programming section 3: the f16 form uses the bf16 map),
+ *   A (weights)      output channel l & 15, k = 8 (l >> 4) + j, j = 0..7: one 16-byte load of the host's repack (nn_weights.h packLayer)
+ *   B (activations)  k = 8 (l >> 4) + j at pixel l & 15: eight consecutive channels of one pixel, one 16-byte load of an NHWC tensor whose
+ *                    channel count is a multiple of 32
+ *   D                pixel l & 15, output channels 4 (l >> 4) + r, r = 0..3: one 8-byte store.
+ * A k-block lies in source A or in source B, never across (both are padded to 32 channels, and the repack puts zero weights on the padding).
+ * Every activation load is predicated on its tap lying inside the picture; a lane whose pixel is past the row end loads whatever taps are inside
+ * and stores nothing; no lane reads or writes outside a tensor's padded extent. */
+#include "nn_launch.h"
+#include "tb_math.h"
+
+#define NN_THREADS 256u
+#define NN_WAVES (NN_THREADS / 64u)
+
+namespace {
+
+typedef _Float16 nn_half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 nn_half4 __attribute__((ext_vector_type(4)));
+typedef float nn_float4 __attribute__((ext_vector_type(4)));
+
+struct NnConv {
+    const uint16_t* inA; const uint16_t* inB; const uint16_t* weight; const float* bias; uint16_t* out;
+    uint32_t width, height, padA, padB /* padded channels of the sources; padB 0 = no source B */, upsampleA, cOut, outPadded, relu;
+    uint32_t tilesX, units /* tilesX * height * (outPadded / (16 NB)) */;
+};
+
+template <int NB> __global__ __launch_bounds__(NN_THREADS) void nn_conv3x3_kernel(const NnConv p)
+{
+    const uint32_t lane = threadIdx.x & 63u, unit = blockIdx.x * NN_WAVES + (threadIdx.x >> 6); /* a wave's unit: one tile of one row, one group of output channels */
+    if (unit >= p.units) return; /* the whole wave */
+    const uint32_t tile = unit % p.tilesX, rest = unit / p.tilesX, y = rest % p.height, group = rest / p.height;
+    const uint32_t px = lane & 15u, quarter = lane >> 4, x = tile * 16u + px;
+    const uint32_t kBlocksA = p.padA / 32u, kBlocks = kBlocksA + p.padB / 32u, outBlocks = p.outPadded / 16u;
+    const uint32_t widthA = p.upsampleA ? p.width / 2u : p.width;
+    nn_float4 acc[NB];
+    for (int b = 0; b < NB; b++) acc[b] = nn_float4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t tap = 0; tap < 9u; tap++) {
+        const int32_t sx = (int32_t)x + (int32_t)(tap % 3u) - 1, sy = (int32_t)y + (int32_t)(tap / 3u) - 1;
+        /* of the tap, not of the lane's pixel: a lane past the row end may still load (in bounds) */
+        const bool inside = sx >= 0 && sy >= 0 && sx < (int32_t)p.width && sy < (int32_t)p.height;
+        const size_t pixelA = p.upsampleA ? (size_t)((uint32_t)sy >> 1) * widthA + ((uint32_t)sx >> 1) : (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
+        const size_t pixelB = (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
+        for (uint32_t kb = 0; kb < kBlocks; kb++) {
+            nn_half8 act = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (inside) {
+                const uint16_t* src = kb < kBlocksA ? p.inA + pixelA * p.padA + kb * 32u : p.inB + pixelB * p.padB + (kb - kBlocksA) * 32u;
+                act = *(const nn_half8*)(src + quarter * 8u);
+            }
+            const nn_half8* w = (const nn_half8*)p.weight + ((size_t)(tap * kBlocks + kb) * outBlocks + group * (uint32_t)NB) * 64u + lane;
+            for (int b = 0; b < NB; b++) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[b * 64], act, acc[b], 0, 0, 0);
+        }
+    }
+    if (x >= p.width) return;
+    uint16_t* const o = p.out + ((size_t)y * p.width + x) * p.outPadded;
+    for (int b = 0; b < NB; b++) {
+        const uint32_t c0 = (group * (uint32_t)NB + (uint32_t)b) * 16u + quarter * 4u;
+        const nn_float4 bias = *(const nn_float4*)(p.bias + c0);
+        nn_half4 h;
+        for (int r = 0; r < 4; r++) {
+            float v = acc[b][r] + bias[r];
+            if (p.relu) v = v < 0.0f ? 0.0f : v;      /* a NaN stays */
+            h[r] = c0 + (uint32_t)r < p.cOut ? (_Float16)v : (_Float16)0.0f; /* the padded channels hold zeros whatever the sums were */
+        }
+        *(nn_half4*)(o + c0) = h;
+    }
+}
+
+__device__ __forceinline__ _Float16 nn_max(_Float16 a, _Float16 b) { return (a > b || a != a) ? a : b; } /* a NaN on either side wins */
+
+__global__ __launch_bounds__(NN_THREADS) void nn_maxpool2x2_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, uint32_t width, uint32_t channels,
+    uint64_t items /* output pixels * channels / 8 */)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * NN_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const uint32_t groups = channels / 8u, g = (uint32_t)(i % groups), ow = width / 2u;
+    const uint64_t pixel = i / groups; const uint32_t ox = (uint32_t)(pixel % ow); const uint64_t oy = pixel / ow;
+    const uint16_t* s = in + ((oy * 2u) * width + ox * 2u) * channels + g * 8u;
+    const size_t row = (size_t)width * channels;
+    const nn_half8 a = *(const nn_half8*)s, b = *(const nn_half8*)(s + channels), c = *(const nn_half8*)(s + row), d = *(const nn_half8*)(s + row + channels);
+    nn_half8 m;
+    for (int j = 0; j < 8; j++) m[j] = nn_max(nn_max(a[j], b[j]), nn_max(c[j], d[j]));
+    *(nn_half8*)(out + pixel * channels + g * 8u) = m;
+}
+
+/* a lane writes 8 channels of one pixel: group 0 = channels 0-7, group 1 = channel 8 and zeros, groups 2 and 3 zeros */
+__global__ __launch_bounds__(NN_THREADS) void nn_pack_input_kernel(const TbFloat4* __restrict__ color, const TbFloat4* __restrict__ albedo,
+    const TbFloat4* __restrict__ normal, uint16_t* __restrict__ out, uint32_t width, uint32_t height, uint32_t paddedW, uint32_t items)
+{
+    const uint32_t i = blockIdx.x * NN_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const uint32_t g = i & 3u, pixel = i >> 2, x = pixel % paddedW, y = pixel / paddedW;
+    nn_half8 h = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (x < width && y < height && g < 2u) {
+        const size_t s = (size_t)y * width + x;
+        if (g == 0u) {
+            const TbFloat4 c = color[s];
+            h[0] = (_Float16)c.x; h[1] = (_Float16)c.y; h[2] = (_Float16)c.z;
+            if (albedo) { const TbFloat4 a = albedo[s], n = normal[s]; h[3] = (_Float16)a.x; h[4] = (_Float16)a.y; h[5] = (_Float16)a.z; h[6] = (_Float16)n.x; h[7] = (_Float16)n.y; }
+        } else if (albedo) h[0] = (_Float16)normal[s].z;
+    }
+    *(nn_half8*)(out + (size_t)i * 8u) = h;
+}
+
+__global__ __launch_bounds__(NN_THREADS) void nn_unpack_output_kernel(const uint16_t* __restrict__ in, TbFloat4* __restrict__ out, uint32_t width, uint32_t paddedW,
+    uint32_t nPixels)
+{
+    const uint32_t i = blockIdx.x * NN_THREADS + threadIdx.x;
+    if (i >= nPixels) return;
+    const uint32_t x = i % width, y = i / width;
+    const nn_half4 h = *(const nn_half4*)(in + ((size_t)y * paddedW + x) * 32u);
+    out[i] = TbFloat4{(float)h[0], (float)h[1], (float)h[2], 1.0f};
+}
+
+__global__ __launch_bounds__(NN_THREADS) void nn_resolve_aux_kernel(const TbFloat4* __restrict__ gAlbedo, const TbFloat4* __restrict__ gNormal,
+    TbFloat4* __restrict__ albedo, TbFloat4* __restrict__ normal, uint32_t nPixels)
+{
+    const uint32_t i = blockIdx.x * NN_THREADS + threadIdx.x;
+    if (i >= nPixels) return;
+    const TbFloat4 a = gAlbedo[i], n = gNormal[i];
+    albedo[i] = TbFloat4{a.x / a.w, a.y / a.w, a.z / a.w, 1.0f};
+    const float hits = n.w; /* as dn_resolve_guides_kernel (dn_kernels.hip) resolves the filter's normals */
+    TbFloat4 on{0.0f, 0.0f, 0.0f, 1.0f};
+    if (hits > 0.0f) { on.x = n.x / hits; on.y = n.y / hits; on.z = n.z / hits; }
+    if (hits > 1.0f) {
+        const float l = tb_sqrt((on.x * on.x + on.y * on.y) + on.z * on.z);
+        if (l > 0.0f) { on.x = on.x / l; on.y = on.y / l; on.z = on.z / l; } else { on.x = 0.0f; on.y = 0.0f; on.z = 0.0f; }
+    }
+    normal[i] = on;
+}
+
+__global__ __launch_bounds__(NN_THREADS) void nn_to_rgba8_kernel(const TbFloat4* __restrict__ in, uint32_t* __restrict__ out, uint32_t nPixels)
+{
+    const uint32_t i = blockIdx.x * NN_THREADS + threadIdx.x;
+    if (i >= nPixels) return;
+    const TbFloat4 o = in[i]; /* post_kernels.hip's R8G8B8A8_UNORM store */
+    const uint32_t r = (uint32_t)(tb_saturate(o.x) * 255.0f + 0.5f), g = (uint32_t)(tb_saturate(o.y) * 255.0f + 0.5f), b = (uint32_t)(tb_saturate(o.z) * 255.0f + 0.5f);
+    out[i] = r | (g << 8) | (b << 16) | 0xff000000u;
+}
+
+bool nn_frame(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H <= (1ull << 24); }
+bool nn_tensor(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
+bool nn_channels(uint32_t c) { return c >= 1u && c <= 512u; }
+uint32_t nn_groups(uint64_t items) { return (uint32_t)((items + NN_THREADS - 1u) / NN_THREADS); }
+
+} // namespace
+
+extern "C" hipError_t nn_launch_conv3x3(hipStream_t stream, uint32_t width, uint32_t height, const uint16_t* inA, uint32_t cA, uint32_t upsampleA,
+    const uint16_t* inB, uint32_t cB, const uint16_t* weight, const float* bias, uint32_t cOut, uint32_t relu, uint16_t* out)
+{
+    if (!nn_frame(width, height) || !nn_tensor(inA) || !nn_tensor(weight) || !nn_tensor(bias) || !nn_tensor(out) || !nn_channels(cA) || !nn_channels(cOut))
+        return hipErrorInvalidValue;
+    if ((cB != 0u) != (inB != nullptr) || (cB && (!nn_tensor(inB) || !nn_channels(cB)))) return hipErrorInvalidValue;
+    if (upsampleA && ((width | height) & 1u)) return hipErrorInvalidValue;
+    if (out == inA || out == inB) return hipErrorInvalidValue;
+    NnConv p;
+    p.inA = inA; p.inB = inB; p.weight = weight; p.bias = bias; p.out = out;
+    p.width = width; p.height = height; p.padA = nn_padded_channels(cA); p.padB = cB ? nn_padded_channels(cB) : 0u; p.upsampleA = upsampleA ? 1u : 0u;
+    p.cOut = cOut; p.outPadded = nn_padded_channels(cOut); p.relu = relu ? 1u : 0u;
+    p.tilesX = (width + 15u) / 16u;
+    const bool four = p.outPadded % 64u == 0u; /* 64 output channels per wave where they divide, else 32: an activation fragment feeds that many MFMAs */
+    const uint64_t units = (uint64_t)p.tilesX * height * (p.outPadded / (four ? 64u : 32u)); /* < 2^24 * 16 */
+    p.units = (uint32_t)units;
+    const dim3 grid((uint32_t)((units + NN_WAVES - 1u) / NN_WAVES)), block(NN_THREADS);
+    if (four) hipLaunchKernelGGL(nn_conv3x3_kernel<4>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(nn_conv3x3_kernel<2>, grid, block, 0, stream, p);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t nn_launch_maxpool2x2(hipStream_t stream, uint32_t width, uint32_t height, uint32_t channels, const uint16_t* in, uint16_t* out)
+{
+    if (!nn_frame(width, height) || ((width | height) & 1u) || !channels || channels % 32u || channels > 512u || !nn_tensor(in) || !nn_tensor(out) || in == out)
+        return hipErrorInvalidValue;
+    const uint64_t items = (uint64_t)(width / 2u) * (height / 2u) * (channels / 8u);
+    hipLaunchKernelGGL(nn_maxpool2x2_kernel, dim3(nn_groups(items)), dim3(NN_THREADS), 0, stream, in, out, width, channels, items);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t nn_launch_pack_input(hipStream_t stream, uint32_t width, uint32_t height, uint32_t paddedW, uint32_t paddedH, const TbFloat4* color,
+    const TbFloat4* albedo, const TbFloat4* normal, uint16_t* out)
+{
+    if (!nn_frame(width, height) || paddedW < width || paddedH < height || !nn_frame(paddedW, paddedH) || !nn_tensor(color) || !nn_tensor(out))
+        return hipErrorInvalidValue;
+    if ((albedo != nullptr) != (normal != nullptr) || (albedo && (!nn_tensor(albedo) || !nn_tensor(normal)))) return hipErrorInvalidValue;
+    const uint32_t items = paddedW * paddedH * 4u; /* <= 2^26 */
+    hipLaunchKernelGGL(nn_pack_input_kernel, dim3(nn_groups(items)), dim3(NN_THREADS), 0, stream, color, albedo, normal, out, width, height, paddedW, items);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t nn_launch_unpack_output(hipStream_t stream, uint32_t width, uint32_t height, uint32_t paddedW, const uint16_t* in, TbFloat4* out)
+{
+    if (!nn_frame(width, height) || paddedW < width || !nn_tensor(in) || !nn_tensor(out)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nn_unpack_output_kernel, dim3(nn_groups((uint64_t)width * height)), dim3(NN_THREADS), 0, stream, in, out, width, paddedW, width * height);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t nn_launch_resolve_aux(hipStream_t stream, uint32_t width, uint32_t height, const TbFloat4* gAlbedo, const TbFloat4* gNormal, TbFloat4* albedo,
+    TbFloat4* normal)
+{
+    if (!nn_frame(width, height) || !nn_tensor(gAlbedo) || !nn_tensor(gNormal) || !nn_tensor(albedo) || !nn_tensor(normal)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nn_resolve_aux_kernel, dim3(nn_groups((uint64_t)width * height)), dim3(NN_THREADS), 0, stream, gAlbedo, gNormal, albedo, normal, width * height);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t nn_launch_to_rgba8(hipStream_t stream, uint32_t width, uint32_t height, const TbFloat4* in, uint32_t* out)
+{
+    if (!nn_frame(width, height) || !nn_tensor(in) || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nn_to_rgba8_kernel, dim3(nn_groups((uint64_t)width * height)), dim3(NN_THREADS), 0, stream, in, out, width * height);
+    return hipGetLastError();
+}
