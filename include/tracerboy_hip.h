@@ -510,17 +510,33 @@ int tb_upscale(tb_context* ctx, const tb_post_settings* post, uint32_t output_ty
  * tb_run_neural: the network on host surfaces (width x height RGBA32F, .xyz read; out gets (r, g, b, 1)).  Needs tb_neural_load; albedo and
  * normal are given exactly when the weights have 9 inputs.  Bit for bit the chain of tb_run_conv3x3 calls on the packed input (channels colour,
  * albedo, normal).  Reads and writes nothing else the context holds.  At most 2^24 pixels after the extension to multiples of 16.
- * tb_denoise_neural: the stage. Colour is the float image tb_post_process(post, TB_OUTPUT_TYPE_LIT) writes at the rendered size (option
- * "post_denoised" included); with 9-input weights albedo is sum.xyz / sum.w of guide surface TB_GUIDE_ALBEDO and the normals are those option
+ * tb_denoise_neural: the stage. Colour is what the reference's network reads: the 8-bit picture tb_post_process(post, TB_OUTPUT_TYPE_LIT) writes at the
+ * rendered size (option "post_denoised" included), each channel k / 255 in fp32 -- the reference's post-process surface has the back buffer's format,
+ * R8G8B8A8_UNORM (TracerBoy.cpp:3817-3829, D3D12App.cpp:3), its view is OpenImageDenoise::Run's input (TracerBoy.cpp:3309-3318) and
+ * ImageToTensorCS.hlsl:22-32 loads it as float3 -- so the colour is clamped to [0, 1], quantised, and a NaN of the float picture (the default AgX
+ * punchy tonemapper gives one for a black pixel) goes in as 0.  The quantisation happens inside the pack (no extra pass, no 8-bit surface).  With
+ * 9-input weights albedo is sum.xyz / sum.w of guide surface TB_GUIDE_ALBEDO and the normals are those option
  * "denoise_guides" = 1 gives the a-trous filter (the mean over the frames that hit, several brought to length 1, zero where nothing was hit), both of
- * valid guide surfaces (tb_render_guides). The float result goes to rgba_f32_or_null (width * height * 4 floats), its 8-bit conversion as the output
- * stage does it (clamp, scale, + 0.5, truncate) to rgba8_or_null. Synchronous. Like tb_denoise it writes neither the accumulation surfaces nor AOVs,
- * frame counter, history, guides or denoised surfaces: tb_accum_digest is the same before and after. Its activation buffers belong to the context
- * (sized at the first use, kept while the size holds, released by tb_destroy). TB_E_UNSUPPORTED: a tb_create_multi group. TB_E_INVALID: no weights,
- * nothing rendered, both pointers null, no valid guides with 9-input weights (call tb_render_guides), whatever tb_post_process refuses. The picture
- * goes in as the output stage wrote it: where that holds a NaN (the default AgX punchy tonemapper gives one for a black pixel) the network spreads it
- * over its receptive field -- choose another tonemapper for scenes with black pixels. tb_get_option "last_neural_us": GPU microseconds of the last
- * network, pack to unpack (HIP events); "neural_inputs": 0, 3 or 9. */
+ * valid guide surfaces (tb_render_guides), neither clamped. The float result goes to rgba_f32_or_null (width * height * 4 floats), its 8-bit conversion
+ * as the output stage does it (clamp with NaN -> 0, scale, + 0.5, truncate) to rgba8_or_null. Synchronous. Like tb_denoise it writes neither the
+ * accumulation surfaces nor AOVs, frame counter, history, guides or denoised surfaces: tb_accum_digest is the same before and after. Its activation
+ * buffers belong to the context (sized at the first use, kept while the size holds, released by tb_destroy). TB_E_UNSUPPORTED: a tb_create_multi
+ * group. TB_E_INVALID: no weights, nothing rendered, both pointers null, no valid guides with 9-input weights (call tb_render_guides), whatever
+ * tb_post_process refuses. tb_run_neural takes its floats as they are: a non-finite value given there spreads over the network's receptive field
+ * (about 95 pixels each way) and no further. tb_get_option "last_neural_us": GPU microseconds of the last network, pack to unpack (HIP events);
+ * "neural_inputs": 0, 3 or 9.
+ * tb_run_nn_pack / tb_run_nn_unpack / tb_run_nn_resolve_aux / tb_run_nn_to_rgba8: the four helper kernels around the layers, like tb_run_composite:
+ * host arrays, temporary device buffers, no scene, no weights, nothing the context holds is read or written.  Surfaces are width x height RGBA32F,
+ * row 0 = top; a tensor is padded_h x padded_w x 32 binary16 (as bits), padded sizes >= the picture's (the network uses the next multiples of 16).
+ *   pack: channels 0-2 colour.xyz, and with albedo and normal (both or neither) 3-5 albedo.xyz, 6-8 normal.xyz, each rounded once to binary16 (nearest
+ *     even); every other channel and every pixel outside width x height is zero.  unorm_color != 0: the colour first goes through the 8-bit store,
+ *     k = (uint32)(saturate(x) * 255 + 0.5) with NaN -> 0, then (float)k / 255 -- the stage's form; 0 is tb_run_neural's.
+ *   unpack: out = (channels 0-2 of the tensor at (y, x) as fp32, 1).
+ *   resolve aux: albedo = (sum.xyz / sum.w, 1); normals = (sum.xyz / hits, 1) with hits = sum.w > 0, brought to length 1 when hits > 1 (zero when
+ *     that length is 0), (0, 0, 0, 1) when hits is 0.
+ *   to rgba8: (uint32)(saturate(x) * 255 + 0.5) per channel with NaN -> 0, alpha 255.
+ *   TB_E_INVALID (the message names the cause): a null required array, albedo without normal or the reverse, a zero dimension, more than 2^24
+ *   pixels (padded ones included), a padded size below the picture's. */
 typedef struct tb_nn_info { uint32_t in_channels; uint32_t out_channels[16]; uint32_t in_channels_of[16]; uint64_t weight_bytes; } tb_nn_info;
 typedef struct tb_conv3x3_desc { uint32_t width, height;      /* of the convolution's output before pooling */
                                  uint32_t c_a, c_b, c_out;    /* channels of source A, source B (0 = none), output */
@@ -533,6 +549,12 @@ int tb_run_conv3x3(tb_context* ctx, const tb_conv3x3_desc* d, const uint16_t* in
 int tb_run_neural(tb_context* ctx, uint32_t width, uint32_t height, const float* color_rgba,
                   const float* albedo_rgba_or_null, const float* normal_rgba_or_null, float* out_rgba);
 int tb_denoise_neural(tb_context* ctx, const tb_post_settings* post, float* rgba_f32_or_null, uint8_t* rgba8_or_null);
+int tb_run_nn_pack(tb_context* ctx, uint32_t width, uint32_t height, uint32_t padded_w, uint32_t padded_h, uint32_t unorm_color, const float* color_rgba,
+                   const float* albedo_rgba_or_null, const float* normal_rgba_or_null, uint16_t* out_tensor);
+int tb_run_nn_unpack(tb_context* ctx, uint32_t width, uint32_t height, uint32_t padded_w, uint32_t padded_h, const uint16_t* tensor, float* out_rgba);
+int tb_run_nn_resolve_aux(tb_context* ctx, uint32_t width, uint32_t height, const float* albedo_sum, const float* normal_sum, float* out_albedo,
+                          float* out_normal);
+int tb_run_nn_to_rgba8(tb_context* ctx, uint32_t width, uint32_t height, const float* rgba, uint8_t* out_rgba8);
 
 /* ---- host-only half of LoadScene (no device needed) ------------------------------------------------
  * The same parse / convert / BVH-build code tb_load_scene runs, exposed separately so that the

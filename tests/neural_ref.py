@@ -1,6 +1,7 @@
 """The neural still denoiser restated on the CPU (include/tracerboy_hip.h, the neural section).
 
-Two things:
+Three things:
+  * the helper kernels around the layers: pack_input / extend16, rgba8_of (the 8-bit store) and unorm_color (its way back);
   * the layer arithmetic and the network's graph in torch: conv_ref, net_ref (and net_chain, the same graph through the library's layer seam);
   * a reader and a writer of the TZA weights container, written from its layout, independent of csrc/host/nn_weights.cpp.
 
@@ -158,6 +159,23 @@ def pack_input(color, albedo=None, normal=None):
     planes = [np.asarray(s, np.float32)[..., :3] for s in (color, albedo, normal) if s is not None]
     with np.errstate(over="ignore"):
         return np.concatenate(planes, -1).astype(np.float16)
+
+
+def rgba8_of(f):
+    """The output stage's R8G8B8A8_UNORM store of an (H, W, 4) picture: NaN -> 0, clamp to [0, 1], * 255 + 0.5 in float32, truncate; alpha 255."""
+    x = np.asarray(f, np.float32)[..., :3]
+    x = np.where(np.isnan(x), np.float32(0), x)
+    x = np.clip(x, np.float32(0), np.float32(1)) * np.float32(255) + np.float32(0.5)
+    out = np.full(np.asarray(f).shape, 255, np.uint8)
+    out[..., :3] = x.astype(np.uint32)
+    return out
+
+
+def unorm_color(rgba8):
+    """What a network loads from an R8G8B8A8_UNORM picture: k / 255 in float32 per channel, alpha 1.  (H, W, 4) uint8 -> float32."""
+    out = np.ones(np.asarray(rgba8).shape, np.float32)
+    out[..., :3] = np.asarray(rgba8)[..., :3].astype(np.float32) / np.float32(255)
+    return out
 
 
 def extend16(x):

@@ -24,6 +24,13 @@ def test_header_declares_the_survey_boundary():
         assert required in names
 
 
+def test_header_declares_the_neural_denoiser_and_its_hooks():
+    names = declared_functions()
+    for required in ["tb_nn_weights_info", "tb_neural_load", "tb_run_conv3x3", "tb_run_neural", "tb_denoise_neural",
+                     "tb_run_nn_pack", "tb_run_nn_unpack", "tb_run_nn_resolve_aux", "tb_run_nn_to_rgba8"]:
+        assert required in names
+
+
 def test_library_exports_every_declared_symbol(built):
     from tracerboy_amd import api
     L = ctypes.CDLL(api.LIB_PATH)

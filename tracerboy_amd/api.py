@@ -111,6 +111,10 @@ def lib():
         "tb_run_conv3x3": (C.c_int, [vp, P(abi.tb_conv3x3_desc)] + [vp] * 5),
         "tb_run_neural": (C.c_int, [vp, C.c_uint32, C.c_uint32] + [vp] * 4),
         "tb_denoise_neural": (C.c_int, [vp, P(abi.tb_post_settings), vp, vp]),
+        "tb_run_nn_pack": (C.c_int, [vp] + [C.c_uint32] * 5 + [vp] * 4),
+        "tb_run_nn_unpack": (C.c_int, [vp] + [C.c_uint32] * 4 + [vp, vp]),
+        "tb_run_nn_resolve_aux": (C.c_int, [vp, C.c_uint32, C.c_uint32] + [vp] * 4),
+        "tb_run_nn_to_rgba8": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
         "tb_variant_stash_entries": (C.c_int, [C.c_char_p]),
         "tb_frame_groups": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "tb_state_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), C.c_float, C.c_uint32]),
@@ -620,13 +624,51 @@ class TracerBoy:
         return out
 
     def DenoiseNeural(self, postSettings=None, rgba8=True):
-        """PostProcess at the rendered size, then the network on that picture and, with 9-input weights, on the albedo and normals of the guide
-        pass (tb_denoise_neural; RenderGuides first).  Returns (float32 HxWx4 picture, uint8 HxWx4 picture or None)."""
+        """PostProcess at the rendered size, then the network on its 8-bit picture (each channel k / 255, as the reference's network reads it) and,
+        with 9-input weights, on the albedo and normals of the guide pass (tb_denoise_neural; RenderGuides first).  Returns (float32 HxWx4 picture, uint8 HxWx4 picture or None)."""
         ps = postSettings if postSettings is not None else GetDefaultPostProcessSettings()
         f = np.empty((self.height, self.width, 4), np.float32)
         b = np.empty((self.height, self.width, 4), np.uint8) if rgba8 else None
         self._check(self._L.tb_denoise_neural(self._ctx, C.byref(ps), _np_ptr(f), _np_ptr(b) if rgba8 else None))
         return f, b
+
+    def RunNnPack(self, color, albedo=None, normal=None, unorm_color=False):
+        """nn_pack_input on host surfaces (tb_run_nn_pack): (H, W, 4) float32 each, albedo and normal both or neither.  Returns the network's input,
+        (H0, W0, 32) float16 with H0, W0 the next multiples of 16.  unorm_color: the colour goes through the 8-bit store, as in the stage."""
+        f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (color, albedo, normal)]
+        h, w = f[0].shape[:2]
+        assert all(a is None or a.shape == (h, w, 4) for a in f), "surfaces are (H, W, 4)"
+        out = np.empty((h + -h % 16, w + -w % 16, 32), np.float16)
+        self._check(self._L.tb_run_nn_pack(self._ctx, w, h, out.shape[1], out.shape[0], int(bool(unorm_color)), *[None if a is None else _np_ptr(a) for a in f],
+                                           _np_ptr(out)))
+        return out
+
+    def RunNnUnpack(self, tensor, width, height):
+        """nn_unpack_output on a host tensor (tb_run_nn_unpack): (H0, W0, 32) float16 -> (height, width, 4) float32, channels 0-2 and alpha 1."""
+        t = np.ascontiguousarray(tensor, np.float16)
+        assert t.ndim == 3 and t.shape[2] == 32, "the tensor is (H0, W0, 32)"
+        out = np.empty((height, width, 4), np.float32)
+        self._check(self._L.tb_run_nn_unpack(self._ctx, width, height, t.shape[1], t.shape[0], _np_ptr(t), _np_ptr(out)))
+        return out
+
+    def RunNnResolveAux(self, albedo_sum, normal_sum):
+        """nn_resolve_aux on host copies of the albedo and normal guide sums (tb_run_nn_resolve_aux), (H, W, 4) float32 each.  Returns (albedo,
+        normal) as the network's pack reads them."""
+        a, n = np.ascontiguousarray(albedo_sum, np.float32), np.ascontiguousarray(normal_sum, np.float32)
+        h, w = a.shape[:2]
+        assert a.shape == n.shape == (h, w, 4), "surfaces are (H, W, 4)"
+        albedo, normal = np.empty_like(a), np.empty_like(a)
+        self._check(self._L.tb_run_nn_resolve_aux(self._ctx, w, h, _np_ptr(a), _np_ptr(n), _np_ptr(albedo), _np_ptr(normal)))
+        return albedo, normal
+
+    def RunNnToRgba8(self, image):
+        """nn_to_rgba8 on a host surface (tb_run_nn_to_rgba8): (H, W, 4) float32 -> (H, W, 4) uint8."""
+        a = np.ascontiguousarray(image, np.float32)
+        h, w = a.shape[:2]
+        assert a.shape == (h, w, 4), "the surface is (H, W, 4)"
+        out = np.empty((h, w, 4), np.uint8)
+        self._check(self._L.tb_run_nn_to_rgba8(self._ctx, w, h, _np_ptr(a), _np_ptr(out)))
+        return out
 
     @staticmethod
     def _fsr_surface(image):

@@ -62,8 +62,9 @@
  * 8-bit conversion, .pfm / .exr the float LDR picture -- the POST-PROCESSED one, as with --upscale.  A file with 9 inputs also reads the mean albedo
  * and normals of the guide pass: the first hits of the last min(K, frames held) frames are traced again after the last frame, as --denoise-guides
  * does it, K = 8 unless --denoise-guides K says otherwise (which here does not imply --denoise); a file with 3 inputs takes no --denoise-guides.
- * The network reads the float picture as the output stage wrote it, NaN included, and spreads one over its whole receptive field: the tool warns when
- * the result holds values that are not finite (the default tonemapper gives NaN for a black pixel; --tonemap 0 does not).
+ * The network reads the output stage's 8-bit picture (k / 255 per channel, as the reference's network does): clamped, and a NaN of the float picture
+ * -- the default tonemapper gives one for a black pixel -- is 0 there, so every tonemapper works.  The tool still warns when the result holds values
+ * that are not finite (a non-finite albedo or normal, or an overflow inside the network).
  * Not together with --denoise (and its --denoise-iterations / --denoise-demodulate), --upscale, --render-scale or --ranks N > 1.  Mistakes, an
  * unreadable or malformed FILE.tza among them, are reported before any device call (exit status 2). */
 #include "../../../include/tracerboy_hip.h"
@@ -425,10 +426,9 @@ int main(int argc, char** argv)
         if ((rc = tb_denoise_neural(ctx, &post, imgF.data(), png ? img.data() : nullptr))) return fail(ctx, "tb_denoise_neural", rc);
         printf("neural denoise: %lld input channels, %.3f ms on the GPU\n", (long long)tb_get_option(ctx, "neural_inputs"),
                (double)tb_get_option(ctx, "last_neural_us") / 1e3);
-        size_t notFinite = 0; /* a NaN of the post-processed picture spreads over the network's whole receptive field */
+        size_t notFinite = 0; /* the colour goes in clamped; a non-finite guide value or an overflow inside the network would still show here */
         for (float v : imgF) notFinite += !(v - v == 0.0f);
-        if (notFinite) fprintf(stderr, "tracerboy-hip: warning: %zu values of the network's picture are not finite: the post-processed picture held some "
-            "(the AgX tonemappers, 5 and the default 6, give NaN for a black pixel); try --tonemap 0\n", notFinite);
+        if (notFinite) fprintf(stderr, "tracerboy-hip: warning: %zu values of the network's picture are not finite\n", notFinite);
         if (png) { if ((rc = tb_write_image_rgba8(out.c_str(), W, H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc); }
         else if ((rc = tb_write_image_f32(out.c_str(), W, H, imgF.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
     } else if (upW) { /* the output stage at the rendered size, then FSR 1 to the picture's */

@@ -36,8 +36,9 @@ std::vector<uint16_t> padChannels(const uint16_t* in, size_t pixels, uint32_t c)
 }
 
 /* The 16 layers on the context's activation buffers, enqueued on its stream: color / albedo / normal are width x height RGBA32F device surfaces
- * (albedo and normal null with 3-input weights), out likewise.  The picture is zero-extended to multiples of 16 and the result cropped. */
-void runNetwork(tb_context* c, uint32_t width, uint32_t height, const void* color, const void* albedo, const void* normal, void* out)
+ * (albedo and normal null with 3-input weights), out likewise.  The picture is zero-extended to multiples of 16 and the result cropped.
+ * unormColor: the colour is packed through the R8G8B8A8_UNORM store (nn_launch_pack_input). */
+void runNetwork(tb_context* c, uint32_t width, uint32_t height, const void* color, const void* albedo, const void* normal, bool unormColor, void* out)
 {
     tb_context::Neural& n = c->nn;
     const uint32_t W0 = tbnn::roundUp(width, 16u), H0 = tbnn::roundUp(height, 16u);
@@ -58,7 +59,7 @@ void runNetwork(tb_context* c, uint32_t width, uint32_t height, const void* colo
     auto pool = [&](uint32_t l, uint32_t lvl, const uint16_t* in, uint16_t* dst) {
         HIP_TRY(nn_launch_maxpool2x2(s, W0 >> lvl, H0 >> lvl, nn_padded_channels(co[l]), in, dst));
     };
-    HIP_TRY(nn_launch_pack_input(s, width, height, W0, H0, (const TbFloat4*)color, (const TbFloat4*)albedo, (const TbFloat4*)normal, x));
+    HIP_TRY(nn_launch_pack_input(s, width, height, W0, H0, (const TbFloat4*)color, (const TbFloat4*)albedo, (const TbFloat4*)normal, unormColor, x));
     conv(E0, 0, x, false, nullptr, a);
     conv(E1, 0, a, false, nullptr, b); pool(E1, 0, b, skip[0]);
     conv(E2, 1, skip[0], false, nullptr, a); pool(E2, 1, a, skip[1]);
@@ -81,10 +82,10 @@ const char* pictureRefusal(uint32_t W, uint32_t H)
     return nullptr;
 }
 
-void timedNetwork(tb_context* c, uint32_t W, uint32_t H, const void* color, const void* albedo, const void* normal, void* out)
+void timedNetwork(tb_context* c, uint32_t W, uint32_t H, const void* color, const void* albedo, const void* normal, bool unormColor, void* out)
 {
     HIP_TRY(hipEventRecord(c->nn.ev[0].create(), c->stream));
-    runNetwork(c, W, H, color, albedo, normal, out);
+    runNetwork(c, W, H, color, albedo, normal, unormColor, out);
     HIP_TRY(hipEventRecord(c->nn.ev[1].create(), c->stream));
 }
 
@@ -163,9 +164,73 @@ int tb_run_neural(tb_context* c, uint32_t W, uint32_t H, const float* color, con
         const DevBuf dColor = staged(color, bytes), dOut = scratch(bytes);
         DevBuf dAlbedo, dNormal;
         if (aux) { dAlbedo = staged(albedo, bytes); dNormal = staged(normal, bytes); }
-        timedNetwork(c, W, H, dColor.p, dAlbedo.p, dNormal.p, dOut.p);
+        timedNetwork(c, W, H, dColor.p, dAlbedo.p, dNormal.p, false, dOut.p);
         HIP_TRY(hipStreamSynchronize(c->stream));
         readTime(c);
+        copyBack(out, dOut);
+        return TB_OK;
+    });
+}
+
+/* The four helper kernels of nn_kernels.hip on host arrays, like tb_run_composite: temporary device buffers, the context's stream, nothing else. */
+int tb_run_nn_pack(tb_context* c, uint32_t W, uint32_t H, uint32_t paddedW, uint32_t paddedH, uint32_t unormColor, const float* color, const float* albedo,
+                   const float* normal, uint16_t* out)
+{
+    return guarded(c, [&]() {
+        if (!color || !out) return fail(c, TB_E_INVALID, "tb_run_nn_pack: null array");
+        if ((albedo != nullptr) != (normal != nullptr)) return fail(c, TB_E_INVALID, "tb_run_nn_pack: albedo and normal are given together or not at all");
+        if (const char* why = surfaceRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_nn_pack: ") + why);
+        if (paddedW < W || paddedH < H) return fail(c, TB_E_INVALID, "tb_run_nn_pack: the padded size is smaller than the picture");
+        if (const char* why = surfaceRefusal(paddedW, paddedH)) return fail(c, TB_E_INVALID, std::string("tb_run_nn_pack: padded: ") + why);
+        const size_t bytes = (size_t)W * H * sizeof(TbFloat4);
+        const DevBuf dColor = staged(color, bytes), dOut = scratch(tensorBytes(paddedW, paddedH, 9u));
+        DevBuf dAlbedo, dNormal;
+        if (albedo) { dAlbedo = staged(albedo, bytes); dNormal = staged(normal, bytes); }
+        HIP_TRY(nn_launch_pack_input(c->stream, W, H, paddedW, paddedH, (const TbFloat4*)dColor.p, (const TbFloat4*)dAlbedo.p, (const TbFloat4*)dNormal.p,
+            unormColor, (uint16_t*)dOut.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        copyBack(out, dOut);
+        return TB_OK;
+    });
+}
+
+int tb_run_nn_unpack(tb_context* c, uint32_t W, uint32_t H, uint32_t paddedW, uint32_t paddedH, const uint16_t* in, float* out)
+{
+    return guarded(c, [&]() {
+        if (!in || !out) return fail(c, TB_E_INVALID, "tb_run_nn_unpack: null array");
+        if (const char* why = surfaceRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_nn_unpack: ") + why);
+        if (paddedW < W || paddedH < H) return fail(c, TB_E_INVALID, "tb_run_nn_unpack: the padded size is smaller than the picture");
+        if (const char* why = surfaceRefusal(paddedW, paddedH)) return fail(c, TB_E_INVALID, std::string("tb_run_nn_unpack: padded: ") + why);
+        const DevBuf dIn = staged(in, tensorBytes(paddedW, paddedH, 3u)), dOut = scratch((size_t)W * H * sizeof(TbFloat4));
+        HIP_TRY(nn_launch_unpack_output(c->stream, W, H, paddedW, (const uint16_t*)dIn.p, (TbFloat4*)dOut.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        copyBack(out, dOut);
+        return TB_OK;
+    });
+}
+
+int tb_run_nn_resolve_aux(tb_context* c, uint32_t W, uint32_t H, const float* albedoSum, const float* normalSum, float* albedo, float* normal)
+{
+    return guarded(c, [&]() {
+        if (!albedoSum || !normalSum || !albedo || !normal) return fail(c, TB_E_INVALID, "tb_run_nn_resolve_aux: null array");
+        if (const char* why = surfaceRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_nn_resolve_aux: ") + why);
+        const size_t bytes = (size_t)W * H * sizeof(TbFloat4);
+        const DevBuf dA = staged(albedoSum, bytes), dN = staged(normalSum, bytes), dAlbedo = scratch(bytes), dNormal = scratch(bytes);
+        HIP_TRY(nn_launch_resolve_aux(c->stream, W, H, (const TbFloat4*)dA.p, (const TbFloat4*)dN.p, (TbFloat4*)dAlbedo.p, (TbFloat4*)dNormal.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        copyBack(albedo, dAlbedo); copyBack(normal, dNormal);
+        return TB_OK;
+    });
+}
+
+int tb_run_nn_to_rgba8(tb_context* c, uint32_t W, uint32_t H, const float* in, uint8_t* out)
+{
+    return guarded(c, [&]() {
+        if (!in || !out) return fail(c, TB_E_INVALID, "tb_run_nn_to_rgba8: null array");
+        if (const char* why = surfaceRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_nn_to_rgba8: ") + why);
+        const DevBuf dIn = staged(in, (size_t)W * H * sizeof(TbFloat4)), dOut = scratch((size_t)W * H * 4u);
+        HIP_TRY(nn_launch_to_rgba8(c->stream, W, H, (const TbFloat4*)dIn.p, (uint32_t*)dOut.p));
+        HIP_TRY(hipStreamSynchronize(c->stream));
         copyBack(out, dOut);
         return TB_OK;
     });
@@ -192,7 +257,8 @@ int tb_denoise_neural(tb_context* c, const tb_post_settings* post, float* rgbaF3
         if (aux) { ensure(n.aux[0], px * sizeof(TbFloat4)); ensure(n.aux[1], px * sizeof(TbFloat4));
             HIP_TRY(nn_launch_resolve_aux(c->stream, W, H, (const TbFloat4*)c->guides.sum[0].p, (const TbFloat4*)c->guides.sum[1].p, (TbFloat4*)n.aux[0].p,
                 (TbFloat4*)n.aux[1].p)); }
-        timedNetwork(c, W, H, c->postOut.p, aux ? n.aux[0].p : nullptr, aux ? n.aux[1].p : nullptr, n.result.p);
+        /* the reference's network reads its R8G8B8A8_UNORM post-process surface: the colour is packed through that store */
+        timedNetwork(c, W, H, c->postOut.p, aux ? n.aux[0].p : nullptr, aux ? n.aux[1].p : nullptr, true, n.result.p);
         if (rgba8) { ensure(n.rgba8, px * 4); HIP_TRY(nn_launch_to_rgba8(c->stream, W, H, (const TbFloat4*)n.result.p, (uint32_t*)n.rgba8.p)); }
         HIP_TRY(hipStreamSynchronize(c->stream));
         readTime(c);

@@ -95,9 +95,13 @@ __global__ __launch_bounds__(NN_THREADS) void nn_maxpool2x2_kernel(const uint16_
     *(nn_half8*)(out + pixel * channels + g * 8u) = m;
 }
 
-/* a lane writes 8 channels of one pixel: group 0 = channels 0-7, group 1 = channel 8 and zeros, groups 2 and 3 zeros */
+/* post_kernels.hip's R8G8B8A8_UNORM store of one channel: clamp (NaN -> 0), scale, + 0.5, truncate */
+__device__ __forceinline__ uint32_t nn_unorm8(float x) { return (uint32_t)(tb_saturate(x) * 255.0f + 0.5f); }
+
+/* a lane writes 8 channels of one pixel: group 0 = channels 0-7, group 1 = channel 8 and zeros, groups 2 and 3 zeros.  unormColor: the colour goes
+ * through the 8-bit store and back, k / 255 in fp32, before its one rounding to binary16 -- what a network reads from an R8G8B8A8_UNORM picture */
 __global__ __launch_bounds__(NN_THREADS) void nn_pack_input_kernel(const TbFloat4* __restrict__ color, const TbFloat4* __restrict__ albedo,
-    const TbFloat4* __restrict__ normal, uint16_t* __restrict__ out, uint32_t width, uint32_t height, uint32_t paddedW, uint32_t items)
+    const TbFloat4* __restrict__ normal, uint16_t* __restrict__ out, uint32_t width, uint32_t height, uint32_t paddedW, uint32_t items, uint32_t unormColor)
 {
     const uint32_t i = blockIdx.x * NN_THREADS + threadIdx.x;
     if (i >= items) return;
@@ -106,7 +110,8 @@ __global__ __launch_bounds__(NN_THREADS) void nn_pack_input_kernel(const TbFloat
     if (x < width && y < height && g < 2u) {
         const size_t s = (size_t)y * width + x;
         if (g == 0u) {
-            const TbFloat4 c = color[s];
+            TbFloat4 c = color[s];
+            if (unormColor) { c.x = (float)nn_unorm8(c.x) / 255.0f; c.y = (float)nn_unorm8(c.y) / 255.0f; c.z = (float)nn_unorm8(c.z) / 255.0f; }
             h[0] = (_Float16)c.x; h[1] = (_Float16)c.y; h[2] = (_Float16)c.z;
             if (albedo) { const TbFloat4 a = albedo[s], n = normal[s]; h[3] = (_Float16)a.x; h[4] = (_Float16)a.y; h[5] = (_Float16)a.z; h[6] = (_Float16)n.x; h[7] = (_Float16)n.y; }
         } else if (albedo) h[0] = (_Float16)normal[s].z;
@@ -146,7 +151,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_to_rgba8_kernel(const TbFloat4*
     const uint32_t i = blockIdx.x * NN_THREADS + threadIdx.x;
     if (i >= nPixels) return;
     const TbFloat4 o = in[i]; /* post_kernels.hip's R8G8B8A8_UNORM store */
-    const uint32_t r = (uint32_t)(tb_saturate(o.x) * 255.0f + 0.5f), g = (uint32_t)(tb_saturate(o.y) * 255.0f + 0.5f), b = (uint32_t)(tb_saturate(o.z) * 255.0f + 0.5f);
+    const uint32_t r = nn_unorm8(o.x), g = nn_unorm8(o.y), b = nn_unorm8(o.z);
     out[i] = r | (g << 8) | (b << 16) | 0xff000000u;
 }
 
@@ -189,13 +194,13 @@ extern "C" hipError_t nn_launch_maxpool2x2(hipStream_t stream, uint32_t width, u
 }
 
 extern "C" hipError_t nn_launch_pack_input(hipStream_t stream, uint32_t width, uint32_t height, uint32_t paddedW, uint32_t paddedH, const TbFloat4* color,
-    const TbFloat4* albedo, const TbFloat4* normal, uint16_t* out)
+    const TbFloat4* albedo, const TbFloat4* normal, uint32_t unormColor, uint16_t* out)
 {
     if (!nn_frame(width, height) || paddedW < width || paddedH < height || !nn_frame(paddedW, paddedH) || !nn_tensor(color) || !nn_tensor(out))
         return hipErrorInvalidValue;
     if ((albedo != nullptr) != (normal != nullptr) || (albedo && (!nn_tensor(albedo) || !nn_tensor(normal)))) return hipErrorInvalidValue;
     const uint32_t items = paddedW * paddedH * 4u; /* <= 2^26 */
-    hipLaunchKernelGGL(nn_pack_input_kernel, dim3(nn_groups(items)), dim3(NN_THREADS), 0, stream, color, albedo, normal, out, width, height, paddedW, items);
+    hipLaunchKernelGGL(nn_pack_input_kernel, dim3(nn_groups(items)), dim3(NN_THREADS), 0, stream, color, albedo, normal, out, width, height, paddedW, items, unormColor ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -22,9 +22,11 @@ hipError_t nn_launch_conv3x3(hipStream_t stream, uint32_t width, uint32_t height
 hipError_t nn_launch_maxpool2x2(hipStream_t stream, uint32_t width, uint32_t height, uint32_t channels, const uint16_t* in, uint16_t* out);
 /* The network's input: paddedW x paddedH x 32 channels.  Channels 0-2 are color.xyz, with albedo and normal (both or neither) 3-5 albedo.xyz and
  * 6-8 normal.xyz, rounded to binary16 (nearest even); everything else, and every pixel outside width x height, is zero.  The surfaces are
- * width x height RGBA32F, row 0 = top. */
+ * width x height RGBA32F, row 0 = top.  unormColor: each colour channel first goes through the output stage's R8G8B8A8_UNORM store and back --
+ * k = (uint32)(saturate(x) * 255 + 0.5) with NaN -> 0, then (float)k / 255 in fp32 -- which is what the reference's network loads from its
+ * 8-bit post-process surface; albedo and normal are never clamped. */
 hipError_t nn_launch_pack_input(hipStream_t stream, uint32_t width, uint32_t height, uint32_t paddedW, uint32_t paddedH, const TbFloat4* color,
-                                const TbFloat4* albedo, const TbFloat4* normal, uint16_t* out);
+                                const TbFloat4* albedo, const TbFloat4* normal, uint32_t unormColor, uint16_t* out);
 /* (r, g, b, 1) of channels 0-2 of a paddedW x paddedH x 32-channel tensor, cropped to width x height */
 hipError_t nn_launch_unpack_output(hipStream_t stream, uint32_t width, uint32_t height, uint32_t paddedW, const uint16_t* in, TbFloat4* out);
 /* the guide sums (tb_render_guides) as the network reads them: albedo = sum.xyz / sum.w; normals as dn_launch_resolve_guides gives them
