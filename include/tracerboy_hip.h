@@ -583,6 +583,11 @@ int tb_host_scene_layout_b(tb_host_scene* s, const TbNodeB** nodes, uint32_t* nu
  * (off_nodes / off_tris are filled with the image). */
 typedef struct tb_lds_image_info { uint32_t bytes, off_nodes, off_tris, num_nodes, num_tris, node_stride, tri_copies, root_ref, stack_depth; } tb_lds_image_info;
 int tb_host_scene_lds_image(tb_host_scene* s, uint8_t* out, uint32_t capacity, tb_lds_image_info* info);
+/* Whether every index the kernels can form into the shading tables is in range (host/lds_image.h SceneTablesInRange, what a context asks of a scene
+ * before it launches the copy that fetches those tables unguarded): 1 or 0, TB_E_INVALID for a null table with a count.  hit_groups: 4 words per
+ * record -- MaterialIndex, first vertex float, first index, unused. */
+int tb_host_scene_tables_in_range(const TbTriB* tris, uint32_t num_tris, const uint32_t* hit_groups, uint32_t num_hit_groups, const uint32_t* indices,
+    uint32_t num_indices, uint32_t num_vertex_floats, uint32_t num_materials);
 /* Diagnostic: the build's own parse of a PBRT file in the record format of oracle/ref_dump.cpp. */
 int tb_host_pbrt_dump(const char* pbrt_path, const char* out_path, char* err, uint32_t err_len);
 int tb_host_scene_triangles(tb_host_scene* s, const float** positions, uint32_t* num_vertices, const uint32_t** tri_vertex_index,

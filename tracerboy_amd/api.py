@@ -137,6 +137,7 @@ def lib():
         "tb_host_scene_frame_constants": (C.c_int, [vp, P(abi.tb_output_settings), C.c_uint32, C.c_float, P(abi.TbPerFrameConstants)]),
         "tb_host_scene_layout_b": (C.c_int, [vp, P(P(abi.TbNodeB)), P(C.c_uint32), P(P(abi.TbTriB)), P(C.c_uint32), P(C.c_uint32)]),
         "tb_host_scene_lds_image": (C.c_int, [vp, P(C.c_uint8), C.c_uint32, P(abi.tb_lds_image_info)]),
+        "tb_host_scene_tables_in_range": (C.c_int, [P(abi.TbTriB), C.c_uint32, P(C.c_uint32), C.c_uint32, P(C.c_uint32)] + [C.c_uint32] * 3),
         "tb_host_scene_triangles": (C.c_int, [vp, P(P(C.c_float)), P(C.c_uint32), P(P(C.c_uint32)), P(P(C.c_uint32)), P(P(C.c_uint32)), P(P(C.c_uint32)), P(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():

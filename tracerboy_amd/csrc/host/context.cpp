@@ -151,7 +151,7 @@ int tb_set_material(tb_context* c, int id, const TbMaterial* in)
         HIP_TRY(hipMemcpy((void*)&c->ds.materials[id].m, in, sizeof *in, hipMemcpyHostToDevice));
         c->sceneFeatures = sceneFeatureMask(c->scene);
         c->ds.textureUse = sceneTextureUse(c); /* the edit may be the scene's first texture or normal map */
-        resetHistory(c); c->materialEdits++;
+        resetHistory(c); c->materialEdits++; /* (c->tablesInRange stands: the edit changes no count and no index) */
         for (tb_context* p : c->group.peers) { const int rc = tb_set_material(p, id, in); if (rc != TB_OK) return rc; }
         return TB_OK;
     });

@@ -147,6 +147,9 @@ struct tb_context {
     std::vector<DevBuf> sceneBufs;
     TbDeviceScene ds{};
     uint32_t sceneFeatures = 0; bool sceneInLds = false;
+    /* every index the kernels can form into the shading tables is in range (lds_image.h SceneTablesInRange; finalizeScene).  A material edit
+     * keeps it: it changes no count and no index.  The copy for scenes in LDS, which fetches unguarded, needs it (context_render.cpp pickCopy) */
+    bool tablesInRange = false;
     /* surfaces */
     uint32_t width = 0, height = 0;
     DevBuf output, jittered, aov[8], stats, rayStats, packed;

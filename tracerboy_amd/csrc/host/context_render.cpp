@@ -499,6 +499,7 @@ static void fillTargets(RenderCall& r)
     if (r.count || opt<OPT_debug_profile_groups>(c)) { ensure(c->rayStats, 21 * 8); if (c->samplesRendered == 0) HIP_TRY(hipMemsetAsync(c->rayStats.p, 0, 21 * 8, c->stream));
         tg.rayStats = (unsigned long long*)c->rayStats.p; }
     MakeFrameConstants(c->scene, c->camera, r.s, c->samplesRendered, r.timeSeed, c->selX, c->selY, r.pf);
+    if (const int64_t lights = opt<OPT_debug_light_count>(c)) r.pf.LightCount = (uint32_t)std::min<int64_t>(lights, 0xffffffffll);
     if (opt<OPT_camera_constants>(c) != 0) cameraConstants(r.pf, W, H, tg);
 }
 
@@ -575,7 +576,12 @@ static void pickCopy(RenderCall& r)
      * the occupancy copy) */
     const PtShape planned{r.mode, r.groups, r.adaptive, r.count, c->sceneInLds, r.twoLevel, plan.compact_nodes != 0, plan.stack_overflow_entries != 0, true,
         plan.prepass != TB_PLAN_PREPASS_OFF, false, plan.guided_groups != 0};
-    if (r.copy == v->hi && v->lds && pt_pick_form(*v->lds->row, planned).ok && LdsCopyFits(v->wavesLds(), c->ds.stackDepth, c->ds.ldsBlobBytes)) {
+    /* that copy fetches the shading tables without bounds checks (kernels/pt_variant_matte6.hip): only for a scene whose tables the host has checked
+     * (lds_image.h SceneTablesInRange) and a call whose light indices stay inside the light table -- the index is (uint32_t)(rnd * LightCount) with
+     * rnd < 1, and below 2^23 the fp32 product cannot round up to LightCount.  Any other keeps the occupancy copy with its guards */
+    const bool tablesChecked = c->tablesInRange && r.pf.LightCount <= c->ds.numLights && r.pf.LightCount < (1u << 23);
+    if (r.copy == v->hi && v->lds && pt_pick_form(*v->lds->row, planned).ok && LdsCopyFits(v->wavesLds(), c->ds.stackDepth, c->ds.ldsBlobBytes) &&
+        tablesChecked) {
         r.copy = v->lds; c->lastCopyWaves = v->wavesLds(); }
     /* the adaptive launch, one pixel per lane, is the base copy's; the list-driven frame-group launch (rule TB_PLAN_RULE_ADAPTIVE_GROUPS) keeps the copy
      * chosen above */

@@ -327,6 +327,8 @@ void finalizeScene(tb_context* c, bool build)
     d.materials = upload(c, devMat); d.numMaterials = (uint32_t)s.materials.size();
     d.textureData = upload(c, s.textureData); d.numTextureData = (uint32_t)s.textureData.size();
     d.lights = upload(c, devLight); d.numLights = (uint32_t)s.lights.size();
+    c->tablesInRange = SceneTablesInRange(s.trisB.data(), s.trisB.size(), devHit.data(), devHit.size(), s.indexBuffer.data(), s.indexBuffer.size(),
+        s.vertexBuffer.size(), s.materials.size());
     d.images = upload(c, s.images); d.numImages = (uint32_t)s.images.size();
     d.texelPool = upload(c, s.texelPool);
     d.envMap = upload(c, s.envMap); d.envWidth = s.envWidth; d.envHeight = s.envHeight;

@@ -224,6 +224,14 @@ int tb_host_scene_lds_image(tb_host_scene* h, uint8_t* out, uint32_t capacity, t
     memcpy(out, im.bytes.data(), im.bytes.size());
     return TB_OK;
 }
+int tb_host_scene_tables_in_range(const TbTriB* tris, uint32_t numTris, const uint32_t* hitGroups, uint32_t numHitGroups, const uint32_t* indices,
+    uint32_t numIndices, uint32_t numVertexFloats, uint32_t numMaterials)
+{
+    if ((numTris && !tris) || (numHitGroups && !hitGroups) || (numIndices && !indices)) return TB_E_INVALID;
+    std::vector<TbDevHitGroup> hg(numHitGroups);
+    for (uint32_t i = 0; i < numHitGroups; i++) hg[i] = TbDevHitGroup{hitGroups[4 * i], hitGroups[4 * i + 1], hitGroups[4 * i + 2], 0};
+    return SceneTablesInRange(tris, numTris, hg.data(), hg.size(), indices, numIndices, numVertexFloats, numMaterials) ? 1 : 0;
+}
 int tb_host_scene_triangles(tb_host_scene* h, const float** pos, uint32_t* nv, const uint32_t** tvi, const uint32_t** tg, const uint32_t** tp,
     const uint32_t** tf, uint32_t* nt)
 {

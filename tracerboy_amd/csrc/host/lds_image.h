@@ -48,6 +48,26 @@ inline LdsImage BuildLdsImage(const TbNodeB* nodes, size_t numNodes, const TbTri
     return im;
 }
 
+/* Whether every index the kernels can form into the shading tables is in range (pt_device.hpp fetch_surface, load_vertex, fetch_material,
+ * shadow_hit_is_light): for every triangle record its geometry index, the index triple of its primitive, the three vertices the triple names and
+ * the hit group's material.  The tables in their device form: hit groups with offsets in elements, vertices as floats, 8 per vertex.  Sums in 64
+ * bits: an index near 2^32, whose 32-bit sum would wrap into range on the device, is out of range here.  The copy whose fetches carry no bounds
+ * check (kernels/pt_variant_matte6.hip) runs only for a scene this holds for (context_render.cpp pickCopy); light indices are checked per call. */
+inline bool SceneTablesInRange(const TbTriB* tris, size_t numTris, const TbDevHitGroup* hitGroups, size_t numHitGroups, const uint32_t* indices,
+    size_t numIndices, size_t numVertexFloats, size_t numMaterials)
+{
+    for (size_t i = 0; i < numTris; i++) {
+        if (tris[i].geometryIndex >= numHitGroups) return false;
+        const TbDevHitGroup& g = hitGroups[tris[i].geometryIndex];
+        const uint64_t iAt = (uint64_t)g.iFirst + 3ull * tris[i].primitiveIndex;
+        if (iAt + 3ull > numIndices) return false;
+        for (int k = 0; k < 3; k++)
+            if (8ull * indices[iAt + k] + g.vFirst + 8ull > numVertexFloats) return false;
+        if (g.MaterialIndex >= numMaterials) return false;
+    }
+    return true;
+}
+
 /* entries per lane of the traversal stack: a root-to-leaf path of bvhMaxDepth nodes has bvhMaxDepth - 1 inner nodes, each of which parks at most
  * one far child, so a walk never holds more than bvhMaxDepth - 1 entries.  The spare one is entry 0 of the walks that keep a sentinel there
  * (pt_device.hpp, the LDS steps) */

@@ -18,6 +18,7 @@ enum : uint32_t {
     X(primary_prepass, 1, 0) X(first_bounce, 0, 0) X(compact_hits, 1, 0) X(compact_stamp_bits, 32, 0) X(overlap_launches, 1, 0) \
     X(guided_groups, 1, 0) X(costly_first, 1, 0) X(costly_late_samples, 1ll << 40, 0) X(banded_items, 0, 0) X(camera_constants, 1, 0) \
     X(count_rays, 0, OPT_RESETS_HISTORY) X(aov, 0, OPT_RESETS_HISTORY) X(force_full_variant, 0, 0) X(debug_profile_groups, 0, 0) X(alpha_test, 0, 0) \
+    X(debug_light_count, 0, OPT_RESETS_HISTORY | OPT_NOT_NEGATIVE) /* not 0: a call's TbPerFrameConstants::LightCount, whatever the scene holds (tests) */ \
     X(post_denoised, 0, 0) /* tb_post_process(LIT) reads the denoised still of tb_denoise */ \
     X(denoise_guides, 0, 0) /* tb_denoise: 0 = the last frame's AOVs, 1 = the guide pass's normals and positions, 2 = 1 + albedo demodulation */ \
     X(adaptive, 0, 0) X(adaptive_min_frames, 1024 /* the reference's */, OPT_NOT_NEGATIVE) X(adaptive_test, 0, OPT_ZERO_OR_ONE) \

@@ -337,8 +337,43 @@ TBD void walk_owns(tb3& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z));
  *     keeps the ADDRESS of its top entry.  A push is an add and a write, a pop a read and an add -- no count to compare with zero, no branch, no
  *     address made from the count: the pop that finds nothing reads DONE.  A walk holds at most stackDepth - 1 entries (host/lds_image.h), so the
  *     column's stackDepth entries hold them and the sentinel;
+ *   - a leaf is tested with tri_test_lds below: permuted copies only, one predicate in front of the division (docs/experiments/r10.md).  The walk
+ *     assumes what its image gives it: every leaf ref names a record of six permuted copies, no instance base, and a feature set without the alpha
+ *     filter (the static_assert in traverse).
  * (Carrying "is it an inner node" as one value for the parking ballot and the loop's mask removes a v_cmp and adds ten scalar mask instructions
  * per step: -6 %, docs/experiments/r8_one_predicate.patch.) */
+/* The triangle test of the LDS steps (docs/experiments/r10.md): tri_test's permuted branch -- the LDS image holds permuted copies only, its kernels
+ * carry no alpha filter and no instance base -- with ONE predicate in front of the division.  tri_test leaves through four early returns, which the
+ * structurizer turns into nested exec regions: 13 scalar mask instructions and 7 branches and waits per pass of a kernel that pays per issued
+ * instruction, scalar ones included.  Here every lane at a leaf computes U, V, W, det, T and sT, the rejections are combined without short circuit,
+ * and the IEEE division, t0 and the hit update stay under the one `if`.  Every arithmetic operation, its operands and its order are tri_test's, and
+ * the comparisons are the same comparisons (NaN and a zero det decide as they did); a lane that would have returned early computes values nobody
+ * reads. */
+TBD void tri_test_lds(Hit& best, float tMin, const RayPre& r, const TbTriB& tri)
+{
+    const tbf2 oxy = {r.operm.x, r.operm.y}, shear = {r.shear.x, r.shear.y};
+    float Az = tri.v0[2] - r.operm.z, Bz = tri.v1[2] - r.operm.z, Cz = tri.v2[2] - r.operm.z;
+    const tbf2 A = __builtin_elementwise_fma(-shear, f2_splat(Az), f2_ld(tri.v0) - oxy);
+    const tbf2 B = __builtin_elementwise_fma(-shear, f2_splat(Bz), f2_ld(tri.v1) - oxy);
+    const tbf2 C = __builtin_elementwise_fma(-shear, f2_splat(Cz), f2_ld(tri.v2) - oxy);
+    const tbf2 pu = C * B.yx, pv = A * C.yx, pw = B * A.yx;
+    const float U = pu.x - pu.y, V = pv.x - pv.y, W = pw.x - pw.y;
+    const float det = U + V + W;
+    const bool mixed = ((U < 0.0f) | (V < 0.0f) | (W < 0.0f)) & ((U > 0.0f) | (V > 0.0f) | (W > 0.0f));
+    Az = r.shear.z * Az; Bz = r.shear.z * Bz; Cz = r.shear.z * Cz;
+    const float T = tb_fma(W, Cz, tb_fma(V, Bz, U * Az));
+    float sT = tb_abs(T);
+    if ((T > 0.0f) != (det > 0.0f)) sT = -sT;
+    const bool cand = !mixed & (det != 0.0f) & !((sT < 0.0f) | (sT > best.t * tb_abs(det)));
+    if (cand) {
+        const float rcpDet = 1.0f / det;
+        const float t0 = T * rcpDet;
+        if (t0 < best.t && t0 > tMin) {
+            best.t = t0; best.u = V * rcpDet; best.v = W * rcpDet;
+            best.prim = tri.primitiveIndex; best.geom = tri.geometryIndex;
+        }
+    }
+}
 typedef const __attribute__((address_space(3))) uint8_t* LdsBytes;
 TBD uint32_t lds_address(const void* p) { return (uint32_t)(uintptr_t)(LdsBytes)p; } /* of a pointer into LDS */
 TBD const uint8_t* lds_pointer(uint32_t a) { return (const uint8_t*)(LdsBytes)(uintptr_t)a; }
@@ -381,7 +416,7 @@ TBD bool traverse(const SceneRefs& sc, const TbDeviceScene& ds, tb3 o, tb3 d, Hi
     constexpr uint32_t DONE = 0xffffffffu; /* has the leaf bit set, so it also leaves the inner loop */
     const int PARK_MIN = (int)ds.parkMin; /* option "park_min", default 8 */
     if constexpr (LDS_STEPS) {
-        static_assert(!HYBRID && !NODEC, "the LDS steps: whole stack in LDS, layout B");
+        static_assert(!HYBRID && !NODEC && !ALPHA, "the LDS steps: whole stack in LDS, layout B, no alpha filter");
         const uint32_t image = lds_address(sc.nodes);
         const uint32_t leafAdd = (r.permUnits << 4) + (TB_BVH_LEAF_FLAG + image + ds.offTris);
         const uint32_t* sp = stack; /* the lane's top entry */
@@ -423,7 +458,7 @@ TBD bool traverse(const SceneRefs& sc, const TbDeviceScene& ds, tb3 o, tb3 d, Hi
                 if (PROFILE) prof_hit(prof, PROF_LEAF);
                 const TbTriB tri = ((const TriB16*)lds_pointer(ref + leafAdd))->t;
                 if (RAY_COUNTERS) tris++;
-                tri_test<ALPHA>(best, MIN_T, o, r, tri, true, sc, ds);
+                tri_test_lds(best, MIN_T, r, tri);
                 ref = *sp; sp -= stride;
             }
             inner = __ballot((int32_t)ref >= 0);
@@ -625,11 +660,19 @@ struct __attribute__((aligned(16))) Vertex8 { float f[8]; };   /* N.xyz, UV.xy, 
 struct Index3 { uint32_t a, b, c; };
 
 /* out-of-range reads return 0 like the reference's raw buffer loads; a record is either wholly inside or treated as absent */
+/* PT_TABLES_CHECKED (defined by pt_variant_matte6.hip alone): the unit's launches are of scenes whose tables the host has checked
+ * (host/lds_image.h SceneTablesInRange) and of calls whose light indices stay below numLights (context_render.cpp pickCopy), so no index can be out
+ * of range and fetch_surface, load_vertex, fetch_material, shadow_hit_is_light and fetch_light fetch without the compare, the exec region and the
+ * zeros of the other case: nine sites per trip round the bounce loop, 50 of its v_mov (docs/experiments/r10.md). */
 struct __attribute__((aligned(16))) Vertex4 { float f[4]; };
 TBD Vertex8 load_vertex(const SceneRefs& sc, uint32_t firstFloat, bool second = true)
 {
     /* two 16-B pieces: normal and u; v and the tangent (second false: not fetched, zeros).  A vertex is wholly inside the buffer or absent. */
+#ifdef PT_TABLES_CHECKED
+    const bool inside = true;
+#else
     const bool inside = firstFloat + 8u <= sc.numVertexFloats;
+#endif
     Vertex4 a, b;
     for (int k = 0; k < 4; k++) a.f[k] = b.f[k] = 0.0f;
     if (inside) a = *(const Vertex4*)(sc.vertices + firstFloat);
@@ -643,12 +686,17 @@ TBD Vertex8 load_vertex(const SceneRefs& sc, uint32_t firstFloat, bool second = 
  * reads a texture (TbDeviceScene::textureUse) */
 TBD void fetch_surface(const SceneRefs& sc, const Hit& h, Surface& s, bool needTangent, bool needUV = true)
 {
+#ifdef PT_TABLES_CHECKED
+    const TbDevHitGroup rec = sc.hitGroups[h.geom];
+    const Index3 ix = *(const Index3*)(sc.indices + (rec.iFirst + h.prim * 3));
+#else
     TbDevHitGroup rec;
     if (h.geom < sc.numHitGroups) rec = sc.hitGroups[h.geom];
     else { rec.MaterialIndex = 0; rec.vFirst = 0; rec.iFirst = 0; rec.pad = 0; }
     const uint32_t iAt = rec.iFirst + h.prim * 3;
     Index3 ix; ix.a = ix.b = ix.c = 0u;
     if (iAt + 3u <= sc.numIndices) ix = *(const Index3*)(sc.indices + iAt);
+#endif
     const float bx = 1 - h.u - h.v, by = h.u, bz = h.v; /* GetBarycentrics3 :135-138 */
     const Vertex8 v0 = load_vertex(sc, 8 * ix.a + rec.vFirst, needUV), v1 = load_vertex(sc, 8 * ix.b + rec.vFirst, needUV),
                   v2 = load_vertex(sc, 8 * ix.c + rec.vFirst, needUV);
@@ -772,18 +820,26 @@ TBD tb3 sample_environment(const TbDeviceScene& ds, tb3 v)
 /* ---- materials: RayGenCommon.h:298-341, kernel.glsl:1224-1246 ---------------------------------- */
 TBD TbMaterial fetch_material(const SceneRefs& sc, uint32_t id)
 {
+#ifdef PT_TABLES_CHECKED
+    return sc.materials[id].m;
+#else
     TbMaterial m;
     if (id < sc.numMaterials) m = sc.materials[id].m; else memset(&m, 0, sizeof m);
     return m;
+#endif
 }
 
 /* Outcome of a shadow feeler's first hit when GetMaterial draws no random number (no mix materials): only the LIGHT
  * flag of the base material matters (kernel.glsl:1460-1516; texture overrides never touch that flag). */
 TBD bool shadow_hit_is_light(const SceneRefs& sc, uint32_t geom)
 {
+#ifdef PT_TABLES_CHECKED
+    return (sc.materials[sc.hitGroups[geom].MaterialIndex].m.Flags & TB_MAT_LIGHT) != 0;
+#else
     const uint32_t mi = geom < sc.numHitGroups ? sc.hitGroups[geom].MaterialIndex : 0u;
     const int flags = mi < sc.numMaterials ? sc.materials[mi].m.Flags : 0;
     return (flags & TB_MAT_LIGHT) != 0;
+#endif
 }
 
 TBD bool is_valid_hit(const SceneRefs& sc, const TbDeviceScene& ds, uint32_t geom, uint32_t prim, float u, float v)
@@ -1039,9 +1095,13 @@ TBD void path_pre_extend(Path& p, const TbPerFrameConstants& pf)
 /* GetOneLightSample, RayGenCommon.h:170-261 */
 TBD TbLight fetch_light(const SceneRefs& sc, uint32_t i)
 {
+#ifdef PT_TABLES_CHECKED
+    return sc.lights[i].l;
+#else
     TbLight l;
     if (i < sc.numLights) l = sc.lights[i].l; else memset(&l, 0, sizeof l);
     return l;
+#endif
 }
 TBD tb3 random_barycentric(float& seed, float time)
 {
