@@ -335,7 +335,8 @@ uint64_t tb_state_digest_host(const void* words, uint64_t n_words);
  * three treelet passes = the tree the reference's PREFER_FAST_TRACE build traverses, 4 = the same built on the GPU), "flatten_instances".
  * Builder 1: "reinsertion_passes" (-1 = the library's choice), "reinsertion_share" (percent of the subtrees a pass tries, largest first),
  * "presplit" (percent of extra references from cutting the triangles with the largest, emptiest boxes before the build; 0 = off, the default:
- * measured to raise box tests).  Launch policy: "frame_group", "guided_groups" (0 never, 1 = calls that wait [default], 2 always: the frame
+ * measured to raise box tests), "wave_tree" (-1 = the library's choice: on where reinsertion passes run, 0 = off, 1 = on: for a scene that will be LDS-resident the tree is then
+ * optimised for what a 64-lane wave pays, host/wave_cost.h; every other scene's tree is untouched).  Launch policy: "frame_group", "guided_groups" (0 never, 1 = calls that wait [default], 2 always: the frame
  * groups of a region shrink over the last groups of a launch), "primary_prepass", "overlap_launches", "costly_first" (+ "costly_late_samples"), "high_occupancy", "stack_lds_cap",
  * "compact_hits", "camera_constants", "texture_use_hint", "node_layout", "node_order" -- each described where launch_plan.h / context_render.cpp use it.
  * Adaptive sampling: "adaptive" (0/1), "adaptive_min_frames", "adaptive_test" (0 = the skip test runs before every frame
@@ -563,7 +564,8 @@ int tb_run_nn_to_rgba8(tb_context* ctx, uint32_t width, uint32_t height, const f
 typedef struct tb_host_scene tb_host_scene;
 /* load_flags: bit 0 = flatten instanced shapes (option "flatten_instances"), bit 1 = do NOT flip texture v (the Assimp
  * convention; .pbrt / .pbf loads flip: m_flipTextureUVs, TracerBoy.cpp:1208,1222; option "flip_texture_uvs" = 0).
- * bvh_builder: option "bvh_builder" in bits 0-7; for builder 1 optionally (reinsertion passes + 1) << 8 and (share of the subtrees a
+ * bvh_builder: option "bvh_builder" in bits 0-5; for builder 1 optionally (wave_tree + 1) << 6 -- option "wave_tree": 1 = off, 2 = on --,
+ * (reinsertion passes + 1) << 8 and (share of the subtrees a
  * pass tries, percent) << 16 -- options "reinsertion_passes" / "reinsertion_share" -- and (percent of extra references from pre-splitting the
  * triangles with the emptiest boxes, <= 127) << 24 -- option "presplit"; a zero field leaves the library's own choice. */
 int tb_host_scene_load(const char* pbrt_path, int bvh_builder, int load_flags, tb_host_scene** out, char* err, uint32_t err_len);
@@ -588,6 +590,25 @@ int tb_host_scene_lds_image(tb_host_scene* s, uint8_t* out, uint32_t capacity, t
  * record -- MaterialIndex, first vertex float, first index, unused. */
 int tb_host_scene_tables_in_range(const TbTriB* tris, uint32_t num_tris, const uint32_t* hit_groups, uint32_t num_hit_groups, const uint32_t* indices,
     uint32_t num_indices, uint32_t num_vertex_floats, uint32_t num_materials);
+/* What a 64-lane wave pays to walk a tree (host/wave_cost.h; builder 1's wave stage, option "wave_tree").  Trips of a wave through the inner loop's
+ * body and leaf passes under the schedule of the LDS-resident walk, the lanes active in them, passes whose leaf step no lane takes, and
+ * cost = inner_trips x inner_insts + leaf_trips x leaf_insts of tb_wave_stage_info. */
+typedef struct tb_wave_trips { uint64_t inner_trips, leaf_trips, idle_passes, inner_active, leaf_active; double cost; } tb_wave_trips;
+/* what the wave stage did when the scene was built: ran = 0 where it did not run (option off, another builder, a scene that is not LDS-resident);
+ * before / after: its model rays over the tree it was given and the tree it returned (trips and cost only); depth_limit in nodes */
+typedef struct tb_wave_stage_info { uint32_t ran, rays, seed, park_min, depth_limit, moves, evaluations, inner_insts, leaf_insts, reserved;
+    tb_wave_trips before, after; double milliseconds; } tb_wave_stage_info;
+/* up to 64 step strings of 'I' (inner node visited) and 'L' (triangle tested), each ended by a 0, replayed in lock step */
+int tb_wave_replay(const char* const* steps, uint32_t lanes, uint32_t park_min, tb_wave_trips* out);
+/* n rays over the tree of a one-level host scene with the kernels' rule: steps per ray and, where steps != null, the step strings back to back, each
+ * ended by a 0 (TB_E_INVALID where steps_capacity is short).  t_max = null: the closest-hit walk's */
+int tb_host_scene_wave_walk(tb_host_scene* s, uint32_t n, const float* origins, const float* dirs, const float* t_max, uint32_t* inner_steps,
+    uint32_t* leaf_steps, char* steps, uint64_t steps_capacity);
+/* the wave stage's model rays of a scene, `waves` waves of 64 (0 / 0 / -1: the stage's own seed, size and share of feeler waves); returns their number */
+int tb_host_scene_wave_rays(tb_host_scene* s, uint32_t seed, uint32_t waves, int feeler_percent, float* origins, float* dirs, float* t_max, uint32_t capacity);
+/* ... and what they cost over the scene's tree (park_min 0: that of a scene in LDS) */
+int tb_host_scene_wave_cost(tb_host_scene* s, uint32_t seed, uint32_t waves, int feeler_percent, uint32_t park_min, tb_wave_trips* out);
+int tb_host_scene_wave_stage(tb_host_scene* s, tb_wave_stage_info* out);
 /* Diagnostic: the build's own parse of a PBRT file in the record format of oracle/ref_dump.cpp. */
 int tb_host_pbrt_dump(const char* pbrt_path, const char* out_path, char* err, uint32_t err_len);
 int tb_host_scene_triangles(tb_host_scene* s, const float** positions, uint32_t* num_vertices, const uint32_t** tri_vertex_index,

@@ -88,6 +88,44 @@ def lockstep(samples, park_min=8):
     return total
 
 
+def lockstep_queue(samples, park_min=2, region=16, waves=4):
+    """pt_persistent's frame-group form as rounds 8 and 11 replayed it: a workgroup of `waves` waves owns a region x region block of the picture and
+    its samples form one queue, frame by frame; a lane that has finished its sample takes the queue's next one at the top of its wave's next
+    iteration; per iteration slot 1 = bounce ray, slot 2 = shadow feeler (the lock-step two-slot schedule); the wave that is earliest in time acts
+    next.  Returns the summed Wave."""
+    total = Wave(park_min)
+    regions = collections.defaultdict(list)
+    for (x, y, f), rays in samples.items():
+        regions[(x // region, y // region)].append(((f, (y % region) * region + x % region), rays))
+    for key in sorted(regions):
+        queue = [rays for _, rays in sorted(regions[key], key=lambda e: e[0])]
+        qi = 0
+        cur = [[None] * 64 for _ in range(waves)]; pos = [[0] * 64 for _ in range(waves)]; clock = [0.0] * waves
+        while True:
+            acted = False
+            for i in sorted(range(waves), key=lambda k: clock[k]):
+                for l in range(64):
+                    if cur[i][l] is None and qi < len(queue): cur[i][l] = queue[qi]; pos[i][l] = 0; qi += 1
+                live = [l for l in range(64) if cur[i][l] is not None]
+                if not live: continue
+                for kind in ("E", "S"):
+                    w = Wave(park_min); n = 0
+                    for l in live:
+                        q = cur[i][l]
+                        if pos[i][l] < len(q) and (q[pos[i][l]][0] == kind or (kind == "E" and q[pos[i][l]][0] == "W")):
+                            w.give(l, q[pos[i][l]][1]); pos[i][l] += 1; n += 1
+                    if n:
+                        while w.nbusy(): w.round()
+                        clock[i] += w.cost(); total.merge(w)
+                clock[i] += 1.0
+                for l in live:
+                    if pos[i][l] >= len(cur[i][l]): cur[i][l] = None
+                acted = True
+                break
+            if not acted: break
+    return total
+
+
 def lockstep_regen(samples, regen_thresh=1, park_min=8, costs=(1100.0, 750.0, 400.0, 250.0, 300.0)):
     """pt_persistent with its non-traversal phases priced too (wave-instructions per trip: regenerate, closest-hit
     shading, scatter, shadow slot, ray setup) and a regeneration threshold: finished lanes start their next sample only

@@ -187,6 +187,17 @@ class tb_lds_image_info(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("bytes", "off_nodes", "off_tris", "num_nodes", "num_tris", "node_stride", "tri_copies", "root_ref", "stack_depth")]
 
 
+class tb_wave_trips(C.Structure):
+    """include/tracerboy_hip.h tb_wave_trips: what a 64-lane wave pays for a set of walks (csrc/host/wave_cost.h)."""
+    _fields_ = [(n, C.c_uint64) for n in ("inner_trips", "leaf_trips", "idle_passes", "inner_active", "leaf_active")] + [("cost", C.c_double)]
+
+
+class tb_wave_stage_info(C.Structure):
+    """include/tracerboy_hip.h tb_wave_stage_info: what builder 1's wave stage did when a host scene was built."""
+    _fields_ = [(n, C.c_uint32) for n in ("ran", "rays", "seed", "park_min", "depth_limit", "moves", "evaluations", "inner_insts", "leaf_insts",
+                                          "reserved")] + [("before", tb_wave_trips), ("after", tb_wave_trips), ("milliseconds", C.c_double)]
+
+
 class tb_state_info(C.Structure):
     """include/tracerboy_hip.h tb_state_info: the header of a render-state file."""
     _fields_ = [("version", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("first_frame", C.c_uint32), ("next_frame", C.c_uint32),

@@ -139,6 +139,11 @@ def lib():
         "tb_host_scene_lds_image": (C.c_int, [vp, P(C.c_uint8), C.c_uint32, P(abi.tb_lds_image_info)]),
         "tb_host_scene_tables_in_range": (C.c_int, [P(abi.TbTriB), C.c_uint32, P(C.c_uint32), C.c_uint32, P(C.c_uint32)] + [C.c_uint32] * 3),
         "tb_host_scene_triangles": (C.c_int, [vp, P(P(C.c_float)), P(C.c_uint32), P(P(C.c_uint32)), P(P(C.c_uint32)), P(P(C.c_uint32)), P(P(C.c_uint32)), P(C.c_uint32)]),
+        "tb_wave_replay": (C.c_int, [P(C.c_char_p), C.c_uint32, C.c_uint32, P(abi.tb_wave_trips)]),
+        "tb_host_scene_wave_walk": (C.c_int, [vp, C.c_uint32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32), C.c_char_p, C.c_uint64]),
+        "tb_host_scene_wave_rays": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32]),
+        "tb_host_scene_wave_cost": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, P(abi.tb_wave_trips)]),
+        "tb_host_scene_wave_stage": (C.c_int, [vp, P(abi.tb_wave_stage_info)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export what the header declares
@@ -299,10 +304,12 @@ class HostScene:
     """Host-only LoadScene (parse + convert + BVH build): no GPU needed, renders nothing."""
 
     def __init__(self, path=None, procedural=None, bvh_builder=0, flatten_instances=True, flip_texture_uvs=True, reinsertion_passes=None,
-                 reinsertion_share=None, presplit=None):
+                 reinsertion_share=None, presplit=None, wave_tree=None):
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
-        # the builder word of include/tracerboy_hip.h: builder | (passes + 1) << 8 | share << 16
+        # the builder word of include/tracerboy_hip.h: builder | (wave_tree + 1) << 6 | (passes + 1) << 8 | share << 16
+        if wave_tree is not None:
+            bvh_builder |= (1 + (1 if wave_tree else 0)) << 6
         if reinsertion_passes is not None:
             bvh_builder |= (int(reinsertion_passes) + 1) << 8
         if reinsertion_share is not None:
@@ -387,6 +394,62 @@ class HostScene:
         if rc != 0:
             raise TracerBoyError(rc, "tb_host_scene_lds_image")
         return buf, info
+
+    # ---- what a wave pays for the tree (csrc/host/wave_cost.h) ----
+    def wave_stage(self):
+        """tb_wave_stage_info: what builder 1's wave stage did when this scene was built (ran = 0: it did not run)."""
+        info = abi.tb_wave_stage_info()
+        rc = lib().tb_host_scene_wave_stage(self._h, C.byref(info))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_wave_stage")
+        return info
+
+    def wave_rays(self, seed=0, waves=0, feeler_percent=-1):
+        """(origins, dirs, t_max) of the wave stage's model rays for this scene; 0 / 0 / -1: the stage's own seed, size and feeler share."""
+        fp = C.POINTER(C.c_float)
+        n = lib().tb_host_scene_wave_rays(self._h, seed, waves, feeler_percent, None, None, None, 0)
+        if n < 0:
+            raise TracerBoyError(n, "tb_host_scene_wave_rays")
+        o = np.zeros((n, 3), dtype=np.float32); d = np.zeros((n, 3), dtype=np.float32); t = np.zeros(n, dtype=np.float32)
+        lib().tb_host_scene_wave_rays(self._h, seed, waves, feeler_percent, o.ctypes.data_as(fp), d.ctypes.data_as(fp), t.ctypes.data_as(fp), n)
+        return o, d, t
+
+    def wave_walk(self, origins, dirs, t_max=None, want_steps=False):
+        """The single-ray walk of wave_cost.h over this scene's tree: (inner steps, leaf steps[, step strings]) per ray."""
+        fp = C.POINTER(C.c_float); up = C.POINTER(C.c_uint32)
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3); d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        t = None if t_max is None else np.ascontiguousarray(t_max, dtype=np.float32)
+        n = len(o); inner = np.zeros(n, dtype=np.uint32); leaf = np.zeros(n, dtype=np.uint32)
+        rc = lib().tb_host_scene_wave_walk(self._h, n, o.ctypes.data_as(fp), d.ctypes.data_as(fp), None if t is None else t.ctypes.data_as(fp),
+                                           inner.ctypes.data_as(up), leaf.ctypes.data_as(up), None, 0)
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_wave_walk")
+        if not want_steps:
+            return inner, leaf
+        cap = int(inner.sum()) + int(leaf.sum()) + n
+        buf = C.create_string_buffer(cap)
+        rc = lib().tb_host_scene_wave_walk(self._h, n, o.ctypes.data_as(fp), d.ctypes.data_as(fp), None if t is None else t.ctypes.data_as(fp), None, None, buf, cap)
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_wave_walk")
+        return inner, leaf, [w.decode() for w in buf.raw[:cap].split(b"\0")[:n]]
+
+    def wave_cost(self, seed=0, waves=0, feeler_percent=-1, park_min=0):
+        """tb_wave_trips of the model rays over this scene's tree."""
+        out = abi.tb_wave_trips()
+        rc = lib().tb_host_scene_wave_cost(self._h, seed, waves, feeler_percent, park_min, C.byref(out))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_wave_cost")
+        return out
+
+
+def wave_replay(steps, park_min=2):
+    """tb_wave_trips of up to 64 step strings of 'I' / 'L' replayed in lock step under the LDS-resident walk's schedule (tb_wave_replay)."""
+    arr = (C.c_char_p * max(len(steps), 1))(*[s.encode() for s in steps])
+    out = abi.tb_wave_trips()
+    rc = lib().tb_wave_replay(arr, len(steps), park_min, C.byref(out))
+    if rc != 0:
+        raise TracerBoyError(rc, "tb_wave_replay")
+    return out
 
 
 class TracerBoy:

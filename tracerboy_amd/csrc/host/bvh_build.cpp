@@ -17,10 +17,14 @@
  * tb_host_scene_view) and layout B (what the kernels fetch, tb_abi.h).
  */
 #include "host_scene.h"
+#include "launch_plan.h"
+#include "lds_image.h"
+#include "wave_cost.h"
 #include "../../../include/tb_vec.h"
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -373,7 +377,8 @@ void presplitReferences(const HostScene& s, Tree& t, int percent)
  * 32.9 to 26.7.  Moves that would deepen the tree beyond depthLimit are skipped (the traversal stack in LDS is as deep as
  * the tree).  Works on node ids: inner 0..N-2 with the root at 0, leaf N-1+k = order[k].  (Measured and dropped: accepting
  * moves by the simulated cost of the kernels' own walk over path-traced sample rays, child order included -- 47.9 box
- * tests on cornell-box, the same frame time.) */
+ * tests on cornell-box, the same frame time: the mean of single rays is not what a lock-step wave pays.  The wave stage
+ * below, optimizeForWaves, goes on from the tree these passes leave with the cost of a wave's trips, for LDS-resident scenes.) */
 void optimizeByReinsertion(const HostScene& s, Tree& t, int maxPasses, double minGain)
 {
     const uint32_t N = t.N; if (N < 4) return;
@@ -452,6 +457,115 @@ void optimizeByReinsertion(const HostScene& s, Tree& t, int maxPasses, double mi
         cost = now;
         if (!goOn) break;
     }
+}
+
+/* ---- wave stage (option "wave_tree"; docs/experiments/r11.md) --------------------------------------------------------------------------
+ * The passes above minimise what a random single ray pays.  The kernel of an LDS-resident scene walks 64 rays in lock step and pays for the longest
+ * lane of each wave: about 21 inner trips per wave-level walk against 7.4 inner steps per ray on cornell-box.  This stage takes the tree the area
+ * passes left and goes on with the same cut-and-reinsert move, judged by what a wave pays: wave_cost.h walks a fixed set of model rays, made from
+ * the scene's surfaces alone, replays them 64 at a time under the LDS steps' schedule and prices the trips in wave instructions.  For each cut
+ * subtree only the kWaveStagePlaces best places by induced area are priced (the ranking the branch-and-bound above descends by); a move is kept
+ * when the price falls, so the stage never returns a tree it prices above the one it was given.  Node 0 stays the root.  A move may not deepen the
+ * tree beyond what the area passes allow, nor beyond the depth at which the scene stays LDS-resident and the six-wave copy's workgroups still fit
+ * (LdsCopyFits, launch_plan.h) where they did.  It runs only for scenes that will be LDS-resident -- the size test of lds_image.h, from the counts
+ * -- so every other tree is byte for byte what the area passes left.
+ * Size: 24 waves of 64 rays, 42 % of them feelers (the share of feelers among the rays of the oracle's cornell-box log at depth 8: 0.423).  The
+ * 36 triangles of cornell-box are searched in 0.6 s on one core (409 trees priced; 48 waves find the same gain in 1.1 s).  Priced on the oracle's
+ * ray log of cornell-box 64 x 64 x 32 (scripts/wave_tree_price.py): 190.1 -> 180.7 wave instructions per sample, -5.0 %, where the model rays
+ * say -7.7 %; searches from two other seeds price at -4.7 % and -3.8 %.  (Model rays that all leave towards the scene's centre instead of either
+ * side by the hash: -3.7 % / -4.3 % on the log, dropped.) */
+constexpr bool kWaveTreeByDefault = true; /* option wave_tree = -1 */
+constexpr uint32_t kWaveStageWaves = 24, kWaveStageFeelerPercent = 42, kWaveStageSeed = 0x7b01u, kWaveStagePasses = 4, kWaveStagePlaces = 3;
+
+bool willBeLdsResident(const HostScene& s, uint32_t N, uint32_t depthNodes)
+{
+    if (!s.instances.empty() || !s.ldsSceneBudget) return false;
+    return LdsSceneBytes(N > 1 ? N - 1 : 1, N, s.hitGroups.size(), s.indexBuffer.size(), s.vertexBuffer.size(), s.materials.size(), s.lights.size(),
+        WalkStackDepth(depthNodes)) <= s.ldsSceneBudget;
+}
+
+void optimizeForWaves(const HostScene& s, Tree& t, HostScene::WaveStageReport& rep)
+{
+    const uint32_t N = t.N; if (N < 4) return;
+    const auto started = std::chrono::steady_clock::now();
+    const uint32_t M = 2 * N - 1, NONE = 0xffffffffu;
+    auto isLeaf = [&](uint32_t x) { return x >= N - 1; };
+    /* the leaves: bounds for the fit, triangles for the walk */
+    std::vector<tb3> lmn(N), lmx(N);
+    WaveTree wt; wt.v0.resize(N); wt.v1.resize(N); wt.v2.resize(N);
+    for (uint32_t k = 0; k < N; k++) { const Bounds b = boundsOfRef(s, t, t.order[k]); lmn[k] = b.mn; lmx[k] = b.mx;
+        const uint32_t tri = triOfRef(t, t.order[k]); wt.v0[k] = P(s, tri, 0); wt.v1[k] = P(s, tri, 1); wt.v2[k] = P(s, tri, 2); }
+    WaveSurfaces surf; WaveSurfacesOf(s, surf);
+    std::vector<WaveRay> rays;
+    WaveModelRays(surf, kWaveStageSeed, kWaveStageWaves, kWaveStageFeelerPercent, rays);
+    if (rays.empty()) return;
+    std::vector<char> arena;
+    uint32_t depthNow = 0;
+    auto price = [&]() { depthNow = WaveTreeFit(wt, N, t.left.data(), t.right.data(), lmn.data(), lmx.data()); rep.evaluations++;
+        return WaveCostOfTree(wt, rays, kLdsSceneParkMin, arena); };
+    WaveTrips cur = price();
+    /* depth limits, in nodes like HostScene::bvhMaxDepth: the area passes' step, the LDS budget, the six-wave copy */
+    const uint32_t d0 = depthNow, image = (uint32_t)LdsImageBytes(N - 1, N);
+    const bool sixFit = LdsCopyFits(6, WalkStackDepth(d0), image);
+    auto depthOk = [&](uint32_t d) { return d <= (d0 <= 31u ? 31u : (d0 <= 39u ? 39u : d0)) && willBeLdsResident(s, N, d) &&
+        (!sixFit || LdsCopyFits(6, WalkStackDepth(d), image)); };
+    uint32_t depthLimit = d0; while (depthOk(depthLimit + 1)) depthLimit++;
+    rep.ran = 1; rep.rays = (uint32_t)rays.size(); rep.seed = kWaveStageSeed; rep.parkMin = kLdsSceneParkMin; rep.depthLimit = depthLimit;
+    rep.innerBefore = cur.inner; rep.leafBefore = cur.leaf; rep.costBefore = cur.cost();
+
+    std::vector<uint32_t> parent(M, NONE);
+    for (uint32_t i = 0; i + 1 < N; i++) { parent[t.left[i]] = i; parent[t.right[i]] = i; }
+    std::vector<Bounds> box(M); std::vector<float> sa(M);
+    std::vector<uint32_t> pre, st;
+    auto refitBelow = [&](uint32_t root) { /* builder boxes of a subtree, bottom-up; leaves the subtree's nodes in `pre` */
+        pre.clear(); st.clear(); st.push_back(root);
+        while (!st.empty()) { const uint32_t x = st.back(); st.pop_back(); pre.push_back(x); if (!isLeaf(x)) { st.push_back(t.left[x]); st.push_back(t.right[x]); } }
+        for (size_t w = pre.size(); w-- > 0;) { const uint32_t x = pre[w];
+            if (isLeaf(x)) { Bounds b; b.mx = lmx[x - (N - 1)]; b.mn = tb3_min(lmn[x - (N - 1)], b.mx - tb3_splat(0.001f)); box[x] = b; }
+            else { box[x] = box[t.left[x]]; grow(box[x], box[t.right[x]]); }
+            sa[x] = area(box[x]); } };
+    auto replaceChild = [&](uint32_t p, uint32_t from, uint32_t to) { if (t.left[p] == from) t.left[p] = to; else t.right[p] = to; parent[to] = p; };
+    struct Place { float induced; uint32_t node; };
+    std::vector<Place> places; std::vector<uint32_t> cand(M - 1), inTree;
+    for (uint32_t pass = 0; pass < kWaveStagePasses; pass++) {
+        bool moved = false;
+        refitBelow(0);
+        for (uint32_t x = 1; x < M; x++) cand[x - 1] = x;
+        std::stable_sort(cand.begin(), cand.end(), [&](uint32_t a, uint32_t b) { return sa[a] > sa[b]; });
+        for (uint32_t x : cand) {
+            const uint32_t p = parent[x]; if (p == NONE || p == 0) continue; /* children of the root stay: node 0 remains the root */
+            const uint32_t g = parent[p], oldLeft = t.left[p], oldRight = t.right[p], sib = oldLeft == x ? oldRight : oldLeft;
+            const bool pWasLeft = t.left[g] == p;
+            replaceChild(g, p, sib); parent[p] = NONE;
+            refitBelow(x); const Bounds bx = box[x];
+            refitBelow(0); inTree = pre;
+            places.clear();
+            for (uint32_t y : inTree) { if (y == 0 || y == sib) continue;
+                Bounds u = box[y]; grow(u, bx); float induced = area(u);
+                for (uint32_t a = parent[y]; a != NONE; a = parent[a]) { Bounds w = box[a]; grow(w, bx); induced += area(w) - sa[a]; }
+                places.push_back(Place{induced, y}); }
+            std::stable_sort(places.begin(), places.end(), [](const Place& a, const Place& b) { return a.induced < b.induced; });
+            uint32_t best = NONE; WaveTrips bestTrips = cur;
+            for (size_t k = 0; k < places.size() && k < kWaveStagePlaces; k++) {
+                const uint32_t y = places[k].node, q = parent[y];
+                replaceChild(q, y, p); t.left[p] = y; t.right[p] = x; parent[y] = p; parent[x] = p;
+                const WaveTrips tr = price();
+                if (depthNow <= depthLimit && tr.cost() < bestTrips.cost()) { best = y; bestTrips = tr; }
+                replaceChild(q, p, y); parent[p] = NONE;
+            }
+            if (best != NONE) {
+                const uint32_t q = parent[best];
+                replaceChild(q, best, p); t.left[p] = best; t.right[p] = x; parent[best] = p; parent[x] = p;
+                cur = bestTrips; moved = true; rep.moves++;
+            } else { /* back where it was, child order included */
+                if (pWasLeft) t.left[g] = p; else t.right[g] = p;
+                parent[p] = g; t.left[p] = oldLeft; t.right[p] = oldRight; parent[sib] = p; parent[x] = p;
+            }
+        }
+        if (!moved) break;
+    }
+    rep.innerAfter = cur.inner; rep.leafAfter = cur.leaf; rep.costAfter = cur.cost();
+    rep.milliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count();
 }
 
 /* ---- treelet passes (builder 3) -------------------------------------------------------------------------------------
@@ -557,6 +671,15 @@ void BuildBvhSingle(HostScene& s, int builder)
         buildSah(s, t);
         const int passes = s.reinsertionPasses >= 0 ? s.reinsertionPasses : (N <= 4096 ? 16 : 3); /* option "reinsertion_passes" */
         if (passes > 0) optimizeByReinsertion(s, t, passes, N <= 4096 ? 1e-6 : 5e-3);
+        /* option "wave_tree": the wave stage, for a scene that will be LDS-resident (at the depth the tree has now; the stage keeps it so) */
+        s.waveStage = HostScene::WaveStageReport{};
+        /* (the library's own choice: where the reinsertion passes run -- reinsertion_passes = 0 asks for the top-down tree as it was built) */
+        const bool waveStage = s.waveTree >= 0 ? s.waveTree != 0 : (kWaveTreeByDefault && passes > 0);
+        if (waveStage && N >= 4) {
+            std::vector<tb3> mn(N, tb3_splat(0.0f)); WaveTree probe; /* the depth alone: boxes of no matter */
+            const uint32_t depth = WaveTreeFit(probe, N, t.left.data(), t.right.data(), mn.data(), mn.data());
+            if (willBeLdsResident(s, N, depth)) optimizeForWaves(s, t, s.waveStage);
+        }
     } else {
         buildLbvh(s, t);
         if (builder == 3) treeletPasses(s, t, 3);
@@ -758,6 +881,7 @@ void BuildBvhWith(HostScene& s, const std::function<void(HostScene&)>& single, c
         HostScene::Blas& bl = s.blas[b];
         HostScene tmp;
         tmp.reinsertionPasses = s.reinsertionPasses; tmp.reinsertionShare = s.reinsertionShare; tmp.presplitPercent = s.presplitPercent;
+        tmp.waveTree = 0; /* a two-level scene is never LDS-resident */
         tmp.positions.swap(s.positions);
         tmp.triVertexIndex.assign(s.triVertexIndex.begin() + 3ull * bl.firstTri, s.triVertexIndex.begin() + 3ull * (bl.firstTri + bl.numTris));
         tmp.triGeometry.assign(s.triGeometry.begin() + bl.firstTri, s.triGeometry.begin() + bl.firstTri + bl.numTris);
@@ -799,6 +923,24 @@ void BuildBvhWith(HostScene& s, const std::function<void(HostScene&)>& single, c
     }
     s.bvhA.swap(allA); s.nodesB.swap(allNodes); s.trisB.swap(allTris);
     s.bvhMaxDepth = tlasDepth + maxBlasDepth; /* the walk's stack holds top-level entries below the bottom-level ones */
+}
+
+void WaveSurfacesOf(const HostScene& s, WaveSurfaces& surf)
+{
+    surf = WaveSurfaces{};
+    for (uint32_t tri = 0; tri < (uint32_t)s.triGeometry.size(); tri++) {
+        for (int k = 0; k < 3; k++) surf.v.push_back(P(s, tri, k));
+        const uint32_t g = s.triGeometry[tri], m = g < s.hitGroups.size() ? s.hitGroups[g].MaterialIndex : 0xffffffffu;
+        surf.emits.push_back(m < s.materials.size() && (s.materials[m].Flags & TB_MAT_LIGHT) ? 1 : 0);
+    }
+    for (const TbLight& l : s.lights) if (l.LightType == TB_LIGHT_TYPE_AREA) {
+        surf.light.push_back(tb3_make(l.P0.x, l.P0.y, l.P0.z)); surf.light.push_back(tb3_make(l.P1.x, l.P1.y, l.P1.z));
+        surf.light.push_back(tb3_make(l.P2.x, l.P2.y, l.P2.z)); }
+}
+
+void WaveStageSize(uint32_t& seed, uint32_t& waves, uint32_t& feelerPercent, uint32_t& places)
+{
+    seed = kWaveStageSeed; waves = kWaveStageWaves; feelerPercent = kWaveStageFeelerPercent; places = kWaveStagePlaces;
 }
 
 } // namespace tbhost

@@ -268,6 +268,8 @@ void finalizeScene(tb_context* c, bool build)
     const bool twoLevel = !s.instances.empty();
     s.reinsertionPasses = (int)opt<OPT_reinsertion_passes>(c); s.reinsertionShare = (int)opt<OPT_reinsertion_share>(c);
     s.presplitPercent = (int)std::max<int64_t>(0, std::min<int64_t>(400, opt<OPT_presplit>(c)));
+    s.waveTree = (int)opt<OPT_wave_tree>(c);
+    s.ldsSceneBudget = opt<OPT_scene_in_lds>(c) != 0 ? (uint32_t)std::max<int64_t>(0, std::min<int64_t>(0x7fffffff, opt<OPT_lds_scene_budget>(c))) : 0u;
     if (build) {
     /* every bottom-level structure and the top level on the GPU (GpuBVH2Builder.cpp:498-501: the same passes, no treelets at the top) */
     if (twoLevel && (builder == 2 || builder == 4))
@@ -339,13 +341,10 @@ void finalizeScene(tb_context* c, bool build)
     d.textureUse = sceneTextureUse(c);
     /* LDS image of the walk: nodes and permuted triangles (lds_image.h) */
     {
-        /* the shading records stay in memory (pt_scene.h); the budget still counts them, so that which scenes are LDS-resident is as before */
-        auto r16 = [](size_t b) { return (b + 15) / 16 * 16; };
-        const size_t shadingBytes = r16(devHit.size() * sizeof(TbDevHitGroup)) + r16(s.indexBuffer.size() * 4) + r16(s.vertexBuffer.size() * 4) +
-            r16(devMat.size() * sizeof(TbDevMaterial)) + r16(devLight.size() * sizeof(TbDevLight));
+        /* the size test of lds_image.h (builder 1's wave stage asks the same before it runs) */
         size_t budget = (size_t)opt<OPT_lds_scene_budget>(c);
-        c->sceneInLds = LdsImageBytes(s.nodesB.size(), s.trisB.size()) + shadingBytes + (size_t)d.stackDepth * 256 * 4 <= budget &&
-            opt<OPT_scene_in_lds>(c) != 0 && !twoLevel;
+        c->sceneInLds = LdsSceneBytes(s.nodesB.size(), s.trisB.size(), devHit.size(), s.indexBuffer.size(), s.vertexBuffer.size(), devMat.size(),
+            devLight.size(), d.stackDepth) <= budget && opt<OPT_scene_in_lds>(c) != 0 && !twoLevel;
         d.ldsBlob = nullptr; d.ldsBlobBytes = 0; d.offNodes = d.offTris = 0;
         if (c->sceneInLds) {   /* (built only for the scenes that use it: six copies of every triangle of a large scene are gigabytes) */
             const LdsImage image = BuildLdsImage(s.nodesB.data(), s.nodesB.size(), s.trisB.data(), s.trisB.size());
@@ -354,7 +353,7 @@ void finalizeScene(tb_context* c, bool build)
         /* measured on MI355X: LDS-resident scenes are nearly insensitive (at five waves per SIMD 1-2 is best: 6 745 / 6 730 against
          * 6 680 at 4, 6 230 at 12), scenes fetched through the caches gain ~5 % from a late switch to the leaf phase (16-24) */
         const int64_t* parkMin = c->options.ifSet<OPT_park_min>();
-        d.parkMin = (uint32_t)std::max<int64_t>(1, parkMin ? *parkMin : (c->sceneInLds ? 2 : 24));
+        d.parkMin = (uint32_t)std::max<int64_t>(1, parkMin ? *parkMin : (c->sceneInLds ? (int64_t)kLdsSceneParkMin : 24));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->sceneFeatures = sceneFeatureMask(s);

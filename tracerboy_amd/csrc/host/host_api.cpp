@@ -6,6 +6,7 @@
 #include "lds_image.h"
 #include "options.h"
 #include "tb_state.h"
+#include "wave_cost.h"
 
 #include <cstring>
 #include <memory>
@@ -142,14 +143,39 @@ struct tb_host_scene { HostScene scene; };
 
 static int hostFail(char* err, uint32_t n, int code, const std::string& m) { if (err && n) { strncpy(err, m.c_str(), n - 1); err[n - 1] = 0; } return code; }
 
-/* bvh_builder of the host-scene entry points: builder | (reinsertion passes + 1) << 8 | reinsertion share (percent) << 16 | presplit (percent, <= 127) << 24; a zero field =
- * the library's own choice (options "reinsertion_passes" / "reinsertion_share" of a context) */
+/* bvh_builder of the host-scene entry points: builder (bits 0-5) | (wave_tree + 1) << 6 | (reinsertion passes + 1) << 8 | reinsertion share (percent) << 16 |
+ * presplit (percent, <= 127) << 24; a zero field = the library's own choice (options "wave_tree" / "reinsertion_passes" / "reinsertion_share" of a context) */
+static int builderOfWord(int word) { return word & 0x3f; }
 static void applyBuilderWord(HostScene& s, int word)
 {
-    const int passes = (word >> 8) & 0xff, share = (word >> 16) & 0xff, presplit = (word >> 24) & 0x7f;
+    const int wave = (word >> 6) & 3, passes = (word >> 8) & 0xff, share = (word >> 16) & 0xff, presplit = (word >> 24) & 0x7f;
+    if (wave) s.waveTree = wave == 1 ? 0 : 1;
     if (passes) s.reinsertionPasses = passes - 1;
     if (share) s.reinsertionShare = share;
     if (presplit) s.presplitPercent = presplit;
+}
+
+/* the tree of a built one-level scene, read back from its layout-A image, as wave_cost.h walks it */
+static bool waveTreeOfScene(const HostScene& s, WaveTree& w)
+{
+    if (!s.instances.empty() || s.bvhA.size() < 16) return false;
+    uint32_t hdr[4]; memcpy(hdr, s.bvhA.data(), 16);
+    const uint32_t N = (uint32_t)s.trisB.size();
+    if (!N || (uint64_t)hdr[0] + 32ull * (2ull * N - 1) > s.bvhA.size() || (uint64_t)hdr[1] + 40ull * N > s.bvhA.size()) return false;
+    const TbAabbNode* nodes = (const TbAabbNode*)(s.bvhA.data() + hdr[0]);
+    w.N = N; w.center.resize(2 * N - 1); w.half.resize(2 * N - 1); w.left.assign(N - 1, 0); w.right.assign(N - 1, 0);
+    w.v0.resize(N); w.v1.resize(N); w.v2.resize(N);
+    for (uint32_t i = 0; i < 2 * N - 1; i++) {
+        w.center[i] = tb3_make(nodes[i].center[0], nodes[i].center[1], nodes[i].center[2]);
+        w.half[i] = tb3_make(nodes[i].halfDim[0], nodes[i].halfDim[1], nodes[i].halfDim[2]);
+        if (i < N - 1) { w.left[i] = nodes[i].flags & TB_BVH_INDEX_MASK; w.right[i] = nodes[i].rightNodeIndex;
+            if (w.left[i] >= 2 * N - 1 || w.right[i] >= 2 * N - 1) return false; }
+    }
+    for (uint32_t k = 0; k < N; k++) { /* leaf N-1+k holds triangle k of the image (its index field is k) */
+        float v[9]; memcpy(v, s.bvhA.data() + hdr[1] + 40ull * k + 4, 36);
+        w.v0[k] = tb3_make(v[0], v[1], v[2]); w.v1[k] = tb3_make(v[3], v[4], v[5]); w.v2[k] = tb3_make(v[6], v[7], v[8]);
+    }
+    return true;
 }
 
 int tb_host_scene_load(const char* path, int builder, int loadFlags, tb_host_scene** out, char* err, uint32_t errLen)
@@ -160,7 +186,7 @@ int tb_host_scene_load(const char* path, int builder, int loadFlags, tb_host_sce
         std::shared_ptr<PbrtScene> ps = importScene(path);
         tb_host_scene* h = new tb_host_scene();
         ConvertOptions co; co.flattenInstances = (loadFlags & 1) != 0; co.flipTextureUVs = (loadFlags & 2) == 0;
-        try { ConvertScene(*ps, h->scene, co); applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builder & 0xff); } catch (...) { delete h; throw; }
+        try { ConvertScene(*ps, h->scene, co); applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builderOfWord(builder)); } catch (...) { delete h; throw; }
         *out = h; return TB_OK;
     } catch (const std::exception& e) {
         std::string m = e.what();
@@ -176,7 +202,7 @@ int tb_host_scene_procedural(int kind, uint32_t tris, uint32_t seed, int builder
     *out = nullptr;
     try {
         tb_host_scene* h = new tb_host_scene();
-        try { MakeProceduralScene(h->scene, kind, tris, seed); applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builder & 0xff); } catch (...) { delete h; throw; }
+        try { MakeProceduralScene(h->scene, kind, tris, seed); applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builderOfWord(builder)); } catch (...) { delete h; throw; }
         *out = h; return TB_OK;
     } catch (const std::exception& e) { return hostFail(err, errLen, TB_E_INVALID, e.what()); }
 }
@@ -240,6 +266,84 @@ int tb_host_scene_triangles(tb_host_scene* h, const float** pos, uint32_t* nv, c
     if (pos) *pos = s.positions.data(); if (nv) *nv = (uint32_t)(s.positions.size() / 3);
     if (tvi) *tvi = s.triVertexIndex.data(); if (tg) *tg = s.triGeometry.data(); if (tp) *tp = s.triPrimitive.data(); if (tf) *tf = s.triFlags.data();
     if (nt) *nt = (uint32_t)s.triGeometry.size();
+    return TB_OK;
+}
+
+/* ---- what a wave pays for a tree (wave_cost.h) -------------------------------------------------- */
+static void tripsOut(const WaveTrips& w, tb_wave_trips* o)
+{
+    o->inner_trips = w.inner; o->leaf_trips = w.leaf; o->idle_passes = w.idle; o->inner_active = w.innerActive; o->leaf_active = w.leafActive;
+    o->cost = w.cost();
+}
+int tb_wave_replay(const char* const* steps, uint32_t lanes, uint32_t parkMin, tb_wave_trips* out)
+{
+    if (!out || lanes > kWaveLanes || (lanes && !steps)) return TB_E_INVALID;
+    uint32_t len[kWaveLanes] = {};
+    for (uint32_t l = 0; l < lanes; l++) { if (!steps[l]) return TB_E_INVALID; len[l] = (uint32_t)strlen(steps[l]);
+        for (uint32_t k = 0; k < len[l]; k++) if (steps[l][k] != 'I' && steps[l][k] != 'L') return TB_E_INVALID; }
+    tripsOut(WaveReplay(steps, len, lanes, parkMin), out);
+    return TB_OK;
+}
+int tb_host_scene_wave_walk(tb_host_scene* h, uint32_t n, const float* origins, const float* dirs, const float* tMax, uint32_t* innerSteps,
+    uint32_t* leafSteps, char* steps, uint64_t stepsCapacity)
+{
+    if (!h || (n && (!origins || !dirs))) return TB_E_INVALID;
+    WaveTree w; if (!waveTreeOfScene(h->scene, w)) return TB_E_UNSUPPORTED;
+    std::vector<char> one; uint64_t used = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        WaveRay r; r.o = tb3_make(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]); r.d = tb3_make(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+        r.tMax = tMax ? tMax[i] : kWaveMaxT; WaveRayPrepare(r);
+        one.clear(); WaveWalk(w, r, one);
+        uint32_t in = 0; for (char c : one) in += c == 'I' ? 1u : 0u;
+        if (innerSteps) innerSteps[i] = in; if (leafSteps) leafSteps[i] = (uint32_t)one.size() - in;
+        if (steps) { /* the strings back to back, each ended by a 0 */
+            if (used + one.size() + 1 > stepsCapacity) return TB_E_INVALID;
+            if (!one.empty()) memcpy(steps + used, one.data(), one.size());
+            used += one.size(); steps[used++] = 0;
+        }
+    }
+    return TB_OK;
+}
+static bool modelRaysOf(const HostScene& s, uint32_t seed, uint32_t waves, int feelerPercent, std::vector<WaveRay>& rays)
+{
+    uint32_t dSeed, dWaves, dFeelers, places; WaveStageSize(dSeed, dWaves, dFeelers, places);
+    WaveSurfaces surf; WaveSurfacesOf(s, surf);
+    WaveModelRays(surf, seed ? seed : dSeed, waves ? waves : dWaves, feelerPercent < 0 ? dFeelers : (uint32_t)std::min(feelerPercent, 100), rays);
+    return !rays.empty();
+}
+int tb_host_scene_wave_rays(tb_host_scene* h, uint32_t seed, uint32_t waves, int feelerPercent, float* origins, float* dirs, float* tMax, uint32_t capacity)
+{
+    if (!h || waves > (1u << 16)) return TB_E_INVALID;
+    std::vector<WaveRay> rays; modelRaysOf(h->scene, seed, waves, feelerPercent, rays);
+    if (origins || dirs || tMax) {
+        if (capacity < rays.size()) return TB_E_INVALID;
+        for (size_t i = 0; i < rays.size(); i++) {
+            if (origins) { origins[3 * i] = rays[i].o.x; origins[3 * i + 1] = rays[i].o.y; origins[3 * i + 2] = rays[i].o.z; }
+            if (dirs) { dirs[3 * i] = rays[i].d.x; dirs[3 * i + 1] = rays[i].d.y; dirs[3 * i + 2] = rays[i].d.z; }
+            if (tMax) tMax[i] = rays[i].tMax;
+        }
+    }
+    return (int)rays.size();
+}
+int tb_host_scene_wave_cost(tb_host_scene* h, uint32_t seed, uint32_t waves, int feelerPercent, uint32_t parkMin, tb_wave_trips* out)
+{
+    if (!h || !out || waves > (1u << 16)) return TB_E_INVALID;
+    WaveTree w; if (!waveTreeOfScene(h->scene, w)) return TB_E_UNSUPPORTED;
+    std::vector<WaveRay> rays; if (!modelRaysOf(h->scene, seed, waves, feelerPercent, rays)) return TB_E_UNSUPPORTED;
+    std::vector<char> arena;
+    tripsOut(WaveCostOfTree(w, rays, parkMin ? parkMin : kLdsSceneParkMin, arena), out);
+    return TB_OK;
+}
+int tb_host_scene_wave_stage(tb_host_scene* h, tb_wave_stage_info* o)
+{
+    if (!h || !o) return TB_E_INVALID;
+    const HostScene::WaveStageReport& r = h->scene.waveStage;
+    memset(o, 0, sizeof *o);
+    o->ran = r.ran; o->rays = r.rays; o->seed = r.seed; o->park_min = r.parkMin; o->depth_limit = r.depthLimit; o->moves = r.moves;
+    o->evaluations = r.evaluations; o->inner_insts = kWaveInnerInsts; o->leaf_insts = kWaveLeafInsts;
+    o->before.inner_trips = r.innerBefore; o->before.leaf_trips = r.leafBefore; o->before.cost = r.costBefore;
+    o->after.inner_trips = r.innerAfter; o->after.leaf_trips = r.leafAfter; o->after.cost = r.costAfter;
+    o->milliseconds = r.milliseconds;
     return TB_OK;
 }
 

@@ -56,6 +56,14 @@ struct HostScene {
     /* builder 1: percent of extra references the builder may make by cutting the triangles with the emptiest boxes in two before it builds
      * (bvh_build.cpp presplitReferences; option "presplit"); 0 = one reference per triangle */
     int presplitPercent = 0;
+    /* builder 1: the wave stage after the reinsertion passes (bvh_build.cpp optimizeForWaves; option "wave_tree"): -1 = the library's own choice (on where
+     * reinsertion passes run), 0 = off, 1 = on.  It runs only for a scene that will be LDS-resident: one level, and within ldsSceneBudget bytes by the size test of lds_image.h
+     * (options "lds_scene_budget" / "scene_in_lds"; 0 = no scene is) */
+    int waveTree = -1;
+    uint32_t ldsSceneBudget = 40u * 1024u;
+    /* what the wave stage did at the last build: costs in wave instructions over its own model rays (wave_cost.h) */
+    struct WaveStageReport { uint32_t ran = 0, rays = 0, seed = 0, parkMin = 0, depthLimit = 0, moves = 0, evaluations = 0;
+        uint64_t innerBefore = 0, leafBefore = 0, innerAfter = 0, leafAfter = 0; double costBefore = 0, costAfter = 0, milliseconds = 0; } waveStage;
 };
 
 struct ConvertOptions {
@@ -80,6 +88,10 @@ void BuildBvh(HostScene& scene, int builder);
 typedef std::function<void(HostScene&, const std::vector<float>& blasRootBoxes, std::vector<TbNodeB>& topNodes, uint32_t& rootRef,
     uint32_t& depth)> TlasBuilder;
 void BuildBvhWith(HostScene& scene, const std::function<void(HostScene&)>& single, const TlasBuilder& tlas);
+/* builder 1's wave stage (bvh_build.cpp, wave_cost.h): the surfaces its model rays start from, and the size of its ray set */
+struct WaveSurfaces;
+void WaveSurfacesOf(const HostScene& scene, WaveSurfaces& out);
+void WaveStageSize(uint32_t& seed, uint32_t& waves, uint32_t& feelerPercent, uint32_t& places);
 
 /* Procedural stand-ins (procedural.cpp) */
 void MakeProceduralScene(HostScene& out, int kind, uint32_t targetTriangles, uint32_t seed);

@@ -14,6 +14,21 @@ inline size_t LdsImageBytes(size_t numNodes, size_t numTris)
     return (numNodes * TB_LDS_NODE_STRIDE + 15) / 16 * 16 + (numTris * TB_LDS_TRI_COPIES * sizeof(TbTriB) + 15) / 16 * 16;
 }
 
+/* parkMin of a scene in LDS where option "park_min" is not set (context_scene.cpp has the measurements; the wave stage replays with it) */
+constexpr uint32_t kLdsSceneParkMin = 2;
+
+/* What the budget of an LDS-resident scene counts (option "lds_scene_budget"), from the counts alone: the image, the shading records in their device
+ * form -- they stay in memory (pt_scene.h), the budget still counts them, so that which scenes are LDS-resident is as it was -- and the stacks of a
+ * workgroup.  context_scene.cpp decides with it, and builder 1 asks it before the scene is built (bvh_build.cpp, the wave stage). */
+inline size_t LdsSceneBytes(size_t numNodes, size_t numTris, size_t numHitGroups, size_t numIndices, size_t numVertexFloats, size_t numMaterials,
+    size_t numLights, uint32_t stackDepth)
+{
+    auto r16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t shadingBytes = r16(numHitGroups * sizeof(TbDevHitGroup)) + r16(numIndices * 4) + r16(numVertexFloats * 4) +
+        r16(numMaterials * sizeof(TbDevMaterial)) + r16(numLights * sizeof(TbDevLight));
+    return LdsImageBytes(numNodes, numTris) + shadingBytes + (size_t)stackDepth * 256 * 4;
+}
+
 /* Nodes first, TB_LDS_NODE_STRIDE apart, then TB_LDS_TRI_COPIES axis-permuted copies of every triangle (copy = kz * 2 + swapped, (kx, ky) = the
  * two axes after kz, swapped when d[kz] < 0).  Child refs are offsets in 16-B units (pt_scene.h): an inner ref from the first node record, a leaf
  * ref -- leaf flag in the sign bit -- from the first triangle record to the triangle's first copy.  The root's ref, 0 or LEAF | 0, is the same
