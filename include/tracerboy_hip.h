@@ -557,6 +557,62 @@ int tb_run_nn_resolve_aux(tb_context* ctx, uint32_t width, uint32_t height, cons
                           float* out_normal);
 int tb_run_nn_to_rgba8(tb_context* ctx, uint32_t width, uint32_t height, const float* rgba, uint8_t* out_rgba8);
 
+/* ---- neural 2 x super-resolution ------------------------------------------------
+ * <-> the reference's DirectMLSuperResolutionPass (DirectMLSuperResolution.cpp:304-409 the graph, :986-1091 the run, :1128-1219 the weights;
+ * ImageToTensorCS.hlsl, TensorToImageCS.hlsl), what it upscales with when built with PREFER_OIDN 0 (pch.h:10-14, TracerBoy.cpp:3289-3303): the frame
+ * is rendered at half size and the network gives the full-size picture.  Seven convolutions, zero padding (K - 1) / 2, stride 1:
+ *   conv1 3 -> 32, 5 x 5; conv2 32 -> 64, 3 x 3; conv3 64 -> 64, 3 x 3, at width x height; nearest upsample x 2; conv_up1/conv 64 -> 32, 5 x 5;
+ *   conv4 32 -> 32; conv5 32 -> 32; conv6 32 -> 3, all 3 x 3, at 2 width x 2 height; bias + ReLU after every layer but conv6, which has neither.
+ * The result is |half(conv6 + the input nearest-upsampled x 2)| with alpha 1 (the abs: TensorToImageCS.hlsl:50).  The library ships no weights: the
+ * caller names a file of the reference's container (TracerBoy/ML/weights.bin).  The layer arithmetic is the neural section's contract
+ * (tests/sr_ref.py restates it in torch); the residual add is the exact sum of two binary16 values, rounded once.
+ *
+ * tb_sr_weights_info: host only, no context.  The container: int32 tensor count, then per tensor u32 name length (at most 255), the name, u32 element
+ * count and that many binary32 values (DirectMLSuperResolution.cpp:94-160).  A layer's filter is `<name>/weights` (oihw), and every layer but conv6
+ * has `<name>/BatchNorm/scale` and `/shift`.  The file holds no shapes: kernel[] is the graph's (5, 3, 3, 5, 3, 3, 3), out_channels the scale
+ * tensor's length (3 for conv6), in_channels the filter's count / (out * K * K); each 1 ... 256, and the chain closes (3 in, 3 out, a layer reads what
+ * its predecessor wrote).  weight_bytes: the binary16 bytes of all folded filters and biases.  TB_E_IO: the file cannot be read.  TB_E_PARSE (err
+ * names the tensor and the cause): a negative count, a name longer than 255, anything that runs past the end of the file, a missing tensor, a count
+ * that does not divide, a chain that does not close.
+ * tb_sr_read_layer: host only.  The folded binary16 values of one layer (0 ... 6): filter * scale[o] as one fp32 multiply, then the reference's
+ * Float16Compressor::compress (DirectMLSuperResolution.cpp:47-63), restated bit for bit -- it truncates where a rounding would round, and gives
+ * infinity for everything above 65504; the bias is compress(shift[o]).  weight_oihw holds out * in * K * K values, bias_or_null out (untouched for
+ * layer 6, which has none).
+ * tb_sr_load: the same read, then the repack for the kernel and the upload; replaces weights loaded before.
+ * tb_run_conv: the layer seam, like tb_run_conv3x3 (host arrays of binary16 bits in unpadded NHWC order, temporary device buffers, nothing the
+ * context holds is read or written) with a kernel of 3 or 5 and an optional bias.  form: 0, the plain form, a wave per 16 pixels of a row with every
+ * fragment from memory; 1, the staged form, a workgroup per 32 x 8 pixels with its input tile and halo in LDS; the results are the same bits.  The
+ * staged form holds at most 64 input channels, each source padded to a multiple of 32.  TB_E_INVALID (the message names the cause): a null required
+ * pointer, a zero size, an odd width or height with upsample_a, more than 512 channels in a tensor, more than 2^24 pixels, a kernel other than 3 or
+ * 5, a form above 1, form 1 with more input channels than it holds.
+ * tb_run_sr_finish: the residual add on host arrays: residual (2 in_h) x (2 in_w) x 3 and input in_h x in_w x 3, binary16 bits; out_rgba gets
+ * (|half(residual + input at (y >> 1, x >> 1))|, 1) as fp32, (2 in_w) * (2 in_h) * 4 floats.
+ * tb_run_sr: the network on a host surface (width x height RGBA32F, .xyz read as they are); out_rgba is 2 width x 2 height.  Needs tb_sr_load.
+ * Bit for bit the pack, seven tb_run_conv calls and tb_run_sr_finish.  tb_set_option "sr_conv_form" (0 or 1; default 1, the staged form, which
+ * takes half the time) picks the form of its convolutions; a layer with more input channels than the staged form holds runs in the plain form.
+ * tb_upscale_neural: the stage.  The network's input is what the reference's reads: the 8-bit picture tb_post_process(post, TB_OUTPUT_TYPE_LIT)
+ * writes at the rendered size (option "post_denoised" included), each channel k / 255 (the neural section argues the surface's format).  The float
+ * result goes to rgba_f32_or_null (2 width * 2 height * 4 floats), its 8-bit conversion as the output stage does it to rgba8_or_null.  Synchronous.
+ * It writes neither the accumulation surfaces nor anything another stage reads: tb_accum_digest is the same before and after.  Its weights and
+ * activation buffers belong to the context (sized at the first use, kept while the size holds, released by tb_destroy).  TB_E_UNSUPPORTED: a
+ * tb_create_multi group.  TB_E_INVALID: no weights, nothing rendered, both pointers null, more than 2^24 output pixels, whatever tb_post_process
+ * refuses.  tb_get_option "last_sr_us": GPU microseconds of the last network, pack to finish (HIP events); "sr_loaded": 0 or 1; "sr_conv_form":
+ * the form the network's convolutions run in. */
+typedef struct tb_sr_info { uint32_t in_channels[7], out_channels[7], kernel[7]; uint64_t weight_bytes; } tb_sr_info;
+typedef struct tb_conv_desc { uint32_t width, height;       /* of the convolution's output */
+                              uint32_t c_a, c_b, c_out;     /* channels of source A, source B (0 = none), output */
+                              uint32_t kernel;              /* 3 | 5 */
+                              uint32_t upsample_a, relu;
+                              uint32_t form;                /* 0 plain, 1 staged */ } tb_conv_desc;
+int tb_sr_weights_info(const char* path, tb_sr_info* out, char* err, uint32_t err_len);
+int tb_sr_read_layer(const char* path, uint32_t layer, uint16_t* weight_oihw, uint16_t* bias_or_null, char* err, uint32_t err_len);
+int tb_sr_load(tb_context* ctx, const char* path);
+int tb_run_conv(tb_context* ctx, const tb_conv_desc* d, const uint16_t* in_a, const uint16_t* in_b_or_null, const uint16_t* weight_oihw,
+                const uint16_t* bias_or_null, uint16_t* out);
+int tb_run_sr_finish(tb_context* ctx, uint32_t in_w, uint32_t in_h, const uint16_t* residual_2w2h3, const uint16_t* input_wh3, float* out_rgba);
+int tb_run_sr(tb_context* ctx, uint32_t width, uint32_t height, const float* color_rgba, float* out_rgba);
+int tb_upscale_neural(tb_context* ctx, const tb_post_settings* post, float* rgba_f32_or_null, uint8_t* rgba8_or_null);
+
 /* ---- host-only half of LoadScene (no device needed) ------------------------------------------------
  * The same parse / convert / BVH-build code tb_load_scene runs, exposed separately so that the
  * scene conversion and the BVH can be inspected and checked on machines without a GPU.  Nothing here

@@ -170,6 +170,16 @@ class tb_conv3x3_desc(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "c_a", "c_b", "c_out", "upsample_a", "pool", "relu")]
 
 
+class tb_sr_info(C.Structure):
+    """include/tracerboy_hip.h tb_sr_info: the channel counts and filter sizes of a super-resolution weights file's 7 layers (tb_sr_weights_info)."""
+    _fields_ = [("in_channels", C.c_uint32 * 7), ("out_channels", C.c_uint32 * 7), ("kernel", C.c_uint32 * 7), ("weight_bytes", C.c_uint64)]
+
+
+class tb_conv_desc(C.Structure):
+    """include/tracerboy_hip.h tb_conv_desc: one 3 x 3 or 5 x 5 layer at the layer seam (tb_run_conv)."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "c_a", "c_b", "c_out", "kernel", "upsample_a", "relu", "form")]
+
+
 class tb_readback_stats(C.Structure):
     _fields_ = [("ActiveWaves", C.c_uint32), ("ActivePixels", C.c_uint32), ("SelectedPixelDistance", C.c_float), ("SelectedMaterialID", C.c_int32),
                 ("rays", TbRayStats)]

@@ -115,6 +115,13 @@ def lib():
         "tb_run_nn_unpack": (C.c_int, [vp] + [C.c_uint32] * 4 + [vp, vp]),
         "tb_run_nn_resolve_aux": (C.c_int, [vp, C.c_uint32, C.c_uint32] + [vp] * 4),
         "tb_run_nn_to_rgba8": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
+        "tb_sr_weights_info": (C.c_int, [C.c_char_p, P(abi.tb_sr_info), C.c_char_p, C.c_uint32]),
+        "tb_sr_read_layer": (C.c_int, [C.c_char_p, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32]),
+        "tb_sr_load": (C.c_int, [vp, C.c_char_p]),
+        "tb_run_conv": (C.c_int, [vp, P(abi.tb_conv_desc)] + [vp] * 5),
+        "tb_run_sr_finish": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "tb_run_sr": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
+        "tb_upscale_neural": (C.c_int, [vp, P(abi.tb_post_settings), vp, vp]),
         "tb_variant_stash_entries": (C.c_int, [C.c_char_p]),
         "tb_frame_groups": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "tb_state_begin": (C.c_int, [vp, C.c_uint32, C.c_uint32, P(abi.tb_output_settings), C.c_float, C.c_uint32]),
@@ -197,6 +204,31 @@ def NeuralWeightsInfo(path):
     if rc != 0:
         raise TracerBoyError(rc, err.value.decode(errors="replace"))
     return info
+
+
+SR_LAYERS = ("conv1", "conv2", "conv3", "conv_up1/conv", "conv4", "conv5", "conv6")
+
+
+def SrWeightsInfo(path):
+    """The channel counts and filter sizes of a weights file of the neural 2 x super-resolution (tb_sr_weights_info; host only, no device): a
+    tb_sr_info whose arrays follow SR_LAYERS.  Raises TracerBoyError with code -3 (unreadable) or -4 (the message names the tensor and the cause)."""
+    info, err = abi.tb_sr_info(), C.create_string_buffer(512)
+    rc = lib().tb_sr_weights_info(os.fsencode(path), C.byref(info), err, 512)
+    if rc != 0:
+        raise TracerBoyError(rc, err.value.decode(errors="replace"))
+    return info
+
+
+def SrReadLayer(path, layer):
+    """One layer of such a file as the network uses it (tb_sr_read_layer; host only): (weight (out, in, K, K) float16 with the batch-norm scale
+    folded in, bias (out,) float16 or None for the last layer), converted as the reference converts them."""
+    info = SrWeightsInfo(path)
+    o, i, k = info.out_channels[layer], info.in_channels[layer], info.kernel[layer]
+    weight, bias, err = np.empty((o, i, k, k), np.float16), np.empty((o,), np.float16), C.create_string_buffer(512)
+    rc = lib().tb_sr_read_layer(os.fsencode(path), layer, _np_ptr(weight), _np_ptr(bias), err, 512)
+    if rc != 0:
+        raise TracerBoyError(rc, err.value.decode(errors="replace"))
+    return weight, (bias if layer < 6 else None)
 
 
 def VariantWavesHi(name):
@@ -694,6 +726,55 @@ class TracerBoy:
         f = np.empty((self.height, self.width, 4), np.float32)
         b = np.empty((self.height, self.width, 4), np.uint8) if rgba8 else None
         self._check(self._L.tb_denoise_neural(self._ctx, C.byref(ps), _np_ptr(f), _np_ptr(b) if rgba8 else None))
+        return f, b
+
+    def LoadUpscaleWeights(self, path):
+        """Read a weights file of the neural 2 x super-resolution, fold and repack it for the kernel and upload it (tb_sr_load, DESIGN.md section
+        16); replaces weights loaded before.  Option "sr_loaded" is 1 afterwards."""
+        self._check(self._L.tb_sr_load(self._ctx, os.fsencode(path)))
+
+    def RunConv(self, in_a, weight, bias=None, in_b=None, upsample_a=False, relu=True, form=0):
+        """One layer at the layer seam (tb_run_conv): in_a (H, W, c_a) -- (H / 2, W / 2, c_a) with upsample_a -- and in_b (H, W, c_b) or None,
+        weight (c_out, c_a + c_b, K, K) with K 3 or 5, bias (c_out,) or None, all float16.  Returns (H, W, c_out) float16."""
+        a = np.ascontiguousarray(in_a, np.float16); b = None if in_b is None else np.ascontiguousarray(in_b, np.float16)
+        w = np.ascontiguousarray(weight, np.float16); bi = None if bias is None else np.ascontiguousarray(bias, np.float16)
+        H, W = (a.shape[0] * 2, a.shape[1] * 2) if upsample_a else a.shape[:2]
+        if b is not None: H, W = b.shape[:2]
+        c_b = 0 if b is None else b.shape[2]
+        assert w.ndim == 4 and w.shape[1] == a.shape[2] + c_b and w.shape[2] == w.shape[3], "weight is (c_out, c_a + c_b, K, K)"
+        assert bi is None or bi.shape == (w.shape[0],), "bias is (c_out,)"
+        d = abi.tb_conv_desc(W, H, a.shape[2], c_b, w.shape[0], w.shape[2], int(bool(upsample_a)), int(bool(relu)), form)
+        out = np.empty((H, W, w.shape[0]), np.float16)
+        self._check(self._L.tb_run_conv(self._ctx, C.byref(d), _np_ptr(a), None if b is None else _np_ptr(b), _np_ptr(w), None if bi is None else _np_ptr(bi),
+                                        _np_ptr(out)))
+        return out
+
+    def RunSrFinish(self, residual, picture):
+        """The network's residual add (tb_run_sr_finish): residual (2 H, 2 W, 3) and picture (H, W, 3) float16.  Returns (2 H, 2 W, 4) float32:
+        |half(residual + picture nearest-upsampled x 2)| and alpha 1."""
+        r, p = np.ascontiguousarray(residual, np.float16), np.ascontiguousarray(picture, np.float16)
+        h, w = p.shape[:2]
+        assert p.shape == (h, w, 3) and r.shape == (2 * h, 2 * w, 3), "residual is (2 H, 2 W, 3), picture (H, W, 3)"
+        out = np.empty((2 * h, 2 * w, 4), np.float32)
+        self._check(self._L.tb_run_sr_finish(self._ctx, w, h, _np_ptr(r), _np_ptr(p), _np_ptr(out)))
+        return out
+
+    def RunUpscaleNeural(self, color):
+        """The super-resolution network on a host surface (tb_run_sr): (H, W, 4) float32, .xyz read.  Returns (2 H, 2 W, 4) float32, alpha 1."""
+        f = np.ascontiguousarray(color, np.float32)
+        h, w = f.shape[:2]
+        assert f.shape == (h, w, 4), "the surface is (H, W, 4)"
+        out = np.empty((2 * h, 2 * w, 4), np.float32)
+        self._check(self._L.tb_run_sr(self._ctx, w, h, _np_ptr(f), _np_ptr(out)))
+        return out
+
+    def UpscaleNeural(self, postSettings=None, rgba8=True):
+        """PostProcess at the rendered size, then the super-resolution network on its 8-bit picture (each channel k / 255, as the reference's network
+        reads it; tb_upscale_neural).  Returns (float32 2Hx2Wx4 picture, uint8 2Hx2Wx4 picture or None)."""
+        ps = postSettings if postSettings is not None else GetDefaultPostProcessSettings()
+        f = np.empty((2 * self.height, 2 * self.width, 4), np.float32)
+        b = np.empty((2 * self.height, 2 * self.width, 4), np.uint8) if rgba8 else None
+        self._check(self._L.tb_upscale_neural(self._ctx, C.byref(ps), _np_ptr(f), _np_ptr(b) if rgba8 else None))
         return f, b
 
     def RunNnPack(self, color, albedo=None, normal=None, unorm_color=False):

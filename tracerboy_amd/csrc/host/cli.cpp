@@ -7,6 +7,7 @@
  *                 [--denoise] [--denoise-iterations N] [--denoise-guides K [--denoise-demodulate]]
  *                 [--upscale WxH | --render-scale F] [--fsr-sharpness S]
  *                 [--denoise-neural FILE.tza [--denoise-guides K]]
+ *                 [--upscale-neural FILE.bin]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -66,7 +67,14 @@
  * -- the default tonemapper gives one for a black pixel -- is 0 there, so every tonemapper works.  The tool still warns when the result holds values
  * that are not finite (a non-finite albedo or normal, or an overflow inside the network).
  * Not together with --denoise (and its --denoise-iterations / --denoise-demodulate), --upscale, --render-scale or --ranks N > 1.  Mistakes, an
- * unreadable or malformed FILE.tza among them, are reported before any device call (exit status 2). */
+ * unreadable or malformed FILE.tza among them, are reported before any device call (exit status 2).
+ *
+ * --upscale-neural FILE.bin (tb_sr_load / tb_upscale_neural): the finished render is post-processed at its own size and brought
+ * to 2 --width x 2 --height by the reference's super-resolution network, whose weights FILE.bin holds (the reference's ML/weights.bin; the tool
+ * ships none).  --out is the network's picture: .png its 8-bit conversion, .pfm / .exr the float LDR picture, as with --denoise-neural; the network
+ * reads the output stage's 8-bit picture here, too.  With --denoise the denoised picture is what is upscaled.  Not together with --upscale,
+ * --render-scale, --denoise-neural (the reference builds with one network or the other) or --ranks N > 1.  Mistakes, an unreadable or malformed
+ * FILE.bin among them, are reported before any device call (exit status 2). */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -164,14 +172,14 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
     float adaptive = -1.0f; long long adaptiveAfter = 1024, adaptiveChunk = 64; int adaptiveTest = 0;
     std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
     bool sppSet = false, timeSet = false, denoise = false, demodulate = false; long long denoiseIterations = -1, denoiseGuides = 0;
-    std::string neural; bool denoiseFlag = false; /* --denoise itself, not what --denoise-guides implies */
+    std::string neural, neuralUp; bool denoiseFlag = false; /* --denoise itself, not what --denoise-guides implies */
     uint32_t upW = 0, upH = 0; float renderScale = 0.0f, fsrSharpness = -1.0f; bool upscaleSet = false, renderScaleSet = false, sharpnessSet = false;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
@@ -206,6 +214,7 @@ int main(int argc, char** argv)
         else if (k == "--fsr-sharpness") { char* end = nullptr; fsrSharpness = strtof(v, &end); sharpnessSet = true;
             if (end == v || *end || !(fsrSharpness >= 0.0f) || !(fsrSharpness < 1e30f)) { fprintf(stderr, "--fsr-sharpness is a finite number of stops, 0 or more\n"); return 2; } }
         else if (k == "--denoise-neural") neural = v;
+        else if (k == "--upscale-neural") neuralUp = v;
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -227,6 +236,13 @@ int main(int argc, char** argv)
             neural.c_str()); return 2; }
         if (nn.in_channels == 9u && !denoiseGuides) denoiseGuides = 8;
         denoise = false; /* --denoise-guides K: the network's guides, not the filter's */
+    }
+    if (!neuralUp.empty()) {
+        if (upscaleSet || renderScaleSet) { fprintf(stderr, "--upscale-neural does not go with --upscale or --render-scale: the network is the upscaler\n"); return 2; }
+        if (!neural.empty()) { fprintf(stderr, "--upscale-neural does not go with --denoise-neural: the two networks are not chained\n"); return 2; }
+        if (ranks > 1) { fprintf(stderr, "--upscale-neural does not go with --ranks: the network does not run across a device group\n"); return 2; }
+        tb_sr_info sr; char err[512] = "";
+        if (tb_sr_weights_info(neuralUp.c_str(), &sr, err, sizeof err)) { fprintf(stderr, "--upscale-neural %s: %s\n", neuralUp.c_str(), err); return 2; }
     }
     const bool states = !saveState.empty() || !resume.empty() || !adds.empty() || frameA >= 0 || checkpointEvery != 0;
     if (states && ranks > 1) { fprintf(stderr,
@@ -302,6 +318,8 @@ int main(int argc, char** argv)
     if (upW && (upW < W || upH < H || (uint64_t)upW * upH > (1ull << 24))) { /* before the render, not after it */
         fprintf(stderr, "tracerboy-hip: cannot upscale the %ux%u render to %ux%u: FSR 1 only upscales, to at most 2^24 pixels\n", W, H, upW, upH);
         tb_destroy(ctx); return 2; }
+    if (!neuralUp.empty() && (uint64_t)W * H * 4u > (1ull << 24)) { /* likewise */
+        fprintf(stderr, "tracerboy-hip: cannot upscale the %ux%u render to twice that: more than 2^24 pixels\n", W, H); tb_destroy(ctx); return 2; }
     const uint32_t start = done;
     auto checkpoint = [&]() { return checkpointEvery > 0 ? tb_state_save(ctx, saveState.c_str()) : 0; };
     if (adaptive < 0.0f) {
@@ -402,7 +420,7 @@ int main(int argc, char** argv)
     if (denoise) { /* after --save-state: a state is the raw accumulation */
         tb_denoiser_settings dn; tb_default_denoiser_settings(&dn);
         if (denoiseIterations >= 0) dn.WaveletIterations = (uint32_t)denoiseIterations;
-        if (!png && !upW) denoised.resize((size_t)W * H * 4);
+        if (!png && !upW && neuralUp.empty()) denoised.resize((size_t)W * H * 4);
         if (denoiseGuides) { /* the last min(K, frames held) frames of the state's range, traced again */
             const uint32_t next = tb_samples_rendered(ctx), first = (uint32_t)tb_get_option(ctx, "state_first_frame");
             const uint32_t k = (uint32_t)std::min<long long>(denoiseGuides, (long long)next - (long long)first);
@@ -412,7 +430,7 @@ int main(int argc, char** argv)
         }
         if ((rc = tb_denoise(ctx, &dn, denoised.empty() ? nullptr : denoised.data()))) return fail(ctx, "tb_denoise", rc);
         printf("denoise: %u a-trous passes, %.3f ms on the GPU\n", dn.WaveletIterations, (double)tb_get_option(ctx, "last_denoise_us") / 1e3);
-        if ((png || upW) && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
+        if ((png || upW || !neuralUp.empty()) && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
     }
     if (!neural.empty()) { /* the output stage, then the network; after --save-state: a state is the raw accumulation */
         if ((rc = tb_neural_load(ctx, neural.c_str()))) return fail(ctx, "tb_neural_load", rc);
@@ -431,6 +449,16 @@ int main(int argc, char** argv)
         if (notFinite) fprintf(stderr, "tracerboy-hip: warning: %zu values of the network's picture are not finite\n", notFinite);
         if (png) { if ((rc = tb_write_image_rgba8(out.c_str(), W, H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc); }
         else if ((rc = tb_write_image_f32(out.c_str(), W, H, imgF.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
+    } else if (!neuralUp.empty()) { /* the output stage at the rendered size, then the network to twice that */
+        if ((rc = tb_sr_load(ctx, neuralUp.c_str()))) return fail(ctx, "tb_sr_load", rc);
+        std::vector<uint8_t> img(png ? (size_t)W * H * 16 : 0); std::vector<float> imgF((size_t)W * H * 16);
+        if ((rc = tb_upscale_neural(ctx, &post, imgF.data(), png ? img.data() : nullptr))) return fail(ctx, "tb_upscale_neural", rc);
+        printf("neural upscale: %ux%u -> %ux%u, %.3f ms on the GPU\n", W, H, 2u * W, 2u * H, (double)tb_get_option(ctx, "last_sr_us") / 1e3);
+        size_t notFinite = 0; /* the picture goes in clamped; an overflow inside the network would still show here */
+        for (float v : imgF) notFinite += !(v - v == 0.0f);
+        if (notFinite) fprintf(stderr, "tracerboy-hip: warning: %zu values of the network's picture are not finite\n", notFinite);
+        if (png) { if ((rc = tb_write_image_rgba8(out.c_str(), 2u * W, 2u * H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc); }
+        else if ((rc = tb_write_image_f32(out.c_str(), 2u * W, 2u * H, imgF.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
     } else if (upW) { /* the output stage at the rendered size, then FSR 1 to the picture's */
         std::vector<uint8_t> img(png ? (size_t)upW * upH * 4 : 0); std::vector<float> imgF(png ? 0 : (size_t)upW * upH * 4);
         if ((rc = tb_upscale(ctx, &post, TB_OUTPUT_TYPE_LIT, upW, upH, fsrSharpness, png ? nullptr : imgF.data(), png ? img.data() : nullptr)))

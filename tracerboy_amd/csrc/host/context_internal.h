@@ -12,6 +12,7 @@
  *   context_guides.cpp  the guide pass of that denoise: first hits traced again and summed over frames
  *   context_upscale.cpp FSR 1 upscaling of the post-processed picture: EASU + RCAS
  *   context_neural.cpp  the neural still denoiser: the OIDN U-Net on the matrix cores, its layer seam and its stage
+ *   context_sr.cpp      the neural 2 x super-resolution: the reference's DirectML network on the matrix cores, its seams and its stage
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -54,6 +55,8 @@ extern "C" {
 typedef hipError_t (*wf_variant_fn)(TB_WAVEFRONT_ARGS);
 TB_WAVEFRONT(wf_launch_matte) TB_WAVEFRONT(wf_launch_env) TB_WAVEFRONT(wf_launch_surf) TB_WAVEFRONT(wf_launch_sss) TB_WAVEFRONT(wf_launch_vol)
 }
+
+namespace tbnn { struct PackedLayer; } /* nn_weights.h */
 
 namespace tbctx {
 using namespace tbhost;
@@ -202,6 +205,15 @@ struct tb_context {
         DevBuf weight[16], bias[16], input, pingPong[2], skip[3], aux[2], result, rgba8;
         tbctx::DevEvent ev[2]; float lastMs = 0.0f;
     } nn;
+    /* the neural 2 x super-resolution (context_sr.cpp).  loaded: tb_sr_load has succeeded; in / out / kernel: the seven layers'
+     * channel counts and filter sizes; weight / bias: the layers repacked for nn_convk (the last has no bias).  Activations, sized at the first use
+     * and kept while the size holds: the packed input and two tensors the layers alternate between.  result, rgba8: tb_upscale_neural's float
+     * picture and its 8-bit one.  lastMs: option last_sr_us */
+    struct Sr {
+        bool loaded = false; uint32_t in[7] = {}, out[7] = {}, kernel[7] = {};
+        DevBuf weight[7], bias[7], input, pingPong[2], result, rgba8;
+        tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+    } sr;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -326,5 +338,10 @@ int runAtrousPasses(hipStream_t stream, uint32_t W, uint32_t H, uint32_t n, cons
     DevBuf (&pingPong)[2], const tb_denoiser_settings& dn, uint32_t frameCount);
 /* context_guides.cpp: the guide surfaces belong to the context as it is now */
 bool guidesCurrent(const tb_context* c);
+/* context_neural.cpp, shared with context_sr.cpp: the bytes of a w x h tensor with its channels padded to 32; a layer's repacked weights on the device
+ * (bias as fp32, zeros where the layer has none); unpadded NHWC on the host -> channels padded to 32 */
+size_t tensorBytes(uint32_t w, uint32_t h, uint32_t channels);
+void uploadLayer(const tbnn::PackedLayer& p, DevBuf& weight, DevBuf& bias);
+std::vector<uint16_t> padChannels(const uint16_t* in, size_t pixels, uint32_t c);
 
 } // namespace tbctx

@@ -10,11 +10,7 @@
 using namespace tbhost;
 using namespace tbctx;
 
-namespace {
-
-enum { E0, E1, E2, E3, E4, E5A, E5B, D4A, D4B, D3A, D3B, D2A, D2B, D1A, D1B, D0 }; /* tbnn::kLayerNames */
-
-const uint32_t kMaxSeamChannels = 512;
+namespace tbctx {
 
 size_t tensorBytes(uint32_t w, uint32_t h, uint32_t channels) { return (size_t)w * h * nn_padded_channels(channels) * sizeof(uint16_t); }
 
@@ -34,6 +30,14 @@ std::vector<uint16_t> padChannels(const uint16_t* in, size_t pixels, uint32_t c)
     for (size_t i = 0; i < pixels; i++) memcpy(&v[i * pad], in + i * c, c * sizeof(uint16_t));
     return v;
 }
+
+} // namespace tbctx
+
+namespace {
+
+enum { E0, E1, E2, E3, E4, E5A, E5B, D4A, D4B, D3A, D3B, D2A, D2B, D1A, D1B, D0 }; /* tbnn::kLayerNames */
+
+const uint32_t kMaxSeamChannels = 512;
 
 /* The 16 layers on the context's activation buffers, enqueued on its stream: color / albedo / normal are width x height RGBA32F device surfaces
  * (albedo and normal null with 3-input weights), out likewise.  The picture is zero-extended to multiples of 16 and the result cropped.

@@ -71,6 +71,9 @@ const Query kQueries[] = {
     Q("last_rcas_us", microseconds(c->fsr.lastRcasMs))
     /* the neural still denoiser: the last network, pack to unpack (HIP events); the input channels of the loaded weights, 0 = none */
     Q("last_neural_us", microseconds(c->nn.lastMs)) Q("neural_inputs", c->nn.inputs)
+    /* the neural 2 x super-resolution: the last network, pack to finish (HIP events); weights are loaded; the form its convolutions run in (the option, or
+     * its default where nobody set it) */
+    Q("last_sr_us", microseconds(c->sr.lastMs)) Q("sr_loaded", c->sr.loaded ? 1 : 0) Q("sr_conv_form", opt<OPT_sr_conv_form>(c))
     Q("last_guides_us", microseconds(c->guides.lastMs)) /* the last tb_render_guides, its kernel alone (HIP events) */
     Q("last_guides_stack_overflow", c->guides.lastOverflow) /* stack entries per lane the last pass kept in global memory (the HYBRID form) */
     Q("last_copy_waves", c->lastCopyWaves)

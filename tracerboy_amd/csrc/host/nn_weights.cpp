@@ -169,17 +169,17 @@ Weights readTza(const char* path)
     return parseTza(bytes.data(), bytes.size());
 }
 
-PackedLayer packLayer(uint32_t cA, uint32_t cB, uint32_t cOut, const uint16_t* weightOihw, const uint16_t* bias)
+PackedLayer packLayer(uint32_t cA, uint32_t cB, uint32_t cOut, const uint16_t* weightOihw, const uint16_t* bias, uint32_t taps)
 {
     PackedLayer p;
     p.cA = cA; p.cB = cB; p.cOut = cOut;
     const uint32_t padA = roundUp(cA, 32u), padB = roundUp(cB, 32u), cIn = cA + cB;
     p.kBlocks = (padA + padB) / 32u; p.outPadded = roundUp(cOut, 32u);
     const uint32_t outBlocks = p.outPadded / 16u;
-    p.weight.assign((size_t)9u * p.kBlocks * outBlocks * 64u * 8u, 0);
+    p.weight.assign((size_t)taps * p.kBlocks * outBlocks * 64u * 8u, 0);
     p.bias.assign(p.outPadded, 0.0f);
-    for (uint32_t o = 0; o < cOut; o++) p.bias[o] = floatFromHalf(bias[o]);
-    for (uint32_t tap = 0; tap < 9u; tap++)
+    for (uint32_t o = 0; bias && o < cOut; o++) p.bias[o] = floatFromHalf(bias[o]);
+    for (uint32_t tap = 0; tap < taps; tap++)
         for (uint32_t kb = 0; kb < p.kBlocks; kb++)
             for (uint32_t ob = 0; ob < outBlocks; ob++)
                 for (uint32_t lane = 0; lane < 64u; lane++)
@@ -189,7 +189,7 @@ PackedLayer packLayer(uint32_t cA, uint32_t cB, uint32_t cOut, const uint16_t* w
                         uint32_t i;
                         if (k < padA) { if (k >= cA) continue; i = k; } else { if (k - padA >= cB) continue; i = cA + (k - padA); }
                         if (o >= cOut) continue;
-                        p.weight[((((size_t)tap * p.kBlocks + kb) * outBlocks + ob) * 64u + lane) * 8u + j] = weightOihw[((size_t)o * cIn + i) * 9u + tap];
+                        p.weight[((((size_t)tap * p.kBlocks + kb) * outBlocks + ob) * 64u + lane) * 8u + j] = weightOihw[((size_t)o * cIn + i) * taps + tap];
                     }
     return p;
 }

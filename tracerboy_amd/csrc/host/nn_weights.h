@@ -27,11 +27,13 @@ float floatFromHalf(uint16_t h);
 
 inline uint32_t roundUp(uint32_t v, uint32_t to) { return (v + to - 1u) / to * to; }
 
-/* One layer as nn_conv3x3 reads it.  The kernel's K axis is source A's channels padded to a multiple of 32, then source B's padded likewise;
- * its output channels are padded to a multiple of 32.  weight: [tap = ky * 3 + kx][K / 32][padded out / 16][lane 0..63][8] binary16, where lane l's
+/* One layer as nn_conv3x3 and nn_convk (nn_convk_kernels.hip) read it.  The kernel's K axis is source A's channels padded to a multiple of 32, then
+ * source B's padded likewise; its output channels are padded to a multiple of 32.  taps: 9 for a 3 x 3 filter, 25 for a 5 x 5 one (nn_convk alone).
+ * weight: [tap = ky * 3 + kx (ky * 5 + kx)][K / 32][padded out / 16][lane 0..63][8] binary16, where lane l's
  * eight values are output channel 16 * block + (l & 15) at k = 32 * kblock + 8 * (l >> 4) + j -- the A fragment of
- * v_mfma_f32_16x16x32_f16 as one 16-byte load; zero wherever a padded channel is involved.  bias: fp32, zero past the count. */
+ * v_mfma_f32_16x16x32_f16 as one 16-byte load; zero wherever a padded channel is involved.  bias: fp32, zero past the count (all zero for a null
+ * bias). */
 struct PackedLayer { uint32_t cA = 0, cB = 0, cOut = 0, kBlocks = 0, outPadded = 0; std::vector<uint16_t> weight; std::vector<float> bias; };
-PackedLayer packLayer(uint32_t cA, uint32_t cB, uint32_t cOut, const uint16_t* weightOihw, const uint16_t* bias);
+PackedLayer packLayer(uint32_t cA, uint32_t cB, uint32_t cOut, const uint16_t* weightOihw, const uint16_t* bias, uint32_t taps = 9u);
 
 } // namespace tbnn

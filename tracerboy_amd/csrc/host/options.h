@@ -21,6 +21,7 @@ enum : uint32_t {
     X(debug_light_count, 0, OPT_RESETS_HISTORY | OPT_NOT_NEGATIVE) /* not 0: a call's TbPerFrameConstants::LightCount, whatever the scene holds (tests) */ \
     X(post_denoised, 0, 0) /* tb_post_process(LIT) reads the denoised still of tb_denoise */ \
     X(denoise_guides, 0, 0) /* tb_denoise: 0 = the last frame's AOVs, 1 = the guide pass's normals and positions, 2 = 1 + albedo demodulation */ \
+    X(sr_conv_form, 1, OPT_ZERO_OR_ONE) /* the convolutions of the super-resolution network: 0 = plain, 1 = staged in LDS (the same bits, half the time) */ \
     X(adaptive, 0, 0) X(adaptive_min_frames, 1024 /* the reference's */, OPT_NOT_NEGATIVE) X(adaptive_test, 0, OPT_ZERO_OR_ONE) \
     X(wavefront_paths, 16ll << 20, 0) X(wavefront_grid, 256 * 8, 0) X(wavefront_segment, 4096, 0) X(wavefront_sort, 0, 0) X(wavefront_refill, 0, 0) \
     X(pooled_paths, 2, 0) X(pooled_samples, 256ll << 20, 0) X(pooled_profile, 0, 0) \

@@ -35,4 +35,18 @@ hipError_t nn_launch_resolve_aux(hipStream_t stream, uint32_t width, uint32_t he
                                  TbFloat4* normal);
 /* (x, y, z, w) -> R8G8B8A8_UNORM as the output stage stores it: clamp, scale, + 0.5, truncate; alpha 255 */
 hipError_t nn_launch_to_rgba8(hipStream_t stream, uint32_t width, uint32_t height, const TbFloat4* in, uint32_t* out);
+
+/* nn_convk_kernels.hip: the layers of the 2 x super-resolution network.
+ * nn_launch_conv3x3 with a kernel x kernel filter, kernel 3 or 5, zero padding (kernel - 1) / 2 on every side, and an optional bias (null: none).
+ * weight and bias: tbnn::packLayer's for (cA, cB, cOut, kernel * kernel taps).  form: 0, the plain form -- a wave per 16 pixels of a row, every
+ * fragment from memory; 1, the staged form -- a workgroup per 32 x 8 pixels, its input tile and halo in LDS, four rows per weight fragment; the
+ * same bits either way.  The staged form holds at most two k-blocks (nn_convk_staged_fits); more are refused like every other bad argument
+ * (hipErrorInvalidValue). */
+static inline bool nn_convk_staged_fits(uint32_t cA, uint32_t cB) { return nn_padded_channels(cA) + (cB ? nn_padded_channels(cB) : 0u) <= 64u; }
+hipError_t nn_launch_convk(hipStream_t stream, uint32_t width, uint32_t height, uint32_t kernel, uint32_t form, const uint16_t* inA, uint32_t cA,
+                           uint32_t upsampleA, const uint16_t* inB, uint32_t cB, const uint16_t* weight, const float* bias, uint32_t cOut, uint32_t relu,
+                           uint16_t* out);
+/* out[y][x] = (|half(residual[y][x][c] + input[y >> 1][x >> 1][c])| for c = 0, 1, 2; 1) at (2 inW) x (2 inH): the exact sum of the two binary16
+ * values rounded once, then its sign cleared (a NaN stays a NaN).  Both tensors have 32 channels; at most 2^24 output pixels. */
+hipError_t nn_launch_sr_finish(hipStream_t stream, uint32_t inW, uint32_t inH, const uint16_t* residual, const uint16_t* input, TbFloat4* out);
 }
