@@ -238,6 +238,44 @@ int tb_read_denoise_stage(tb_context* ctx, int stage, float* rgba);
 int tb_render_guides(tb_context* ctx, uint32_t first_frame, uint32_t n_frames);
 int tb_read_guide(tb_context* ctx, int which, float* rgba);
 
+/* ---- sample budgets (no reference counterpart: its only control is the frame-rate target) -------------------
+ * budget[y * width + x] is the global frame index at which pixel (x, y) stops receiving samples.  The context keeps a device copy; NULL clears it,
+ * and without a budget every call is planned and launched as it always was, bit for bit.  Setting, changing or clearing a budget resets no
+ * history, and a budget is not part of a render state.  While one is set, a tb_render / tb_render_async of n frames that starts at frame
+ * F0 = tb_samples_rendered is a per-call adaptive call (tb_plan_input::adaptive = 2, plan rules 8 / 7, the call from frame 0 included):
+ *   pixel p receives ALL n samples of the call -- the samples a plain call adds, in frame order -- iff F0 < budget[p], and none otherwise;
+ *   with options "adaptive" = 1 and "adaptive_test" = 1 and F0 > adaptive_min_frames the skip test must be false as well.
+ * So a pixel's sums are, bit for bit, the plain render's at some call boundary; a budget is exact where the calls are cut at its values.  A budget
+ * need not be monotone in time: raise a pixel's later and it resumes.  A budgeted call from frame 0 first clears both accumulation surfaces: a
+ * pixel that was never sampled holds (0, 0, 0, 0) on both -- 0 / 0 = NaN in tb_post_process's float picture, 0 in its 8-bit one.  The AOVs of a
+ * pixel that is not live in a call are those of a pixel the adaptive launch skips (normal (0, 0, 0, 1), custom (0, 0, 0, 1) or the LIVE_PIXELS
+ * tint); tb_denoise passes such pixels through.  tb_render_realtime ignores the budget, as it ignores "adaptive".  A tile assignment with
+ * world > 1 works: only owned pixels are listed.  tb_get_option: "budget_set"; "last_budgeted" (the last call was planned under a budget);
+ * "last_adaptive" is 1 and "last_live_pixels" the pixels listed for such a call.
+ * TB_E_INVALID (the message names the cause): tb_set_sample_budget with a zero size or more than 2^24 pixels, or while option "count_rays" is set
+ * (and "count_rays" while a budget is set); tb_render with a budget whose size is not the render's, or with "adaptive" = 1 and "adaptive_test" = 0
+ * (the per-frame test would need a budget test inside the kernels); tb_read_sample_budget without a budget.  TB_E_UNSUPPORTED: a tb_create_multi
+ * group. */
+int tb_set_sample_budget(tb_context* ctx, uint32_t width, uint32_t height, const uint32_t* budget_or_null);
+int tb_read_sample_budget(tb_context* ctx, uint32_t* out);
+/* The noise target: with F = tb_samples_rendered, every pixel that is still live (budget > F) stops -- budget = F -- iff F >= min_frames, it holds
+ * samples (n = output.w > 0) and either its mean c = output.xyz / n is black (every channel <= 0) or m > 0, n - m > 0 (m = jittered.w) and
+ * V < rel_error^2 (luma(c)^2 + 0.01), V being section 12's dual-buffer variance of the mean's luminance, prepared and 3x3-prefiltered from the current
+ * sums into scratch of this call's own (tb_denoise's surfaces stay as valid or invalid as they were); IEEE fp32, NaN compares false (such a pixel
+ * stays live).  Creates an all-0xffffffff budget if none is set.  stopped_or_null: the pixels stopped by this call; live_or_null: the pixels with
+ * budget > F afterwards.  Synchronous.  Writes nothing but the budget: tb_accum_digest, frame counter, history and guides are unchanged.
+ * A failure leaves no budget the caller did not set.  tb_get_option "last_budget_stop_us": GPU microseconds of the last call's three passes (HIP
+ * events).  With a tile assignment (world > 1) the call judges the whole surface: pixels of other ranks' tiles hold zeros, never stop and count
+ * as live unless the budget is 0 there (set it so), and along tile borders their zero variance enters the owned neighbours' prefiltered estimate,
+ * which is then lower than a one-context render's -- such pixels may stop a call earlier.
+ * TB_E_INVALID: rel_error negative or not finite; nothing rendered; the last render was tb_render_realtime; a budget of another size than the
+ * rendered frame; more than 2^24 pixels; option "count_rays" where the call would create the budget.  TB_E_UNSUPPORTED: a tb_create_multi group.
+ * tb_run_budget_stop: the kernel seam, like tb_run_denoise_pass -- host arrays of the two sums (width*height*4 floats each) and the budget (in and
+ * out), temporary buffers, nothing of the context but its stream; `frame` stands for F. */
+int tb_budget_stop_converged(tb_context* ctx, float rel_error, uint32_t min_frames, uint64_t* stopped_or_null, uint64_t* live_or_null);
+int tb_run_budget_stop(tb_context* ctx, uint32_t width, uint32_t height, const float* output, const float* jittered, uint32_t* budget, float rel_error,
+                       uint32_t min_frames, uint32_t frame, uint64_t* stopped_or_null, uint64_t* live_or_null);
+
 /* <-> ReadbackStats copy (TracerBoy.cpp:2946, D3D12App.cpp:195-201) */
 int tb_read_stats(tb_context* ctx, tb_readback_stats* out);
 /* Wave-occupancy profile of the last counting render (option "count_rays"): 7 pairs (active lane-executions,

@@ -68,6 +68,10 @@ def lib():
         "tb_read_denoise_stage": (C.c_int, [vp, C.c_int, vp]),
         "tb_render_guides": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "tb_read_guide": (C.c_int, [vp, C.c_int, vp]),
+        "tb_set_sample_budget": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+        "tb_read_sample_budget": (C.c_int, [vp, vp]),
+        "tb_budget_stop_converged": (C.c_int, [vp, C.c_float, C.c_uint32, P(C.c_uint64), P(C.c_uint64)]),
+        "tb_run_budget_stop": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32, C.c_uint32, P(C.c_uint64), P(C.c_uint64)]),
         "tb_post_process": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, vp, vp]),
         "tb_read_averaged_luminance": (C.c_int, [vp, P(C.c_float)]),
         "tb_write_image_rgba8": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, vp]),
@@ -500,6 +504,7 @@ class TracerBoy:
         if rc != 0:
             raise TracerBoyError(rc, (self._L.tb_last_error(None) or b"").decode(errors="replace"))
         self.width = self.height = 0
+        self._budget_shape = None
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -942,6 +947,44 @@ class TracerBoy:
         out = np.empty((height, width, 4), np.float32)
         self._check(self._L.tb_run_composite(self._ctx, width, height, *[None if a is None else _np_ptr(a) for a in f], _np_ptr(out)))
         return out
+
+    # -- sample budgets ---------------------------------------------------
+    def SetSampleBudget(self, budget):
+        """budget: an (H, W) uint32 array -- per pixel the global frame index at which it stops receiving samples -- or None to clear it
+        (tb_set_sample_budget).  While one is set a Render that starts at frame F0 gives pixel p all of its frames iff F0 < budget[p]."""
+        if budget is None:
+            self._check(self._L.tb_set_sample_budget(self._ctx, 0, 0, None))
+            self._budget_shape = None
+            return
+        b = np.ascontiguousarray(budget, np.uint32)
+        if b.ndim != 2:
+            raise ValueError("SetSampleBudget: an (H, W) array")
+        self._check(self._L.tb_set_sample_budget(self._ctx, b.shape[1], b.shape[0], _np_ptr(b)))
+        self._budget_shape = b.shape
+
+    def SampleBudget(self):
+        """The budget the context holds, (H, W) uint32 (tb_read_sample_budget); TracerBoyError without one."""
+        out = np.empty(self._budget_shape or (max(self.height, 1), max(self.width, 1)), np.uint32)
+        self._check(self._L.tb_read_sample_budget(self._ctx, _np_ptr(out)))
+        return out
+
+    def StopConverged(self, rel_error, min_frames=64):
+        """The noise target (tb_budget_stop_converged): every live pixel whose estimated relative error is below rel_error stops at the current
+        frame.  Returns (pixels stopped by this call, pixels still live)."""
+        stopped, live = C.c_uint64(), C.c_uint64()
+        self._check(self._L.tb_budget_stop_converged(self._ctx, rel_error, min_frames, C.byref(stopped), C.byref(live)))
+        self._budget_shape = self._budget_shape or (self.height, self.width)     # (the call makes an all-live budget where there is none)
+        return int(stopped.value), int(live.value)
+
+    def RunBudgetStop(self, output, jittered, budget, rel_error, min_frames, frame):
+        """budget_stop_kernel behind section 12's prepare and prefilter, on host arrays (tb_run_budget_stop): (H, W, 4) float32 sums, (H, W) uint32
+        budget.  Returns (the budget afterwards, stopped, live)."""
+        o, q = np.ascontiguousarray(output, np.float32), np.ascontiguousarray(jittered, np.float32)
+        b = np.array(budget, np.uint32, order="C")
+        stopped, live = C.c_uint64(), C.c_uint64()
+        self._check(self._L.tb_run_budget_stop(self._ctx, o.shape[1], o.shape[0], _np_ptr(o), _np_ptr(q), _np_ptr(b), rel_error, min_frames, frame,
+                                               C.byref(stopped), C.byref(live)))
+        return b, int(stopped.value), int(live.value)
 
 
 def unpack_gathered(width, height, world, tile_w, tile_h, per_rank_packed):

@@ -8,6 +8,7 @@
  *                 [--upscale WxH | --render-scale F] [--fsr-sharpness S]
  *                 [--denoise-neural FILE.tza [--denoise-guides K]]
  *                 [--upscale-neural FILE.bin]
+ *                 [--crop X0,Y0,X1,Y1] [--spp-map FILE] [--noise-target T [--noise-after F] [--noise-chunk C]]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -74,7 +75,25 @@
  * ships none).  --out is the network's picture: .png its 8-bit conversion, .pfm / .exr the float LDR picture, as with --denoise-neural; the network
  * reads the output stage's 8-bit picture here, too.  With --denoise the denoised picture is what is upscaled.  Not together with --upscale,
  * --render-scale, --denoise-neural (the reference builds with one network or the other) or --ranks N > 1.  Mistakes, an unreadable or malformed
- * FILE.bin among them, are reported before any device call (exit status 2). */
+ * FILE.bin among them, are reported before any device call (exit status 2).
+ *
+ * Sample budgets (tb_set_sample_budget / tb_budget_stop_converged): three flags that decide WHERE the samples go; they combine
+ * (a pixel is sampled while all of them say so).  --crop X0,Y0,X1,Y1: only the pixels of the half-open window are rendered (budget 0xffffffff inside, 0
+ * outside).  --spp-map FILE (.hdr .pfm .png .tga, of the frame's size): pixel p gets (uint32_t)(saturate(red) * spp + 0.5f) samples; the calls are
+ * cut at the sorted distinct counts, so every pixel gets exactly its own; more than 256 distinct counts are refused.  --noise-target T: one call of
+ * min(F, spp) frames (--noise-after, default 64), then calls of C frames (--noise-chunk, default 64), each preceded by tb_budget_stop_converged(T, F):
+ * a pixel stops once the estimated standard error of its mean's luminance, relative to sqrt(luma^2 + 0.01), is below T; rendering ends early when
+ * no pixel is live; one line per call: frames so far, live pixels at the call's start, milliseconds.  With --adaptive P --adaptive-test call the
+ * reference's skip test applies as well, at the frames of its own schedule.  Pixels that were never sampled are 0 in .pfm / .exr files (the linear
+ * radiance, and --denoise's picture) and in every .png; the float output stage has 0 / 0 = NaN for them, which FSR would spread: --upscale to a
+ * float file is refused with these flags.  A state holds the sums, not the budget: give the flags again with --resume; --spp-map counts from frame 0
+ * and does not go with --frames.  With --ranks every rank budgets its own tiles (0 outside them) and judges the noise target on its own surface,
+ * where the tiles of other ranks hold zeros: along tile borders the prefiltered variance is lower than in a one-GPU run, so those pixels may stop
+ * a call earlier -- a --ranks noise-target picture is not bit for bit the one-GPU one (crop and map pictures are).  The closing line counts the
+ * samples actually taken (live pixels x frames of every call; with --ranks it keeps the full frame's count).
+ * Exit status 2, before any device call: a malformed or empty window, T not finite or not above 0, a map that cannot be read, any of the three
+ * with --adaptive unless --adaptive-test call, with --upscale-neural or with --render-scale; a window outside the frame or a map of another size
+ * likewise where --width and --height are given, otherwise as soon as the scene (or the state) has told the frame's size. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -172,7 +191,7 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C]\n"); return 2; }
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
@@ -180,6 +199,8 @@ int main(int argc, char** argv)
     std::string saveState, resume; std::vector<std::string> adds; long long frameA = -1, frameB = -1, checkpointEvery = 0;
     bool sppSet = false, timeSet = false, denoise = false, demodulate = false; long long denoiseIterations = -1, denoiseGuides = 0;
     std::string neural, neuralUp; bool denoiseFlag = false; /* --denoise itself, not what --denoise-guides implies */
+    long long crop[4] = {0, 0, 0, 0}; bool cropSet = false; std::string sppMap; float noiseTarget = 0.0f; bool noiseSet = false;
+    long long noiseAfter = 64, noiseChunk = 64;
     uint32_t upW = 0, upH = 0; float renderScale = 0.0f, fsrSharpness = -1.0f; bool upscaleSet = false, renderScaleSet = false, sharpnessSet = false;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
@@ -213,6 +234,13 @@ int main(int argc, char** argv)
             if (end == v || *end || !(renderScale > 0.0f) || !(renderScale <= 1.0f)) { fprintf(stderr, "--render-scale is above 0 and at most 1\n"); return 2; } }
         else if (k == "--fsr-sharpness") { char* end = nullptr; fsrSharpness = strtof(v, &end); sharpnessSet = true;
             if (end == v || *end || !(fsrSharpness >= 0.0f) || !(fsrSharpness < 1e30f)) { fprintf(stderr, "--fsr-sharpness is a finite number of stops, 0 or more\n"); return 2; } }
+        else if (k == "--crop") { const char* p = v; char* end = nullptr; cropSet = true;
+            for (int j = 0; j < 4 && p; j++) { crop[j] = strtoll(p, &end, 10); p = end != p && *end == (j < 3 ? ',' : '\0') && crop[j] >= 0 && crop[j] <= 16384 ? end + 1 : nullptr; }
+            if (!p || crop[2] <= crop[0] || crop[3] <= crop[1]) { fprintf(stderr, "--crop is X0,Y0,X1,Y1 with 0 <= X0 < X1 and 0 <= Y0 < Y1 (half-open)\n"); return 2; } }
+        else if (k == "--spp-map") sppMap = v;
+        else if (k == "--noise-target") { char* end = nullptr; noiseTarget = strtof(v, &end); noiseSet = true;
+            if (end == v || *end || !(noiseTarget > 0.0f) || !(noiseTarget < 3.0e38f)) { fprintf(stderr, "--noise-target is a finite relative error above 0\n"); return 2; } }
+        else if (k == "--noise-after") noiseAfter = atoll(v); else if (k == "--noise-chunk") noiseChunk = atoll(v);
         else if (k == "--denoise-neural") neural = v;
         else if (k == "--upscale-neural") neuralUp = v;
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
@@ -225,6 +253,17 @@ int main(int argc, char** argv)
     const bool forceRccl = getenv("TB_CLI_FORCE_RCCL") && atoi(getenv("TB_CLI_FORCE_RCCL")) != 0;
     if (ranks < 1) { fprintf(stderr, "--ranks must be at least 1\n"); return 2; }
     if (adaptiveAfter < 0 || adaptiveChunk < 1) { fprintf(stderr, "--adaptive-after must not be negative, --adaptive-chunk must be at least 1\n"); return 2; }
+    /* sample budgets */
+    const bool budgeted = cropSet || !sppMap.empty() || noiseSet;
+    if (noiseAfter < 0 || noiseAfter > 0xffffffffll || noiseChunk < 1) { fprintf(stderr, "--noise-after must not be negative, --noise-chunk must be at least 1\n"); return 2; }
+    if (budgeted && adaptive >= 0.0f && adaptiveTest != 1) { fprintf(stderr,
+        "--crop, --spp-map and --noise-target go with --adaptive only as --adaptive-test call: a budget is applied once per call\n"); return 2; }
+    if (budgeted && !neuralUp.empty()) { fprintf(stderr, "--crop, --spp-map and --noise-target do not go with --upscale-neural\n"); return 2; }
+    if (!sppMap.empty() && frameA >= 0) { fprintf(stderr,
+        "--spp-map does not go with --frames: its counts are samples from frame 0 on\n"); return 2; }
+    if (budgeted && upscaleSet && !(out.size() >= 4 && out.compare(out.size() - 4, 4, ".png") == 0)) { fprintf(stderr,
+        "--crop, --spp-map and --noise-target go with --upscale only for a .png: the float chain would spread the NaN of never-sampled pixels\n"); return 2; }
+    if (budgeted && renderScaleSet) { fprintf(stderr, "--crop, --spp-map and --noise-target do not go with --render-scale: they are given in rendered pixels\n"); return 2; }
     if (!neural.empty()) {
         if (denoiseFlag || denoiseIterations >= 0 || demodulate) { fprintf(stderr,
             "--denoise-neural does not go with --denoise, --denoise-iterations or --denoise-demodulate: the network stands in place of the a-trous filter\n"); return 2; }
@@ -256,6 +295,33 @@ int main(int argc, char** argv)
     if (upscaleSet && renderScaleSet) { fprintf(stderr, "--upscale and --render-scale do not go together: --render-scale upscales to --width x --height\n"); return 2; }
     if (sharpnessSet && !upscaleSet && !renderScaleSet) { fprintf(stderr, "--fsr-sharpness needs --upscale or --render-scale\n"); return 2; }
     if (renderScaleSet && !resume.empty()) { fprintf(stderr, "--render-scale does not go with --resume: the state decides the rendered size\n"); return 2; }
+    std::vector<float> mapRgba; uint32_t mapW = 0, mapH = 0;
+    if (!sppMap.empty()) { /* host only: decoded before any device call */
+        int normalized = 0, alpha = 0;
+        if (tb_decode_image(sppMap.c_str(), &mapW, &mapH, &normalized, &alpha, nullptr) || !mapW || !mapH) {
+            fprintf(stderr, "--spp-map %s: cannot be read as an image (.hdr .pfm .png .tga)\n", sppMap.c_str()); return 2; }
+        mapRgba.resize((size_t)mapW * mapH * 4);
+        if (tb_decode_image(sppMap.c_str(), &mapW, &mapH, &normalized, &alpha, mapRgba.data())) {
+            fprintf(stderr, "--spp-map %s: cannot be read as an image (.hdr .pfm .png .tga)\n", sppMap.c_str()); return 2; }
+    }
+    std::vector<uint32_t> mapBudget, mapCuts; /* per pixel; its sorted distinct values */
+    if (!sppMap.empty()) {
+        mapBudget.resize((size_t)mapW * mapH);
+        for (size_t i = 0; i < mapBudget.size(); i++) { const float red = mapRgba[4 * i], sat = red > 0.0f ? (red < 1.0f ? red : 1.0f) : 0.0f; /* (NaN: 0) */
+            mapBudget[i] = (uint32_t)(sat * (float)spp + 0.5f); }
+        mapCuts = mapBudget; std::sort(mapCuts.begin(), mapCuts.end()); mapCuts.erase(std::unique(mapCuts.begin(), mapCuts.end()), mapCuts.end());
+        if (mapCuts.size() > 256) { fprintf(stderr, "--spp-map %s holds %zu distinct sample counts: at most 256 (every count is a call of its own)\n",
+            sppMap.c_str(), mapCuts.size()); return 2; }
+    }
+    /* the frame's size against window and map: exit status 2; before any device call where --width and --height say it */
+    auto budgetFits = [&](uint32_t fw, uint32_t fh) {
+        if (cropSet && (crop[2] > (long long)fw || crop[3] > (long long)fh)) {
+            fprintf(stderr, "--crop %lld,%lld,%lld,%lld lies outside the %ux%u frame\n", crop[0], crop[1], crop[2], crop[3], fw, fh); return false; }
+        if (!sppMap.empty() && (mapW != fw || mapH != fh)) {
+            fprintf(stderr, "--spp-map %s is %ux%u, the frame %ux%u\n", sppMap.c_str(), mapW, mapH, fw, fh); return false; }
+        return true;
+    };
+    if (budgeted && W && H && resume.empty() && !budgetFits(W, H)) return 2;
     if (ranks > 1 && !envRank) return spawnRanks(argc, argv, ranks);
     if (envRank && (!getenv("TB_CLI_WORLD") || atoi(getenv("TB_CLI_WORLD")) < 1 || atoi(envRank) < 0 || atoi(envRank) >= atoi(getenv("TB_CLI_WORLD")) ||
                     (atoi(getenv("TB_CLI_WORLD")) > 1 && !getenv("TB_CLI_ID_FILE")))) {
@@ -321,8 +387,47 @@ int main(int argc, char** argv)
     if (!neuralUp.empty() && (uint64_t)W * H * 4u > (1ull << 24)) { /* likewise */
         fprintf(stderr, "tracerboy-hip: cannot upscale the %ux%u render to twice that: more than 2^24 pixels\n", W, H); tb_destroy(ctx); return 2; }
     const uint32_t start = done;
+    uint64_t sampled = 0; /* budgeted runs: the samples actually taken, live pixels x frames of every call (this rank's) */
     auto checkpoint = [&]() { return checkpointEvery > 0 ? tb_state_save(ctx, saveState.c_str()) : 0; };
-    if (adaptive < 0.0f) {
+    if (budgeted) {
+        /* Sample budgets.  Window and map make the budget before the first call (a rank's also holds 0 outside its tiles, so
+         * that its live counts are its own); a noise target alone lets its first call run plain and tb_budget_stop_converged make the budget.  The
+         * calls are cut where anything can change: at the map's counts, at the noise target's grid (frame F, then every C), at --adaptive's own
+         * grid (frame F' + 1, then every C'), at --checkpoint-every. */
+        if (!budgetFits(W, H)) { tb_destroy(ctx); return 2; }
+        if (cropSet || !sppMap.empty() || world > 1) {
+            std::vector<uint32_t> budget((size_t)W * H, 0xffffffffu);
+            const uint32_t tilesX = (W + TILE - 1) / TILE;
+            for (uint32_t y = 0; y < H; y++) for (uint32_t x = 0; x < W; x++) {
+                uint32_t& b = budget[(size_t)y * W + x];
+                if (!mapBudget.empty()) b = mapBudget[(size_t)y * W + x];
+                if (cropSet && (x < crop[0] || x >= crop[2] || y < crop[1] || y >= crop[3])) b = 0;
+                if (world > 1 && ((y / TILE) * tilesX + x / TILE) % (uint32_t)world != (uint32_t)rank) b = 0;
+            }
+            if ((rc = tb_set_sample_budget(ctx, W, H, budget.data()))) return fail(ctx, "tb_set_sample_budget", rc);
+        }
+        const uint32_t noiseStart = (uint32_t)std::min<long long>(noiseAfter, target), plainEnd = (uint32_t)std::min<long long>(adaptiveAfter + 1, target);
+        while (done < target) {
+            long long next = target;
+            for (uint32_t cut : mapCuts) if (cut > done) { next = std::min<long long>(next, cut); break; }
+            if (noiseSet) next = std::min<long long>(next, done < noiseStart ? (long long)noiseStart : done + noiseChunk - (done - noiseStart) % noiseChunk);
+            if (adaptive >= 0.0f) next = std::min<long long>(next, done < plainEnd ? (long long)plainEnd : done + adaptiveChunk - (done - plainEnd) % adaptiveChunk);
+            if (checkpointEvery > 0) next = std::min<long long>(next, (long long)done + checkpointEvery);
+            if (noiseSet && done >= noiseStart && done > start) { /* (never before this run's first call: a --frames job holds nothing yet) */
+                uint64_t stopped = 0, live = 0;
+                if ((rc = tb_budget_stop_converged(ctx, noiseTarget, (uint32_t)noiseAfter, &stopped, &live))) return fail(ctx, "tb_budget_stop_converged", rc);
+                if (live == 0) { printf("noise target: %u frames, every pixel has stopped\n", done); break; }
+            }
+            const uint32_t n = (uint32_t)(next - done);
+            if ((rc = tb_render(ctx, W, H, n, &s, t))) return fail(ctx, "tb_render", rc);
+            const float callMs = tb_last_render_ms(ctx);
+            const long long live = (long long)tb_get_option(ctx, "last_live_pixels");
+            done += n; ms += callMs; sampled += (uint64_t)std::max<long long>(live, 0) * n;
+            if (world > 1) printf("budget rank %d: %u frames, %lld live pixels, %.3f ms\n", rank, done, live, callMs);
+            else printf("budget: %u frames, %lld live pixels, %.3f ms\n", done, live, callMs);
+            if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+        }
+    } else if (adaptive < 0.0f) {
         if (!states) { /* the plain render: one call */
             if ((rc = tb_render(ctx, W, H, spp, &s, t))) return fail(ctx, "tb_render", rc);
             ms = tb_last_render_ms(ctx); done = spp;
@@ -482,7 +587,9 @@ int main(int argc, char** argv)
     }
     printf("%s: %u triangles, %ux%u x %u spp, depth %d, %d GPU%s: %.2f ms (%.1f Msamples/s), scene load + BVH %.2f s -> %s\n",
            scene.c_str(), info.numTriangles, W, H, spp, s.MaxBounces, world, world > 1 ? "s (tiles gathered over RCCL)" : "", ms,
-               ms > 0.0f ? (double)W * H * (spp - start) / (ms * 1e3) : 0.0, loadS, out.c_str());
+               ms > 0.0f ? (budgeted && world == 1 ? (double)sampled : (double)W * H * (spp - start)) / (ms * 1e3) : 0.0, loadS, out.c_str());
+    if (budgeted && world == 1) printf("budget: %llu samples taken of the %llu a full render of these frames takes\n", (unsigned long long)sampled,
+        (unsigned long long)W * H * (spp - start));
     tb_destroy(ctx);
     return 0;
 }

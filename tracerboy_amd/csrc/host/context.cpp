@@ -283,6 +283,9 @@ int tb_set_option(tb_context* c, const char* name, int64_t v)
     /* the adaptive launch has no counting copy */
     if (v && ((k == OPT_adaptive && opt<OPT_count_rays>(c)) || (k == OPT_count_rays && opt<OPT_adaptive>(c))))
         return fail(c, TB_E_INVALID, "tb_set_option: options \"adaptive\" and \"count_rays\" exclude each other (the counting kernels have no adaptive copy)");
+    /* ... nor has a call under a sample budget, which runs the same launch */
+    if (v && k == OPT_count_rays && c->budget.set) return fail(c, TB_E_INVALID,
+        "tb_set_option: option \"count_rays\" and a sample budget exclude each other (the counting kernels have no list-driven copy): clear the budget first");
     c->options.value[k] = v; c->options.isSet[k] = true;
     if (kOptions[k].flags & OPT_RESETS_HISTORY) resetHistory(c);
     return TB_OK;

@@ -13,6 +13,7 @@
  *   context_upscale.cpp FSR 1 upscaling of the post-processed picture: EASU + RCAS
  *   context_neural.cpp  the neural still denoiser: the OIDN U-Net on the matrix cores, its layer seam and its stage
  *   context_sr.cpp      the neural 2 x super-resolution: the reference's DirectML network on the matrix cores, its seams and its stage
+ *   context_budget.cpp  sample budgets: set / read, the noise target that stops converged pixels, its kernel seam
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -140,6 +141,11 @@ struct tb_context {
     DevBuf regionCost, regionOrder[2]; uint64_t regionCostKey = ~0ull; /* costly regions first (TbDeviceTargets::regionCost / regionOrder): 2^20 counts; per side stream 1 + 2 x regions words */
     /* the adaptive launch (option "adaptive"): live list, its count and the list pass's scratch (pt_launch_live_list); what the last call was */
     DevBuf liveList; size_t liveCountOffset = 0; /* bytes of scratch before the count word */ bool lastAdaptive = false; uint64_t lastOwnedPixels = 0;
+    /* the sample budget (context_budget.cpp): per pixel the global frame index at which it stops receiving samples; set: one is
+     * held (values: its device copy, width x height words); lastBudgeted: the last call was planned under it.  stop: tb_budget_stop_converged's
+     * scratch -- section 12's prepared and filtered surfaces of its own, and its two counters */
+    struct Budget { DevBuf values, prepared, filtered, counts; bool set = false; uint32_t width = 0, height = 0; bool lastBudgeted = false;
+        tbctx::DevEvent ev[2]; float lastStopMs = 0.0f; /* option last_budget_stop_us: the last noise target's three passes (HIP events) */ } budget;
     DevBuf stackOverflow; /* split traversal stack of the higher-occupancy kernel copies on deep trees (pt_scene.h) */
     std::vector<const void*> warmedLaunchers; /* frame-group kernels that have run once on both side streams (renderImpl) */
     uint32_t fgLaunch = 0; bool sideOrdered = false; /* sideOrdered: the side streams have been ordered after everything else on `stream` */

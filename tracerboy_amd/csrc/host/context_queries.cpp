@@ -78,6 +78,9 @@ const Query kQueries[] = {
     Q("last_guides_stack_overflow", c->guides.lastOverflow) /* stack entries per lane the last pass kept in global memory (the HYBRID form) */
     Q("last_copy_waves", c->lastCopyWaves)
     Q("last_adaptive", c->lastAdaptive ? 1 : 0) /* the adaptive launch: did the last call run it */
+    /* sample budgets: one is set; the last call was planned under it (its live pixels: last_live_pixels) */
+    Q("budget_set", c->budget.set ? 1 : 0) Q("last_budgeted", c->budget.lastBudgeted ? 1 : 0)
+    Q("last_budget_stop_us", microseconds(c->budget.lastStopMs)) /* the last tb_budget_stop_converged: prepare, prefilter, stop (HIP events) */
     Q("adaptive_min_frames", opt<OPT_adaptive_min_frames>(c))
     Q("last_live_pixels", lastLivePixels(c)) Q("last_variant", lastVariantId(c))
 };

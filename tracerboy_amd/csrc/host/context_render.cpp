@@ -179,6 +179,7 @@ static uint64_t ownedFramePixels(uint32_t W, uint32_t H, const TbTileMap& t)
 struct RenderCall {
     tb_context* c; uint32_t W, H, n; tb_output_settings s; float timeSeed; bool sync;
     bool aov, count, adaptive, perCall /* option adaptive_test = 1 */, clearStats; int64_t adaptiveMin, pipe;
+    bool budgeted, skipTest; /* planned under a sample budget; ... whose list pass applies the adaptive skip test too */
     TbPerFrameConstants pf; TbDeviceTargets tg;
     const Variant* v; int variantIndex; bool twoLevel; tb_plan_input pin; tb_launch_plan plan;
     bool wavefront, pooled, split, groups; /* of the first plan (a plan made again for layout C changes none of them) */
@@ -455,6 +456,12 @@ static void decideAdaptive(RenderCall& r)
     r.perCall = opt<OPT_adaptive_test>(c) == 1;
     r.adaptive = opt<OPT_adaptive>(c) != 0 && !r.count && !r.s.RenderModeRealTime &&
         (r.perCall ? (int64_t)c->samplesRendered : (int64_t)c->samplesRendered + (int64_t)r.n - 1) > r.adaptiveMin;
+    /* A sample budget (tb_set_sample_budget) is the list pass's second source: every call under it, the one from frame 0
+     * included, is a per-call adaptive call -- live at its first frame F0 iff F0 < budget, and, where options adaptive and adaptive_test are on and
+     * F0 is past the threshold, iff the skip test does not hold either.  Real time ignores it, as it ignores option adaptive. */
+    r.budgeted = c->budget.set && !r.s.RenderModeRealTime;
+    if (r.budgeted) { r.skipTest = r.adaptive; r.adaptive = r.perCall = true; }
+    c->budget.lastBudgeted = r.budgeted;
     c->lastAdaptive = r.adaptive; c->lastOwnedPixels = ownedFramePixels(r.W, r.H, c->tiles);
     /* 4 = the split-role kernel where it exists, the lock-step kernel (0) elsewhere */
     r.pipe = opt<OPT_pipeline>(c) == 4 ? 0 : opt<OPT_pipeline>(c);
@@ -673,8 +680,10 @@ static void buildLiveList(RenderCall& r)
     c->liveCountOffset = scratch;
     /* (tested per call, the one-pixel-per-lane kernel's guard `frame > adaptiveMinFrames` before each later frame must never hold) */
     tg.liveCount = (const uint32_t*)(base + scratch); tg.liveList = tg.liveCount + TB_LIVE_COUNT_WORDS; tg.adaptiveMinFrames = r.perCall ? 0xffffffffu : (uint32_t)r.adaptiveMin;
-    HIP_TRY(pt_launch_live_list(c->stream, tg.output, tg.jittered, &c->tiles, r.W, r.H, c->samplesRendered, (uint32_t)r.adaptiveMin, r.pf.MinConvergence,
-        tg.aovNormals, tg.aovCustom, r.s.OutputType == TB_OUTPUT_TYPE_LIVE_PIXELS ? 1 : 0, base, (uint32_t*)tg.liveList, (uint32_t*)tg.liveCount));
+    /* (under a budget without the skip test no frame is past the threshold) */
+    const uint32_t minFrames = r.budgeted && !r.skipTest ? 0xffffffffu : (uint32_t)r.adaptiveMin;
+    HIP_TRY(pt_launch_live_list(c->stream, tg.output, tg.jittered, r.budgeted ? (const uint32_t*)c->budget.values.p : nullptr, &c->tiles, r.W, r.H,
+        c->samplesRendered, minFrames, r.pf.MinConvergence, tg.aovNormals, tg.aovCustom, r.s.OutputType == TB_OUTPUT_TYPE_LIVE_PIXELS ? 1 : 0, base, (uint32_t*)tg.liveList, (uint32_t*)tg.liveCount));
 }
 
 /* the path-tracing launches of the call: one of the other pipelines, one launch of the lock-step kernel on the main stream, or frame groups */
@@ -712,6 +721,16 @@ static int closeCall(RenderCall& r)
 int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_output_settings* settings, float timeSeed, bool sync)
 {
     RenderCall r{}; r.c = c; r.W = W; r.H = H; r.n = n; r.timeSeed = timeSeed; r.sync = sync;
+    if (c->budget.set && !(settings && settings->RenderModeRealTime)) { /* before anything is resized or forgotten */
+        if (W != c->budget.width || H != c->budget.height) return fail(c, TB_E_INVALID, "tb_render: the sample budget is " + std::to_string(c->budget.width) +
+            " x " + std::to_string(c->budget.height) + ", the render " + std::to_string(W) + " x " + std::to_string(H) +
+            ": set a budget of the render's size or clear it (tb_set_sample_budget)");
+        if (opt<OPT_count_rays>(c)) return fail(c, TB_E_INVALID,
+            "tb_render: a sample budget and option \"count_rays\" exclude each other (the counting kernels have no list-driven copy)");
+        if (opt<OPT_adaptive>(c) && opt<OPT_adaptive_test>(c) == 0) return fail(c, TB_E_INVALID,
+            "tb_render: a sample budget with option \"adaptive\" needs \"adaptive_test\" = 1: the budget is applied once per call, the per-frame skip test "
+            "would need a budget test inside the kernels");
+    }
     if (const int rc = beginCall(r, settings)) return rc;
     if (n == 0) return TB_OK;
     decideAdaptive(r);
@@ -726,6 +745,11 @@ int renderImpl(tb_context* c, uint32_t W, uint32_t H, uint32_t n, const tb_outpu
     c->kernelEventStamp++; /* this render records evKernelStart / evKernel */
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     if (r.clearStats && !r.overlap) HIP_TRY(hipMemsetAsync(c->stats.p, 0, 16, c->stream)); /* (an overlapped call: on the stream of its first launch) */
+    /* a plain call zeroes a pixel's sums through its frame-0 sample, the list-driven fold and the one-pixel-per-lane adaptive kernel write listed
+     * pixels only: a budgeted call from frame 0 clears both surfaces first, so that a pixel that was never sampled reads (0, 0, 0, 0) */
+    if (r.budgeted && c->samplesRendered == 0) {
+        HIP_TRY(hipMemsetAsync(c->output.p, 0, c->output.bytes, c->stream)); HIP_TRY(hipMemsetAsync(c->jittered.p, 0, c->jittered.bytes, c->stream));
+    }
     if (r.adaptive) buildLiveList(r);
     dispatch(r);
     return closeCall(r);

@@ -118,6 +118,35 @@ __global__ __launch_bounds__(DN_THREADS) void dn_finish_remod_kernel(const TbFlo
     final[i] = TbFloat4{x.x * dn_demod(a.x, a.w), x.y * dn_demod(a.y, a.w), x.z * dn_demod(a.z, a.w), 1.0f};
 }
 
+/* ---- the noise target of a sample budget (tb_budget_stop_converged) ----
+ * A pixel that is still live at frame F (budget > F) stops -- budget = F -- once F has reached minFrames, the pixel holds samples and either its mean
+ * is black or the prefiltered variance of the mean's luminance (filtered.w, the two passes above) is below relError^2 (luma^2 + 0.01), the floor of
+ * section 12's relMSE.  NaN compares false: such a pixel stays live.  Every lane of a wave reaches the ballots; counts[0] += the pixels stopped,
+ * counts[1] += the pixels live afterwards, one integer add per wave -- whatever the order, the same sums. */
+__global__ __launch_bounds__(DN_THREADS) void budget_stop_kernel(const TbFloat4* __restrict__ output, const TbFloat4* __restrict__ jittered,
+    const TbFloat4* __restrict__ filtered, uint32_t* __restrict__ budget, uint32_t nPixels, uint32_t F, uint32_t minFrames, float relError,
+    unsigned long long* __restrict__ counts)
+{
+    const uint32_t i = blockIdx.x * DN_THREADS + threadIdx.x;
+    bool stop = false, liveAfter = false;
+    if (i < nPixels && budget[i] > F) {
+        const TbFloat4 o = output[i], q = jittered[i];
+        const float n = o.w, m = q.w, r = n - m;
+        if (F >= minFrames && n > 0.0f) {
+            const float cx = o.x / n, cy = o.y / n, cz = o.z / n;
+            const float l = dn_luma(cx, cy, cz), V = filtered[i].w;
+            const float threshold = (relError * relError) * ((l * l) + 0.01f);
+            stop = (cx <= 0.0f && cy <= 0.0f && cz <= 0.0f) || (m > 0.0f && r > 0.0f && V < threshold);
+        }
+        if (stop) budget[i] = F; else liveAfter = true;
+    }
+    const unsigned long long s = __ballot(stop), l = __ballot(liveAfter);
+    if ((threadIdx.x & 63u) == 0) {
+        if (s) atomicAdd(&counts[0], (unsigned long long)__popcll(s));
+        if (l) atomicAdd(&counts[1], (unsigned long long)__popcll(l));
+    }
+}
+
 /* a frame has at most 16384 pixels a side (tb_render): 2^28 pixels, 2^20 workgroups */
 bool dn_frame(uint32_t W, uint32_t H, uint32_t* nPixels, uint32_t* groups)
 {
@@ -176,5 +205,14 @@ extern "C" hipError_t dn_launch_finish_remod(hipStream_t stream, const TbFloat4*
     uint32_t nPixels, groups;
     if (!dn_frame(W, H, &nPixels, &groups) || !dn_surface(in) || !dn_surface(gAlbedo) || !dn_surface(final)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dn_finish_remod_kernel, dim3(groups), dim3(DN_THREADS), 0, stream, in, gAlbedo, final, nPixels);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t dn_launch_budget_stop(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const TbFloat4* filtered, uint32_t* budget,
+    uint32_t W, uint32_t H, uint32_t frame, uint32_t minFrames, float relError, unsigned long long* counts)
+{
+    uint32_t nPixels, groups;
+    if (!dn_frame(W, H, &nPixels, &groups) || !dn_surface(output) || !dn_surface(jittered) || !dn_surface(filtered) || !budget || !counts) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(budget_stop_kernel, dim3(groups), dim3(DN_THREADS), 0, stream, output, jittered, filtered, budget, nPixels, frame, minFrames, relError, counts);
     return hipGetLastError();
 }

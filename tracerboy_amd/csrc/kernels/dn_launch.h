@@ -24,4 +24,9 @@ hipError_t dn_launch_prepare_demod(hipStream_t stream, const TbFloat4* output, c
                                    uint32_t W, uint32_t H);
 /* final[i] = (in[i].xyz * d, 1) */
 hipError_t dn_launch_finish_remod(hipStream_t stream, const TbFloat4* in, const TbFloat4* gAlbedo, TbFloat4* final, uint32_t W, uint32_t H);
+/* The noise target of a sample budget.  filtered: dn_launch_prepare + dn_launch_prefilter of output / jittered; budget: W x H
+ * frame indices.  A pixel with budget > frame gets budget = frame iff frame >= minFrames, it holds samples and its mean is black or filtered.w <
+ * relError^2 (luma(mean)^2 + 0.01).  counts[0] += pixels stopped, counts[1] += pixels still live (budget > frame) afterwards: zero them first. */
+hipError_t dn_launch_budget_stop(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const TbFloat4* filtered, uint32_t* budget,
+                                 uint32_t W, uint32_t H, uint32_t frame, uint32_t minFrames, float relError, unsigned long long* counts);
 }

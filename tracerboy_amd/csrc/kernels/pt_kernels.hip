@@ -235,6 +235,38 @@ __global__ __launch_bounds__(256) void live_list_count(const TbFloat4* __restric
     if (threadIdx.x == 0) counts[region] = waveLive[0] + waveLive[1] + waveLive[2] + waveLive[3];
 }
 
+/* live_list_count for a call under a sample budget (tb_set_sample_budget): the same lane mapping, ballots and AOV writes; a
+ * pixel is live iff the launch's first frame is below its budget -- and, where the adaptive test is on too (minFrames is 0xffffffff where it is
+ * not: no frame is past it), the skip test does not hold.  The surfaces are read only where the skip test or the LIVE_PIXELS tint needs them. */
+__global__ __launch_bounds__(256) void live_list_count_budget(const TbFloat4* __restrict__ output, const TbFloat4* __restrict__ jittered,
+    const uint32_t* __restrict__ budget, TbTileMap tiles, uint32_t W, uint32_t H, uint32_t frame, uint32_t minFrames, float minConvergence,
+    unsigned long long* __restrict__ masks, uint32_t* __restrict__ counts, TbFloat4* __restrict__ aovNormals, TbFloat4* __restrict__ aovCustom,
+    uint32_t livePixelsMode)
+{
+    __shared__ uint32_t waveLive[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, region = blockIdx.x;
+    uint32_t bx, by; block_region(tiles, W, H, region, bx, by);
+    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u), y = by * 16u + (wave >> 1) * 8u + (lane >> 3);
+    bool live = x < W && y < H;
+    if (live) {
+        const size_t pix = (size_t)y * W + x;
+        bool skip = !(frame < budget[pix]);
+        const bool test = !skip && frame > minFrames;
+        TbFloat4 o = {0, 0, 0, 0};
+        if (test || (skip && aovCustom && livePixelsMode)) o = output[pix];
+        if (test) skip = tb_adaptive_skip(o, jittered[pix], minConvergence);
+        if (skip) {
+            live = false;
+            if (aovNormals) aovNormals[pix] = TbFloat4{0, 0, 0, 1.0f};
+            if (aovCustom) aovCustom[pix] = livePixelsMode ? TbFloat4{o.x / o.w, o.y / o.w, o.z / o.w, o.w / o.w} : TbFloat4{0, 0, 0, 1.0f};
+        }
+    }
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) { masks[(size_t)region * 4u + wave] = m; waveLive[wave] = (uint32_t)__popcll(m); }
+    __syncthreads();
+    if (threadIdx.x == 0) counts[region] = waveLive[0] + waveLive[1] + waveLive[2] + waveLive[3];
+}
+
 /* one workgroup: thread t sums a contiguous run of the counts, the 1024 sums are scanned in LDS, the runs are rewritten as first entries */
 __global__ __launch_bounds__(1024) void live_list_scan(uint32_t* __restrict__ counts, uint32_t regions, uint32_t* __restrict__ total)
 {
@@ -296,15 +328,18 @@ hipError_t pt_launch_region_order(hipStream_t stream, const uint32_t* cost, cons
     return hipGetLastError();
 }
 
-/* TbDeviceTargets::liveList / liveCount for the launch whose first frame is `frame` (live_list_* above).  scratch: tb_live_list_scratch_bytes(regions). */
-hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const TbTileMap* tiles, uint32_t W, uint32_t H,
-                               uint32_t frame, uint32_t minFrames, float minConvergence, TbFloat4* aovNormals, TbFloat4* aovCustom, int livePixelsMode,
-                               void* scratch, uint32_t* list, uint32_t* count)
+/* TbDeviceTargets::liveList / liveCount for the launch whose first frame is `frame` (live_list_* above).  scratch: tb_live_list_scratch_bytes(regions).
+ * budget: null, or W x H frame indices (live_list_count_budget in live_list_count's place; minFrames 0xffffffff: no skip test) */
+hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const uint32_t* budget, const TbTileMap* tiles, uint32_t W,
+                               uint32_t H, uint32_t frame, uint32_t minFrames, float minConvergence, TbFloat4* aovNormals, TbFloat4* aovCustom,
+                               int livePixelsMode, void* scratch, uint32_t* list, uint32_t* count)
 {
     const uint32_t regions = tb_persistent_grid(W, H, *tiles);
     unsigned long long* masks = (unsigned long long*)scratch;
     uint32_t* counts = (uint32_t*)(masks + (size_t)regions * 4u);
-    if (regions) hipLaunchKernelGGL(live_list_count, dim3(regions), dim3(256), 0, stream, output, jittered, *tiles, W, H, frame, minFrames, minConvergence, masks,
+    if (regions && budget) hipLaunchKernelGGL(live_list_count_budget, dim3(regions), dim3(256), 0, stream, output, jittered, budget, *tiles, W, H, frame,
+        minFrames, minConvergence, masks, counts, aovNormals, aovCustom, livePixelsMode ? 1u : 0u);
+    else if (regions) hipLaunchKernelGGL(live_list_count, dim3(regions), dim3(256), 0, stream, output, jittered, *tiles, W, H, frame, minFrames, minConvergence, masks,
         counts, aovNormals, aovCustom, livePixelsMode ? 1u : 0u);
     hipLaunchKernelGGL(live_list_scan, dim3(1), dim3(1024), 0, stream, counts, regions, count);
     if (regions) hipLaunchKernelGGL(live_list_scatter, dim3(regions), dim3(256), 0, stream, *tiles, W, H, (const unsigned long long*)masks,

@@ -31,9 +31,11 @@ hipError_t pt_launch_region_order(hipStream_t stream, const uint32_t* cost, cons
                                   uint32_t numGroups, uint32_t lateFrom, uint32_t* order, uint32_t* keys);
 /* the adaptive launch's live list (pt_kernels.hip live_list_*): list = W x H words at most, *count; scratch = tb_live_list_scratch_bytes(regions) */
 static inline size_t tb_live_list_scratch_bytes(uint32_t regions) { return (size_t)regions * 36u; }
-hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const TbTileMap* tiles, uint32_t W, uint32_t H,
-                               uint32_t frame, uint32_t minFrames, float minConvergence, TbFloat4* aovNormals, TbFloat4* aovCustom, int livePixelsMode,
-                               void* scratch, uint32_t* list, uint32_t* count);
+/* budget: null, or the W x H frame indices of tb_set_sample_budget -- a pixel is live iff frame < budget[pixel] and, where frame > minFrames, the
+ * skip test does not hold (live_list_count_budget; minFrames = 0xffffffff: the budget alone) */
+hipError_t pt_launch_live_list(hipStream_t stream, const TbFloat4* output, const TbFloat4* jittered, const uint32_t* budget, const TbTileMap* tiles, uint32_t W,
+                               uint32_t H, uint32_t frame, uint32_t minFrames, float minConvergence, TbFloat4* aovNormals, TbFloat4* aovCustom,
+                               int livePixelsMode, void* scratch, uint32_t* list, uint32_t* count);
 hipError_t pt_launch_accumulate_samples(hipStream_t stream, const TbFloat4* samples, uint32_t W, uint32_t H, uint32_t firstFrame, uint32_t numFrames,
     const TbTileMap* tiles,
                                         TbFloat4* output, TbFloat4* jittered);
