@@ -2,7 +2,8 @@
 
 Three things:
   * the helper kernels around the layers: pack_input / extend16, rgba8_of (the 8-bit store) and unorm_color (its way back);
-  * the layer arithmetic and the network's graph in torch: conv_ref, net_ref (and net_chain, the same graph through the library's layer seam);
+  * the layer arithmetic (conv_ref / conv_scale, from tests/nn_layer_ref.py) and the network's graph in torch: net_ref (and net_chain, the same
+    graph through the library's layer seam);
   * a reader and a writer of the TZA weights container, written from its layout, independent of csrc/host/nn_weights.cpp.
 
 Tensors are numpy float16, NHWC without a batch axis, (H, W, C); weights are (o, i, 3, 3).
@@ -12,7 +13,8 @@ import struct
 
 import numpy as np
 import torch
-import torch.nn.functional as F
+
+from nn_layer_ref import conv_ref, conv_scale      # the layer, restated once for both networks
 
 LAYERS = ("enc_conv0", "enc_conv1", "enc_conv2", "enc_conv3", "enc_conv4", "enc_conv5a", "enc_conv5b", "dec_conv4a", "dec_conv4b", "dec_conv3a",
           "dec_conv3b", "dec_conv2a", "dec_conv2b", "dec_conv1a", "dec_conv1b", "dec_conv0")
@@ -116,43 +118,6 @@ def weights_of(tensors):
 
 
 # ---- the layer and the graph ---------------------------------------------------------------------
-
-def _nchw(x, dtype):
-    return torch.from_numpy(np.ascontiguousarray(x, np.float16).astype(np.float32)).to(dtype).permute(2, 0, 1)[None]
-
-
-def _gather(in_a, in_b, upsample_a, dtype):
-    a = _nchw(in_a, dtype)
-    if upsample_a:
-        a = F.interpolate(a, scale_factor=2, mode="nearest")
-    return a if in_b is None else torch.cat([a, _nchw(in_b, dtype)], 1)
-
-
-def conv_ref(in_a, weight, bias, in_b=None, upsample_a=False, pool=False, relu=True, accumulate=torch.float32):
-    """One layer: F.conv2d in `accumulate` precision on the binary16 inputs with padding 1, + bias, ReLU, a round to binary16, then the max-pool.
-    Returns (H, W, c_out) float16 -- halved with pool."""
-    x = _gather(in_a, in_b, upsample_a, accumulate)
-    w = torch.from_numpy(np.asarray(weight, np.float16).astype(np.float32)).to(accumulate)
-    b = torch.from_numpy(np.asarray(bias, np.float16).astype(np.float32)).to(accumulate)
-    y = F.conv2d(x, w, b, padding=1)
-    if relu:
-        y = F.relu(y)
-    y = y.to(torch.float16)
-    if pool:
-        y = F.max_pool2d(y.float(), 2).to(torch.float16)  # on the rounded values; the maximum of binary16 numbers is one of them
-    return y[0].permute(1, 2, 0).contiguous().numpy()
-
-
-def conv_scale(in_a, weight, bias, in_b=None, upsample_a=False, pool=False):
-    """S of the layer tolerance: conv(|x|, |w|) + |b| at the same element in float64, the maximum over the 2 x 2 window with pool."""
-    x = _gather(in_a, in_b, upsample_a, torch.float64).abs()
-    w = torch.from_numpy(np.asarray(weight, np.float16).astype(np.float64)).abs()
-    b = torch.from_numpy(np.asarray(bias, np.float16).astype(np.float64)).abs()
-    s = F.conv2d(x, w, b, padding=1)
-    if pool:
-        s = F.max_pool2d(s, 2)
-    return s[0].permute(1, 2, 0).contiguous().numpy()
-
 
 def pack_input(color, albedo=None, normal=None):
     """The network's input as the contract packs it: (H, W, 3 or 9) float16, channels colour.xyz, albedo.xyz, normal.xyz, rounded to nearest even."""

@@ -4,7 +4,8 @@ Three things:
   * compress: the reference's binary32 -> binary16 conversion (Float16Compressor::compress), restated from its definition in numpy integer
     arithmetic, independent of csrc/host/sr_weights.cpp; fold: a layer's batch-norm scale multiplied into its filter, then compress;
   * a writer and a reader of the weights container, written from its layout;
-  * the layer arithmetic and the network's graph in torch: conv_ref / conv_scale, net_ref, and net_chain, the same graph through the library's seams.
+  * the layer arithmetic (conv_ref / conv_scale, from tests/nn_layer_ref.py) and the network's graph in torch: net_ref, and net_chain, the same
+    graph through the library's seams.
 
 Tensors are numpy float16, NHWC without a batch axis, (H, W, C); weights are (o, i, K, K).
 """
@@ -13,7 +14,8 @@ import struct
 
 import numpy as np
 import torch
-import torch.nn.functional as F
+
+from nn_layer_ref import conv_ref, conv_scale      # the layer, restated once for both networks
 
 LAYERS = ("conv1", "conv2", "conv3", "conv_up1/conv", "conv4", "conv5", "conv6")
 KERNEL = (5, 3, 3, 5, 3, 3, 3)
@@ -127,39 +129,6 @@ def folded_raw(raw):
 
 
 # ---- the layer and the graph -----------------------------------------------------------------------
-
-def _nchw(x, dtype):
-    return torch.from_numpy(np.ascontiguousarray(x, np.float16).astype(np.float32)).to(dtype).permute(2, 0, 1)[None]
-
-
-def _gather(in_a, in_b, upsample_a, dtype):
-    a = _nchw(in_a, dtype)
-    if upsample_a:
-        a = F.interpolate(a, scale_factor=2, mode="nearest")
-    return a if in_b is None else torch.cat([a, _nchw(in_b, dtype)], 1)
-
-
-def _t(a, dtype):
-    return None if a is None else torch.from_numpy(np.asarray(a, np.float16).astype(np.float32)).to(dtype)
-
-
-def conv_ref(in_a, weight, bias=None, in_b=None, upsample_a=False, relu=True, accumulate=torch.float32):
-    """One layer: cross-correlation in `accumulate` precision on the binary16 inputs with zero padding (K - 1) / 2, + bias where there is one,
-    ReLU where asked, one rounding to binary16.  (H, W, c_out) float16."""
-    k = np.asarray(weight).shape[2]
-    y = F.conv2d(_gather(in_a, in_b, upsample_a, accumulate), _t(weight, accumulate), _t(bias, accumulate), padding=(k - 1) // 2)
-    if relu:
-        y = F.relu(y)
-    return y.to(torch.float16)[0].permute(1, 2, 0).contiguous().numpy()
-
-
-def conv_scale(in_a, weight, bias=None, in_b=None, upsample_a=False):
-    """S of the layer tolerance: conv(|x|, |w|) + |b| at the same element, in float64"""
-    k = np.asarray(weight).shape[2]
-    b = _t(bias, torch.float64)
-    s = F.conv2d(_gather(in_a, in_b, upsample_a, torch.float64).abs(), _t(weight, torch.float64).abs(), None if b is None else b.abs(), padding=(k - 1) // 2)
-    return s[0].permute(1, 2, 0).contiguous().numpy()
-
 
 def pack_input(color):
     """The network's input: .xyz of an (H, W, 4) float32 surface rounded to binary16 (nearest even)"""

@@ -1,4 +1,5 @@
-"""nn_conv3x3 (+ the max-pool) at the layer seam, tb_run_conv3x3, against the torch restatement of the layer contract (tests/neural_ref.py).
+"""nn_convk with K = 3 in its plain form (+ the max-pool) at the layer seam, tb_run_conv3x3, against the torch restatement of the layer contract
+(tests/nn_layer_ref.py, which also holds the check).
 
 The bound is derived, not measured: |y - ref| <= 2^-10 |ref| + 2^-12 S + 2^-24, S = conv(|x|, |w|) + |b| at the same element before pooling (the
 maximum over the 2 x 2 window with pool).  The first term is one binary16 rounding step, for a flip of the last bit; the second is above any fp32
@@ -9,6 +10,7 @@ import pytest
 import torch
 
 import neural_ref as nr
+from nn_layer_ref import check as check_layer
 
 gpu = pytest.mark.gpu
 
@@ -23,22 +25,8 @@ def he(rng, c_out, c_in):
     return (rng.standard_normal((c_out, c_in, 3, 3)) * np.sqrt(2.0 / (9 * c_in))).astype(np.float16), (rng.standard_normal(c_out) * 0.1).astype(np.float16)
 
 
-def check(tb, a, w, b, in_b=None, upsample_a=False, pool=False, relu=True):
-    y = tb.RunConv3x3(a, w, b, in_b=in_b, upsample_a=upsample_a, pool=pool, relu=relu)
-    ref = nr.conv_ref(a, w, b, in_b=in_b, upsample_a=upsample_a, pool=pool, relu=relu)
-    s = nr.conv_scale(a, w, b, in_b=in_b, upsample_a=upsample_a, pool=pool)
-    assert y.shape == ref.shape == s.shape and y.dtype == np.float16
-    y64, r64 = y.astype(np.float64), ref.astype(np.float64)
-    finite = np.isfinite(r64)
-    assert np.array_equal(np.isnan(y64), np.isnan(r64)) and np.array_equal(np.isinf(y64), np.isinf(r64))
-    assert np.array_equal(np.sign(y64[np.isinf(r64)]), np.sign(r64[np.isinf(r64)]))
-    with np.errstate(invalid="ignore"):
-        err = np.abs(y64 - r64)[finite]
-    bound = (2.0 ** -10 * np.abs(r64) + 2.0 ** -12 * s + 2.0 ** -24)[finite]
-    worst = float((err / bound).max()) if err.size else 0.0
-    print("  %s: max |y - ref| = %.3e, %.3f of the bound, %d of %d elements differ" % (y.shape, err.max() if err.size else 0.0, worst, int((err > 0).sum()), err.size))
-    assert worst <= 1.0
-    return y, ref
+def check(tb, a, w, b, **kw):
+    return check_layer(tb.RunConv3x3(a, w, b, **kw), a, w, b, **kw)
 
 
 @gpu

@@ -1,6 +1,6 @@
 """nn_convk in its plain form and nn_sr_finish at their seams, tb_run_conv and tb_run_sr_finish.
 
-Against torch (tests/sr_ref.py) the bound is section 15's, derived, not measured: |y - ref| <= 2^-10 |ref| + 2^-12 S + 2^-24 with
+Against torch (tests/nn_layer_ref.py, which also holds the check) the bound is section 15's, derived, not measured: |y - ref| <= 2^-10 |ref| + 2^-12 S + 2^-24 with
 S = conv(|x|, |w|) + |b| at the same element.  The first term is one binary16 rounding step; the second is above any fp32 summation-order
 difference while taps x channels <= 4096 (this network's largest layer has 25 x 64 = 1600; the largest here 25 x 96 = 2400).  Where the reference
 is infinite or NaN the result must be of the same kind.  The delta filters, the NaN neighbourhood and the residual add are bit-for-bit statements."""
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import sr_ref as sr
+from nn_layer_ref import check as check_layer
 
 pytestmark = pytest.mark.gpu
 
@@ -28,23 +29,8 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint16)
 
 
-def check(tb, a, w, b, in_b=None, upsample_a=False, relu=True):
-    y = tb.RunConv(a, w, b, in_b=in_b, upsample_a=upsample_a, relu=relu)
-    ref = sr.conv_ref(a, w, b, in_b=in_b, upsample_a=upsample_a, relu=relu)
-    s = sr.conv_scale(a, w, b, in_b=in_b, upsample_a=upsample_a)
-    assert y.shape == ref.shape == s.shape and y.dtype == np.float16
-    y64, r64 = y.astype(np.float64), ref.astype(np.float64)
-    finite = np.isfinite(r64)
-    assert np.array_equal(np.isnan(y64), np.isnan(r64)) and np.array_equal(np.isinf(y64), np.isinf(r64))
-    assert np.array_equal(np.sign(y64[np.isinf(r64)]), np.sign(r64[np.isinf(r64)]))
-    with np.errstate(invalid="ignore"):
-        err = np.abs(y64 - r64)[finite]
-    bound = (2.0 ** -10 * np.abs(r64) + 2.0 ** -12 * s + 2.0 ** -24)[finite]
-    worst = float((err / bound).max()) if err.size else 0.0
-    print("  %s K %d: max |y - ref| = %.3e, %.3f of the bound, %d of %d elements differ" % (y.shape, w.shape[2], err.max() if err.size else 0.0, worst,
-                                                                                           int((err > 0).sum()), err.size))
-    assert worst <= 1.0
-    return y, ref
+def check(tb, a, w, b, **kw):
+    return check_layer(tb.RunConv(a, w, b, **kw), a, w, b, **kw)
 
 
 @pytest.mark.parametrize("k", [3, 5])

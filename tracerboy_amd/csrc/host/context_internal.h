@@ -32,6 +32,7 @@
 #include <cstring>
 #include <limits>
 #include <cmath>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -201,24 +202,22 @@ struct tb_context {
     /* FSR 1 upscaling (context_upscale.cpp): per surface type the EASU output and the RCAS output, at the size of the last
      * tb_upscale that ran that chain; events around the passes: [2 t] before EASU, [2 t + 1] between the passes, [4 + t] after RCAS */
     struct Fsr { DevBuf mid[2], out[2]; tbctx::DevEvent ev[6]; float lastUpscaleMs = 0.0f, lastEasuMs = 0.0f, lastRcasMs = 0.0f; } fsr;
+    /* what both neural stages hold.  Activations, sized at the first use and kept while the size holds: the packed input and two tensors the
+     * layers alternate between.  result, rgba8: the stage's float picture and its 8-bit one.  ev, lastMs: around the last network */
+    struct NetStage { DevBuf input, pingPong[2], result, rgba8; tbctx::DevEvent ev[2]; float lastMs = 0.0f; };
     /* the neural still denoiser (context_neural.cpp).  inputs: 0 = no weights loaded, else enc_conv0's input channels (3 or 9);
      * in / out: the layers' channel counts; splitA: how many of a layer's input channels come from its first source (all of them, except where a
-     * decoder reads an upsampled tensor in front of a skip tensor); weight / bias: the layers repacked for nn_conv3x3.  Activations, sized at
-     * the first use and kept while the size holds: the packed input, two tensors the layers alternate between, the three pooled skip tensors.
-     * aux, result, rgba8: tb_denoise_neural's resolved albedo and normals, its float picture and its 8-bit one.  lastMs: option last_neural_us */
-    struct Neural {
+     * decoder reads an upsampled tensor in front of a skip tensor); weight / bias: the layers repacked for nn_convk.  skip: the three pooled skip
+     * tensors; aux: tb_denoise_neural's resolved albedo and normals.  lastMs: option last_neural_us */
+    struct Neural : NetStage {
         uint32_t inputs = 0, in[16] = {}, out[16] = {}, splitA[16] = {};
-        DevBuf weight[16], bias[16], input, pingPong[2], skip[3], aux[2], result, rgba8;
-        tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+        DevBuf weight[16], bias[16], skip[3], aux[2];
     } nn;
     /* the neural 2 x super-resolution (context_sr.cpp).  loaded: tb_sr_load has succeeded; in / out / kernel: the seven layers'
-     * channel counts and filter sizes; weight / bias: the layers repacked for nn_convk (the last has no bias).  Activations, sized at the first use
-     * and kept while the size holds: the packed input and two tensors the layers alternate between.  result, rgba8: tb_upscale_neural's float
-     * picture and its 8-bit one.  lastMs: option last_sr_us */
-    struct Sr {
+     * channel counts and filter sizes; weight / bias: the layers repacked for nn_convk (the last has no bias).  lastMs: option last_sr_us */
+    struct Sr : NetStage {
         bool loaded = false; uint32_t in[7] = {}, out[7] = {}, kernel[7] = {};
-        DevBuf weight[7], bias[7], input, pingPong[2], result, rgba8;
-        tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+        DevBuf weight[7], bias[7];
     } sr;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
@@ -349,5 +348,13 @@ bool guidesCurrent(const tb_context* c);
 size_t tensorBytes(uint32_t w, uint32_t h, uint32_t channels);
 void uploadLayer(const tbnn::PackedLayer& p, DevBuf& weight, DevBuf& bias);
 std::vector<uint16_t> padChannels(const uint16_t* in, size_t pixels, uint32_t c);
+/* The body of both layer seams, tb_run_conv3x3 and tb_run_conv, inside their guarded(): `name` heads the refusals; pool: -1, the seam has no
+ * pool flag; else whether the max-pool follows (out is then halved).  d and every pointer but bias are checked here. */
+int runConvSeam(tb_context* c, const char* name, const tb_conv_desc* d, int pool, const uint16_t* inA, const uint16_t* inB, const uint16_t* weight,
+    const uint16_t* bias, uint16_t* out);
+/* A stage's network and what follows it: `network` enqueues its kernels, which write the outW x outH RGBA32F device surface `result`, between the
+ * stage's two events; then the 8-bit store where rgba8 is asked for, a synchronise, lastMs, and the copies to the host pointers that are not null */
+void runStage(tb_context* c, tb_context::NetStage& n, const std::function<void()>& network, uint32_t outW, uint32_t outH, const void* result,
+    float* rgbaF32, uint8_t* rgba8);
 
 } // namespace tbctx

@@ -1,6 +1,6 @@
 /* context_neural.cpp -- the neural still denoiser (include/tracerboy_hip.h tb_neural_load / tb_run_conv3x3 / tb_run_neural /
  * tb_denoise_neural): the reference's TAAUpscaler::OIDN path (TracerBoy.cpp:3306-3322, OpenImageDenoise.cpp:855-1039) -- the OIDN U-Net of 16
- * 3 x 3 convolutions on the post-processed picture, the mean albedo and the mean normals -- on the fp16 matrix cores (nn_kernels.hip).  The weights
+ * 3 x 3 convolutions on the post-processed picture, the mean albedo and the mean normals -- on the fp16 matrix cores (nn_convk_kernels.hip).  The weights
  * come from a TZA file the caller names (nn_weights.cpp); the library ships none.  Reads what the output stage and the guide pass wrote, writes
  * surfaces of its own: accumulation, AOVs, frame counter, history, guides and denoised surfaces stay as they are. */
 #include "context_internal.h"
@@ -14,7 +14,7 @@ namespace tbctx {
 
 size_t tensorBytes(uint32_t w, uint32_t h, uint32_t channels) { return (size_t)w * h * nn_padded_channels(channels) * sizeof(uint16_t); }
 
-/* a layer's weights on the device, as nn_conv3x3 reads them */
+/* a layer's weights on the device, as nn_convk reads them */
 void uploadLayer(const tbnn::PackedLayer& p, DevBuf& weight, DevBuf& bias)
 {
     ensure(weight, p.weight.size() * sizeof(uint16_t)); ensure(bias, p.bias.size() * sizeof(float));
@@ -31,13 +31,62 @@ std::vector<uint16_t> padChannels(const uint16_t* in, size_t pixels, uint32_t c)
     return v;
 }
 
+int runConvSeam(tb_context* c, const char* name, const tb_conv_desc* d, int pool, const uint16_t* inA, const uint16_t* inB, const uint16_t* weight,
+    const uint16_t* bias, uint16_t* out)
+{
+    const uint32_t kMaxSeamChannels = 512;
+    const auto refuse = [&](const std::string& why) { return fail(c, TB_E_INVALID, std::string(name) + ": " + why); };
+    if (!d || !inA || !weight || !out) return refuse("null pointer");
+    if (const char* why = surfaceRefusal(d->width, d->height)) return refuse(why);
+    if (d->kernel != 3u && d->kernel != 5u) return refuse("kernel " + std::to_string(d->kernel) + " (3 or 5)");
+    if (d->form > 1u) return refuse("form " + std::to_string(d->form) + " (0 plain, 1 staged)");
+    if (!d->c_a || !d->c_out) return refuse("a channel count is 0");
+    if (d->c_a > kMaxSeamChannels || d->c_b > kMaxSeamChannels || d->c_out > kMaxSeamChannels)
+        return refuse("more than " + std::to_string(kMaxSeamChannels) + " channels in a tensor");
+    if ((d->c_b != 0u) != (inB != nullptr)) return refuse("source B is given exactly when c_b is not 0");
+    if ((pool > 0 || d->upsample_a) && ((d->width | d->height) & 1u))
+        return refuse(pool < 0 ? "upsample_a needs an even width and height" : "pool and upsample_a need an even width and height");
+    if (d->form == 1u && !nn_convk_staged_fits(d->c_a, d->c_b)) return refuse("the staged form holds at most 64 input channels, each source padded to a multiple of 32");
+    const uint32_t W = d->width, H = d->height, wA = d->upsample_a ? W / 2u : W, hA = d->upsample_a ? H / 2u : H;
+    const uint32_t wOut = pool > 0 ? W / 2u : W, hOut = pool > 0 ? H / 2u : H, padOut = nn_padded_channels(d->c_out);
+    const std::vector<uint16_t> hostA = padChannels(inA, (size_t)wA * hA, d->c_a);
+    const DevBuf dA = staged(hostA.data(), hostA.size() * sizeof(uint16_t));
+    DevBuf dB;
+    if (inB) { const std::vector<uint16_t> hostB = padChannels(inB, (size_t)W * H, d->c_b); dB = staged(hostB.data(), hostB.size() * sizeof(uint16_t)); }
+    DevBuf dWeight, dBias;
+    uploadLayer(tbnn::packLayer(d->c_a, d->c_b, d->c_out, weight, bias, d->kernel * d->kernel), dWeight, dBias);
+    const DevBuf dConv = scratch(tensorBytes(W, H, d->c_out));
+    HIP_TRY(nn_launch_convk(c->stream, W, H, d->kernel, d->form, (const uint16_t*)dA.p, d->c_a, d->upsample_a, (const uint16_t*)dB.p, d->c_b,
+        (const uint16_t*)dWeight.p, bias ? (const float*)dBias.p : nullptr, d->c_out, d->relu, (uint16_t*)dConv.p));
+    DevBuf dPool;
+    if (pool > 0) { dPool = scratch(tensorBytes(wOut, hOut, d->c_out)); HIP_TRY(nn_launch_maxpool2x2(c->stream, W, H, padOut, (const uint16_t*)dConv.p, (uint16_t*)dPool.p)); }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const DevBuf& result = pool > 0 ? dPool : dConv;
+    std::vector<uint16_t> host(result.bytes / sizeof(uint16_t));
+    copyBack(host.data(), result);
+    for (size_t i = 0; i < (size_t)wOut * hOut; i++) memcpy(out + i * d->c_out, &host[i * padOut], d->c_out * sizeof(uint16_t));
+    return TB_OK;
+}
+
+void runStage(tb_context* c, tb_context::NetStage& n, const std::function<void()>& network, uint32_t outW, uint32_t outH, const void* result,
+    float* rgbaF32, uint8_t* rgba8)
+{
+    const size_t px = (size_t)outW * outH;
+    HIP_TRY(hipEventRecord(n.ev[0].create(), c->stream));
+    network();
+    HIP_TRY(hipEventRecord(n.ev[1].create(), c->stream));
+    if (rgba8) { ensure(n.rgba8, px * 4); HIP_TRY(nn_launch_to_rgba8(c->stream, outW, outH, (const TbFloat4*)result, (uint32_t*)n.rgba8.p)); }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hipEventElapsedTime(&n.lastMs, n.ev[0], n.ev[1]) != hipSuccess) n.lastMs = 0.0f;
+    if (rgbaF32) HIP_TRY(hipMemcpy(rgbaF32, result, px * sizeof(TbFloat4), hipMemcpyDeviceToHost));
+    if (rgba8) HIP_TRY(hipMemcpy(rgba8, n.rgba8.p, px * 4, hipMemcpyDeviceToHost));
+}
+
 } // namespace tbctx
 
 namespace {
 
 enum { E0, E1, E2, E3, E4, E5A, E5B, D4A, D4B, D3A, D3B, D2A, D2B, D1A, D1B, D0 }; /* tbnn::kLayerNames */
-
-const uint32_t kMaxSeamChannels = 512;
 
 /* The 16 layers on the context's activation buffers, enqueued on its stream: color / albedo / normal are width x height RGBA32F device surfaces
  * (albedo and normal null with 3-input weights), out likewise.  The picture is zero-extended to multiples of 16 and the result cropped.
@@ -58,7 +107,7 @@ void runNetwork(tb_context* c, uint32_t width, uint32_t height, const void* colo
     hipStream_t s = c->stream;
     auto conv = [&](uint32_t l, uint32_t lvl, const uint16_t* inA, bool up, const uint16_t* inB, uint16_t* dst) {
         const uint32_t cB = inB ? n.in[l] - n.splitA[l] : 0u;
-        HIP_TRY(nn_launch_conv3x3(s, W0 >> lvl, H0 >> lvl, inA, n.splitA[l], up, inB, cB, (const uint16_t*)n.weight[l].p, (const float*)n.bias[l].p, co[l], 1u, dst));
+        HIP_TRY(nn_launch_convk(s, W0 >> lvl, H0 >> lvl, 3u, 0u, inA, n.splitA[l], up, inB, cB, (const uint16_t*)n.weight[l].p, (const float*)n.bias[l].p, co[l], 1u, dst));
     };
     auto pool = [&](uint32_t l, uint32_t lvl, const uint16_t* in, uint16_t* dst) {
         HIP_TRY(nn_launch_maxpool2x2(s, W0 >> lvl, H0 >> lvl, nn_padded_channels(co[l]), in, dst));
@@ -85,15 +134,6 @@ const char* pictureRefusal(uint32_t W, uint32_t H)
     if ((uint64_t)tbnn::roundUp(W, 16u) * tbnn::roundUp(H, 16u) > (1ull << 24)) return "more than 2^24 pixels once extended to multiples of 16";
     return nullptr;
 }
-
-void timedNetwork(tb_context* c, uint32_t W, uint32_t H, const void* color, const void* albedo, const void* normal, bool unormColor, void* out)
-{
-    HIP_TRY(hipEventRecord(c->nn.ev[0].create(), c->stream));
-    runNetwork(c, W, H, color, albedo, normal, unormColor, out);
-    HIP_TRY(hipEventRecord(c->nn.ev[1].create(), c->stream));
-}
-
-void readTime(tb_context* c) { if (hipEventElapsedTime(&c->nn.lastMs, c->nn.ev[0], c->nn.ev[1]) != hipSuccess) c->nn.lastMs = 0.0f; }
 
 } // namespace
 
@@ -124,33 +164,9 @@ int tb_neural_load(tb_context* c, const char* path)
 int tb_run_conv3x3(tb_context* c, const tb_conv3x3_desc* d, const uint16_t* inA, const uint16_t* inB, const uint16_t* weight, const uint16_t* bias, uint16_t* out)
 {
     return guarded(c, [&]() {
-        if (!d || !inA || !weight || !bias || !out) return fail(c, TB_E_INVALID, "tb_run_conv3x3: null pointer");
-        if (const char* why = surfaceRefusal(d->width, d->height)) return fail(c, TB_E_INVALID, std::string("tb_run_conv3x3: ") + why);
-        if (!d->c_a || !d->c_out) return fail(c, TB_E_INVALID, "tb_run_conv3x3: a channel count is 0");
-        if (d->c_a > kMaxSeamChannels || d->c_b > kMaxSeamChannels || d->c_out > kMaxSeamChannels) return fail(c, TB_E_INVALID,
-            "tb_run_conv3x3: more than " + std::to_string(kMaxSeamChannels) + " channels in a tensor");
-        if ((d->c_b != 0u) != (inB != nullptr)) return fail(c, TB_E_INVALID, "tb_run_conv3x3: source B is given exactly when c_b is not 0");
-        if ((d->pool || d->upsample_a) && ((d->width | d->height) & 1u)) return fail(c, TB_E_INVALID,
-            "tb_run_conv3x3: pool and upsample_a need an even width and height");
-        const uint32_t W = d->width, H = d->height, wA = d->upsample_a ? W / 2u : W, hA = d->upsample_a ? H / 2u : H;
-        const uint32_t wOut = d->pool ? W / 2u : W, hOut = d->pool ? H / 2u : H, padOut = nn_padded_channels(d->c_out);
-        const std::vector<uint16_t> hostA = padChannels(inA, (size_t)wA * hA, d->c_a);
-        const DevBuf dA = staged(hostA.data(), hostA.size() * sizeof(uint16_t));
-        DevBuf dB;
-        if (inB) { const std::vector<uint16_t> hostB = padChannels(inB, (size_t)W * H, d->c_b); dB = staged(hostB.data(), hostB.size() * sizeof(uint16_t)); }
-        DevBuf dWeight, dBias;
-        uploadLayer(tbnn::packLayer(d->c_a, d->c_b, d->c_out, weight, bias), dWeight, dBias);
-        const DevBuf dConv = scratch(tensorBytes(W, H, d->c_out));
-        HIP_TRY(nn_launch_conv3x3(c->stream, W, H, (const uint16_t*)dA.p, d->c_a, d->upsample_a, (const uint16_t*)dB.p, d->c_b, (const uint16_t*)dWeight.p,
-            (const float*)dBias.p, d->c_out, d->relu, (uint16_t*)dConv.p));
-        DevBuf dPool;
-        if (d->pool) { dPool = scratch(tensorBytes(wOut, hOut, d->c_out)); HIP_TRY(nn_launch_maxpool2x2(c->stream, W, H, padOut, (const uint16_t*)dConv.p, (uint16_t*)dPool.p)); }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const DevBuf& result = d->pool ? dPool : dConv;
-        std::vector<uint16_t> host(result.bytes / sizeof(uint16_t));
-        copyBack(host.data(), result);
-        for (size_t i = 0; i < (size_t)wOut * hOut; i++) memcpy(out + i * d->c_out, &host[i * padOut], d->c_out * sizeof(uint16_t));
-        return TB_OK;
+        if (!d || !bias) return fail(c, TB_E_INVALID, "tb_run_conv3x3: null pointer");
+        const tb_conv_desc k = {d->width, d->height, d->c_a, d->c_b, d->c_out, 3u, d->upsample_a, d->relu, 0u};
+        return runConvSeam(c, "tb_run_conv3x3", &k, d->pool ? 1 : 0, inA, inB, weight, bias, out);
     });
 }
 
@@ -168,10 +184,7 @@ int tb_run_neural(tb_context* c, uint32_t W, uint32_t H, const float* color, con
         const DevBuf dColor = staged(color, bytes), dOut = scratch(bytes);
         DevBuf dAlbedo, dNormal;
         if (aux) { dAlbedo = staged(albedo, bytes); dNormal = staged(normal, bytes); }
-        timedNetwork(c, W, H, dColor.p, dAlbedo.p, dNormal.p, false, dOut.p);
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        readTime(c);
-        copyBack(out, dOut);
+        runStage(c, c->nn, [&]() { runNetwork(c, W, H, dColor.p, dAlbedo.p, dNormal.p, false, dOut.p); }, W, H, dOut.p, out, nullptr);
         return TB_OK;
     });
 }
@@ -262,12 +275,8 @@ int tb_denoise_neural(tb_context* c, const tb_post_settings* post, float* rgbaF3
             HIP_TRY(nn_launch_resolve_aux(c->stream, W, H, (const TbFloat4*)c->guides.sum[0].p, (const TbFloat4*)c->guides.sum[1].p, (TbFloat4*)n.aux[0].p,
                 (TbFloat4*)n.aux[1].p)); }
         /* the reference's network reads its R8G8B8A8_UNORM post-process surface: the colour is packed through that store */
-        timedNetwork(c, W, H, c->postOut.p, aux ? n.aux[0].p : nullptr, aux ? n.aux[1].p : nullptr, true, n.result.p);
-        if (rgba8) { ensure(n.rgba8, px * 4); HIP_TRY(nn_launch_to_rgba8(c->stream, W, H, (const TbFloat4*)n.result.p, (uint32_t*)n.rgba8.p)); }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        readTime(c);
-        if (rgbaF32) HIP_TRY(hipMemcpy(rgbaF32, n.result.p, px * sizeof(TbFloat4), hipMemcpyDeviceToHost));
-        if (rgba8) HIP_TRY(hipMemcpy(rgba8, n.rgba8.p, px * 4, hipMemcpyDeviceToHost));
+        runStage(c, n, [&]() { runNetwork(c, W, H, c->postOut.p, aux ? n.aux[0].p : nullptr, aux ? n.aux[1].p : nullptr, true, n.result.p); }, W, H,
+            n.result.p, rgbaF32, rgba8);
         return TB_OK;
     });
 }

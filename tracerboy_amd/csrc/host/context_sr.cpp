@@ -13,8 +13,6 @@ using namespace tbctx;
 
 namespace {
 
-const uint32_t kMaxSeamChannels = 512;
-
 /* The seven layers and the residual add on the context's activation buffers, enqueued on its stream: color is a width x height RGBA32F device
  * surface, out 2 width x 2 height.  unormColor: the colour is packed through the R8G8B8A8_UNORM store (nn_launch_pack_input).  The two
  * upsamples cost no pass: conv_up1 gathers its source at (y >> 1, x >> 1), and so does the residual add.  Option sr_conv_form picks the form of
@@ -48,15 +46,6 @@ const char* pictureRefusal(uint32_t W, uint32_t H)
     return nullptr;
 }
 
-void timedNetwork(tb_context* c, uint32_t W, uint32_t H, const void* color, bool unormColor, void* out)
-{
-    HIP_TRY(hipEventRecord(c->sr.ev[0].create(), c->stream));
-    runNetwork(c, W, H, color, unormColor, out);
-    HIP_TRY(hipEventRecord(c->sr.ev[1].create(), c->stream));
-}
-
-void readTime(tb_context* c) { if (hipEventElapsedTime(&c->sr.lastMs, c->sr.ev[0], c->sr.ev[1]) != hipSuccess) c->sr.lastMs = 0.0f; }
-
 } // namespace
 
 extern "C" {
@@ -83,34 +72,7 @@ int tb_sr_load(tb_context* c, const char* path)
 
 int tb_run_conv(tb_context* c, const tb_conv_desc* d, const uint16_t* inA, const uint16_t* inB, const uint16_t* weight, const uint16_t* bias, uint16_t* out)
 {
-    return guarded(c, [&]() {
-        if (!d || !inA || !weight || !out) return fail(c, TB_E_INVALID, "tb_run_conv: null pointer");
-        if (const char* why = surfaceRefusal(d->width, d->height)) return fail(c, TB_E_INVALID, std::string("tb_run_conv: ") + why);
-        if (d->kernel != 3u && d->kernel != 5u) return fail(c, TB_E_INVALID, "tb_run_conv: kernel " + std::to_string(d->kernel) + " (3 or 5)");
-        if (d->form > 1u) return fail(c, TB_E_INVALID, "tb_run_conv: form " + std::to_string(d->form) + " (0 plain, 1 staged)");
-        if (!d->c_a || !d->c_out) return fail(c, TB_E_INVALID, "tb_run_conv: a channel count is 0");
-        if (d->c_a > kMaxSeamChannels || d->c_b > kMaxSeamChannels || d->c_out > kMaxSeamChannels) return fail(c, TB_E_INVALID,
-            "tb_run_conv: more than " + std::to_string(kMaxSeamChannels) + " channels in a tensor");
-        if ((d->c_b != 0u) != (inB != nullptr)) return fail(c, TB_E_INVALID, "tb_run_conv: source B is given exactly when c_b is not 0");
-        if (d->upsample_a && ((d->width | d->height) & 1u)) return fail(c, TB_E_INVALID, "tb_run_conv: upsample_a needs an even width and height");
-        if (d->form == 1u && !nn_convk_staged_fits(d->c_a, d->c_b)) return fail(c, TB_E_INVALID,
-            "tb_run_conv: the staged form holds at most 64 input channels, each source padded to a multiple of 32");
-        const uint32_t W = d->width, H = d->height, wA = d->upsample_a ? W / 2u : W, hA = d->upsample_a ? H / 2u : H, padOut = nn_padded_channels(d->c_out);
-        const std::vector<uint16_t> hostA = padChannels(inA, (size_t)wA * hA, d->c_a);
-        const DevBuf dA = staged(hostA.data(), hostA.size() * sizeof(uint16_t));
-        DevBuf dB;
-        if (inB) { const std::vector<uint16_t> hostB = padChannels(inB, (size_t)W * H, d->c_b); dB = staged(hostB.data(), hostB.size() * sizeof(uint16_t)); }
-        DevBuf dWeight, dBias;
-        uploadLayer(tbnn::packLayer(d->c_a, d->c_b, d->c_out, weight, bias, d->kernel * d->kernel), dWeight, dBias);
-        const DevBuf dOut = scratch(tensorBytes(W, H, d->c_out));
-        HIP_TRY(nn_launch_convk(c->stream, W, H, d->kernel, d->form, (const uint16_t*)dA.p, d->c_a, d->upsample_a, (const uint16_t*)dB.p, d->c_b,
-            (const uint16_t*)dWeight.p, bias ? (const float*)dBias.p : nullptr, d->c_out, d->relu, (uint16_t*)dOut.p));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<uint16_t> host(dOut.bytes / sizeof(uint16_t));
-        copyBack(host.data(), dOut);
-        for (size_t i = 0; i < (size_t)W * H; i++) memcpy(out + i * d->c_out, &host[i * padOut], d->c_out * sizeof(uint16_t));
-        return TB_OK;
-    });
+    return guarded(c, [&]() { return runConvSeam(c, "tb_run_conv", d, -1, inA, inB, weight, bias, out); });
 }
 
 int tb_run_sr_finish(tb_context* c, uint32_t inW, uint32_t inH, const uint16_t* residual, const uint16_t* input, float* out)
@@ -138,10 +100,7 @@ int tb_run_sr(tb_context* c, uint32_t W, uint32_t H, const float* color, float* 
         if (const char* why = pictureRefusal(W, H)) return fail(c, TB_E_INVALID, std::string("tb_run_sr: ") + why);
         const size_t bytes = (size_t)W * H * sizeof(TbFloat4);
         const DevBuf dColor = staged(color, bytes), dOut = scratch(bytes * 4u);
-        timedNetwork(c, W, H, dColor.p, false, dOut.p);
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        readTime(c);
-        copyBack(out, dOut);
+        runStage(c, c->sr, [&]() { runNetwork(c, W, H, dColor.p, false, dOut.p); }, W * 2u, H * 2u, dOut.p, out, nullptr);
         return TB_OK;
     });
 }
@@ -161,12 +120,7 @@ int tb_upscale_neural(tb_context* c, const tb_post_settings* post, float* rgbaF3
         const size_t px = (size_t)W * H * 4u;
         ensure(n.result, px * sizeof(TbFloat4));
         /* the reference's network reads its R8G8B8A8_UNORM post-process surface: the colour is packed through that store */
-        timedNetwork(c, W, H, c->postOut.p, true, n.result.p);
-        if (rgba8) { ensure(n.rgba8, px * 4); HIP_TRY(nn_launch_to_rgba8(c->stream, W * 2u, H * 2u, (const TbFloat4*)n.result.p, (uint32_t*)n.rgba8.p)); }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        readTime(c);
-        if (rgbaF32) HIP_TRY(hipMemcpy(rgbaF32, n.result.p, px * sizeof(TbFloat4), hipMemcpyDeviceToHost));
-        if (rgba8) HIP_TRY(hipMemcpy(rgba8, n.rgba8.p, px * 4, hipMemcpyDeviceToHost));
+        runStage(c, n, [&]() { runNetwork(c, W, H, c->postOut.p, true, n.result.p); }, W * 2u, H * 2u, n.result.p, rgbaF32, rgba8);
         return TB_OK;
     });
 }

@@ -1,5 +1,5 @@
 /* nn_weights.h -- the weights of the still denoiser's U-Net as nn_weights.cpp reads them from a TZA container, and the
- * repack of one layer for nn_conv3x3 (nn_kernels.hip).  No HIP header: the reader is tested without a device. */
+ * repack of one layer for nn_convk (nn_convk_kernels.hip).  No HIP header: the reader is tested without a device. */
 #pragma once
 #include <stdint.h>
 #include <string>
@@ -27,8 +27,8 @@ float floatFromHalf(uint16_t h);
 
 inline uint32_t roundUp(uint32_t v, uint32_t to) { return (v + to - 1u) / to * to; }
 
-/* One layer as nn_conv3x3 and nn_convk (nn_convk_kernels.hip) read it.  The kernel's K axis is source A's channels padded to a multiple of 32, then
- * source B's padded likewise; its output channels are padded to a multiple of 32.  taps: 9 for a 3 x 3 filter, 25 for a 5 x 5 one (nn_convk alone).
+/* One layer as nn_convk (nn_convk_kernels.hip) reads it.  The kernel's K axis is source A's channels padded to a multiple of 32, then
+ * source B's padded likewise; its output channels are padded to a multiple of 32.  taps: 9 for a 3 x 3 filter, 25 for a 5 x 5 one.
  * weight: [tap = ky * 3 + kx (ky * 5 + kx)][K / 32][padded out / 16][lane 0..63][8] binary16, where lane l's
  * eight values are output channel 16 * block + (l & 15) at k = 32 * kblock + 8 * (l >> 4) + j -- the A fragment of
  * v_mfma_f32_16x16x32_f16 as one 16-byte load; zero wherever a padded channel is involved.  bias: fp32, zero past the count (all zero for a null

@@ -1,15 +1,24 @@
-/* nn_convk_kernels.hip -- the layers of the neural 2 x super-resolution network (launchers in nn_launch.h):
- *   nn_convk_kernel      K x K convolution, K = 3 or 5, + optional bias (+ ReLU) as an implicit GEMM on v_mfma_f32_16x16x32_f16: nn_conv3x3
- *                        (nn_kernels.hip) with the tap count as a template parameter -- the same fragment maps, the same tensors, up to two sources,
- *                        the first optionally nearest-upsampled x 2 as it is gathered
+/* nn_convk_kernels.hip -- the convolution of both networks, the still denoiser's U-Net (K = 3, the plain form) and the 2 x
+ * super-resolution (section 16: K = 3 and 5, either form), and the latter's residual add; launchers in nn_launch.h:
+ *   nn_convk_kernel      K x K convolution, K = 3 or 5, + optional bias (+ ReLU) as an implicit GEMM on v_mfma_f32_16x16x32_f16; reads up to two
+ *                        source tensors in channel order, the first optionally nearest-upsampled x 2 as it is gathered (upsample and concat cost
+ *                        no pass)
  *   nn_convk_staged_kernel  the same convolution, bit for bit, with the input tile of a workgroup staged in LDS once and four output rows
  *                        register-blocked against every weight fragment
  *   nn_sr_finish_kernel  the residual add: |half(conv6 + the input nearest-upsampled x 2)| -> RGBA32F
  *
- * The layer arithmetic is nn_kernels.hip's: binary16 activations and weights, fp32 accumulation (in the matrix core's order), + bias where there is
- * one, max(., 0) where the layer has ReLU, then one rounding to binary16 (nearest even; overflow gives infinity, NaN stays NaN).  Padding is zero,
- * (K - 1) / 2 on every side.  Accumulation order: tap-major (ky, then kx), then the k-blocks of 32 channels, one accumulator per block of 16 output
- * channels.  Both forms keep that order and feed the matrix core the same fragments, so their results are the same bits.
+ * The layer arithmetic: binary16 activations and weights, fp32 accumulation (in the matrix core's order), + bias where there is one, max(., 0)
+ * where the layer has ReLU, then one rounding to binary16 (nearest even; overflow gives infinity, NaN stays NaN).  Padding is zero, (K - 1) / 2 on
+ * every side.  Accumulation order: tap-major (ky, then kx), then the k-blocks of 32 channels, one accumulator per block of 16 output channels.
+ * Both forms keep that order and feed the matrix core the same fragments, so their results are the same bits.
+ *
+ * The GEMM of one wave: D[output channel][pixel] += W[output channel][k] * X[k][pixel] over k = 32 channels of one tap, for 16 consecutive x of one
+ * output row and NB x 16 output channels.  Lane l holds, as the instruction wants them (cdna_hip_programming section 3: the f16 form uses the bf16 map),
+ *   A (weights)      output channel l & 15, k = 8 (l >> 4) + j, j = 0..7: one 16-byte load of the host's repack (nn_weights.h packLayer)
+ *   B (activations)  k = 8 (l >> 4) + j at pixel l & 15: eight consecutive channels of one pixel, one 16-byte load of an NHWC tensor whose
+ *                    channel count is a multiple of 32 (nn_gather)
+ *   D                pixel l & 15, output channels 4 (l >> 4) + r, r = 0..3: one 8-byte store (nn_store).
+ * A k-block lies in source A or in source B, never across (both are padded to 32 channels, and the repack puts zero weights on the padding).
  * Every activation load is predicated on its tap lying inside the picture; a lane whose pixel is past the row end loads whatever taps are inside and
  * stores nothing; no lane reads or writes outside a tensor's padded extent. */
 #include "nn_launch.h"
@@ -29,47 +38,58 @@ struct NnConvK {
     uint32_t tilesX, units /* tilesX * height * (outPadded / (16 NB)) */;
 };
 
+/* eight channels of k-block kb (those of `quarter`) at pixel (sx, sy) of the layer's input: source A's k-blocks, read at (sy >> 1, sx >> 1)
+ * with upsampleA, then source B's; zeros outside the picture -- the padding, and all a lane past the row end may ask for out of bounds */
+__device__ __forceinline__ nn_half8 nn_gather(const NnConvK& p, int32_t sx, int32_t sy, uint32_t kb, uint32_t quarter)
+{
+    nn_half8 act = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (sx >= 0 && sy >= 0 && sx < (int32_t)p.width && sy < (int32_t)p.height) {
+        const uint32_t kBlocksA = p.padA / 32u, widthA = p.upsampleA ? p.width / 2u : p.width;
+        const size_t pixelA = p.upsampleA ? (size_t)((uint32_t)sy >> 1) * widthA + ((uint32_t)sx >> 1) : (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
+        const size_t pixelB = (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
+        const uint16_t* src = kb < kBlocksA ? p.inA + pixelA * p.padA + kb * 32u : p.inB + pixelB * p.padB + (kb - kBlocksA) * 32u;
+        act = *(const nn_half8*)(src + quarter * 8u);
+    }
+    return act;
+}
+
+/* a lane's four sums of output block `block` (16 channels; the lane's are c0 ...) to pixel (x, y): + bias where there is one, ReLU where the layer
+ * has it, one rounding */
+__device__ __forceinline__ void nn_store(const NnConvK& p, uint32_t x, uint32_t y, uint32_t block, uint32_t quarter, nn_float4 acc)
+{
+    const uint32_t c0 = block * 16u + quarter * 4u;
+    nn_float4 bias = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (p.bias) bias = *(const nn_float4*)(p.bias + c0);
+    nn_half4 h;
+    for (int r = 0; r < 4; r++) {
+        float v = acc[r];
+        if (p.bias) v = v + bias[r];
+        if (p.relu) v = v < 0.0f ? 0.0f : v;      /* a NaN stays */
+        h[r] = c0 + (uint32_t)r < p.cOut ? (_Float16)v : (_Float16)0.0f; /* the padded channels hold zeros whatever the sums were */
+    }
+    *(nn_half4*)(p.out + ((size_t)y * p.width + x) * p.outPadded + c0) = h;
+}
+
 template <int NB, int K> __global__ __launch_bounds__(NNK_THREADS) void nn_convk_kernel(const NnConvK p)
 {
     const uint32_t lane = threadIdx.x & 63u, unit = blockIdx.x * NNK_WAVES + (threadIdx.x >> 6); /* a wave's unit: one tile of one row, one group of output channels */
     if (unit >= p.units) return; /* the whole wave */
     const uint32_t tile = unit % p.tilesX, rest = unit / p.tilesX, y = rest % p.height, group = rest / p.height;
     const uint32_t px = lane & 15u, quarter = lane >> 4, x = tile * 16u + px;
-    const uint32_t kBlocksA = p.padA / 32u, kBlocks = kBlocksA + p.padB / 32u, outBlocks = p.outPadded / 16u;
-    const uint32_t widthA = p.upsampleA ? p.width / 2u : p.width;
+    const uint32_t kBlocks = (p.padA + p.padB) / 32u, outBlocks = p.outPadded / 16u;
     nn_float4 acc[NB];
     for (int b = 0; b < NB; b++) acc[b] = nn_float4{0.0f, 0.0f, 0.0f, 0.0f};
     for (uint32_t tap = 0; tap < (uint32_t)(K * K); tap++) {
-        const int32_t sx = (int32_t)x + (int32_t)(tap % (uint32_t)K) - (K - 1) / 2, sy = (int32_t)y + (int32_t)(tap / (uint32_t)K) - (K - 1) / 2;
         /* of the tap, not of the lane's pixel: a lane past the row end may still load (in bounds) */
-        const bool inside = sx >= 0 && sy >= 0 && sx < (int32_t)p.width && sy < (int32_t)p.height;
-        const size_t pixelA = p.upsampleA ? (size_t)((uint32_t)sy >> 1) * widthA + ((uint32_t)sx >> 1) : (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
-        const size_t pixelB = (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
+        const int32_t sx = (int32_t)x + (int32_t)(tap % (uint32_t)K) - (K - 1) / 2, sy = (int32_t)y + (int32_t)(tap / (uint32_t)K) - (K - 1) / 2;
         for (uint32_t kb = 0; kb < kBlocks; kb++) {
-            nn_half8 act = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (inside) {
-                const uint16_t* src = kb < kBlocksA ? p.inA + pixelA * p.padA + kb * 32u : p.inB + pixelB * p.padB + (kb - kBlocksA) * 32u;
-                act = *(const nn_half8*)(src + quarter * 8u);
-            }
+            const nn_half8 act = nn_gather(p, sx, sy, kb, quarter);
             const nn_half8* w = (const nn_half8*)p.weight + ((size_t)(tap * kBlocks + kb) * outBlocks + group * (uint32_t)NB) * 64u + lane;
             for (int b = 0; b < NB; b++) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[b * 64], act, acc[b], 0, 0, 0);
         }
     }
     if (x >= p.width) return;
-    uint16_t* const o = p.out + ((size_t)y * p.width + x) * p.outPadded;
-    for (int b = 0; b < NB; b++) {
-        const uint32_t c0 = (group * (uint32_t)NB + (uint32_t)b) * 16u + quarter * 4u;
-        nn_float4 bias = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (p.bias) bias = *(const nn_float4*)(p.bias + c0);
-        nn_half4 h;
-        for (int r = 0; r < 4; r++) {
-            float v = acc[b][r];
-            if (p.bias) v = v + bias[r];
-            if (p.relu) v = v < 0.0f ? 0.0f : v;      /* a NaN stays */
-            h[r] = c0 + (uint32_t)r < p.cOut ? (_Float16)v : (_Float16)0.0f; /* the padded channels hold zeros whatever the sums were */
-        }
-        *(nn_half4*)(o + c0) = h;
-    }
+    for (int b = 0; b < NB; b++) nn_store(p, x, y, group * (uint32_t)NB + (uint32_t)b, quarter, acc[b]);
 }
 
 /* The staged form.  A workgroup of four waves computes a tile of NNS_TX x NNS_TY output pixels for one group of NB x 16 output channels; wave w
@@ -96,19 +116,11 @@ template <int NB, int K> __global__ __launch_bounds__(NNK_THREADS) void nn_convk
     const uint32_t tilesY = (p.height + NNS_TY - 1u) / NNS_TY;
     const uint32_t tileX = blockIdx.x % p.tilesX, rest = blockIdx.x / p.tilesX, tileY = rest % tilesY, group = rest / tilesY;
     const int32_t originX = (int32_t)(tileX * NNS_TX) - (K - 1) / 2, originY = (int32_t)(tileY * NNS_TY) - (K - 1) / 2; /* of the staged tile, in the picture */
-    const uint32_t kBlocksA = p.padA / 32u, kBlocks = kBlocksA + p.padB / 32u, outBlocks = p.outPadded / 16u;
-    const uint32_t widthA = p.upsampleA ? p.width / 2u : p.width;
+    const uint32_t kBlocks = (p.padA + p.padB) / 32u, outBlocks = p.outPadded / 16u;
     /* consecutive lanes: the four quarters of a pixel's k-block, then the next pixel -- 64 contiguous bytes of memory per pixel */
     for (uint32_t item = threadIdx.x; item < T::pixels * 4u * kBlocks; item += NNK_THREADS) {
         const uint32_t quarter = item & 3u, pixel = (item >> 2) % T::pixels, kb = (item >> 2) / T::pixels;
-        const int32_t sx = originX + (int32_t)(pixel % T::width), sy = originY + (int32_t)(pixel / T::width);
-        nn_half8 act = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (sx >= 0 && sy >= 0 && sx < (int32_t)p.width && sy < (int32_t)p.height) {
-            const size_t pixelA = p.upsampleA ? (size_t)((uint32_t)sy >> 1) * widthA + ((uint32_t)sx >> 1) : (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
-            const size_t pixelB = (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
-            const uint16_t* src = kb < kBlocksA ? p.inA + pixelA * p.padA + kb * 32u : p.inB + pixelB * p.padB + (kb - kBlocksA) * 32u;
-            act = *(const nn_half8*)(src + quarter * 8u);
-        }
+        const nn_half8 act = nn_gather(p, originX + (int32_t)(pixel % T::width), originY + (int32_t)(pixel / T::width), kb, quarter);
         *(nn_half8*)(nns_image + (kb * 4u + quarter) * T::planeBytes + pixel * 16u) = act;
     }
     __syncthreads();
@@ -133,24 +145,8 @@ template <int NB, int K> __global__ __launch_bounds__(NNK_THREADS) void nn_convk
         }
     }
     if (x >= p.width) return;
-    for (uint32_t r = 0; r < NNS_ROWS; r++) {
-        const uint32_t y = y0 + r;
-        if (y >= p.height) break;
-        uint16_t* const o = p.out + ((size_t)y * p.width + x) * p.outPadded;
-        for (int b = 0; b < NB; b++) {
-            const uint32_t c0 = (group * (uint32_t)NB + (uint32_t)b) * 16u + quarter * 4u;
-            nn_float4 bias = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (p.bias) bias = *(const nn_float4*)(p.bias + c0);
-            nn_half4 h;
-            for (int c = 0; c < 4; c++) {
-                float v = acc[r][b][c];
-                if (p.bias) v = v + bias[c];
-                if (p.relu) v = v < 0.0f ? 0.0f : v;      /* a NaN stays */
-                h[c] = c0 + (uint32_t)c < p.cOut ? (_Float16)v : (_Float16)0.0f;
-            }
-            *(nn_half4*)(o + c0) = h;
-        }
-    }
+    for (uint32_t r = 0; r < NNS_ROWS && y0 + r < p.height; r++)
+        for (int b = 0; b < NB; b++) nn_store(p, x, y0 + r, group * (uint32_t)NB + (uint32_t)b, quarter, acc[r][b]);
 }
 
 /* a lane per output pixel: channels 0-2 of both tensors.  The sum of two binary16 values in fp32 and its rounding to binary16 is their exact sum
@@ -170,10 +166,6 @@ __global__ __launch_bounds__(NNK_THREADS) void nn_sr_finish_kernel(const uint16_
     }
     out[i] = TbFloat4{v[0], v[1], v[2], 1.0f};
 }
-
-bool nnk_frame(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H <= (1ull << 24); }
-bool nnk_tensor(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
-bool nnk_channels(uint32_t c) { return c >= 1u && c <= 512u; }
 
 template <int K> void nnk_launch(bool four, dim3 grid, hipStream_t stream, const NnConvK& p)
 {
@@ -195,18 +187,18 @@ template <int K> void nnk_launch_staged(bool four, hipStream_t stream, const NnC
 extern "C" hipError_t nn_launch_convk(hipStream_t stream, uint32_t width, uint32_t height, uint32_t kernel, uint32_t form, const uint16_t* inA, uint32_t cA,
     uint32_t upsampleA, const uint16_t* inB, uint32_t cB, const uint16_t* weight, const float* bias, uint32_t cOut, uint32_t relu, uint16_t* out)
 {
-    if (!nnk_frame(width, height) || !nnk_tensor(inA) || !nnk_tensor(weight) || !nnk_tensor(out) || !nnk_channels(cA) || !nnk_channels(cOut))
+    if (!nn_frame(width, height) || !nn_tensor(inA) || !nn_tensor(weight) || !nn_tensor(out) || !nn_channels(cA) || !nn_channels(cOut))
         return hipErrorInvalidValue;
-    if ((kernel != 3u && kernel != 5u) || form > 1u || (bias && !nnk_tensor(bias))) return hipErrorInvalidValue;
+    if ((kernel != 3u && kernel != 5u) || form > 1u || (bias && !nn_tensor(bias))) return hipErrorInvalidValue;
     if (form == 1u && !nn_convk_staged_fits(cA, cB)) return hipErrorInvalidValue;
-    if ((cB != 0u) != (inB != nullptr) || (cB && (!nnk_tensor(inB) || !nnk_channels(cB)))) return hipErrorInvalidValue;
+    if ((cB != 0u) != (inB != nullptr) || (cB && (!nn_tensor(inB) || !nn_channels(cB)))) return hipErrorInvalidValue;
     if (upsampleA && ((width | height) & 1u)) return hipErrorInvalidValue;
     if (out == inA || out == inB) return hipErrorInvalidValue;
     NnConvK p;
     p.inA = inA; p.inB = inB; p.weight = weight; p.bias = bias; p.out = out;
     p.width = width; p.height = height; p.padA = nn_padded_channels(cA); p.padB = cB ? nn_padded_channels(cB) : 0u; p.upsampleA = upsampleA ? 1u : 0u;
     p.cOut = cOut; p.outPadded = nn_padded_channels(cOut); p.relu = relu ? 1u : 0u;
-    const bool four = p.outPadded % 64u == 0u; /* 64 output channels per wave where they divide, else 32, as nn_conv3x3 */
+    const bool four = p.outPadded % 64u == 0u; /* 64 output channels per wave where they divide, else 32: an activation fragment feeds that many MFMAs */
     if (form == 1u) {
         p.tilesX = (width + NNS_TX - 1u) / NNS_TX; p.units = 0u;
         if (kernel == 3u) nnk_launch_staged<3>(four, stream, p); else nnk_launch_staged<5>(four, stream, p);
@@ -222,7 +214,7 @@ extern "C" hipError_t nn_launch_convk(hipStream_t stream, uint32_t width, uint32
 
 extern "C" hipError_t nn_launch_sr_finish(hipStream_t stream, uint32_t inW, uint32_t inH, const uint16_t* residual, const uint16_t* input, TbFloat4* out)
 {
-    if (!inW || !inH || (uint64_t)inW * inH * 4u > (1ull << 24) || !nnk_tensor(residual) || !nnk_tensor(input) || !nnk_tensor(out)) return hipErrorInvalidValue;
+    if (!inW || !inH || (uint64_t)inW * inH * 4u > (1ull << 24) || !nn_tensor(residual) || !nn_tensor(input) || !nn_tensor(out)) return hipErrorInvalidValue;
     const uint32_t nPixels = inW * inH * 4u;
     hipLaunchKernelGGL(nn_sr_finish_kernel, dim3((nPixels + NNK_THREADS - 1u) / NNK_THREADS), dim3(NNK_THREADS), 0, stream, residual, input, out, inW, nPixels);
     return hipGetLastError();

@@ -1,82 +1,19 @@
-/* nn_kernels.hip -- the layers of the still denoiser's U-Net (launchers in nn_launch.h):
- *   nn_conv3x3_kernel        3 x 3 convolution + bias (+ ReLU) as an implicit GEMM on v_mfma_f32_16x16x32_f16; reads up to two source tensors in
- *                            channel order, the first optionally nearest-upsampled x 2 as it is gathered (upsample and concat cost no pass)
- *   nn_maxpool2x2_kernel     2 x 2 max-pool, stride 2, on the rounded values
- *   nn_pack_input_kernel     three RGBA32F surfaces -> the network's zero-extended NHWC binary16 input
- *   nn_unpack_output_kernel  the 3-channel result -> RGBA32F (r, g, b, 1), cropped
- *   nn_resolve_aux_kernel    the guide sums -> the albedo and normals the network reads
- *   nn_to_rgba8_kernel       the output stage's 8-bit store
- *
- * The layer arithmetic: binary16 activations and weights, fp32 accumulation (in the matrix core's order), + bias, max(., 0) where the layer has
- * ReLU, then one rounding to binary16 (nearest even; overflow gives infinity, NaN stays NaN).  Padding is zero.
- *
- * The GEMM of one wave: D[output channel][pixel] += W[output channel][k] * X[k][pixel] over k = 32 channels of one tap, for 16 consecutive x of one
- * output row and NB x 16 output channels.  Lane l holds, as the instruction wants them (cdna_hip_programming section 3: the f16 form uses the bf16 map),
- *   A (weights)      output channel l & 15, k = 8 (l >> 4) + j, j = 0..7: one 16-byte load of the host's repack (nn_weights.h packLayer)
- *   B (activations)  k = 8 (l >> 4) + j at pixel l & 15: eight consecutive channels of one pixel, one 16-byte load of an NHWC tensor whose
- *                    channel count is a multiple of 32
- *   D                pixel l & 15, output channels 4 (l >> 4) + r, r = 0..3: one 8-byte store.
- * A k-block lies in source A or in source B, never across (both are padded to 32 channels, and the repack puts zero weights on the padding).
- * Every activation load is predicated on its tap lying inside the picture; a lane whose pixel is past the row end loads whatever taps are inside
- * and stores nothing; no lane reads or writes outside a tensor's padded extent. */
+/* nn_kernels.hip -- what the neural networks run besides their convolution (nn_convk_kernels.hip); launchers in nn_launch.h:
+ *   nn_maxpool2x2_kernel     2 x 2 max-pool, stride 2, on the rounded values: the still denoiser's U-Net
+ *   nn_pack_input_kernel     three RGBA32F surfaces -> a network's zero-extended NHWC binary16 input (the U-Net and the super-resolution)
+ *   nn_unpack_output_kernel  the U-Net's 3-channel result -> RGBA32F (r, g, b, 1), cropped
+ *   nn_resolve_aux_kernel    the guide sums -> the albedo and normals the U-Net reads
+ *   nn_to_rgba8_kernel       the output stage's 8-bit store (both stages)
+ * No lane reads or writes outside a tensor's padded extent. */
 #include "nn_launch.h"
 #include "tb_math.h"
 
 #define NN_THREADS 256u
-#define NN_WAVES (NN_THREADS / 64u)
 
 namespace {
 
 typedef _Float16 nn_half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 nn_half4 __attribute__((ext_vector_type(4)));
-typedef float nn_float4 __attribute__((ext_vector_type(4)));
-
-struct NnConv {
-    const uint16_t* inA; const uint16_t* inB; const uint16_t* weight; const float* bias; uint16_t* out;
-    uint32_t width, height, padA, padB /* padded channels of the sources; padB 0 = no source B */, upsampleA, cOut, outPadded, relu;
-    uint32_t tilesX, units /* tilesX * height * (outPadded / (16 NB)) */;
-};
-
-template <int NB> __global__ __launch_bounds__(NN_THREADS) void nn_conv3x3_kernel(const NnConv p)
-{
-    const uint32_t lane = threadIdx.x & 63u, unit = blockIdx.x * NN_WAVES + (threadIdx.x >> 6); /* a wave's unit: one tile of one row, one group of output channels */
-    if (unit >= p.units) return; /* the whole wave */
-    const uint32_t tile = unit % p.tilesX, rest = unit / p.tilesX, y = rest % p.height, group = rest / p.height;
-    const uint32_t px = lane & 15u, quarter = lane >> 4, x = tile * 16u + px;
-    const uint32_t kBlocksA = p.padA / 32u, kBlocks = kBlocksA + p.padB / 32u, outBlocks = p.outPadded / 16u;
-    const uint32_t widthA = p.upsampleA ? p.width / 2u : p.width;
-    nn_float4 acc[NB];
-    for (int b = 0; b < NB; b++) acc[b] = nn_float4{0.0f, 0.0f, 0.0f, 0.0f};
-    for (uint32_t tap = 0; tap < 9u; tap++) {
-        const int32_t sx = (int32_t)x + (int32_t)(tap % 3u) - 1, sy = (int32_t)y + (int32_t)(tap / 3u) - 1;
-        /* of the tap, not of the lane's pixel: a lane past the row end may still load (in bounds) */
-        const bool inside = sx >= 0 && sy >= 0 && sx < (int32_t)p.width && sy < (int32_t)p.height;
-        const size_t pixelA = p.upsampleA ? (size_t)((uint32_t)sy >> 1) * widthA + ((uint32_t)sx >> 1) : (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
-        const size_t pixelB = (size_t)(uint32_t)sy * p.width + (uint32_t)sx;
-        for (uint32_t kb = 0; kb < kBlocks; kb++) {
-            nn_half8 act = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (inside) {
-                const uint16_t* src = kb < kBlocksA ? p.inA + pixelA * p.padA + kb * 32u : p.inB + pixelB * p.padB + (kb - kBlocksA) * 32u;
-                act = *(const nn_half8*)(src + quarter * 8u);
-            }
-            const nn_half8* w = (const nn_half8*)p.weight + ((size_t)(tap * kBlocks + kb) * outBlocks + group * (uint32_t)NB) * 64u + lane;
-            for (int b = 0; b < NB; b++) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[b * 64], act, acc[b], 0, 0, 0);
-        }
-    }
-    if (x >= p.width) return;
-    uint16_t* const o = p.out + ((size_t)y * p.width + x) * p.outPadded;
-    for (int b = 0; b < NB; b++) {
-        const uint32_t c0 = (group * (uint32_t)NB + (uint32_t)b) * 16u + quarter * 4u;
-        const nn_float4 bias = *(const nn_float4*)(p.bias + c0);
-        nn_half4 h;
-        for (int r = 0; r < 4; r++) {
-            float v = acc[b][r] + bias[r];
-            if (p.relu) v = v < 0.0f ? 0.0f : v;      /* a NaN stays */
-            h[r] = c0 + (uint32_t)r < p.cOut ? (_Float16)v : (_Float16)0.0f; /* the padded channels hold zeros whatever the sums were */
-        }
-        *(nn_half4*)(o + c0) = h;
-    }
-}
 
 __device__ __forceinline__ _Float16 nn_max(_Float16 a, _Float16 b) { return (a > b || a != a) ? a : b; } /* a NaN on either side wins */
 
@@ -155,34 +92,9 @@ __global__ __launch_bounds__(NN_THREADS) void nn_to_rgba8_kernel(const TbFloat4*
     out[i] = r | (g << 8) | (b << 16) | 0xff000000u;
 }
 
-bool nn_frame(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H <= (1ull << 24); }
-bool nn_tensor(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
-bool nn_channels(uint32_t c) { return c >= 1u && c <= 512u; }
 uint32_t nn_groups(uint64_t items) { return (uint32_t)((items + NN_THREADS - 1u) / NN_THREADS); }
 
 } // namespace
-
-extern "C" hipError_t nn_launch_conv3x3(hipStream_t stream, uint32_t width, uint32_t height, const uint16_t* inA, uint32_t cA, uint32_t upsampleA,
-    const uint16_t* inB, uint32_t cB, const uint16_t* weight, const float* bias, uint32_t cOut, uint32_t relu, uint16_t* out)
-{
-    if (!nn_frame(width, height) || !nn_tensor(inA) || !nn_tensor(weight) || !nn_tensor(bias) || !nn_tensor(out) || !nn_channels(cA) || !nn_channels(cOut))
-        return hipErrorInvalidValue;
-    if ((cB != 0u) != (inB != nullptr) || (cB && (!nn_tensor(inB) || !nn_channels(cB)))) return hipErrorInvalidValue;
-    if (upsampleA && ((width | height) & 1u)) return hipErrorInvalidValue;
-    if (out == inA || out == inB) return hipErrorInvalidValue;
-    NnConv p;
-    p.inA = inA; p.inB = inB; p.weight = weight; p.bias = bias; p.out = out;
-    p.width = width; p.height = height; p.padA = nn_padded_channels(cA); p.padB = cB ? nn_padded_channels(cB) : 0u; p.upsampleA = upsampleA ? 1u : 0u;
-    p.cOut = cOut; p.outPadded = nn_padded_channels(cOut); p.relu = relu ? 1u : 0u;
-    p.tilesX = (width + 15u) / 16u;
-    const bool four = p.outPadded % 64u == 0u; /* 64 output channels per wave where they divide, else 32: an activation fragment feeds that many MFMAs */
-    const uint64_t units = (uint64_t)p.tilesX * height * (p.outPadded / (four ? 64u : 32u)); /* < 2^24 * 16 */
-    p.units = (uint32_t)units;
-    const dim3 grid((uint32_t)((units + NN_WAVES - 1u) / NN_WAVES)), block(NN_THREADS);
-    if (four) hipLaunchKernelGGL(nn_conv3x3_kernel<4>, grid, block, 0, stream, p);
-    else hipLaunchKernelGGL(nn_conv3x3_kernel<2>, grid, block, 0, stream, p);
-    return hipGetLastError();
-}
 
 extern "C" hipError_t nn_launch_maxpool2x2(hipStream_t stream, uint32_t width, uint32_t height, uint32_t channels, const uint16_t* in, uint16_t* out)
 {

@@ -1,5 +1,8 @@
-/* nn_launch.h -- the launchers of nn_kernels.hip: the layers of the still denoiser's U-Net.  None knows about contexts,
- * weight files or the network's graph.
+/* nn_launch.h -- the launchers of the two neural networks' kernels.  None knows about contexts, weight files or a network's graph.
+ *   nn_convk_kernels.hip  the convolution of both, the still denoiser's U-Net and the 2 x super-resolution (section 16),
+ *                         and the latter's residual add
+ *   nn_kernels.hip        the U-Net's max-pool and the element-wise helpers: pack and 8-bit store (both networks), unpack and the guide
+ *                         resolve (the U-Net)
  * An activation tensor is NHWC binary16 with its channel count padded to a multiple of 32 (nn_padded_channels); the padded channels hold zeros --
  * every kernel here writes them so.  Tensors are 16-byte aligned.  A launcher refuses (hipErrorInvalidValue) a null or misaligned pointer, a zero
  * dimension, more than 2^24 pixels, more than 512 channels in a tensor, and an odd size where a size is halved. */
@@ -9,14 +12,12 @@
 #include "tb_abi.h"
 
 static inline uint32_t nn_padded_channels(uint32_t c) { return (c + 31u) / 32u * 32u; }
+/* what every launcher checks of a picture's size, a tensor's pointer and a tensor's channel count */
+static inline bool nn_frame(uint32_t W, uint32_t H) { return W && H && (uint64_t)W * H <= (1ull << 24); }
+static inline bool nn_tensor(const void* p) { return p && ((uintptr_t)p & 15u) == 0; }
+static inline bool nn_channels(uint32_t c) { return c >= 1u && c <= 512u; }
 
 extern "C" {
-/* out[y][x][o] = half(relu?(bias[o] + sum over the 3 x 3 taps and the input channels of in * weight)), fp32 accumulation, zero padding, for a
- * width x height output.  The input is source A's channels followed by source B's (inB null and cB 0: A alone); both are width x height, except
- * that with upsampleA source A is (width / 2) x (height / 2) and read nearest-upsampled x 2.  weight and bias: tbnn::packLayer's
- * (nn_weights.h) for (cA, cB, cOut).  out has nn_padded_channels(cOut) channels and may alias neither input. */
-hipError_t nn_launch_conv3x3(hipStream_t stream, uint32_t width, uint32_t height, const uint16_t* inA, uint32_t cA, uint32_t upsampleA, const uint16_t* inB,
-                             uint32_t cB, const uint16_t* weight, const float* bias, uint32_t cOut, uint32_t relu, uint16_t* out);
 /* out[y][x][c] = the largest of in[2y .. 2y + 1][2x .. 2x + 1][c] (a NaN among them gives NaN); in is width x height, both even, `channels`
  * counts the padded channels */
 hipError_t nn_launch_maxpool2x2(hipStream_t stream, uint32_t width, uint32_t height, uint32_t channels, const uint16_t* in, uint16_t* out);
@@ -36,12 +37,14 @@ hipError_t nn_launch_resolve_aux(hipStream_t stream, uint32_t width, uint32_t he
 /* (x, y, z, w) -> R8G8B8A8_UNORM as the output stage stores it: clamp, scale, + 0.5, truncate; alpha 255 */
 hipError_t nn_launch_to_rgba8(hipStream_t stream, uint32_t width, uint32_t height, const TbFloat4* in, uint32_t* out);
 
-/* nn_convk_kernels.hip: the layers of the 2 x super-resolution network.
- * nn_launch_conv3x3 with a kernel x kernel filter, kernel 3 or 5, zero padding (kernel - 1) / 2 on every side, and an optional bias (null: none).
- * weight and bias: tbnn::packLayer's for (cA, cB, cOut, kernel * kernel taps).  form: 0, the plain form -- a wave per 16 pixels of a row, every
- * fragment from memory; 1, the staged form -- a workgroup per 32 x 8 pixels, its input tile and halo in LDS, four rows per weight fragment; the
- * same bits either way.  The staged form holds at most two k-blocks (nn_convk_staged_fits); more are refused like every other bad argument
- * (hipErrorInvalidValue). */
+/* nn_convk_kernels.hip.
+ * out[y][x][o] = half(relu?(bias[o] + sum over the kernel x kernel taps and the input channels of in * weight)), fp32 accumulation, for a
+ * width x height output; kernel 3 or 5, zero padding (kernel - 1) / 2 on every side, bias null: none.  The input is source A's channels followed
+ * by source B's (inB null and cB 0: A alone); both are width x height, except that with upsampleA source A is (width / 2) x (height / 2) and read
+ * nearest-upsampled x 2.  weight and bias: tbnn::packLayer's (nn_weights.h) for (cA, cB, cOut, kernel * kernel taps).  out has
+ * nn_padded_channels(cOut) channels and may alias neither input.  form: 0, the plain form -- a wave per 16 pixels of a row, every fragment from
+ * memory; 1, the staged form -- a workgroup per 32 x 8 pixels, its input tile and halo in LDS, four rows per weight fragment; the same bits either
+ * way.  The staged form holds at most two k-blocks (nn_convk_staged_fits); more are refused like every other bad argument (hipErrorInvalidValue). */
 static inline bool nn_convk_staged_fits(uint32_t cA, uint32_t cB) { return nn_padded_channels(cA) + (cB ? nn_padded_channels(cB) : 0u) <= 64u; }
 hipError_t nn_launch_convk(hipStream_t stream, uint32_t width, uint32_t height, uint32_t kernel, uint32_t form, const uint16_t* inA, uint32_t cA,
                            uint32_t upsampleA, const uint16_t* inB, uint32_t cB, const uint16_t* weight, const float* bias, uint32_t cOut, uint32_t relu,
