@@ -651,6 +651,59 @@ int tb_run_sr_finish(tb_context* ctx, uint32_t in_w, uint32_t in_h, const uint16
 int tb_run_sr(tb_context* ctx, uint32_t width, uint32_t height, const float* color_rgba, float* out_rgba);
 int tb_upscale_neural(tb_context* ctx, const tb_post_settings* post, float* rgba_f32_or_null, uint8_t* rgba8_or_null);
 
+/* ---- image-quality metrics (no reference counterpart: the definitions are the standard ones) -------------------
+ * A test picture A against a reference picture R, both RGBA32F of one size w x h, row 0 = top.  RGB is compared, alpha is ignored (a NaN alpha
+ * excludes nothing).  Where A is an accumulation surface, A.rgb = sum.rgb / sum.w, one fp32 division per channel, and a pixel with sum.w == 0 is
+ * UNSAMPLED (outside a crop window, a zero budget).  A pixel is EXCLUDED if it is unsampled or one of its six RGB values is not finite: it is
+ * counted and contributes to nothing.
+ * Pointwise, in fp64 per included pixel and channel: d = (double)A - (double)R, se = d d, ae = |d|, re = se / ((double)R (double)R + rel_epsilon);
+ * per pixel the three channels are added in the order r, g, b; mse, mae, rel_mse = the sums over the included pixels / (3 pixels); max_abs = the
+ * largest ae; psnr = 10 log10(peak^2 / mse) on the host, +inf for mse == 0; pixels == 0: all of them NaN.  The squared-error map holds
+ * (float)((se_r + se_g + se_b) / 3.0) per pixel, 0 at an excluded one.
+ * SSIM (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, K1 0.01, K2 0.03), in fp32 on x < 0 ? 0 : x > peak ? peak : x per channel, an
+ * excluded pixel as 0; valid region only: (w - 10) x (h - 10) windows, none if w < 11 or h < 11.  The eleven weights are the binary32 values
+ * 3a86cab6 3bf8ff01 3d13758c 3ddff87f 3e5a1e20 3e8832b0 and back.  A plane is filtered along rows, then along columns, each as acc = 0; acc = acc +
+ * w[i] x[i] for i = 0..10 (separate multiply and add); five planes per channel: a, r, a a, r r, a r (fp32 products).  Per window
+ * va = Eaa - ma ma, vr = Err - mr mr, c = Ear - ma mr, C1 = (float)((0.01 (double)peak)^2), C2 = (float)((0.03 (double)peak)^2),
+ * s = (((2 ma) mr + C1) (2 c + C2)) / ((ma ma + mr mr + C1) (va + vr + C2)); the window's value is ((double)s_r + s_g + s_b) / 3.0; a window that
+ * holds an excluded pixel is skipped and counted.  The map holds the value rounded to fp32, 0 for a skipped window; ssim is the fp64 mean over
+ * the windows that count, NaN without one.  A == R bit for bit gives exactly 1 in every window.
+ * Sums: every workgroup writes one partial record at its own index and a last kernel adds them in index order -- no floating-point atomic, so
+ * for a given w x h the result is the same bits on every call; the order is not part of the contract, tests/metrics_ref.py holds the sums to the
+ * any-order bound and the maps bit for bit.
+ *
+ * tb_run_compare: the kernel seam, like tb_run_fsr_easu: host arrays (w * h * 4 floats each), temporary device buffers, no scene, nothing the
+ * context holds is read or written.  Flag TB_COMPARE_SUMS: test_rgba holds sums (rgb / w, unsampled pixels), as the accumulation does.
+ * tb_set_reference: uploads the reference the stage compares with; it belongs to the context, is kept until it is replaced or released (NULL)
+ * and goes with tb_destroy.
+ * tb_compare: the stage.  surface TB_COMPARE_MEAN: the accumulation (sums / .w, unsampled pixels excluded); TB_COMPARE_DENOISED: the final
+ * surface of tb_denoise, read as (rgb, 1).  Runs on the context's stream after whatever was enqueued; synchronous; its only read-back is the result
+ * record, and the maps where asked for.  It writes neither the accumulation nor the AOVs, frame counter, history, denoised or guide surfaces:
+ * tb_accum_digest is the same before and after and a render continued afterwards is the uninterrupted one.  Its scratch buffers belong to the
+ * context and are kept while the size holds.  It equals tb_run_compare on host copies of the same two surfaces, field for field, bit for bit.
+ * settings NULL: the defaults.  sq_err_map_or_null: w * h floats; ssim_map_or_null: (w - 10) * (h - 10) floats, untouched without a window.
+ * TB_E_INVALID (the message names the cause): a null required pointer; a zero size or w * h > 2^26; peak or rel_epsilon not finite or <= 0;
+ * unknown flags (TB_COMPARE_SUMS in tb_compare among them) or an unknown surface; no reference set, or one of another size than the rendered
+ * surface; nothing rendered yet; TB_COMPARE_MEAN after tb_render_realtime; TB_COMPARE_DENOISED without a valid denoised surface (the rule of
+ * tb_post_process with option "post_denoised").  TB_E_UNSUPPORTED: tb_set_reference / tb_compare on a tb_create_multi group or a peer handle. */
+#define TB_COMPARE_SSIM 1u /* tb_compare_settings::flags: compute SSIM */
+#define TB_COMPARE_SUMS 2u /* tb_run_compare only: the test picture holds sums */
+#define TB_COMPARE_MEAN 0u
+#define TB_COMPARE_DENOISED 1u
+typedef struct tb_compare_settings { float peak; float rel_epsilon; uint32_t flags; } tb_compare_settings;
+typedef struct tb_compare_result {
+    uint64_t pixels, excluded, unsampled;          /* included pixels; excluded ones; unsampled ones, which are part of the excluded */
+    uint64_t ssim_windows, ssim_windows_skipped;   /* both 0 without TB_COMPARE_SSIM */
+    double mse, mae, rel_mse, max_abs, psnr, ssim; /* ssim NaN without TB_COMPARE_SSIM */
+    float gpu_us;                                  /* HIP events around the kernels of this call */
+} tb_compare_result;
+void tb_default_compare_settings(tb_compare_settings* out); /* peak 1, rel_epsilon 0.01, flags TB_COMPARE_SSIM */
+int tb_run_compare(tb_context* ctx, uint32_t w, uint32_t h, const float* test_rgba, const float* ref_rgba, const tb_compare_settings* settings_or_null,
+                   tb_compare_result* out, float* sq_err_map_or_null, float* ssim_map_or_null);
+int tb_set_reference(tb_context* ctx, uint32_t w, uint32_t h, const float* rgba_or_null);
+int tb_compare(tb_context* ctx, uint32_t surface, const tb_compare_settings* settings_or_null, tb_compare_result* out, float* sq_err_map_or_null,
+               float* ssim_map_or_null);
+
 /* ---- host-only half of LoadScene (no device needed) ------------------------------------------------
  * The same parse / convert / BVH-build code tb_load_scene runs, exposed separately so that the
  * scene conversion and the BVH can be inspected and checked on machines without a GPU.  Nothing here

@@ -180,6 +180,21 @@ class tb_conv_desc(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "c_a", "c_b", "c_out", "kernel", "upsample_a", "relu", "form")]
 
 
+TB_COMPARE_SSIM, TB_COMPARE_SUMS = 1, 2          # tb_compare_settings.flags
+TB_COMPARE_MEAN, TB_COMPARE_DENOISED = 0, 1      # tb_compare's surface
+
+
+class tb_compare_settings(C.Structure):
+    """include/tracerboy_hip.h tb_compare_settings: what the image-quality metrics are told."""
+    _fields_ = [("peak", C.c_float), ("rel_epsilon", C.c_float), ("flags", C.c_uint32)]
+
+
+class tb_compare_result(C.Structure):
+    """include/tracerboy_hip.h tb_compare_result: the metrics of one comparison."""
+    _fields_ = [(n, C.c_uint64) for n in ("pixels", "excluded", "unsampled", "ssim_windows", "ssim_windows_skipped")] + \
+               [(n, C.c_double) for n in ("mse", "mae", "rel_mse", "max_abs", "psnr", "ssim")] + [("gpu_us", C.c_float)]
+
+
 class tb_readback_stats(C.Structure):
     _fields_ = [("ActiveWaves", C.c_uint32), ("ActivePixels", C.c_uint32), ("SelectedPixelDistance", C.c_float), ("SelectedMaterialID", C.c_int32),
                 ("rays", TbRayStats)]
@@ -243,6 +258,7 @@ assert C.sizeof(TbPostConstants) == 36
 assert C.sizeof(TbTemporalConstants) == 144
 assert C.sizeof(TbDenoiserConstants) == 28
 assert C.sizeof(TbFsrConstants) == 80
+assert C.sizeof(tb_compare_settings) == 12 and C.sizeof(tb_compare_result) == 96
 assert C.sizeof(TbPerFrameConstants) == 148
 assert C.sizeof(TbConfigConstants) == 76
 assert C.sizeof(TbLight) == 104

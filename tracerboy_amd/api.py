@@ -110,6 +110,10 @@ def lib():
         "tb_run_fsr_easu": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 5 + [vp, vp]),
         "tb_run_fsr_rcas": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 3 + [vp, vp]),
         "tb_upscale": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp]),
+        "tb_default_compare_settings": (None, [P(abi.tb_compare_settings)]),
+        "tb_run_compare": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, P(abi.tb_compare_settings), P(abi.tb_compare_result), vp, vp]),
+        "tb_set_reference": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+        "tb_compare": (C.c_int, [vp, C.c_uint32, P(abi.tb_compare_settings), P(abi.tb_compare_result), vp, vp]),
         "tb_nn_weights_info": (C.c_int, [C.c_char_p, P(abi.tb_nn_info), C.c_char_p, C.c_uint32]),
         "tb_neural_load": (C.c_int, [vp, C.c_char_p]),
         "tb_run_conv3x3": (C.c_int, [vp, P(abi.tb_conv3x3_desc)] + [vp] * 5),
@@ -184,6 +188,16 @@ def GetDefaultPostProcessSettings():
     s = abi.tb_post_settings()
     lib().tb_default_post_settings(C.byref(s))
     return s
+
+
+def GetDefaultCompareSettings():
+    """The image-quality metrics' defaults (tb_default_compare_settings): peak 1, rel_epsilon 0.01, SSIM on."""
+    s = abi.tb_compare_settings()
+    lib().tb_default_compare_settings(C.byref(s))
+    return s
+
+
+COMPARE_FIELDS = tuple(n for n, _ in abi.tb_compare_result._fields_)
 
 
 def FsrConstants(in_width, in_height, out_width, out_height, sharpness=0.2):
@@ -840,6 +854,53 @@ class TracerBoy:
         out = np.empty_like(a)
         self._check(self._L.tb_run_fsr_rcas(self._ctx, C.byref(constants), surface, a.shape[1], a.shape[0], _np_ptr(a), _np_ptr(out)))
         return out
+
+    # -- image-quality metrics --------------------------------------------
+    @staticmethod
+    def _compare_maps(width, height, maps):
+        """(squared-error map, SSIM map) to hand to the library, or (None, None); the SSIM map is (H - 10, W - 10), empty without a window."""
+        if not maps:
+            return None, None
+        return np.zeros((height, width), np.float32), np.zeros((max(height - 10, 0), max(width - 10, 0)), np.float32)
+
+    @staticmethod
+    def _compare_dict(result, sq, ssim):
+        d = {n: getattr(result, n) for n in COMPARE_FIELDS}
+        if sq is not None:
+            d["sq_err_map"], d["ssim_map"] = sq, ssim
+        return d
+
+    def RunCompare(self, test, ref, settings=None, maps=False):
+        """cmp_pointwise / cmp_ssim / cmp_finish on two host images (H, W, 4) float32 (tb_run_compare); nothing of the context read or written.
+        settings.flags | TB_COMPARE_SUMS: test holds sums (rgb * w, w).  Returns a dict of tb_compare_result's fields; with maps=True also
+        "sq_err_map" (H, W) and "ssim_map" (H - 10, W - 10)."""
+        a, r = np.ascontiguousarray(test, np.float32), np.ascontiguousarray(ref, np.float32)
+        if a.ndim != 3 or a.shape[2] != 4 or a.shape != r.shape:
+            raise ValueError("RunCompare: two (H, W, 4) images of one size")
+        out = abi.tb_compare_result()
+        sq, ssim = self._compare_maps(a.shape[1], a.shape[0], maps)
+        self._check(self._L.tb_run_compare(self._ctx, a.shape[1], a.shape[0], _np_ptr(a), _np_ptr(r), C.byref(settings) if settings is not None else None,
+                                           C.byref(out), _np_ptr(sq) if maps else None, _np_ptr(ssim) if maps and ssim.size else None))
+        return self._compare_dict(out, sq, ssim)
+
+    def SetReference(self, image):
+        """Upload the (H, W, 4) float32 reference picture Compare measures against, or release it with None (tb_set_reference)."""
+        if image is None:
+            self._check(self._L.tb_set_reference(self._ctx, 0, 0, None))
+            return
+        r = np.ascontiguousarray(image, np.float32)
+        if r.ndim != 3 or r.shape[2] != 4:
+            raise ValueError("SetReference: an (H, W, 4) image")
+        self._check(self._L.tb_set_reference(self._ctx, r.shape[1], r.shape[0], _np_ptr(r)))
+
+    def Compare(self, surface=0, settings=None, maps=False):
+        """The metrics of the accumulation's mean (surface 0) or the denoised still (1) against the reference, on the device (tb_compare).
+        Returns what RunCompare returns."""
+        out = abi.tb_compare_result()
+        sq, ssim = self._compare_maps(self.width, self.height, maps)
+        self._check(self._L.tb_compare(self._ctx, surface, C.byref(settings) if settings is not None else None, C.byref(out),
+                                       _np_ptr(sq) if maps else None, _np_ptr(ssim) if maps and ssim.size else None))
+        return self._compare_dict(out, sq, ssim)
 
     def AveragedLuminance(self):
         v = C.c_float()

@@ -9,6 +9,8 @@
  *                 [--denoise-neural FILE.tza [--denoise-guides K]]
  *                 [--upscale-neural FILE.bin]
  *                 [--crop X0,Y0,X1,Y1] [--spp-map FILE] [--noise-target T [--noise-after F] [--noise-chunk C]]
+ *                 [--reference FILE [--metrics-out FILE] [--metrics-every N] [--error-map FILE.pfm]]
+ *   tracerboy-hip --compare A B [--metrics-out FILE] [--device I]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
  * --ranks N (N > 1): the frame tiled across N GPUs of the node, natively.  The process starts N copies of itself -- before it
@@ -93,7 +95,23 @@
  * samples actually taken (live pixels x frames of every call; with --ranks it keeps the full frame's count).
  * Exit status 2, before any device call: a malformed or empty window, T not finite or not above 0, a map that cannot be read, any of the three
  * with --adaptive unless --adaptive-test call, with --upscale-neural or with --render-scale; a window outside the frame or a map of another size
- * likewise where --width and --height are given, otherwise as soon as the scene (or the state) has told the frame's size. */
+ * likewise where --width and --height are given, otherwise as soon as the scene (or the state) has told the frame's size.
+ *
+ * Image-quality metrics (tb_set_reference / tb_compare / tb_run_compare).  --reference FILE (.hdr .pfm .png .tga, of the RENDERED
+ * size -- with --render-scale the shrunk one): the finished accumulation's mean is compared with it on the device and the metrics are printed as one
+ * JSON object on a line of its own: "frames", "surface" ("mean"), then every field of tb_compare_result, a value that is not finite as null.
+ * When --denoise or --denoise-guides ran, a second line with "surface": "denoised" follows for the denoised picture.  --metrics-out FILE writes
+ * these lines to FILE instead.  --metrics-every N renders in calls of N frames -- the loop of --checkpoint-every; with both, the calls are cut at
+ * either grid; with --adaptive or a sample budget, at their own schedule as well -- and writes a "mean" line after each call: the convergence curve
+ * without one frame read back.  The final "mean" line is not repeated when the last call's line already holds the final frame count.
+ * --error-map FILE.pfm: the squared-error map of the last line written (the denoised picture's when there is one), grey, three equal channels.
+ * --metrics-out, --metrics-every and --error-map need --reference; --metrics-every does not go with --ranks N > 1, for the reason the state flags do
+ * not; with --ranks the final line is rank 0's, of the gathered frame.  The metrics flags change no pixel of --out.
+ * --compare A B takes the place of the scene: the two image files (of one size) go through tb_run_compare, the line ("frames": 0, "surface":
+ * "files") goes to standard output or to --metrics-out.  No scene, no render.
+ * Exit status 2, before any device call: a reference or a file of --compare that cannot be read, A and B of different sizes, N below 1, an
+ * --error-map that is no .pfm, a flag without --reference; a reference of another size than the render likewise where --width and --height are
+ * given, otherwise as soon as the scene (or the state) has told the frame's size. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -120,6 +138,58 @@ static int fail(tb_context* c, const char* what, int rc)
 }
 
 extern char** environ;
+
+/* ---- image-quality metrics: one JSON object per line ---- */
+static std::string jsonNumber(double v)
+{
+    if (!(v - v == 0.0)) return "null"; /* NaN, +-inf */
+    char b[40]; snprintf(b, sizeof b, "%.17g", v); return b;
+}
+static std::string metricsJson(uint32_t frames, const char* surface, const tb_compare_result& r)
+{
+    char head[256];
+    snprintf(head, sizeof head, "{\"frames\": %u, \"surface\": \"%s\", \"pixels\": %llu, \"excluded\": %llu, \"unsampled\": %llu, \"ssim_windows\": %llu, "
+        "\"ssim_windows_skipped\": %llu", frames, surface, (unsigned long long)r.pixels, (unsigned long long)r.excluded, (unsigned long long)r.unsampled,
+        (unsigned long long)r.ssim_windows, (unsigned long long)r.ssim_windows_skipped);
+    return std::string(head) + ", \"mse\": " + jsonNumber(r.mse) + ", \"mae\": " + jsonNumber(r.mae) + ", \"rel_mse\": " + jsonNumber(r.rel_mse) +
+        ", \"max_abs\": " + jsonNumber(r.max_abs) + ", \"psnr\": " + jsonNumber(r.psnr) + ", \"ssim\": " + jsonNumber(r.ssim) + ", \"gpu_us\": " +
+        jsonNumber((double)r.gpu_us) + "}";
+}
+/* an image file as RGBA32F (tb_decode_image); false: it cannot be read */
+static bool readImage(const std::string& path, uint32_t& w, uint32_t& h, std::vector<float>& rgba)
+{
+    int normalized = 0, alpha = 0;
+    if (tb_decode_image(path.c_str(), &w, &h, &normalized, &alpha, nullptr) || !w || !h) return false;
+    rgba.resize((size_t)w * h * 4);
+    return tb_decode_image(path.c_str(), &w, &h, &normalized, &alpha, rgba.data()) == 0;
+}
+/* --compare A B: two files through tb_run_compare; no scene */
+static int compareFiles(int argc, char** argv)
+{
+    if (argc < 4) { fprintf(stderr, "--compare takes two image files\n"); return 2; }
+    std::string metricsOut; int device = 0;
+    for (int i = 4; i < argc; i += 2) {
+        const std::string k = argv[i];
+        if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", k.c_str()); return 2; }
+        if (k == "--metrics-out") metricsOut = argv[i + 1]; else if (k == "--device") device = atoi(argv[i + 1]);
+        else { fprintf(stderr, "--compare goes with --metrics-out and --device only, not %s\n", k.c_str()); return 2; }
+    }
+    uint32_t w[2] = {0, 0}, h[2] = {0, 0}; std::vector<float> img[2];
+    for (int j = 0; j < 2; j++) if (!readImage(argv[2 + j], w[j], h[j], img[j])) {
+        fprintf(stderr, "--compare %s: cannot be read as an image (.hdr .pfm .png .tga)\n", argv[2 + j]); return 2; }
+    if (w[0] != w[1] || h[0] != h[1]) { fprintf(stderr, "--compare: %s is %ux%u, %s is %ux%u\n", argv[2], w[0], h[0], argv[3], w[1], h[1]); return 2; }
+    tb_context* ctx = nullptr;
+    int rc = tb_create(&ctx, device);
+    if (rc) return fail(nullptr, "tb_create", rc);
+    tb_compare_result r;
+    if ((rc = tb_run_compare(ctx, w[0], h[0], img[0].data(), img[1].data(), nullptr, &r, nullptr, nullptr))) return fail(ctx, "tb_run_compare", rc);
+    const std::string line = metricsJson(0, "files", r);
+    if (metricsOut.empty()) printf("%s\n", line.c_str());
+    else { FILE* f = fopen(metricsOut.c_str(), "w"); if (!f || fprintf(f, "%s\n", line.c_str()) < 0 || fclose(f)) { perror("tracerboy-hip: --metrics-out");
+        tb_destroy(ctx); return 1; } }
+    tb_destroy(ctx);
+    return 0;
+}
 
 /* ---- RCCL, loaded at run time: the handful of entry points the gather needs (rccl.h) ---- */
 struct RcclId { char internal[128]; };                 /* ncclUniqueId */
@@ -191,7 +261,8 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C --reference FILE --metrics-out FILE --metrics-every N --error-map f.pfm]\n       tracerboy-hip --compare A B [--metrics-out FILE --device I]\n"); return 2; }
+    if (!strcmp(argv[1], "--compare")) return compareFiles(argc, argv);
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;
@@ -201,6 +272,7 @@ int main(int argc, char** argv)
     std::string neural, neuralUp; bool denoiseFlag = false; /* --denoise itself, not what --denoise-guides implies */
     long long crop[4] = {0, 0, 0, 0}; bool cropSet = false; std::string sppMap; float noiseTarget = 0.0f; bool noiseSet = false;
     long long noiseAfter = 64, noiseChunk = 64;
+    std::string reference, metricsOut, errorMap; long long metricsEvery = 0; bool metricsEverySet = false;
     uint32_t upW = 0, upH = 0; float renderScale = 0.0f, fsrSharpness = -1.0f; bool upscaleSet = false, renderScaleSet = false, sharpnessSet = false;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
@@ -242,6 +314,8 @@ int main(int argc, char** argv)
             if (end == v || *end || !(noiseTarget > 0.0f) || !(noiseTarget < 3.0e38f)) { fprintf(stderr, "--noise-target is a finite relative error above 0\n"); return 2; } }
         else if (k == "--noise-after") noiseAfter = atoll(v); else if (k == "--noise-chunk") noiseChunk = atoll(v);
         else if (k == "--denoise-neural") neural = v;
+        else if (k == "--reference") reference = v; else if (k == "--metrics-out") metricsOut = v; else if (k == "--error-map") errorMap = v;
+        else if (k == "--metrics-every") { metricsEvery = atoll(v); metricsEverySet = true; }
         else if (k == "--upscale-neural") neuralUp = v;
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
@@ -283,6 +357,21 @@ int main(int argc, char** argv)
         tb_sr_info sr; char err[512] = "";
         if (tb_sr_weights_info(neuralUp.c_str(), &sr, err, sizeof err)) { fprintf(stderr, "--upscale-neural %s: %s\n", neuralUp.c_str(), err); return 2; }
     }
+    /* image-quality metrics */
+    if (reference.empty() && (!metricsOut.empty() || metricsEverySet || !errorMap.empty())) { fprintf(stderr,
+        "--metrics-out, --metrics-every and --error-map need --reference FILE: the metrics are those against a reference picture\n"); return 2; }
+    if (metricsEverySet && metricsEvery < 1) { fprintf(stderr, "--metrics-every N needs N >= 1\n"); return 2; }
+    if (metricsEvery > 0 && ranks > 1) { fprintf(stderr,
+        "--metrics-every does not go with --ranks: the gather moves the output surface after the last frame only, no rank holds the frame in between\n"); return 2; }
+    if (!errorMap.empty() && !(errorMap.size() >= 4 && errorMap.compare(errorMap.size() - 4, 4, ".pfm") == 0)) { fprintf(stderr, "--error-map writes a .pfm file\n"); return 2; }
+    std::vector<float> refRgba; uint32_t refW = 0, refH = 0;
+    if (!reference.empty() && !readImage(reference, refW, refH, refRgba)) { /* host only: decoded before any device call */
+        fprintf(stderr, "--reference %s: cannot be read as an image (.hdr .pfm .png .tga)\n", reference.c_str()); return 2; }
+    auto referenceFits = [&](uint32_t fw, uint32_t fh) {
+        if (!reference.empty() && (refW != fw || refH != fh)) {
+            fprintf(stderr, "--reference %s is %ux%u, the render %ux%u\n", reference.c_str(), refW, refH, fw, fh); return false; }
+        return true;
+    };
     const bool states = !saveState.empty() || !resume.empty() || !adds.empty() || frameA >= 0 || checkpointEvery != 0;
     if (states && ranks > 1) { fprintf(stderr,
         "--save-state, --resume, --add, --frames and --checkpoint-every do not go with --ranks: the gather moves the output surface only\n"); return 2; }
@@ -322,6 +411,7 @@ int main(int argc, char** argv)
         return true;
     };
     if (budgeted && W && H && resume.empty() && !budgetFits(W, H)) return 2;
+    if (W && H && resume.empty() && !renderScaleSet && !referenceFits(W, H)) return 2;
     if (ranks > 1 && !envRank) return spawnRanks(argc, argv, ranks);
     if (envRank && (!getenv("TB_CLI_WORLD") || atoi(getenv("TB_CLI_WORLD")) < 1 || atoi(envRank) < 0 || atoi(envRank) >= atoi(getenv("TB_CLI_WORLD")) ||
                     (atoi(getenv("TB_CLI_WORLD")) > 1 && !getenv("TB_CLI_ID_FILE")))) {
@@ -386,6 +476,22 @@ int main(int argc, char** argv)
         tb_destroy(ctx); return 2; }
     if (!neuralUp.empty() && (uint64_t)W * H * 4u > (1ull << 24)) { /* likewise */
         fprintf(stderr, "tracerboy-hip: cannot upscale the %ux%u render to twice that: more than 2^24 pixels\n", W, H); tb_destroy(ctx); return 2; }
+    if (!referenceFits(W, H)) { tb_destroy(ctx); return 2; }
+    if (!reference.empty() && (rc = tb_set_reference(ctx, W, H, refRgba.data()))) return fail(ctx, "tb_set_reference", rc);
+    /* a line of metrics: to --metrics-out, else to standard output.  lastLineFrames: the frame count of the last "mean" line */
+    FILE* metricsFile = nullptr; /* opened at the first line: with --ranks only rank 0 writes one */
+    long long lastLineFrames = -1;
+    auto metricsLine = [&](uint32_t surface, uint32_t frames, float* sqErrMap, bool print) {
+        tb_compare_result r;
+        const int e = tb_compare(ctx, surface, nullptr, &r, sqErrMap, nullptr);
+        if (e || !print) return e;
+        const std::string line = metricsJson(frames, surface == TB_COMPARE_MEAN ? "mean" : "denoised", r);
+        if (!metricsOut.empty() && !metricsFile && !(metricsFile = fopen(metricsOut.c_str(), "w"))) { perror("tracerboy-hip: --metrics-out"); return TB_E_IO; }
+        if (metricsFile) { fprintf(metricsFile, "%s\n", line.c_str()); fflush(metricsFile); } else printf("%s\n", line.c_str());
+        if (surface == TB_COMPARE_MEAN) lastLineFrames = frames;
+        return 0;
+    };
+    auto curvePoint = [&](uint32_t frames) { return metricsEvery > 0 ? metricsLine(TB_COMPARE_MEAN, frames, nullptr, true) : 0; };
     const uint32_t start = done;
     uint64_t sampled = 0; /* budgeted runs: the samples actually taken, live pixels x frames of every call (this rank's) */
     auto checkpoint = [&]() { return checkpointEvery > 0 ? tb_state_save(ctx, saveState.c_str()) : 0; };
@@ -413,6 +519,7 @@ int main(int argc, char** argv)
             if (noiseSet) next = std::min<long long>(next, done < noiseStart ? (long long)noiseStart : done + noiseChunk - (done - noiseStart) % noiseChunk);
             if (adaptive >= 0.0f) next = std::min<long long>(next, done < plainEnd ? (long long)plainEnd : done + adaptiveChunk - (done - plainEnd) % adaptiveChunk);
             if (checkpointEvery > 0) next = std::min<long long>(next, (long long)done + checkpointEvery);
+            if (metricsEvery > 0) next = std::min<long long>(next, (long long)done + metricsEvery);
             if (noiseSet && done >= noiseStart && done > start) { /* (never before this run's first call: a --frames job holds nothing yet) */
                 uint64_t stopped = 0, live = 0;
                 if ((rc = tb_budget_stop_converged(ctx, noiseTarget, (uint32_t)noiseAfter, &stopped, &live))) return fail(ctx, "tb_budget_stop_converged", rc);
@@ -426,17 +533,22 @@ int main(int argc, char** argv)
             if (world > 1) printf("budget rank %d: %u frames, %lld live pixels, %.3f ms\n", rank, done, live, callMs);
             else printf("budget: %u frames, %lld live pixels, %.3f ms\n", done, live, callMs);
             if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+            if ((rc = curvePoint(done))) return fail(ctx, "tb_compare", rc);
         }
     } else if (adaptive < 0.0f) {
-        if (!states) { /* the plain render: one call */
+        const bool chunked = states || metricsEvery > 0;
+        if (!chunked) { /* the plain render: one call */
             if ((rc = tb_render(ctx, W, H, spp, &s, t))) return fail(ctx, "tb_render", rc);
             ms = tb_last_render_ms(ctx); done = spp;
         }
-        while (states && done < target) {
-            const uint32_t n = (uint32_t)std::min<long long>(checkpointEvery > 0 ? checkpointEvery : (long long)target - done, (long long)target - done);
-            if ((rc = tb_render(ctx, W, H, n, &s, t))) return fail(ctx, "tb_render", rc);
-            ms += tb_last_render_ms(ctx); done += n;
+        while (chunked && done < target) {
+            long long n = (long long)target - done;
+            if (checkpointEvery > 0) n = std::min<long long>(n, checkpointEvery);
+            if (metricsEvery > 0) n = std::min<long long>(n, metricsEvery);
+            if ((rc = tb_render(ctx, W, H, (uint32_t)n, &s, t))) return fail(ctx, "tb_render", rc);
+            ms += tb_last_render_ms(ctx); done += (uint32_t)n;
             if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+            if ((rc = curvePoint(done))) return fail(ctx, "tb_compare", rc);
         }
     } else {
         /* the plain call: no pixel can skip before frame F + 1; a resumed state that is past it goes straight on with the adaptive calls */
@@ -445,6 +557,7 @@ int main(int argc, char** argv)
             if ((rc = tb_render(ctx, W, H, plainEnd - done, &s, t))) return fail(ctx, "tb_render", rc);
             ms = tb_last_render_ms(ctx); done = plainEnd;
             if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+            if ((rc = curvePoint(done))) return fail(ctx, "tb_compare", rc);
         }
         while (done < target) {
             /* the calls keep the grid of an uninterrupted schedule: with --adaptive-test call the pixels are tested at those frames */
@@ -457,6 +570,7 @@ int main(int argc, char** argv)
             if (world > 1) printf("adaptive rank %d: %u frames, %lld live pixels, %.3f ms\n", rank, done, live, callMs);
             else printf("adaptive: %u frames, %lld live pixels, %.3f ms\n", done, live, callMs);
             if ((rc = checkpoint())) return fail(ctx, "tb_state_save", rc);
+            if ((rc = curvePoint(done))) return fail(ctx, "tb_compare", rc);
             if (live == 0) break;
         }
     }
@@ -536,6 +650,19 @@ int main(int argc, char** argv)
         if ((rc = tb_denoise(ctx, &dn, denoised.empty() ? nullptr : denoised.data()))) return fail(ctx, "tb_denoise", rc);
         printf("denoise: %u a-trous passes, %.3f ms on the GPU\n", dn.WaveletIterations, (double)tb_get_option(ctx, "last_denoise_us") / 1e3);
         if ((png || upW || !neuralUp.empty()) && (rc = tb_set_option(ctx, "post_denoised", 1))) return fail(ctx, "tb_set_option", rc);
+    }
+    if (!reference.empty()) { /* the final lines; the error map is that of the last one */
+        std::vector<float> sq(errorMap.empty() ? 0 : (size_t)W * H);
+        const bool meanMap = !denoise && !sq.empty(), meanLine = lastLineFrames != (long long)spp;
+        if ((meanLine || meanMap) && (rc = metricsLine(TB_COMPARE_MEAN, spp, meanMap ? sq.data() : nullptr, meanLine))) return fail(ctx, "tb_compare", rc);
+        if (denoise && (rc = metricsLine(TB_COMPARE_DENOISED, spp, sq.empty() ? nullptr : sq.data(), true))) return fail(ctx, "tb_compare", rc);
+        if (metricsFile && fclose(metricsFile)) { perror("tracerboy-hip: --metrics-out"); tb_destroy(ctx); return 1; }
+        metricsFile = nullptr;
+        if (!sq.empty()) {
+            std::vector<float> grey((size_t)W * H * 4);
+            for (size_t i = 0; i < sq.size(); i++) { grey[4 * i] = grey[4 * i + 1] = grey[4 * i + 2] = sq[i]; grey[4 * i + 3] = 1.0f; }
+            if ((rc = tb_write_image_f32(errorMap.c_str(), W, H, grey.data()))) return fail(ctx, "tb_write_image_f32 (--error-map)", rc);
+        }
     }
     if (!neural.empty()) { /* the output stage, then the network; after --save-state: a state is the raw accumulation */
         if ((rc = tb_neural_load(ctx, neural.c_str()))) return fail(ctx, "tb_neural_load", rc);

@@ -14,6 +14,7 @@
  *   context_neural.cpp  the neural still denoiser: the OIDN U-Net on the matrix cores, its layer seam and its stage
  *   context_sr.cpp      the neural 2 x super-resolution: the reference's DirectML network on the matrix cores, its seams and its stage
  *   context_budget.cpp  sample budgets: set / read, the noise target that stops converged pixels, its kernel seam
+ *   context_compare.cpp image-quality metrics against a reference image: the kernel seam, the reference, the stage
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -219,6 +220,10 @@ struct tb_context {
         bool loaded = false; uint32_t in[7] = {}, out[7] = {}, kernel[7] = {};
         DevBuf weight[7], bias[7];
     } sr;
+    /* image-quality metrics (context_compare.cpp).  reference: the picture tb_set_reference uploaded, refW x refH (0: none);
+     * scratch: the workgroups' records and the result (cmp_launch.h); sqErr, ssim: the two maps, held once a call has asked for them and while
+     * the size holds.  ev: around the kernels of a tb_compare (tb_compare_result::gpu_us) */
+    struct Compare { DevBuf reference, scratch, sqErr, ssim; uint32_t refW = 0, refH = 0; tbctx::DevEvent ev[2]; } cmp;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
