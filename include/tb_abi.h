@@ -138,6 +138,29 @@ TB_STATIC_ASSERT(sizeof(TbFsrConstants) == 80, "FSR constants are 20 dwords");
 #define TB_FSR_SURFACE_UNORM8 0u /* R8G8B8A8_UNORM in, between the passes and out: the reference's chain */
 #define TB_FSR_SURFACE_F32 1u    /* RGBA32F throughout, alpha 1, no clamp, no quantisation */
 
+/* ---- the ray visualiser -----------------------------------------------
+ * A record of the reference's ray buffer, VisualizationRaysCommon.h: the buffer is a 4-byte count, then up to MAX_VISUALIZER_RAYS records.
+ * HitT: the hit distance, -1 for a miss; BounceCount: (float)bounce of the closest-hit ray (negative would be a feeler: none is recorded). */
+#define TB_MAX_VISUALIZER_RAYS 1024u
+typedef struct TbVisualizerRay { float Origin[3], Direction[3], HitT, BounceCount; } TbVisualizerRay;
+TB_STATIC_ASSERT(sizeof(TbVisualizerRay) == 32, "a visualiser ray is 8 dwords");
+/* One frame of a recorded pixel (tb_record_paths): what the render adds to the output surface for that sample; the frame; where its rays lie in the
+ * ray buffer (0xffffffff: none was stored) and how many the path produced; TB_PATH_* flags. */
+typedef struct TbPathFrame { float sum[4]; uint32_t frame, first_ray, num_rays, flags; } TbPathFrame;
+TB_STATIC_ASSERT(sizeof(TbPathFrame) == 32, "a path frame is 8 dwords");
+#define TB_PATH_JITTERED 1u   /* the sample also went to the jittered surface (frame 0, or the coin below 0.5) */
+#define TB_PATH_REJECTED 2u   /* the NaN filter rejected it: sum is zeros */
+#define TB_PATH_TRUNCATED 4u  /* not all of its rays were stored: the buffer was full */
+/* VisualizationRaysConstants, VisualizeRaysSharedShaderStructs.h:6-23 (20 dwords, float3 + scalar rows) */
+typedef struct TbVisualizeConstants {
+    uint32_t ResolutionX, ResolutionY; float CylinderRadius, FocalLength;
+    float CameraPosition[3]; float LensHeight;
+    float CameraLookAt[3]; float RayDepth;
+    float CameraRight[3]; float Padding2;
+    float CameraUp[3]; int32_t RayCount;
+} TbVisualizeConstants;
+TB_STATIC_ASSERT(sizeof(TbVisualizeConstants) == 80, "VisualizationRaysConstants is 20 dwords");
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

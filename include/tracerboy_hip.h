@@ -524,6 +524,53 @@ int tb_run_fsr_rcas(tb_context* ctx, const TbFsrConstants* constants, uint32_t s
 int tb_upscale(tb_context* ctx, const tb_post_settings* post, uint32_t output_type, uint32_t out_w, uint32_t out_h, float sharpness_stops,
                float* rgba_f32_or_null, uint8_t* rgba8_or_null);
 
+/* ---- the path inspector --------------------------------------------------------
+ * <-> the reference's ray visualiser: TracerBoy::SelectPixel arms a buffer of MAX_VISUALIZER_RAYS rays, the path tracer appends the selected
+ * pixel's bounce rays to it (RayGenCommon.h:600-630, kernel.glsl:1337-1351) and VisualizeRaysCS.hlsl draws them over the post-processed picture
+ * (m_bVisualizeRays, TracerBoy.cpp:3201-3244).  Here nothing is recorded while rendering: a sample's seed depends on (x, y, frame) alone, so
+ * tb_record_paths traces the complete paths of pixel (x, y) again for the frames [first_frame, first_frame + n_frames), 1 <= n_frames <= 4096,
+ * with the context's current size, settings, time seed, camera and option "alpha_test" (what tb_render_guides uses; any frame range, rendered or
+ * not; adaptive retirement and budgets are ignored).  Synchronous.  It writes nothing of the context but the ray buffer: tb_accum_digest, AOVs,
+ * guides, frame counter and history are what they were.
+ *   The ray buffer (tb_abi.h TbVisualizerRay; a count and up to TB_MAX_VISUALIZER_RAYS records): the closest-hit ray of every bounce i > 0 that
+ *   the throughput early-out (kernel.glsl:1319-1326) did not end first -- origin, direction, HitT (the hit distance, -1 for a miss), BounceCount =
+ *   (float)i.  The primary ray, feelers and interior-walk steps are not recorded.  Order: frame ascending, then bounce ascending, whatever the
+ *   scheduling.  Calls append; when the buffer is full further rays are dropped and the count stays at the cap (the reference's counter runs on
+ *   past the end).  rays_total_or_null: the rays this call would have stored without the cap.  tb_clear_paths empties the buffer, and so does
+ *   whatever resets the history (tb_set_camera, a scene load, a resize, a change of history-relevant settings or time seed ...; the reference clears
+ *   on a camera move, TracerBoy.cpp:2771).  tb_read_paths: the count, and min(capacity, count) records where rays_or_null is given.
+ *   frames_or_null: n_frames records (TbPathFrame) for the caller, not kept.  sum: exactly what the render adds to the output surface for that
+ *   sample -- colour after the firefly clamp times the filter weight, then the weight; zeros where the NaN filter rejected it (TB_PATH_REJECTED).
+ *   TB_PATH_JITTERED: it also went to the jittered surface.  first_ray: where the frame's rays begin in the buffer, 0xffffffff when none was stored;
+ *   num_rays: the rays its path produced; TB_PATH_TRUNCATED: the buffer held fewer of them.  Summed in frame order from frame 0 in fp32
+ *   (acc = sum + acc) the records give the output surface's pixel, the flagged ones the jittered surface's, bit for bit.
+ * TB_E_INVALID (the message names the cause): no scene; no size yet; the last render was tb_render_realtime; n_frames out of range; a pixel
+ * outside the frame.  TB_E_UNSUPPORTED: a tb_create_multi group; a tile assignment with world > 1; a traversal stack that does not fit LDS.
+ *
+ * tb_visualize_rays: the overlay.  Needs a tb_post_process result in the context (TB_E_INVALID otherwise) and draws the stored rays over its float
+ * picture into surfaces of its own -- the post output is not modified, a second call does not draw twice; the 8-bit picture is the output stage's
+ * R8G8B8A8_UNORM store of the float one.  Settings (tb_default_visualize_settings: TracerBoy.h:303-306): RayWidth 0.01 the cylinders' radius,
+ * RayDepth 10 -- rays of a bounce above it are skipped, the last one below it is drawn at the fraction RayDepth - bounce of its length --, RayCount 0
+ * = all (the first RayCount rays of the buffer otherwise).  A ray is hidden where the pixel's world position (any |xyz| > 0.0001) is nearer.  That
+ * position comes from TB_AOV_WORLD_POSITION0 + L % 2 of the last frame L where the render had option "aov", else from the guide pass's mean
+ * (position sum / frames that hit, where any hit) while the guides are valid, else there is none and every ray draws on top; tb_get_option
+ * "visualize_depth_source" says which applied to the last call: 1, 2 or 0.  Per pixel: VisualizeRaysCS.hlsl:133-226 in IEEE fp32, unfused, dot =
+ * (x x' + y y') + z z', normalize = v / sqrt(dot), lerp = a + s (b - a); the reference's divisions by zero are kept (tests/visualize_ref.py is the
+ * numpy restatement).  TB_E_UNSUPPORTED: a group, a tile assignment with world > 1.
+ * tb_visualize_constants: host only, no context: VisualizationRaysConstants as TracerBoy.cpp:3216-3228 fills them (RayCount 0 -> 999999).
+ * tb_run_visualize_rays: the kernel seam, like tb_run_fsr_easu: host arrays (rays: n_rays <= TB_MAX_VISUALIZER_RAYS records; scene_rgba, out_rgba and
+ * world_pos_or_null: ResolutionX * ResolutionY * 4 floats, row 0 = top, of the position .xyz is read), temporary buffers, nothing of the context.
+ * tb_get_option "last_paths_us" / "last_visualize_us": GPU microseconds of the last tb_record_paths / tb_visualize_rays (HIP events). */
+typedef struct tb_visualize_settings { float RayWidth, RayDepth; int32_t RayCount; } tb_visualize_settings;
+void tb_default_visualize_settings(tb_visualize_settings* out);
+int tb_record_paths(tb_context* ctx, uint32_t x, uint32_t y, uint32_t first_frame, uint32_t n_frames, TbPathFrame* frames_or_null, uint32_t* rays_total_or_null);
+int tb_clear_paths(tb_context* ctx);
+int tb_read_paths(tb_context* ctx, TbVisualizerRay* rays_or_null, uint32_t capacity, uint32_t* count);
+int tb_visualize_rays(tb_context* ctx, const tb_visualize_settings* settings_or_null, float* rgba_f32_or_null, uint8_t* rgba8_or_null);
+int tb_visualize_constants(const tb_camera* camera, uint32_t width, uint32_t height, const tb_visualize_settings* settings_or_null, TbVisualizeConstants* out);
+int tb_run_visualize_rays(tb_context* ctx, const TbVisualizeConstants* constants, const TbVisualizerRay* rays, uint32_t n_rays, const float* scene_rgba,
+                          const float* world_pos_or_null, float* out_rgba);
+
 /* ---- neural still denoiser -----------------------------------------------------
  * <-> the reference's TAAUpscaler::OIDN path (TracerBoy.cpp:3306-3322; OpenImageDenoise.cpp:855-1039): the OIDN U-Net -- 16 convolutions of 3 x 3,
  * four 2 x 2 max-pools on the way down, four nearest upsamples x 2 on the way up, each concatenated in front of the skip tensor of its size, ReLU

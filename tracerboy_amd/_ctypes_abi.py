@@ -160,6 +160,33 @@ TB_FSR_SURFACE_UNORM8 = 0
 TB_FSR_SURFACE_F32 = 1
 
 
+# the path inspector (include/tb_abi.h)
+TB_MAX_VISUALIZER_RAYS = 1024
+TB_PATH_JITTERED, TB_PATH_REJECTED, TB_PATH_TRUNCATED = 1, 2, 4
+
+
+class TbVisualizerRay(C.Structure):
+    """A record of the reference's ray buffer (VisualizationRaysCommon.h)."""
+    _fields_ = [("Origin", C.c_float * 3), ("Direction", C.c_float * 3), ("HitT", C.c_float), ("BounceCount", C.c_float)]
+
+
+class TbPathFrame(C.Structure):
+    """One frame of a recorded pixel (tb_record_paths)."""
+    _fields_ = [("sum", C.c_float * 4), ("frame", C.c_uint32), ("first_ray", C.c_uint32), ("num_rays", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class TbVisualizeConstants(C.Structure):
+    """VisualizationRaysConstants (VisualizeRaysSharedShaderStructs.h)."""
+    _fields_ = [("ResolutionX", C.c_uint32), ("ResolutionY", C.c_uint32), ("CylinderRadius", C.c_float), ("FocalLength", C.c_float),
+                ("CameraPosition", C.c_float * 3), ("LensHeight", C.c_float), ("CameraLookAt", C.c_float * 3), ("RayDepth", C.c_float),
+                ("CameraRight", C.c_float * 3), ("Padding2", C.c_float), ("CameraUp", C.c_float * 3), ("RayCount", C.c_int32)]
+
+
+class tb_visualize_settings(C.Structure):
+    """include/tracerboy_hip.h tb_visualize_settings: m_VisualizeRayWidth / m_VisualizeRayDepth / m_VisualizeRayCount (TracerBoy.h:303-306)."""
+    _fields_ = [("RayWidth", C.c_float), ("RayDepth", C.c_float), ("RayCount", C.c_int32)]
+
+
 class tb_nn_info(C.Structure):
     """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
     _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]
@@ -258,6 +285,8 @@ assert C.sizeof(TbPostConstants) == 36
 assert C.sizeof(TbTemporalConstants) == 144
 assert C.sizeof(TbDenoiserConstants) == 28
 assert C.sizeof(TbFsrConstants) == 80
+assert C.sizeof(TbVisualizerRay) == 32 and C.sizeof(TbVisualizeConstants) == 80 and C.sizeof(TbPathFrame) == 32
+assert C.sizeof(tb_visualize_settings) == 12
 assert C.sizeof(tb_compare_settings) == 12 and C.sizeof(tb_compare_result) == 96
 assert C.sizeof(TbPerFrameConstants) == 148
 assert C.sizeof(TbConfigConstants) == 76

@@ -110,6 +110,13 @@ def lib():
         "tb_run_fsr_easu": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 5 + [vp, vp]),
         "tb_run_fsr_rcas": (C.c_int, [vp, P(abi.TbFsrConstants)] + [C.c_uint32] * 3 + [vp, vp]),
         "tb_upscale": (C.c_int, [vp, P(abi.tb_post_settings), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp]),
+        "tb_default_visualize_settings": (None, [P(abi.tb_visualize_settings)]),
+        "tb_record_paths": (C.c_int, [vp] + [C.c_uint32] * 4 + [vp, P(C.c_uint32)]),
+        "tb_clear_paths": (C.c_int, [vp]),
+        "tb_read_paths": (C.c_int, [vp, vp, C.c_uint32, P(C.c_uint32)]),
+        "tb_visualize_rays": (C.c_int, [vp, P(abi.tb_visualize_settings), vp, vp]),
+        "tb_visualize_constants": (C.c_int, [P(abi.tb_camera), C.c_uint32, C.c_uint32, P(abi.tb_visualize_settings), P(abi.TbVisualizeConstants)]),
+        "tb_run_visualize_rays": (C.c_int, [vp, P(abi.TbVisualizeConstants), vp, C.c_uint32, vp, vp, vp]),
         "tb_default_compare_settings": (None, [P(abi.tb_compare_settings)]),
         "tb_run_compare": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, P(abi.tb_compare_settings), P(abi.tb_compare_result), vp, vp]),
         "tb_set_reference": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -207,6 +214,28 @@ def FsrConstants(in_width, in_height, out_width, out_height, sharpness=0.2):
     if rc != 0:
         raise TracerBoyError(rc, "tb_fsr_constants: a size is 0 or the sharpness is not finite")
     return k
+
+
+def GetDefaultVisualizeSettings():
+    """GetDefaultOutputSettings().m_debugSettings' ray visualiser part (TracerBoy.h:303-306): RayWidth 0.01, RayDepth 10, RayCount 0 = all."""
+    s = abi.tb_visualize_settings()
+    lib().tb_default_visualize_settings(C.byref(s))
+    return s
+
+
+def VisualizeConstants(camera, width, height, settings=None):
+    """VisualizationRaysConstants as the library fills them for a camera, a picture size and settings (tb_visualize_constants; host only, no device)."""
+    k = abi.TbVisualizeConstants()
+    rc = lib().tb_visualize_constants(C.byref(camera), width, height, C.byref(settings) if settings is not None else None, C.byref(k))
+    if rc != 0:
+        raise TracerBoyError(rc, "tb_visualize_constants: a size is 0")
+    return k
+
+
+# the records of the path inspector as numpy sees them (the layouts of TbPathFrame and TbVisualizerRay)
+PATH_FRAME_DTYPE = np.dtype([("sum", np.float32, 4), ("frame", np.uint32), ("first_ray", np.uint32), ("num_rays", np.uint32), ("flags", np.uint32)])
+VISUALIZER_RAY_DTYPE = np.dtype([("Origin", np.float32, 3), ("Direction", np.float32, 3), ("HitT", np.float32), ("BounceCount", np.float32)])
+assert PATH_FRAME_DTYPE.itemsize == 32 and VISUALIZER_RAY_DTYPE.itemsize == 32
 
 
 NEURAL_LAYERS = ("enc_conv0", "enc_conv1", "enc_conv2", "enc_conv3", "enc_conv4", "enc_conv5a", "enc_conv5b", "dec_conv4a", "dec_conv4b", "dec_conv3a",
@@ -688,6 +717,46 @@ class TracerBoy:
         positions, sum of neighbour distances): (H, W, 4) float32."""
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._L.tb_read_guide(self._ctx, which, _np_ptr(out)))
+        return out
+
+    # -- the path inspector (DESIGN.md section 19) ------------------------------------------------
+    def RecordPaths(self, x, y, first_frame, n_frames):
+        """The complete paths of pixel (x, y) traced again for frames [first_frame, first_frame + n_frames) (tb_record_paths): their bounce rays are
+        appended to the ray buffer.  Returns (frames, rays_total): a structured array (PATH_FRAME_DTYPE) with one record per frame -- what the
+        render adds to the output surface for that sample, where its rays lie, flags -- and the rays the call would have stored without the cap."""
+        frames, total = np.zeros(n_frames, PATH_FRAME_DTYPE), C.c_uint32(0)
+        self._check(self._L.tb_record_paths(self._ctx, x, y, first_frame, n_frames, _np_ptr(frames), C.byref(total)))
+        return frames, int(total.value)
+
+    def ReadPaths(self):
+        """The ray buffer (tb_read_paths): a structured array (VISUALIZER_RAY_DTYPE) of the stored rays, frame by frame, bounce by bounce."""
+        n = C.c_uint32(0)
+        self._check(self._L.tb_read_paths(self._ctx, None, 0, C.byref(n)))
+        rays = np.zeros(n.value, VISUALIZER_RAY_DTYPE)
+        if n.value:
+            self._check(self._L.tb_read_paths(self._ctx, _np_ptr(rays), n.value, C.byref(n)))
+        return rays
+
+    def ClearPaths(self):
+        self._check(self._L.tb_clear_paths(self._ctx))
+
+    def VisualizeRays(self, settings=None, rgba8=True):
+        """The stored rays drawn over the float picture of the last PostProcess (tb_visualize_rays, VisualizeRaysCS.hlsl): returns (float32 HxWx4
+        image, uint8 HxWx4 image or None).  The post output itself is not modified."""
+        f = np.empty((self.height, self.width, 4), np.float32)
+        b = np.empty((self.height, self.width, 4), np.uint8) if rgba8 else None
+        self._check(self._L.tb_visualize_rays(self._ctx, C.byref(settings) if settings is not None else None, _np_ptr(f), _np_ptr(b) if rgba8 else None))
+        return f, b
+
+    def RunVisualizeRays(self, constants, rays, scene, world_pos=None):
+        """vis_overlay on host arrays (tb_run_visualize_rays): rays a VISUALIZER_RAY_DTYPE array (or (n, 8) float32), scene and world_pos (H, W, 4)
+        float32 with H, W from the constants; nothing of the context read or written."""
+        r = np.ascontiguousarray(rays); s = np.ascontiguousarray(scene, np.float32)
+        w = None if world_pos is None else np.ascontiguousarray(world_pos, np.float32)
+        assert r.nbytes % 32 == 0 and s.shape == (constants.ResolutionY, constants.ResolutionX, 4) and (w is None or w.shape == s.shape)
+        out = np.empty_like(s)
+        self._check(self._L.tb_run_visualize_rays(self._ctx, C.byref(constants), _np_ptr(r) if r.nbytes else None, r.nbytes // 32, _np_ptr(s),
+                                                  _np_ptr(w) if w is not None else None, _np_ptr(out)))
         return out
 
     def PostProcess(self, postSettings=None, outputType=0, rgba8=True):

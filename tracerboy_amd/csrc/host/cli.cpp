@@ -10,6 +10,7 @@
  *                 [--upscale-neural FILE.bin]
  *                 [--crop X0,Y0,X1,Y1] [--spp-map FILE] [--noise-target T [--noise-after F] [--noise-chunk C]]
  *                 [--reference FILE [--metrics-out FILE] [--metrics-every N] [--error-map FILE.pfm]]
+ *                 [--visualize-rays X,Y [--visualize-frames A:B] [--visualize-width R] [--visualize-depth D] [--visualize-count N] [--paths-out FILE.jsonl]]
  *   tracerboy-hip --compare A B [--metrics-out FILE] [--device I]
  * Uses only the C ABI (include/tracerboy_hip.h), the way an embedding application would.
  *
@@ -111,7 +112,23 @@
  * "files") goes to standard output or to --metrics-out.  No scene, no render.
  * Exit status 2, before any device call: a reference or a file of --compare that cannot be read, A and B of different sizes, N below 1, an
  * --error-map that is no .pfm, a flag without --reference; a reference of another size than the render likewise where --width and --height are
- * given, otherwise as soon as the scene (or the state) has told the frame's size. */
+ * given, otherwise as soon as the scene (or the state) has told the frame's size.
+ *
+ * The path inspector (tb_record_paths / tb_visualize_rays): --visualize-rays X,Y draws the paths of pixel (X, Y) over the
+ * picture, as the reference does for the pixel SelectPixel names while m_bVisualizeRays is on.  After the render: where it ran without AOVs (no
+ * --denoise) a one-frame guide pass of the last frame supplies the world positions that hide rays behind surfaces (with --denoise-guides K the
+ * mean positions of its K frames do, with --denoise the last frame's AOV); the pixel's paths are traced
+ * again for the frames A:B of --visualize-frames (half-open, any range), by default the last min(64, frames held); the output stage runs; the overlay
+ * runs; --out is written from the overlay: .png its 8-bit picture, .pfm / .exr the float one -- the POST-PROCESSED picture, as with --upscale.
+ * --visualize-width R: the cylinders' radius in world units (m_VisualizeRayWidth, default 0.01); --visualize-depth D: bounces above D are not drawn,
+ * the last one below is drawn at the fraction D - bounce of its length (m_VisualizeRayDepth, default 10); --visualize-count N: only the first N
+ * stored rays (m_VisualizeRayCount, default 0 = all; the buffer holds 1024).  --paths-out FILE.jsonl: one JSON object per recorded frame, on a line
+ * of its own: "frame", "sum" (what the render adds to the output surface for that sample: r g b weight), "flags" (1 also on the jittered surface,
+ * 2 rejected by the NaN filter, 4 not all rays stored), "num_rays" and "rays", the stored ones: "origin", "direction", "hit_t" (-1: a miss),
+ * "bounce"; a value that is not finite is null.  With --denoise the denoised picture is what the rays are drawn over.
+ * Exit status 2, before any device call: a malformed X,Y or A:B, R not finite or not above 0, D not finite, N negative, one of the other five
+ * without --visualize-rays, any of them with --ranks N > 1, --upscale, --render-scale, --upscale-neural or --denoise-neural; a pixel outside the
+ * frame likewise where --width and --height are given, otherwise as soon as the scene (or the state) has told the frame's size. */
 #include "../../../include/tracerboy_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -261,7 +278,7 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C --reference FILE --metrics-out FILE --metrics-every N --error-map f.pfm]\n       tracerboy-hip --compare A B [--metrics-out FILE --device I]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C --reference FILE --metrics-out FILE --metrics-every N --error-map f.pfm --visualize-rays X,Y --visualize-frames A:B --visualize-width R --visualize-depth D --visualize-count N --paths-out f.jsonl]\n       tracerboy-hip --compare A B [--metrics-out FILE --device I]\n"); return 2; }
     if (!strcmp(argv[1], "--compare")) return compareFiles(argc, argv);
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
@@ -273,6 +290,8 @@ int main(int argc, char** argv)
     long long crop[4] = {0, 0, 0, 0}; bool cropSet = false; std::string sppMap; float noiseTarget = 0.0f; bool noiseSet = false;
     long long noiseAfter = 64, noiseChunk = 64;
     std::string reference, metricsOut, errorMap; long long metricsEvery = 0; bool metricsEverySet = false;
+    bool visSet = false, visOther = false; long long visX = 0, visY = 0, visA = -1, visB = -1; std::string pathsOut; /* the path inspector */
+    tb_visualize_settings vis; tb_default_visualize_settings(&vis);
     uint32_t upW = 0, upH = 0; float renderScale = 0.0f, fsrSharpness = -1.0f; bool upscaleSet = false, renderScaleSet = false, sharpnessSet = false;
     for (int i = 2; i < argc; i += 2) {
         std::string k = argv[i];
@@ -317,6 +336,21 @@ int main(int argc, char** argv)
         else if (k == "--reference") reference = v; else if (k == "--metrics-out") metricsOut = v; else if (k == "--error-map") errorMap = v;
         else if (k == "--metrics-every") { metricsEvery = atoll(v); metricsEverySet = true; }
         else if (k == "--upscale-neural") neuralUp = v;
+        else if (k == "--visualize-rays") { char* end = nullptr; visX = strtoll(v, &end, 10); const char* second = end != v && *end == ',' ? end + 1 : nullptr;
+            if (second) visY = strtoll(second, &end, 10);
+            if (!second || end == second || *end || visX < 0 || visY < 0 || visX >= 16384 || visY >= 16384) { fprintf(stderr, "--visualize-rays is X,Y: a pixel of the frame\n"); return 2; }
+            visSet = true; }
+        else if (k == "--visualize-frames") { char* end = nullptr; visA = strtoll(v, &end, 10); visB = end && end != v && *end == ':' ? strtoll(end + 1, &end, 10) : -1;
+            visOther = true;
+            if (visA < 0 || visB <= visA || visB > 0xffffffffll || !end || *end) { fprintf(stderr, "--visualize-frames is A:B with 0 <= A < B\n"); return 2; } }
+        else if (k == "--visualize-width") { char* end = nullptr; vis.RayWidth = strtof(v, &end); visOther = true;
+            if (end == v || *end || !(vis.RayWidth > 0.0f) || !(vis.RayWidth < 3.0e38f)) { fprintf(stderr, "--visualize-width is a finite radius above 0\n"); return 2; } }
+        else if (k == "--visualize-depth") { char* end = nullptr; vis.RayDepth = strtof(v, &end); visOther = true;
+            if (end == v || *end || !(vis.RayDepth - vis.RayDepth == 0.0f)) { fprintf(stderr, "--visualize-depth is a finite number of bounces\n"); return 2; } }
+        else if (k == "--visualize-count") { char* end = nullptr; const long long n = strtoll(v, &end, 10); visOther = true;
+            if (end == v || *end || n < 0 || n > 0x7fffffffll) { fprintf(stderr, "--visualize-count is 0 (all) or a number of rays\n"); return 2; }
+            vis.RayCount = (int32_t)n; }
+        else if (k == "--paths-out") { pathsOut = v; visOther = true; }
         else if (k == "--tonemap") post.TonemapType = (uint32_t)atoi(v);
         else if (k == "--exposure") { if (!strcmp(v, "auto")) post.EnableAutoExposure = 1; else { post.EnableAutoExposure = 0;
             post.ExposureMultiplier = (float)atof(v); } }
@@ -357,6 +391,18 @@ int main(int argc, char** argv)
         tb_sr_info sr; char err[512] = "";
         if (tb_sr_weights_info(neuralUp.c_str(), &sr, err, sizeof err)) { fprintf(stderr, "--upscale-neural %s: %s\n", neuralUp.c_str(), err); return 2; }
     }
+    /* the path inspector */
+    if (visOther && !visSet) { fprintf(stderr,
+        "--visualize-frames, --visualize-width, --visualize-depth, --visualize-count and --paths-out need --visualize-rays X,Y: the pixel whose paths are drawn\n"); return 2; }
+    if (visSet && (ranks > 1 || upscaleSet || renderScaleSet || !neuralUp.empty() || !neural.empty())) { fprintf(stderr,
+        "--visualize-rays does not go with --ranks, --upscale, --render-scale, --upscale-neural or --denoise-neural: the rays are drawn over the output stage's picture of one device\n");
+        return 2; }
+    auto pixelFits = [&](uint32_t fw, uint32_t fh) {
+        if (visSet && (visX >= (long long)fw || visY >= (long long)fh)) {
+            fprintf(stderr, "--visualize-rays %lld,%lld lies outside the %ux%u frame\n", visX, visY, fw, fh); return false; }
+        return true;
+    };
+    if (W && H && resume.empty() && !pixelFits(W, H)) return 2;
     /* image-quality metrics */
     if (reference.empty() && (!metricsOut.empty() || metricsEverySet || !errorMap.empty())) { fprintf(stderr,
         "--metrics-out, --metrics-every and --error-map need --reference FILE: the metrics are those against a reference picture\n"); return 2; }
@@ -477,6 +523,7 @@ int main(int argc, char** argv)
     if (!neuralUp.empty() && (uint64_t)W * H * 4u > (1ull << 24)) { /* likewise */
         fprintf(stderr, "tracerboy-hip: cannot upscale the %ux%u render to twice that: more than 2^24 pixels\n", W, H); tb_destroy(ctx); return 2; }
     if (!referenceFits(W, H)) { tb_destroy(ctx); return 2; }
+    if (!pixelFits(W, H)) { tb_destroy(ctx); return 2; }
     if (!reference.empty() && (rc = tb_set_reference(ctx, W, H, refRgba.data()))) return fail(ctx, "tb_set_reference", rc);
     /* a line of metrics: to --metrics-out, else to standard output.  lastLineFrames: the frame count of the last "mean" line */
     FILE* metricsFile = nullptr; /* opened at the first line: with --ranks only rank 0 writes one */
@@ -664,7 +711,55 @@ int main(int argc, char** argv)
             if ((rc = tb_write_image_f32(errorMap.c_str(), W, H, grey.data()))) return fail(ctx, "tb_write_image_f32 (--error-map)", rc);
         }
     }
-    if (!neural.empty()) { /* the output stage, then the network; after --save-state: a state is the raw accumulation */
+    if (visSet) { /* the occluder, the paths, the output stage, the overlay */
+        const uint32_t next = tb_samples_rendered(ctx), first = (uint32_t)tb_get_option(ctx, "state_first_frame");
+        if (!denoise && next > first) { /* the render ran without AOVs: the last frame's first hits, traced again */
+            if ((rc = tb_render_guides(ctx, next - 1u, 1u))) return fail(ctx, "tb_render_guides", rc);
+        }
+        uint32_t recA = (uint32_t)visA, recB = (uint32_t)visB;
+        if (visA < 0) { recB = next; recA = next - std::min<uint32_t>(64u, next - first); }
+        FILE* pathsFile = nullptr;
+        if (!pathsOut.empty() && !(pathsFile = fopen(pathsOut.c_str(), "w"))) { perror("tracerboy-hip: --paths-out"); tb_destroy(ctx); return 1; }
+        uint64_t raysTotal = 0; double pathsMs = 0.0;
+        std::vector<TbPathFrame> frames; std::vector<TbVisualizerRay> rays;
+        for (uint32_t f = recA; f < recB; ) { /* a call records at most 4096 frames */
+            const uint32_t n = std::min<uint32_t>(4096u, recB - f);
+            uint32_t total = 0, count = 0;
+            frames.resize(n);
+            if ((rc = tb_record_paths(ctx, (uint32_t)visX, (uint32_t)visY, f, n, frames.data(), &total))) return fail(ctx, "tb_record_paths", rc);
+            raysTotal += total; pathsMs += (double)tb_get_option(ctx, "last_paths_us") / 1e3;
+            if (pathsFile) {
+                rays.resize(TB_MAX_VISUALIZER_RAYS);
+                if ((rc = tb_read_paths(ctx, rays.data(), TB_MAX_VISUALIZER_RAYS, &count))) return fail(ctx, "tb_read_paths", rc);
+                for (const TbPathFrame& fr : frames) {
+                    std::string line = "{\"frame\": " + std::to_string(fr.frame) + ", \"sum\": [" + jsonNumber(fr.sum[0]) + ", " + jsonNumber(fr.sum[1]) + ", " +
+                        jsonNumber(fr.sum[2]) + ", " + jsonNumber(fr.sum[3]) + "], \"flags\": " + std::to_string(fr.flags) + ", \"num_rays\": " +
+                        std::to_string(fr.num_rays) + ", \"rays\": [";
+                    const uint32_t stored = fr.first_ray == 0xffffffffu ? 0u : std::min<uint32_t>(fr.num_rays, count - std::min(count, fr.first_ray));
+                    for (uint32_t i = 0; i < stored; i++) {
+                        const TbVisualizerRay& r = rays[fr.first_ray + i];
+                        line += std::string(i ? ", " : "") + "{\"origin\": [" + jsonNumber(r.Origin[0]) + ", " + jsonNumber(r.Origin[1]) + ", " + jsonNumber(r.Origin[2]) +
+                            "], \"direction\": [" + jsonNumber(r.Direction[0]) + ", " + jsonNumber(r.Direction[1]) + ", " + jsonNumber(r.Direction[2]) + "], \"hit_t\": " +
+                            jsonNumber(r.HitT) + ", \"bounce\": " + jsonNumber(r.BounceCount) + "}";
+                    }
+                    fprintf(pathsFile, "%s]}\n", line.c_str());
+                }
+            }
+            f += n;
+        }
+        if (pathsFile && fclose(pathsFile)) { perror("tracerboy-hip: --paths-out"); tb_destroy(ctx); return 1; }
+        uint32_t held = 0;
+        if ((rc = tb_read_paths(ctx, nullptr, 0, &held))) return fail(ctx, "tb_read_paths", rc);
+        printf("paths: pixel (%lld, %lld), frames [%u, %u): %llu rays, %u stored, %.3f ms on the GPU\n", visX, visY, recA, recB, (unsigned long long)raysTotal,
+               held, pathsMs);
+        if ((rc = tb_post_process(ctx, &post, TB_OUTPUT_TYPE_LIT, nullptr, nullptr))) return fail(ctx, "tb_post_process", rc);
+        std::vector<uint8_t> img(png ? (size_t)W * H * 4 : 0); std::vector<float> imgF(png ? 0 : (size_t)W * H * 4);
+        if ((rc = tb_visualize_rays(ctx, &vis, png ? nullptr : imgF.data(), png ? img.data() : nullptr))) return fail(ctx, "tb_visualize_rays", rc);
+        printf("visualize: depth source %lld, %.3f ms on the GPU\n", (long long)tb_get_option(ctx, "visualize_depth_source"),
+               (double)tb_get_option(ctx, "last_visualize_us") / 1e3);
+        if (png) { if ((rc = tb_write_image_rgba8(out.c_str(), W, H, img.data()))) return fail(ctx, "tb_write_image_rgba8", rc); }
+        else if ((rc = tb_write_image_f32(out.c_str(), W, H, imgF.data()))) return fail(ctx, "tb_write_image_f32 (use .png, .pfm or .exr)", rc);
+    } else if (!neural.empty()) { /* the output stage, then the network; after --save-state: a state is the raw accumulation */
         if ((rc = tb_neural_load(ctx, neural.c_str()))) return fail(ctx, "tb_neural_load", rc);
         if (denoiseGuides) { /* the last min(K, frames held) frames of the state's range, traced again */
             const uint32_t next = tb_samples_rendered(ctx), first = (uint32_t)tb_get_option(ctx, "state_first_frame");

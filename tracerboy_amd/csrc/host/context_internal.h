@@ -15,6 +15,7 @@
  *   context_sr.cpp      the neural 2 x super-resolution: the reference's DirectML network on the matrix cores, its seams and its stage
  *   context_budget.cpp  sample budgets: set / read, the noise target that stops converged pixels, its kernel seam
  *   context_compare.cpp image-quality metrics against a reference image: the kernel seam, the reference, the stage
+ *   context_visualize.cpp the path inspector: a pixel's paths recorded again, the ray buffer, the overlay and its kernel seam
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -224,6 +225,14 @@ struct tb_context {
      * scratch: the workgroups' records and the result (cmp_launch.h); sqErr, ssim: the two maps, held once a call has asked for them and while
      * the size holds.  ev: around the kernels of a tb_compare (tb_compare_result::gpu_us) */
     struct Compare { DevBuf reference, scratch, sqErr, ssim; uint32_t refW = 0, refH = 0; tbctx::DevEvent ev[2]; } cmp;
+    /* the path inspector (context_visualize.cpp).  rays: the reference's ray buffer behind 12 B of padding -- the count word,
+     * then at once the records, 16-B aligned; stored: the rays it holds, the host's count (resetHistory and tb_clear_paths zero it; the word on the
+     * device is rewritten by every tb_record_paths).  overflow: the recorder's half of a split stack.  out, out8: the overlay's two pictures;
+     * depthSource: option visualize_depth_source of the last overlay.  evPaths, evOverlay: around the kernels (last_paths_us, last_visualize_us) */
+    struct Visualize {
+        DevBuf rays, overflow, out, out8; uint32_t stored = 0; int depthSource = 0;
+        tbctx::DevEvent evPaths[2], evOverlay[2]; float lastPathsMs = 0.0f, lastOverlayMs = 0.0f;
+    } vis;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -266,7 +275,8 @@ namespace tbctx {
 
 int fail(tb_context* c, int code, const std::string& msg);
 /* forget the accumulated frames: the next render starts at frame 0 (where the kernels overwrite the surfaces instead of adding to them) */
-inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dn.valid = false; c->guides.valid = false; }
+/* (and the recorded paths: they were traced of the scene, camera, size and settings that have just changed) */
+inline void resetHistory(tb_context* c) { c->samplesRendered = 0; c->firstFrame = 0; c->dn.valid = false; c->guides.valid = false; c->vis.stored = 0; }
 /* the accumulation surfaces are about to change (a render, a state that is begun, loaded or added): the denoised surfaces no longer belong to them */
 inline void touchAccumulation(tb_context* c) { c->dn.valid = false; }
 /* an entry point that only a group's own context may be asked */

@@ -76,6 +76,10 @@ const Query kQueries[] = {
     Q("last_sr_us", microseconds(c->sr.lastMs)) Q("sr_loaded", c->sr.loaded ? 1 : 0) Q("sr_conv_form", opt<OPT_sr_conv_form>(c))
     Q("last_guides_us", microseconds(c->guides.lastMs)) /* the last tb_render_guides, its kernel alone (HIP events) */
     Q("last_guides_stack_overflow", c->guides.lastOverflow) /* stack entries per lane the last pass kept in global memory (the HYBRID form) */
+    /* the path inspector: the last tb_record_paths (both runs and the scan) and the last tb_visualize_rays (HIP events); where the last overlay took
+     * its occluder from: 1 the last frame's world-position AOV, 2 the guide pass's mean position, 0 nowhere */
+    Q("last_paths_us", microseconds(c->vis.lastPathsMs)) Q("last_visualize_us", microseconds(c->vis.lastOverlayMs))
+    Q("visualize_depth_source", c->vis.depthSource)
     Q("last_copy_waves", c->lastCopyWaves)
     Q("last_adaptive", c->lastAdaptive ? 1 : 0) /* the adaptive launch: did the last call run it */
     /* sample budgets: one is set; the last call was planned under it (its live pixels: last_live_pixels) */
