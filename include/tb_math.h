@@ -141,6 +141,55 @@ TB_HD float tb_cos(float x)
     return ((q + 1) & 2) ? -c : c;
 }
 
+/* Both values of one argument: one guard, one reduction and one pair of polynomials, then tb_sin's and tb_cos's own quadrant selects.  Each
+ * value is the sequence of operations of tb_sin(x) / tb_cos(x), so the bits are theirs (tests/shading/short_forms_driver.cpp). */
+TB_HD void tb_sincos(float x, float* s, float* c)
+{
+    if (!(tb_abs(x) < 1.0e9f)) { *s = *c = tb_u2f(0x7fc00000u); return; }
+    float r; int q;
+    tb_sincos_reduce(x, &r, &q);
+    const float sp = tb_sin_poly(r), cp = tb_cos_poly(r);
+    const float sv = (q & 1) ? cp : sp, cv = (q & 1) ? sp : cp;
+    *s = (q & 2) ? -sv : sv;
+    *c = ((q + 1) & 2) ? -cv : cv;
+}
+
+/* ---- x / PI without the division ----------------------------------------------------------
+ * x / TB_PI_F, correctly rounded, in three operations where they give it: the product with the binary32 nearest to 1 / PI, its residual (exact in
+ * the fma) and one correction.  A correctly rounded quotient is one value whatever computes it, and for this one denominator every numerator can
+ * be checked: tests/shading/short_forms_driver.cpp runs all 2^32 through tb_div_pi_fast and prints where its bits are the division's.  That is +0
+ * and the longest run of magnitudes right for both signs, 0x0b1ec7a1 (3.06e-32) to the largest finite number.  Below it right and wrong numerators
+ * alternate in 1.48 million shorter runs (the residual or the correction falls among the denormals and rounds once more), and -0 comes out as +0
+ * (its residual is +0).  inf gives NaN, and a NaN's payload is left to the division.  Every numerator outside takes the division. */
+#define TB_RCP_PI_F 0.318309886f /* 0x3ea2f983: the binary32 nearest to 1 / TB_PI_F */
+#define TB_DIV_PI_FAST_MIN_BITS 0x0b1ec7a1u
+#define TB_DIV_PI_FAST_MAX_BITS 0x7f7fffffu
+TB_HD float tb_div_pi_fast(float x) /* the three operations alone: the sweep's subject */
+{
+    const float q = x * TB_RCP_PI_F;
+    const float r = tb_fma(-TB_PI_F, q, x);
+    return tb_fma(r, TB_RCP_PI_F, q);
+}
+TB_HD bool tb_div_pi_is_fast(float x)
+{
+    const float a = tb_abs(x);
+    return (tb_f2u(x) == 0u) | ((a >= tb_u2f(TB_DIV_PI_FAST_MIN_BITS)) & (a <= tb_u2f(TB_DIV_PI_FAST_MAX_BITS))); /* no short circuit: three compares */
+}
+TB_HD float tb_div_pi(float x)
+{
+    if (tb_div_pi_is_fast(x)) return tb_div_pi_fast(x);
+    return x / TB_PI_F;
+}
+
+/* 0.0f / s for s a tb_sqrt result of a sum of squares -- +0, positive (denormal, normal, +inf) or NaN, never -0 and never negative -- without
+ * the division: +0 over a positive s, the invalid operation's NaN (sign bit set, on x86-64 and on gfx950) over +0, and a NaN s itself, which a
+ * square root returns quiet. */
+TB_HD float tb_zero_over_sqrt(float s)
+{
+    const float bad = (s == s) ? tb_u2f(0xffc00000u) : s;
+    return (s > 0.0f) ? 0.0f : bad;
+}
+
 /* ---- asin / acos (Cephes asinf/acosf) ---------------------------------------------------- */
 TB_HD float tb_asin_core(float a) /* 0 <= a <= 0.5 */
 {

@@ -895,15 +895,43 @@ TBD float ggx_ndf(tb3 N, tb3 H, float r2)
     float den = PI * tb_pow(nDotH * nDotH * (a2 - 1.0f) + 1.0f, 2.0f);
     return a2 / den;
 }
+/* PT_SHADING_SHORT_FORMS (defined by pt_variant_matte6.hip alone; docs/experiments/r12.md): the same values in fewer instructions -- the quotients
+ * by PI without the division where tests/shading/short_forms_driver.cpp has shown the bits for every numerator (tb_div_pi), the azimuth's sine and
+ * cosine from one reduction (tb_sincos), and reorient with one square root, two divisions and a select for the component 0 / s (tb_zero_over_sqrt).
+ * Without the define every function here is textually what it was. */
+#ifdef PT_SHADING_SHORT_FORMS
+static_assert(PI == TB_PI_F, "tb_div_pi divides by TB_PI_F");
+/* x / PI.  tb_div_pi's test decides for the wave, not per lane: the three operations where every lane's numerator is one they are right for, the
+ * division for all lanes otherwise.  A lane gets the same bits either way, and a wave-uniform branch is a ballot and a scalar compare where a
+ * per-lane one is an exec region per path: a dozen more scalar instructions per site in the listing, for a division of ten. */
+TBD float div_pi(float x)
+{
+    if (__ballot(!tb_div_pi_is_fast(x)) == 0ull) return tb_div_pi_fast(x);
+    return x / PI;
+}
+TBD float diffuse_brdf(tb3 L, tb3 N) { return div_pi(tb_max(tb3_dot(L, N), 0.0f)); }
+#else
 TBD float diffuse_brdf(tb3 L, tb3 N) { return tb_max(tb3_dot(L, N), 0.0f) / PI; }
+#endif
 
 TBD tb3 reorient(tb3 v, tb3 n) /* ReorientVectorAroundNormal :1001-1015 */
 {
     /* (a select form -- one square root and three divisions on operands chosen per lane -- was measured in round 5, twice, on one box against
      * this form: within +-0.5 % on all six workloads) */
     tb3 t;
+#ifdef PT_SHADING_SHORT_FORMS
+    /* Each lane's operations are those of its own branch below, on operands chosen per lane (the compiler already merged the two branches into
+     * two square roots and three divisions, one of them 0 / s for every lane): one square root, the two divisions whose numerator is not the
+     * literal 0, and for 0 / s its value -- +0, or NaN where s is 0 or NaN (tb_zero_over_sqrt). */
+    const bool xy = tb_abs(n.x) > tb_abs(n.y);
+    const float m = xy ? n.x : n.y;
+    const float s = tb_sqrt(m * m + n.z * n.z);
+    const float d = (xy ? -n.z : n.z) / s, e = (xy ? n.x : -n.y) / s, z = tb_zero_over_sqrt(s);
+    t = tb3_make(xy ? d : z, xy ? z : d, e);
+#else
     if (tb_abs(n.x) > tb_abs(n.y)) t = tb3_make(-n.z, 0, n.x) / tb_sqrt(n.x * n.x + n.z * n.z);
     else t = tb3_make(0, n.z, -n.y) / tb_sqrt(n.y * n.y + n.z * n.z);
+#endif
     tb3 b = tb3_cross(n, t);
     return tb3_normalize(v.x * t + v.y * n + v.z * b);
 }
@@ -1355,7 +1383,13 @@ TBD void path_scatter(Path& p, const TbPerFrameConstants& pf)
         } else {
             A = tb_sqrt(r0); B = tb_sqrt(tb_max(EPSILON, 1.0f - r0));
         }
+#ifdef PT_SHADING_SHORT_FORMS
+        float sinTheta, cosTheta;
+        tb_sincos(theta, &sinTheta, &cosTheta); /* one guard, one reduction, one pair of polynomials for both */
+        const tb3 w = reorient(tb3_make(A * cosTheta, B, A * sinTheta), p.N);
+#else
         const tb3 w = reorient(tb3_make(A * tb_cos(theta), B, A * tb_sin(theta)), p.N);
+#endif
         p.rd = spec ? tb3_reflect(p.prevDir, w) : w;
     } else { /* :1529-1600 */
         bool reflected;
@@ -1374,7 +1408,11 @@ TBD void path_scatter(Path& p, const TbPerFrameConstants& pf)
      * form issues every side's divisions and pow()s for the whole wave.  What the sides have in common is therefore computed once, on operands
      * selected per lane: the half vector's normalisation, the three divisions of T by the pdf, the GGX term.  Each lane's operations and their
      * order are those of its own branch (kernel.glsl:1699-1769). */
+#ifdef PT_SHADING_SHORT_FORMS
+    float diffusePdf = div_pi(tb3_dot(p.rd, p.N)); /* :1699 */
+#else
     float diffusePdf = tb3_dot(p.rd, p.N) / PI; /* :1699 */
+#endif
     const bool anySpec = allowsSpec || metallic;
     tb3 hvN = tb3_splat(0.0f), hvSafe = tb3_splat(0.0f);
     if (anySpec) {

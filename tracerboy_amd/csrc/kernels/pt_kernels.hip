@@ -65,6 +65,8 @@ __global__ void device_math_kernel(int fn, uint32_t n, const float* a, const flo
     case 11: r = x / y; break; case 12: r = tb_frac(tb_sin(x + y) * 43758.5453123f); break; case 13: r = hash13(x, y, 0.0f); break;
     case 14: r = tb_min(x, y); break; case 15: r = tb_max(x, y); break; case 16: r = tb_frac(x); break; case 17: r = tb_floor(x); break;
         case 18: r = tb_rcp(x); break;
+    /* 19 .. 22: the short forms of tb_math.h, which the oracle does not call (device only; tests/test_shading_short_forms.py): tb_sincos's sine, its cosine */
+    case 19: tb_sincos(x, &r, &y); break; case 20: tb_sincos(x, &y, &r); break; case 21: r = tb_div_pi(x); break; case 22: r = tb_zero_over_sqrt(x); break;
     default: break;
     }
     out[i] = r;

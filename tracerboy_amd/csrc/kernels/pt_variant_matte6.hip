@@ -9,4 +9,5 @@
  * is at most numLights and below 2^23 (context_render.cpp pickCopy); any other runs the 5-wave copy, whose fetches are guarded. */
 #define PT_COPY matte6
 #define PT_TABLES_CHECKED 1 /* fetch_surface, load_vertex, fetch_material, fetch_light, shadow_hit_is_light fetch without a bounds check (pt_device.hpp) */
+#define PT_SHADING_SHORT_FORMS 1 /* tb_sincos, x / PI without the division, reorient's zero component by a select (pt_device.hpp) */
 #include "pt_variant.inc"
