@@ -161,6 +161,16 @@ typedef struct TbVisualizeConstants {
 } TbVisualizeConstants;
 TB_STATIC_ASSERT(sizeof(TbVisualizeConstants) == 80, "VisualizationRaysConstants is 20 dwords");
 
+/* ---- ray queries (tracerboy_hip.h tb_trace_rays) --------------------------
+ * A ray of a query, 32 B and 16-B aligned on the device: a candidate counts iff MIN_T < t < min(TMax, MAX_T), the renderer's constants (0.001 and
+ * 999999); of Flags only bit 0 is read.  A hit record, 48 B: the fields of tb_trace_closest; a miss is T = -1, U = V = 0, Prim = Geom =
+ * 0xffffffff, Material = -1, UV = 0, Normal = 0. */
+typedef struct TbQueryRay { float Origin[3]; float TMax; float Direction[3]; uint32_t Flags; } TbQueryRay;
+typedef struct TbQueryHit { float T, U, V; uint32_t Prim; uint32_t Geom; int32_t Material; float UV[2]; float Normal[3]; uint32_t Pad; } TbQueryHit;
+TB_STATIC_ASSERT(sizeof(TbQueryRay) == 32, "a query ray is 8 dwords");
+TB_STATIC_ASSERT(sizeof(TbQueryHit) == 48, "a query hit is 12 dwords");
+#define TB_QUERY_RAY_DISABLED 1u /* Flags bit 0: the ray is not traced; it reads as a miss / not occluded */
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

@@ -571,6 +571,30 @@ int tb_visualize_constants(const tb_camera* camera, uint32_t width, uint32_t hei
 int tb_run_visualize_rays(tb_context* ctx, const TbVisualizeConstants* constants, const TbVisualizerRay* rays, uint32_t n_rays, const float* scene_rgba,
                           const float* world_pos_or_null, float* out_rgba);
 
+/* ---- ray queries -----------------------------------------------------------------
+ * The traversal the renderer uses, as a service: n rays in (tb_abi.h TbQueryRay), closest-hit records (TbQueryHit[n], TB_RAYS_CLOSEST) or
+ * occlusion flags (uint8_t[n], 1 or 0, TB_RAYS_OCCLUDED) out.  Synchronous: runs on the context's stream and returns after the stream has
+ * finished.  Without TB_RAYS_DEVICE both arrays are host arrays, staged in temporary device buffers like tb_trace_closest's; with it they are
+ * device pointers of the context's device (rays and hit records 16-B aligned; the caller orders its own work on them before the call), and the
+ * call allocates nothing -- the context keeps one small buffer, the work counter of the any-hit walk's refilling form, until tb_destroy.
+ *   What a ray means.  MIN_T = 0.001 and MAX_T = 999999 are the renderer's constants.  A candidate counts iff MIN_T < t < min(TMax, MAX_T); TMax
+ *   = +inf, or any value >= MAX_T, is the renderer's ray; a TMax that is a NaN or <= MIN_T gives a miss.  There is no per-ray tmin: move the
+ *   origin instead.  A ray with TB_QUERY_RAY_DISABLED in Flags (only bit 0 is read) is not traced and reads as a miss / not occluded.  Option
+ *   "alpha_test" applies as it does to tb_trace_closest on the same context.
+ *   TB_RAYS_CLOSEST: the closest-hit walk of tb_trace_closest, unchanged; the hit is kept iff t < TMax (the closest hit inside the range exists
+ *   iff the overall closest hit lies inside it), so every field has tb_trace_closest's bits.  A miss: T = -1, U = V = 0, Prim = Geom = 0xffffffff,
+ *   Material = -1, UV = 0, Normal = 0.
+ *   TB_RAYS_OCCLUDED: 1 iff some triangle passes the renderer's triangle test with its closest distance held at min(TMax, MAX_T).  One-level
+ *   scenes run an any-hit walk that ends a ray at its first accepted candidate -- one ray per lane, or from 32 768 triangles a persistent grid
+ *   whose waves refill their idle lanes; which triangle is found, and how rays are scheduled, does not change the answer.  Two-level scenes (option "flatten_instances" = 0) are answered by the closest-hit walk and the comparison t < TMax.
+ * TB_E_NO_SCENE: no scene loaded.  TB_E_INVALID: a null pointer with n > 0; an unknown mode or flag bit; n > 2^31; a misaligned device pointer,
+ * or one that is not memory of the context's device or is too short; a peer handle.  TB_E_UNSUPPORTED: the context of a tb_create_multi group.
+ * n = 0: TB_OK, nothing is launched.  tb_trace_closest stays as it is. */
+#define TB_RAYS_CLOSEST  0u
+#define TB_RAYS_OCCLUDED 1u
+#define TB_RAYS_DEVICE   0x100u       /* rays and out are device pointers of the context's device */
+int tb_trace_rays(tb_context* ctx, uint32_t mode_and_flags, uint64_t n, const TbQueryRay* rays, void* out);
+
 /* ---- neural still denoiser -----------------------------------------------------
  * <-> the reference's TAAUpscaler::OIDN path (TracerBoy.cpp:3306-3322; OpenImageDenoise.cpp:855-1039): the OIDN U-Net -- 16 convolutions of 3 x 3,
  * four 2 x 2 max-pools on the way down, four nearest upsamples x 2 on the way up, each concatenated in front of the skip tensor of its size, ReLU

@@ -187,6 +187,17 @@ class tb_visualize_settings(C.Structure):
     _fields_ = [("RayWidth", C.c_float), ("RayDepth", C.c_float), ("RayCount", C.c_int32)]
 
 
+class TbQueryRay(C.Structure):
+    """A ray of tb_trace_rays (tb_abi.h): a candidate counts iff MIN_T < t < min(TMax, MAX_T); Flags bit 0 = not traced."""
+    _fields_ = [("Origin", C.c_float * 3), ("TMax", C.c_float), ("Direction", C.c_float * 3), ("Flags", C.c_uint32)]
+
+
+class TbQueryHit(C.Structure):
+    """A hit record of tb_trace_rays (tb_abi.h): tb_trace_closest's fields; T = -1 for a miss."""
+    _fields_ = [("T", C.c_float), ("U", C.c_float), ("V", C.c_float), ("Prim", C.c_uint32), ("Geom", C.c_uint32), ("Material", C.c_int32),
+                ("UV", C.c_float * 2), ("Normal", C.c_float * 3), ("Pad", C.c_uint32)]
+
+
 class tb_nn_info(C.Structure):
     """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
     _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]
@@ -287,6 +298,7 @@ assert C.sizeof(TbDenoiserConstants) == 28
 assert C.sizeof(TbFsrConstants) == 80
 assert C.sizeof(TbVisualizerRay) == 32 and C.sizeof(TbVisualizeConstants) == 80 and C.sizeof(TbPathFrame) == 32
 assert C.sizeof(tb_visualize_settings) == 12
+assert C.sizeof(TbQueryRay) == 32 and C.sizeof(TbQueryHit) == 48
 assert C.sizeof(tb_compare_settings) == 12 and C.sizeof(tb_compare_result) == 96
 assert C.sizeof(TbPerFrameConstants) == 148
 assert C.sizeof(TbConfigConstants) == 76

@@ -117,6 +117,7 @@ def lib():
         "tb_visualize_rays": (C.c_int, [vp, P(abi.tb_visualize_settings), vp, vp]),
         "tb_visualize_constants": (C.c_int, [P(abi.tb_camera), C.c_uint32, C.c_uint32, P(abi.tb_visualize_settings), P(abi.TbVisualizeConstants)]),
         "tb_run_visualize_rays": (C.c_int, [vp, P(abi.TbVisualizeConstants), vp, C.c_uint32, vp, vp, vp]),
+        "tb_trace_rays": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp]),
         "tb_default_compare_settings": (None, [P(abi.tb_compare_settings)]),
         "tb_run_compare": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, P(abi.tb_compare_settings), P(abi.tb_compare_result), vp, vp]),
         "tb_set_reference": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -233,6 +234,59 @@ def VisualizeConstants(camera, width, height, settings=None):
 
 
 # the records of the path inspector as numpy sees them (the layouts of TbPathFrame and TbVisualizerRay)
+# ray queries (tb_trace_rays; tb_abi.h TbQueryRay / TbQueryHit)
+RAYS_CLOSEST, RAYS_OCCLUDED, RAYS_DEVICE = 0, 1, 0x100
+QUERY_RAY_DISABLED = 1
+QUERY_RAY_DTYPE = np.dtype([("Origin", np.float32, 3), ("TMax", np.float32), ("Direction", np.float32, 3), ("Flags", np.uint32)])
+QUERY_HIT_DTYPE = np.dtype([("T", np.float32), ("U", np.float32), ("V", np.float32), ("Prim", np.uint32), ("Geom", np.uint32), ("Material", np.int32),
+                            ("UV", np.float32, 2), ("Normal", np.float32, 3), ("Pad", np.uint32)])
+
+
+def make_query_rays(origins, dirs, tmax=np.inf, disabled=None):
+    """(n, 3) origins and directions packed into QUERY_RAY_DTYPE; tmax: a scalar or n values (inf: the renderer's ray); disabled: n booleans."""
+    o = np.asarray(origins, np.float32); d = np.asarray(dirs, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("make_query_rays: origins and dirs are (n, 3) arrays of one length")
+    rays = np.zeros(o.shape[0], QUERY_RAY_DTYPE)
+    rays["Origin"] = o; rays["Direction"] = d
+    rays["TMax"] = np.broadcast_to(np.asarray(tmax, np.float32), (o.shape[0],))
+    if disabled is not None:
+        rays["Flags"] = np.where(np.broadcast_to(np.asarray(disabled, bool), (o.shape[0],)), QUERY_RAY_DISABLED, 0)
+    return rays
+
+
+def _is_torch_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+
+
+def _check_query_rays(rays, mode, device):
+    """What TraceRays accepts, checked before any library call (a wrong array must never reach the kernel as a wrong pointer): True for a torch
+    tensor (the device path), False for a numpy array (the host path); ValueError otherwise."""
+    if mode not in (RAYS_CLOSEST, RAYS_OCCLUDED):
+        raise ValueError("TraceRays: mode is RAYS_CLOSEST or RAYS_OCCLUDED, not %r" % (mode,))
+    if _is_torch_tensor(rays):
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("TraceRays: a tensor of rays is float32 of shape (n, 8), not %s %s" % (rays.dtype, tuple(rays.shape)))
+        if not rays.is_contiguous():
+            raise ValueError("TraceRays: the tensor of rays is not contiguous")
+        if rays.device.type != "cuda" or rays.device.index != device:
+            raise ValueError("TraceRays: the tensor of rays is on %s, the context on cuda:%d" % (rays.device, device))
+        if rays.data_ptr() % 16:
+            raise ValueError("TraceRays: the tensor of rays is not 16-B aligned")
+        return True
+    if not isinstance(rays, np.ndarray):
+        raise ValueError("TraceRays: rays are a numpy array or a torch tensor, not %s" % type(rays).__name__)
+    if rays.dtype == QUERY_RAY_DTYPE:
+        if rays.ndim != 1:
+            raise ValueError("TraceRays: an array of QUERY_RAY_DTYPE has one dimension, not %d" % rays.ndim)
+    elif rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("TraceRays: rays are QUERY_RAY_DTYPE or float32 of shape (n, 8), not %s %s" % (rays.dtype, rays.shape))
+    if not rays.flags["C_CONTIGUOUS"]:
+        raise ValueError("TraceRays: the array of rays is not contiguous")
+    return False
+
+
 PATH_FRAME_DTYPE = np.dtype([("sum", np.float32, 4), ("frame", np.uint32), ("first_ray", np.uint32), ("num_rays", np.uint32), ("flags", np.uint32)])
 VISUALIZER_RAY_DTYPE = np.dtype([("Origin", np.float32, 3), ("Direction", np.float32, 3), ("HitT", np.float32), ("BounceCount", np.float32)])
 assert PATH_FRAME_DTYPE.itemsize == 32 and VISUALIZER_RAY_DTYPE.itemsize == 32
@@ -548,6 +602,7 @@ class TracerBoy:
             raise TracerBoyError(rc, (self._L.tb_last_error(None) or b"").decode(errors="replace"))
         self.width = self.height = 0
         self._budget_shape = None
+        self._device = int(devices[0]) if devices is not None else int(device_id)
 
     # -- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -1045,6 +1100,24 @@ class TracerBoy:
         self._check(self._L.tb_trace_closest(self._ctx, n, _np_ptr(o), _np_ptr(d), _np_ptr(r["t"]), _np_ptr(r["material"]), _np_ptr(r["bary"]),
                                              _np_ptr(r["prim"]), _np_ptr(r["geom"]), _np_ptr(r["normal"]), _np_ptr(r["uv"]), _np_ptr(r["boxes"]), _np_ptr(r["tris"])))
         return r
+
+    def TraceRays(self, rays, mode=RAYS_CLOSEST):
+        """tb_trace_rays: closest hits (RAYS_CLOSEST) or any-hit occlusion (RAYS_OCCLUDED) of the caller's rays.
+        A numpy array -- QUERY_RAY_DTYPE (make_query_rays), or float32 of shape (n, 8): origin, TMax, direction, the flags' bits -- takes the host
+        path and returns a QUERY_HIT_DTYPE array / a uint8 array.  A torch tensor, float32 (n, 8), contiguous, on the context's device, takes the
+        device path with zero copy: torch's current stream on that device is synchronised first, and the result is a float32 (n, 12) tensor (the
+        integer fields through .view(torch.int32)) / a uint8 (n,) tensor that torch allocated.  Anything else: ValueError, before any library call."""
+        on_device = _check_query_rays(rays, mode, getattr(self, "_device", 0))
+        n = int(rays.shape[0])
+        if on_device:
+            import torch
+            out = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if mode == RAYS_CLOSEST else torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()
+            self._check(self._L.tb_trace_rays(self._ctx, mode | RAYS_DEVICE, n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty(n, QUERY_HIT_DTYPE if mode == RAYS_CLOSEST else np.uint8)
+        self._check(self._L.tb_trace_rays(self._ctx, mode, n, _np_ptr(rays), _np_ptr(out)))
+        return out
 
     def DeviceMath(self, fn, a, b=None):
         a = np.ascontiguousarray(a, np.float32)

@@ -16,6 +16,7 @@
  *   context_budget.cpp  sample budgets: set / read, the noise target that stops converged pixels, its kernel seam
  *   context_compare.cpp image-quality metrics against a reference image: the kernel seam, the reference, the stage
  *   context_visualize.cpp the path inspector: a pixel's paths recorded again, the ray buffer, the overlay and its kernel seam
+ *   context_rays.cpp    ray queries: tb_trace_rays, closest hits and any-hit occlusion of a caller's rays, host arrays or device buffers
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -233,6 +234,9 @@ struct tb_context {
         DevBuf rays, overflow, out, out8; uint32_t stored = 0; int depthSource = 0;
         tbctx::DevEvent evPaths[2], evOverlay[2]; float lastPathsMs = 0.0f, lastOverlayMs = 0.0f;
     } vis;
+    /* ray queries (context_rays.cpp).  counter: the work counter of the any-hit walk's refilling form, made at its first
+     * launch and kept: the device path of tb_trace_rays allocates nothing per call */
+    struct RayQueries { DevBuf counter; } rq;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
