@@ -595,6 +595,49 @@ int tb_run_visualize_rays(tb_context* ctx, const TbVisualizeConstants* constants
 #define TB_RAYS_DEVICE   0x100u       /* rays and out are device pointers of the context's device */
 int tb_trace_rays(tb_context* ctx, uint32_t mode_and_flags, uint64_t n, const TbQueryRay* rays, void* out);
 
+/* ---- dynamic scenes (no reference counterpart: its scene is frozen once LoadScene returns) -------------------------
+ * Vertices and instance transforms are STAGED by the three calls below; nothing a render or a trace reads changes until tb_commit_geometry, which
+ * waits for the context's stream and then applies everything staged.  A commit with nothing staged is TB_OK and does nothing.
+ * Vertex numbering: that of the scene's position / vertex arrays, all geometries back to back; tb_scene_info::numVertices bounds it and
+ * tb_geometry_vertex_range gives the range of one geometry (hit-group record).  Coordinates are in the space those arrays hold (world space for a
+ * one-level scene).  xyz: n_vertices triples.  Without TB_UPDATE_DEVICE a host array: it is checked for finite values (TB_E_INVALID otherwise) and
+ * copied before the call returns.  With it a device pointer of the context's device, read where it lies on the context's stream (tb_stream,
+ * tb_sync) without a staging copy; its VALUES ARE NOT CHECKED -- a position that is not finite gives boxes no ray enters, that is misses, never an
+ * access out of range, because the topology does not change.
+ * tb_update_normals writes the Normal field of the 32-B vertex records (TbVertex); UVs and tangents stay.  Nothing is recomputed: the caller
+ * brings the normals that go with its positions.
+ * tb_commit_geometry(0), the refit: the tree keeps its topology -- every child reference, the sorted order of the triangles, their metadata -- and
+ * every stored box becomes what the builder's fit pass gives for that topology and the new positions, bit for bit:
+ *   leaf    mn = min(v0, v1, v2), mx = max(v0, v1, v2); mn = min(mn, mx - 0.001f); c = (mn + mx) * 0.5f, h = mx - c
+ *   parent  from the children's STORED boxes: mn = min(lc - lh, rc - rh), mx = max(lc + lh, rc + rh), then the same c, h
+ * so a refit from the positions a scene was loaded with gives back the loaded tree.  On the device it runs as one launch over the triangles and one
+ * per level of a schedule made once; the only value the host reads is the 24-byte root box.  The compact nodes (option "node_layout") and the LDS
+ * image of an LDS-resident scene are made again from the new tree.  The host copies (tb_host_scene_view, tb_scene_digest, tb_scene_info_get) are
+ * brought up from the device when they are next asked for, not at the commit.
+ * tb_commit_geometry(TB_GEOMETRY_REBUILD): the refit, then the tree a fresh load of the moved scene would build (option "bvh_builder"), slow; for
+ * meshes that have deformed past what a refit tree serves well.  It also rebuilds, with nothing staged, a tree that has been refit.
+ * tb_set_instance_transforms (two-level scenes: option "flatten_instances" = 0 with instances): object_to_world_3x4 holds n_instances row-major 3 x 4
+ * matrices (host memory).  The commit derives worldToObject as the loader does and builds the top level again (same bytes as a load of the scene
+ * with those transforms); the bottom levels are untouched.
+ * After a commit that changed something: the history is reset (tb_samples_rendered is 0), tb_scene_digest differs -- a render state saved before
+ * cannot be resumed onto the moved scene --, tb_scene_info's sceneMin / sceneMax follow.  The dynamic state (a device copy of the positions, per
+ * triangle its vertex numbers, per node its parent, the level schedule) is made at the first of these calls and released with the scene; a context
+ * that never calls them allocates and launches nothing for it.  tb_get_option "last_refit_us": GPU microseconds of the last refit's kernels.
+ * Refusals; each leaves the scene and the staged data as they were (the message names the cause).  TB_E_NO_SCENE: no scene.  TB_E_INVALID: a range
+ * past the end; a null pointer with n > 0; unknown flag bits; a host value that is not finite; a transform whose 3 x 3 part is singular or not finite.
+ * TB_E_UNSUPPORTED: a tb_create_multi group (ranks that are separate processes each call the update themselves); tb_update_positions /
+ * tb_update_normals on a two-level scene; tb_set_instance_transforms on a scene without instances; TB_GEOMETRY_REBUILD of a two-level scene; a tree
+ * of pre-split references (option "presplit"); at the commit, staged vertices of a geometry whose material is emissive that differ from the scene's
+ * (each emissive triangle has a TbLight that carries its positions, normals and area, and the light table is not made again): the message names the
+ * geometry.  Not offered: adding or removing triangles, motion blur. */
+#define TB_UPDATE_DEVICE    0x100u   /* xyz is a device pointer of the context's device (the value and meaning of TB_RAYS_DEVICE) */
+#define TB_GEOMETRY_REBUILD 1u       /* tb_commit_geometry: build a new topology */
+int tb_update_positions(tb_context* ctx, uint32_t flags, uint32_t first_vertex, uint32_t n_vertices, const float* xyz);
+int tb_update_normals(tb_context* ctx, uint32_t flags, uint32_t first_vertex, uint32_t n_vertices, const float* xyz);
+int tb_set_instance_transforms(tb_context* ctx, uint32_t first_instance, uint32_t n_instances, const float* object_to_world_3x4);
+int tb_commit_geometry(tb_context* ctx, uint32_t flags);
+int tb_geometry_vertex_range(tb_context* ctx, uint32_t geometry, uint32_t* first_vertex, uint32_t* n_vertices);
+
 /* ---- neural still denoiser -----------------------------------------------------
  * <-> the reference's TAAUpscaler::OIDN path (TracerBoy.cpp:3306-3322; OpenImageDenoise.cpp:855-1039): the OIDN U-Net -- 16 convolutions of 3 x 3,
  * four 2 x 2 max-pools on the way down, four nearest upsamples x 2 on the way up, each concatenated in front of the skip tensor of its size, ReLU

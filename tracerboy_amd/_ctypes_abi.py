@@ -218,6 +218,7 @@ class tb_conv_desc(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "c_a", "c_b", "c_out", "kernel", "upsample_a", "relu", "form")]
 
 
+TB_UPDATE_DEVICE, TB_GEOMETRY_REBUILD = 0x100, 1  # include/tracerboy_hip.h: tb_update_positions / tb_update_normals flags; tb_commit_geometry flags
 TB_COMPARE_SSIM, TB_COMPARE_SUMS = 1, 2          # tb_compare_settings.flags
 TB_COMPARE_MEAN, TB_COMPARE_DENOISED = 0, 1      # tb_compare's surface
 

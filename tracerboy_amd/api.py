@@ -118,6 +118,11 @@ def lib():
         "tb_visualize_constants": (C.c_int, [P(abi.tb_camera), C.c_uint32, C.c_uint32, P(abi.tb_visualize_settings), P(abi.TbVisualizeConstants)]),
         "tb_run_visualize_rays": (C.c_int, [vp, P(abi.TbVisualizeConstants), vp, C.c_uint32, vp, vp, vp]),
         "tb_trace_rays": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp]),
+        "tb_update_positions": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+        "tb_update_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+        "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+        "tb_commit_geometry": (C.c_int, [vp, C.c_uint32]),
+        "tb_geometry_vertex_range": (C.c_int, [vp, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "tb_default_compare_settings": (None, [P(abi.tb_compare_settings)]),
         "tb_run_compare": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, P(abi.tb_compare_settings), P(abi.tb_compare_result), vp, vp]),
         "tb_set_reference": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -285,6 +290,34 @@ def _check_query_rays(rays, mode, device):
     if not rays.flags["C_CONTIGUOUS"]:
         raise ValueError("TraceRays: the array of rays is not contiguous")
     return False
+
+
+# dynamic scenes (tb_update_positions .. tb_commit_geometry)
+UPDATE_DEVICE, GEOMETRY_REBUILD = 0x100, 1
+
+
+def _check_vertex_array(what, a, first, device):
+    """What UpdatePositions / UpdateNormals accept, checked before any library call: True for a torch tensor (the device path), False for a numpy
+    array (the host path); ValueError otherwise."""
+    if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or first > 0xffffffff:
+        raise ValueError("%s: first is a vertex number, not %r" % (what, first))
+    if _is_torch_tensor(a):
+        import torch
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+            raise ValueError("%s: a tensor is float32 of shape (n, 3), not %s %s" % (what, a.dtype, tuple(a.shape)))
+        if not a.is_contiguous():
+            raise ValueError("%s: the tensor is not contiguous" % what)
+        if a.device.type != "cuda" or a.device.index != device:
+            raise ValueError("%s: the tensor is on %s, the context on cuda:%d" % (what, a.device, device))
+    elif not isinstance(a, np.ndarray):
+        raise ValueError("%s: a numpy array or a torch tensor, not %s" % (what, type(a).__name__))
+    elif a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s: an array is float32 of shape (n, 3), not %s %s" % (what, a.dtype, a.shape))
+    elif not a.flags["C_CONTIGUOUS"]:
+        raise ValueError("%s: the array is not contiguous" % what)
+    if first + int(a.shape[0]) > 0xffffffff:
+        raise ValueError("%s: first + n is no vertex number" % what)
+    return _is_torch_tensor(a)
 
 
 PATH_FRAME_DTYPE = np.dtype([("sum", np.float32, 4), ("frame", np.uint32), ("first_ray", np.uint32), ("num_rays", np.uint32), ("flags", np.uint32)])
@@ -1118,6 +1151,49 @@ class TracerBoy:
         out = np.empty(n, QUERY_HIT_DTYPE if mode == RAYS_CLOSEST else np.uint8)
         self._check(self._L.tb_trace_rays(self._ctx, mode, n, _np_ptr(rays), _np_ptr(out)))
         return out
+
+    # -- dynamic scenes ----------------------------------------------------
+    def _update_vertices(self, what, fn_name, a, first):
+        on_device = _check_vertex_array(what, a, first, getattr(self, "_device", 0))
+        n = int(a.shape[0])
+        fn = getattr(self._L, fn_name)
+        if on_device:
+            import torch
+            torch.cuda.current_stream(a.device).synchronize()
+            self._check(fn(self._ctx, UPDATE_DEVICE, first, n, C.c_void_p(a.data_ptr() or None)))
+            self._check(self._L.tb_sync(self._ctx))                 # the tensor has been read: torch may give its memory to another
+        else:
+            self._check(fn(self._ctx, 0, first, n, _np_ptr(a)))
+
+    def UpdatePositions(self, a, first=0):
+        """tb_update_positions: stage new positions of the vertices first .. first + n.  a: float32 (n, 3), a numpy array (checked for finite values)
+        or a contiguous torch tensor on the context's device (read where it lies, values unchecked).  Anything else: ValueError, before any library
+        call.  Nothing changes until CommitGeometry."""
+        self._update_vertices("UpdatePositions", "tb_update_positions", a, first)
+
+    def UpdateNormals(self, a, first=0):
+        """tb_update_normals: stage new shading normals (the Normal field of the vertex records) of the vertices first .. first + n; a as for UpdatePositions."""
+        self._update_vertices("UpdateNormals", "tb_update_normals", a, first)
+
+    def SetInstanceTransforms(self, m, first=0):
+        """tb_set_instance_transforms: stage objectToWorld of the instances first .. first + n of a two-level scene; m: float32 (n, 3, 4) or (n, 12)."""
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or first > 0xffffffff:
+            raise ValueError("SetInstanceTransforms: first is an instance number, not %r" % (first,))
+        if not isinstance(m, np.ndarray) or m.dtype != np.float32 or not (m.ndim == 3 and m.shape[1:] == (3, 4) or m.ndim == 2 and m.shape[1] == 12):
+            raise ValueError("SetInstanceTransforms: m is a float32 numpy array of shape (n, 3, 4) or (n, 12)")
+        if not m.flags["C_CONTIGUOUS"]:
+            raise ValueError("SetInstanceTransforms: the array is not contiguous")
+        self._check(self._L.tb_set_instance_transforms(self._ctx, first, int(m.shape[0]), _np_ptr(m)))
+
+    def CommitGeometry(self, rebuild=False):
+        """tb_commit_geometry: apply what was staged -- a refit of the tree as it stands, or (rebuild) the tree a fresh load of the moved scene builds."""
+        self._check(self._L.tb_commit_geometry(self._ctx, GEOMETRY_REBUILD if rebuild else 0))
+
+    def GeometryVertexRange(self, g):
+        """tb_geometry_vertex_range: (first vertex, number of vertices) of geometry (hit-group record) g."""
+        first, count = C.c_uint32(), C.c_uint32()
+        self._check(self._L.tb_geometry_vertex_range(self._ctx, int(g), C.byref(first), C.byref(count)))
+        return first.value, count.value
 
     def DeviceMath(self, fn, a, b=None):
         a = np.ascontiguousarray(a, np.float32)

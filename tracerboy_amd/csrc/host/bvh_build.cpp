@@ -925,6 +925,30 @@ void BuildBvhWith(HostScene& s, const std::function<void(HostScene&)>& single, c
     s.bvhMaxDepth = tlasDepth + maxBlasDepth; /* the walk's stack holds top-level entries below the bottom-level ones */
 }
 
+void RebuildTopLevel(HostScene& s, const TlasBuilder& tlas)
+{
+    const uint32_t M = (uint32_t)s.instances.size();
+    if (M == 0) throw std::runtime_error("RebuildTopLevel: the scene has no instances");
+    std::vector<Bounds> blasRoot(s.blas.size());
+    uint32_t maxBlasDepth = 0;
+    for (size_t b = 0; b < s.blas.size(); b++) {
+        const TbAabbNode* root = (const TbAabbNode*)(s.bvhA.data() + s.blas[b].offsetA + 16);
+        const tb3 c = tb3_make(root->center[0], root->center[1], root->center[2]), h = tb3_make(root->halfDim[0], root->halfDim[1], root->halfDim[2]);
+        blasRoot[b].mn = c - h; blasRoot[b].mx = c + h;
+        maxBlasDepth = std::max(maxBlasDepth, s.blas[b].depth);
+    }
+    std::vector<TbNodeB> top; uint32_t tlasDepth = 0; float rc[3], rh[3];
+    if (tlas) {
+        std::vector<float> boxes(6 * blasRoot.size());
+        for (size_t b = 0; b < blasRoot.size(); b++) { const float v[6] = {blasRoot[b].mn.x, blasRoot[b].mn.y, blasRoot[b].mn.z, blasRoot[b].mx.x,
+            blasRoot[b].mx.y, blasRoot[b].mx.z}; memcpy(&boxes[6 * b], v, sizeof v); }
+        tlas(s, boxes, top, s.rootRefB, tlasDepth);
+    } else BuildTlas(s, blasRoot, top, s.rootRefB, tlasDepth, rc, rh);
+    for (uint32_t i = 0; i + 1 < M; i++) s.nodesB[i] = top[i];
+    for (uint32_t i = 0; i < M; i++) memcpy(s.instancesB[i].worldToObject, s.instances[i].worldToObject, 48);
+    s.bvhMaxDepth = tlasDepth + maxBlasDepth;
+}
+
 void WaveSurfacesOf(const HostScene& s, WaveSurfaces& surf)
 {
     surf = WaveSurfaces{};

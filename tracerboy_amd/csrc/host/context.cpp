@@ -119,8 +119,7 @@ int tb_scene_info_get(tb_context* c, tb_scene_info* o)
 {
     if (!c || !o) return TB_E_INVALID;
     if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-    fillSceneInfo(c->scene, o);
-    return TB_OK;
+    return guarded(c, [&]() { refreshHostScene(c); fillSceneInfo(c->scene, o); return TB_OK; });
 }
 
 void tb_default_output_settings(tb_output_settings* o) { if (o) DefaultOutputSettings(*o); }
@@ -295,6 +294,8 @@ int tb_host_scene_view(tb_context* c, TbSceneView* v)
 {
     if (!c || !v) return TB_E_INVALID;
     if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
+    const int rc = guarded(c, [&]() { refreshHostScene(c); return TB_OK; }); /* a commit leaves the host geometry stale (context_dynamic.cpp) */
+    if (rc != TB_OK) return rc;
     fillView(c->scene, v);
     return TB_OK;
 }

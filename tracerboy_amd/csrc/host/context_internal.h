@@ -16,6 +16,7 @@
  *   context_budget.cpp  sample budgets: set / read, the noise target that stops converged pixels, its kernel seam
  *   context_compare.cpp image-quality metrics against a reference image: the kernel seam, the reference, the stage
  *   context_visualize.cpp the path inspector: a pixel's paths recorded again, the ray buffer, the overlay and its kernel seam
+ *   context_dynamic.cpp dynamic scenes: staged vertices and instance transforms, the refit commit, the host copies' refresh
  *   context_rays.cpp    ray queries: tb_trace_rays, closest hits and any-hit occlusion of a caller's rays, host arrays or device buffers
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
@@ -34,6 +35,7 @@
 #include <atomic>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <cmath>
 #include <functional>
 #include <stdexcept>
@@ -237,6 +239,22 @@ struct tb_context {
     /* ray queries (context_rays.cpp).  counter: the work counter of the any-hit walk's refilling form, made at its first
      * launch and kept: the device path of tb_trace_rays allocates nothing per call */
     struct RayQueries { DevBuf counter; } rq;
+    /* dynamic geometry (context_dynamic.cpp): made at the first tb_update_* / tb_set_instance_transforms of a scene, released
+     * with the scene (releaseScene); a context that never updates holds none of it.  positions / normals: the staged arrays, 3 floats per vertex
+     * (normals at the first tb_update_normals); triVerts, triSlot, nodeSlot, schedule, rootBox: the tables of refit_launch.h, made once per
+     * topology, with their host halves.  dirtyPositions / dirtyNormals: the staged vertex ranges [first, end) since the last commit;
+     * transforms / transformStaged: staged objectToWorld rows per instance.  hostStale: a commit has changed the device tree and c->scene's bvhA,
+     * nodesB, trisB, positions (and, vertexBufferStale, vertexBuffer) are what they were before -- refreshHostScene brings them up on first demand.
+     * refitSinceBuild: the tree's topology was built of other positions than it holds.  lastMs: option last_refit_us */
+    struct Dynamic {
+        bool ready = false, hostStale = false, vertexBufferStale = false, refitSinceBuild = false;
+        DevBuf positions, normals, triVerts, triSlot, nodeSlot, schedule, levelFirstDevice, rootBox;
+        std::vector<uint32_t> hostTriVerts, levelFirst;
+        std::vector<std::pair<uint32_t, uint32_t>> dirtyPositions, dirtyNormals;
+        std::vector<float> transforms; std::vector<uint8_t> transformStaged;
+        tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+    };
+    std::unique_ptr<Dynamic> dyn;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -344,6 +362,12 @@ uint32_t sceneTextureUse(const tb_context* c);
 uint32_t settingsFeatureMask(const tb_context* c, const tb_output_settings& s, bool aov);
 void ensureCompactNodes(tb_context* c);
 void finalizeScene(tb_context* c, bool build = true); /* build = false: c->scene already holds a built, reordered tree (a peer of a multi-device group) */
+void BuildTlasGpu(tb_context* c, HostScene& s, const std::vector<float>& blasBoxes, std::vector<TbNodeB>& top, uint32_t& rootRef, uint32_t& depth);
+/* context_dynamic.cpp: the host copies of the geometry (HostScene::bvhA, nodesB, trisB, positions, vertexBuffer, sceneMin / sceneMax) as the device
+ * holds them now.  Every reader of those members outside the load path calls it first; it does nothing unless a commit has left them stale */
+void refreshHostScene(tb_context* c);
+/* context_rays.cpp: why a device pointer the caller gave is refused -- `bytes` from it must lie inside one allocation of the context's device; null: it is not */
+const char* devicePointerRefusal(const tb_context* c, const void* p, size_t bytes);
 /* context_render.cpp */
 bool historyRelevantChange(const tb_output_settings& a, const tb_output_settings& b);
 int deviceCUs(tb_context* c);

@@ -80,6 +80,8 @@ const Query kQueries[] = {
      * its occluder from: 1 the last frame's world-position AOV, 2 the guide pass's mean position, 0 nowhere */
     Q("last_paths_us", microseconds(c->vis.lastPathsMs)) Q("last_visualize_us", microseconds(c->vis.lastOverlayMs))
     Q("visualize_depth_source", c->vis.depthSource)
+    /* dynamic scenes: the kernels of the last refit (HIP events); the scene holds a dynamic state; its host geometry is stale */
+    Q("last_refit_us", microseconds(c->dyn ? c->dyn->lastMs : 0.0f)) Q("dynamic_state", c->dyn ? 1 : 0) Q("host_geometry_stale", c->dyn && c->dyn->hostStale ? 1 : 0)
     Q("last_copy_waves", c->lastCopyWaves)
     Q("last_adaptive", c->lastAdaptive ? 1 : 0) /* the adaptive launch: did the last call run it */
     /* sample budgets: one is set; the last call was planned under it (its live pixels: last_live_pixels) */

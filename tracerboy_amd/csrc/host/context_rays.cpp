@@ -9,6 +9,20 @@
 using namespace tbhost;
 using namespace tbctx;
 
+/* a device pointer the caller gave: `bytes` from it lie inside one allocation of the context's device */
+const char* tbctx::devicePointerRefusal(const tb_context* c, const void* p, size_t bytes)
+{
+    hipPointerAttribute_t a; hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError(); /* the refusal is ours: the runtime's error does not stay behind */
+        return "not a device pointer";
+    }
+    if (a.type != hipMemoryTypeDevice) return "not device memory";
+    if (a.device != c->device) return "memory of another device than the context's";
+    if ((size_t)((const uint8_t*)p - (const uint8_t*)base) + bytes > size) return "the array runs past its allocation";
+    return nullptr;
+}
+
 namespace {
 
 /* why tb_trace_rays refuses its arguments; null: it does not.  (What needs the context -- a scene, a group -- is asked there.) */
@@ -23,20 +37,6 @@ const char* raysRefusal(uint32_t modeAndFlags, uint64_t n, const void* rays, con
         if ((uintptr_t)rays & 15u) return "device rays are not 16-B aligned";
         if (mode == TB_RAYS_CLOSEST && ((uintptr_t)out & 15u)) return "device hit records are not 16-B aligned";
     }
-    return nullptr;
-}
-
-/* a device pointer the caller gave: `bytes` from it lie inside one allocation of the context's device */
-const char* devicePointerRefusal(const tb_context* c, const void* p, size_t bytes)
-{
-    hipPointerAttribute_t a; hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError(); /* the refusal is ours: the runtime's error does not stay behind */
-        return "not a device pointer";
-    }
-    if (a.type != hipMemoryTypeDevice) return "not device memory";
-    if (a.device != c->device) return "memory of another device than the context's";
-    if ((size_t)((const uint8_t*)p - (const uint8_t*)base) + bytes > size) return "the array runs past its allocation";
     return nullptr;
 }
 

@@ -8,6 +8,7 @@ namespace tbctx {
 void releaseScene(tb_context* c)
 {
     c->sceneBufs.clear();
+    c->dyn.reset(); /* the dynamic state belongs to the scene's buffers and topology (context_dynamic.cpp) */
     memset(&c->ds, 0, sizeof c->ds);
 }
 
@@ -199,6 +200,7 @@ void ensureCompactNodes(tb_context* c)
 {
     if (c->compactTried || c->ds.nodesC) return;
     c->compactTried = true;
+    refreshHostScene(c);
     const HostScene& s = c->scene;
     if (!s.instances.empty() || (s.rootRefB & TB_BVH_LEAF_FLAG)) return;
     try {

@@ -320,6 +320,9 @@ void InverseAffineTransform(const float t[12], float o[12])
 
 } // namespace
 
+void InvertInstanceTransform(const float objectToWorld[12], float worldToObject[12]) { InverseAffineTransform(objectToWorld, worldToObject); }
+float InstanceTransformDeterminant(const float objectToWorld[12]) { return Determinant(objectToWorld); }
+
 void ConvertScene(const PbrtScene& in, HostScene& out, const ConvertOptions& opt)
 {
     out = HostScene();

@@ -88,6 +88,13 @@ void BuildBvh(HostScene& scene, int builder);
 typedef std::function<void(HostScene&, const std::vector<float>& blasRootBoxes, std::vector<TbNodeB>& topNodes, uint32_t& rootRef,
     uint32_t& depth)> TlasBuilder;
 void BuildBvhWith(HostScene& scene, const std::function<void(HostScene&)>& single, const TlasBuilder& tlas);
+/* A two-level scene's top level again, from HostScene::instances as they are now (bvh_build.cpp; tb_set_instance_transforms): tlasA, the M - 1
+ * top-level nodes at the head of nodesB, instancesB's worldToObject, rootRefB and bvhMaxDepth -- what a build of the scene with those transforms
+ * gives.  tlas: as for BuildBvhWith (null: the host's BuildTlas).  The bottom levels are not touched. */
+void RebuildTopLevel(HostScene& scene, const TlasBuilder& tlas);
+/* the loader's inverse of an instance transform (host_scene.cpp InverseAffineTransform: the fallback layer's fp32 expressions) and its determinant */
+void InvertInstanceTransform(const float objectToWorld[12], float worldToObject[12]);
+float InstanceTransformDeterminant(const float objectToWorld[12]);
 /* builder 1's wave stage (bvh_build.cpp, wave_cost.h): the surfaces its model rays start from, and the size of its ray set */
 struct WaveSurfaces;
 void WaveSurfacesOf(const HostScene& scene, WaveSurfaces& out);

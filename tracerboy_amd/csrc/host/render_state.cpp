@@ -102,7 +102,7 @@ bool sameTiles(const TbTileMap& t, const tb_state_info& h) { return t.rank == h.
 uint64_t sceneDigestCached(tb_context* c)
 {
     const uint64_t key = ((uint64_t)c->sceneGeneration << 32) | c->materialEdits;
-    if (c->sceneDigestKey != key) { c->sceneDigest = sceneDigestOf(c->scene); c->sceneDigestKey = key; }
+    if (c->sceneDigestKey != key) { refreshHostScene(c); c->sceneDigest = sceneDigestOf(c->scene); c->sceneDigestKey = key; }
     return c->sceneDigest;
 }
 
