@@ -171,6 +171,16 @@ TB_STATIC_ASSERT(sizeof(TbQueryRay) == 32, "a query ray is 8 dwords");
 TB_STATIC_ASSERT(sizeof(TbQueryHit) == 48, "a query hit is 12 dwords");
 #define TB_QUERY_RAY_DISABLED 1u /* Flags bit 0: the ray is not traced; it reads as a miss / not occluded */
 
+/* ---- radiance queries (tracerboy_hip.h tb_trace_radiance) -----------------
+ * A ray of a radiance query, 32 B and 16-B aligned on the device: where a path starts, its direction (a unit vector: it is not normalised) or, in
+ * hemisphere mode, the unit surface normal, and the two numbers that stand where the pixel coordinates stand in the renderer's seed
+ * hash13(x, y, frame).  A call: the samples [first_sample, first_sample + num_samples) of every ray, the distance the seed has moved before the
+ * path starts, and TB_RADIANCE_* mode and flags. */
+typedef struct TbRadianceRay { float Origin[3]; float SeedX; float Direction[3]; float SeedY; } TbRadianceRay;
+typedef struct TbRadianceCall { uint32_t first_sample, num_samples; float seed_advance; uint32_t mode_and_flags; } TbRadianceCall;
+TB_STATIC_ASSERT(sizeof(TbRadianceRay) == 32, "a radiance ray is 8 dwords");
+TB_STATIC_ASSERT(sizeof(TbRadianceCall) == 16, "a radiance call is 4 dwords");
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

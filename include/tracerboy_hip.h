@@ -595,6 +595,47 @@ int tb_run_visualize_rays(tb_context* ctx, const TbVisualizeConstants* constants
 #define TB_RAYS_DEVICE   0x100u       /* rays and out are device pointers of the context's device */
 int tb_trace_rays(tb_context* ctx, uint32_t mode_and_flags, uint64_t n, const TbQueryRay* rays, void* out);
 
+/* ---- radiance queries ------------------------------------------------------------
+ * The path tracer on the caller's rays: the light arriving along n rays (tb_abi.h TbRadianceRay), num_samples paths each, summed per ray.
+ * Synchronous like tb_trace_rays, on host arrays (staged, nothing kept) or, with TB_RADIANCE_DEVICE, on device pointers of the context's device
+ * (16-B aligned; the context keeps one work counter and, on trees deeper than the LDS share, the overflow half of the stacks).
+ *   Sample k of ray i has the number s = first_sample + k and starts with the seed hash13(SeedX, SeedY, (float)s) + seed_advance, the sum taken
+ *   the way rand() moves a seed: floor(seed_advance) fp32 additions of 1 (at most 1024 of them), then one addition of the rest (a negative
+ *   advance: one addition of all of it).  hash13 carries bits below the ulp of the sum, so the steps are not the one addition, and only the steps
+ *   land where the renderer lands: for a camera ray of pixel (x, y) that is the seed of frame s once path_begin has drawn its pixel jitter
+ *   (tb_make_camera_rays reports that distance).  The path starts at Origin along Direction with throughput 1, radiance 0, bounce 0, and runs the renderer's loop -- closest hit,
+ *   shading, next-event estimation, the feeler, scattering, the interior walk, Russian roulette -- under the frame constants of `settings`
+ *   (null: the defaults), `time`, the scene's lights and the current camera; MaxBounces 0 ends it at once.  AOVs, the heatmap, pixel picking and
+ *   the real-time mode are not part of a query (RenderModeRealTime: TB_E_UNSUPPORTED).  Option "alpha_test" applies.
+ *   A sample's result is the path's radiance, min(., FireflyClampValue) where that is >= EPSILON; a result with a NaN is rejected.
+ *   out[i] = (sum r, sum g, sum b, number of accepted samples), summed in fp32 in sample order from 0 -- from out[i] as it stands with
+ *   TB_RADIANCE_ACCUMULATE, so a call over [a, c) equals the calls over [a, b) and [b, c) accumulated, bit for bit.
+ *   TB_RADIANCE_HEMISPHERE: Direction is a unit surface normal; every sample first draws two random numbers r0, r1 and starts along
+ *   GenerateCosineWeightedDirection(normal, r0, r1) (kernel.glsl:1025-1046), its seed two further.  pi * sum / count is the irradiance; the library
+ *   does not multiply.
+ *   A ray whose direction is all zero or not finite, or whose origin is not finite, is not traced: out[i] is zeros, or stays under accumulate.
+ * tb_make_camera_rays: the renderer's camera rays of frame `frame` for the pixels [x0, x1) x [y0, y1) of a W x H picture, row-major in the window:
+ * origin and direction as path_begin leaves them (pixel jitter, depth of field), SeedX = x, SeedY = y.  *seed_advance_out: how far path_begin
+ * moved the seed (16 without blue noise, 0 with it).  flags: 0 or TB_RADIANCE_DEVICE (out is a device pointer).  A filter whose weight is not 1
+ * (triangle, Gaussian) is TB_E_UNSUPPORTED: the record has no weight.  So tb_trace_radiance(samples 1, first_sample f, that advance) on the rays of
+ * frame f adds to out what tb_render adds to the accumulation surface in frame f.
+ * TB_E_NO_SCENE: no scene.  TB_E_INVALID: a null pointer with n > 0; an unknown mode or flag bit; num_samples 0 or above 2^24; n > 2^31;
+ * first_sample + num_samples past 2^32; a seed_advance that is not finite; an empty or outside window; a misaligned or foreign device pointer; a peer handle.  TB_E_UNSUPPORTED:
+ * a tb_create_multi group; real-time settings; a stack deeper than LDS.  n = 0: TB_OK, nothing is launched.
+ * tb_get_option "last_radiance_us" (GPU microseconds of the last query's launches), "last_radiance_variant" (the feature set's id, as
+ * "last_variant"), "last_radiance_form" (0 one ray per lane, 1 the refilling grid). */
+#define TB_RADIANCE_RAY        0u
+#define TB_RADIANCE_HEMISPHERE 1u
+#define TB_RADIANCE_DEVICE     0x100u   /* rays and out are device pointers of the context's device (the value and meaning of TB_RAYS_DEVICE) */
+#define TB_RADIANCE_ACCUMULATE 0x200u   /* the sums start from out[i] */
+int tb_trace_radiance(tb_context* ctx, const tb_output_settings* settings_or_null, float time, const TbRadianceCall* call, uint64_t n,
+                      const TbRadianceRay* rays, TbFloat4* out);
+/* host only, no context: why tb_trace_radiance refuses these arguments before it looks at its context -- TB_OK, or TB_E_INVALID with the reason in
+ * why (why_bytes of room; may be null) */
+int tb_radiance_refusal(const TbRadianceCall* call, uint64_t n, const void* rays, const void* out, char* why_or_null, uint32_t why_bytes);
+int tb_make_camera_rays(tb_context* ctx, const tb_output_settings* settings_or_null, float time, uint32_t width, uint32_t height,
+                        uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t frame, uint32_t flags, TbRadianceRay* out, float* seed_advance_out);
+
 /* ---- dynamic scenes (no reference counterpart: its scene is frozen once LoadScene returns) -------------------------
  * Vertices and instance transforms are STAGED by the three calls below; nothing a render or a trace reads changes until tb_commit_geometry, which
  * waits for the context's stream and then applies everything staged.  A commit with nothing staged is TB_OK and does nothing.

@@ -198,6 +198,16 @@ class TbQueryHit(C.Structure):
                 ("UV", C.c_float * 2), ("Normal", C.c_float * 3), ("Pad", C.c_uint32)]
 
 
+class TbRadianceRay(C.Structure):
+    """A ray of tb_trace_radiance (tb_abi.h): where a path starts, its unit direction (hemisphere mode: the unit normal), the seed's two coordinates."""
+    _fields_ = [("Origin", C.c_float * 3), ("SeedX", C.c_float), ("Direction", C.c_float * 3), ("SeedY", C.c_float)]
+
+
+class TbRadianceCall(C.Structure):
+    """A call of tb_trace_radiance (tb_abi.h): the samples [first_sample, first_sample + num_samples), the seed's advance, TB_RADIANCE_* mode | flags."""
+    _fields_ = [("first_sample", C.c_uint32), ("num_samples", C.c_uint32), ("seed_advance", C.c_float), ("mode_and_flags", C.c_uint32)]
+
+
 class tb_nn_info(C.Structure):
     """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
     _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]
@@ -300,6 +310,7 @@ assert C.sizeof(TbFsrConstants) == 80
 assert C.sizeof(TbVisualizerRay) == 32 and C.sizeof(TbVisualizeConstants) == 80 and C.sizeof(TbPathFrame) == 32
 assert C.sizeof(tb_visualize_settings) == 12
 assert C.sizeof(TbQueryRay) == 32 and C.sizeof(TbQueryHit) == 48
+assert C.sizeof(TbRadianceRay) == 32 and C.sizeof(TbRadianceCall) == 16
 assert C.sizeof(tb_compare_settings) == 12 and C.sizeof(tb_compare_result) == 96
 assert C.sizeof(TbPerFrameConstants) == 148
 assert C.sizeof(TbConfigConstants) == 76

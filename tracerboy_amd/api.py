@@ -118,6 +118,9 @@ def lib():
         "tb_visualize_constants": (C.c_int, [P(abi.tb_camera), C.c_uint32, C.c_uint32, P(abi.tb_visualize_settings), P(abi.TbVisualizeConstants)]),
         "tb_run_visualize_rays": (C.c_int, [vp, P(abi.TbVisualizeConstants), vp, C.c_uint32, vp, vp, vp]),
         "tb_trace_rays": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp]),
+        "tb_trace_radiance": (C.c_int, [vp, P(abi.tb_output_settings), C.c_float, P(abi.TbRadianceCall), C.c_uint64, vp, vp]),
+        "tb_radiance_refusal": (C.c_int, [P(abi.TbRadianceCall), C.c_uint64, vp, vp, C.c_char_p, C.c_uint32]),
+        "tb_make_camera_rays": (C.c_int, [vp, P(abi.tb_output_settings), C.c_float] + [C.c_uint32] * 8 + [vp, P(C.c_float)]),
         "tb_update_positions": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_update_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -290,6 +293,86 @@ def _check_query_rays(rays, mode, device):
     if not rays.flags["C_CONTIGUOUS"]:
         raise ValueError("TraceRays: the array of rays is not contiguous")
     return False
+
+
+# radiance queries (tb_trace_radiance / tb_make_camera_rays; tb_abi.h TbRadianceRay / TbRadianceCall)
+RADIANCE_RAY, RADIANCE_HEMISPHERE, RADIANCE_DEVICE, RADIANCE_ACCUMULATE = 0, 1, 0x100, 0x200
+RADIANCE_RAY_DTYPE = np.dtype([("Origin", np.float32, 3), ("SeedX", np.float32), ("Direction", np.float32, 3), ("SeedY", np.float32)])
+assert RADIANCE_RAY_DTYPE.itemsize == 32
+
+
+def make_radiance_rays(origins, dirs_or_normals, seed_xy=None):
+    """(n, 3) origins and unit directions (hemisphere mode: unit normals) packed into RADIANCE_RAY_DTYPE; seed_xy: (n, 2) numbers that stand where the
+    pixel coordinates stand in the renderer's seed -- by default (i % 4096, i // 4096), distinct whole numbers per ray."""
+    o = np.asarray(origins, np.float32); d = np.asarray(dirs_or_normals, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("make_radiance_rays: origins and directions are (n, 3) arrays of one length")
+    n = o.shape[0]
+    if seed_xy is None:
+        i = np.arange(n, dtype=np.int64)
+        seed = np.stack([i % 4096, i // 4096], axis=1).astype(np.float32)
+    else:
+        seed = np.asarray(seed_xy, np.float32)
+        if seed.shape != (n, 2):
+            raise ValueError("make_radiance_rays: seed_xy is an (n, 2) array")
+    rays = np.zeros(n, RADIANCE_RAY_DTYPE)
+    rays["Origin"] = o; rays["Direction"] = d; rays["SeedX"] = seed[:, 0]; rays["SeedY"] = seed[:, 1]
+    return rays
+
+
+def _check_count(what, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or v > hi:
+        raise ValueError("%s: %s is a whole number in [%d, %d], not %r" % (what, name, lo, hi, v))
+    return int(v)
+
+
+def _check_radiance_call(rays, samples, first_sample, seed_advance, mode, out, device):
+    """What TraceRadiance accepts, checked before any library call: True for torch tensors (the device path), False for numpy arrays (the host
+    path); ValueError otherwise."""
+    if isinstance(mode, bool) or mode not in (RADIANCE_RAY, RADIANCE_HEMISPHERE):
+        raise ValueError("TraceRadiance: mode is RADIANCE_RAY or RADIANCE_HEMISPHERE, not %r" % (mode,))
+    _check_count("TraceRadiance", "samples", samples, 1, 1 << 24)
+    _check_count("TraceRadiance", "first_sample", first_sample, 0, (1 << 32) - samples)
+    if isinstance(seed_advance, bool) or not isinstance(seed_advance, (int, float, np.integer, np.floating)) or not np.isfinite(seed_advance):
+        raise ValueError("TraceRadiance: seed_advance is a finite number, not %r" % (seed_advance,))
+    if _is_torch_tensor(rays):
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("TraceRadiance: a tensor of rays is float32 of shape (n, 8), not %s %s" % (rays.dtype, tuple(rays.shape)))
+        if not rays.is_contiguous():
+            raise ValueError("TraceRadiance: the tensor of rays is not contiguous")
+        if rays.device.type != "cuda" or rays.device.index != device:
+            raise ValueError("TraceRadiance: the tensor of rays is on %s, the context on cuda:%d" % (rays.device, device))
+        if rays.data_ptr() % 16:
+            raise ValueError("TraceRadiance: the tensor of rays is not 16-B aligned")
+        if out is not None:
+            if not _is_torch_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (int(rays.shape[0]), 4):
+                raise ValueError("TraceRadiance: out is a float32 tensor of shape (n, 4) like the rays")
+            if not out.is_contiguous() or out.device != rays.device or out.data_ptr() % 16:
+                raise ValueError("TraceRadiance: out is contiguous, 16-B aligned and on the rays' device")
+        return True
+    if not isinstance(rays, np.ndarray):
+        raise ValueError("TraceRadiance: rays are a numpy array or a torch tensor, not %s" % type(rays).__name__)
+    if rays.dtype == RADIANCE_RAY_DTYPE:
+        if rays.ndim != 1:
+            raise ValueError("TraceRadiance: an array of RADIANCE_RAY_DTYPE has one dimension, not %d" % rays.ndim)
+    elif rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("TraceRadiance: rays are RADIANCE_RAY_DTYPE or float32 of shape (n, 8), not %s %s" % (rays.dtype, rays.shape))
+    if not rays.flags["C_CONTIGUOUS"]:
+        raise ValueError("TraceRadiance: the array of rays is not contiguous")
+    if out is not None:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != (rays.shape[0], 4):
+            raise ValueError("TraceRadiance: out is a float32 numpy array of shape (n, 4) like the rays")
+        if not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError("TraceRadiance: out is contiguous and writeable")
+    return False
+
+
+def RadianceRefusal(call, n, rays_address, out_address):
+    """tb_radiance_refusal (host only): why tb_trace_radiance refuses these arguments before it looks at its context -- None, or the reason."""
+    why = C.create_string_buffer(96)
+    rc = lib().tb_radiance_refusal(C.byref(call) if call is not None else None, n, C.c_void_p(rays_address or None), C.c_void_p(out_address or None), why, 96)
+    return None if rc == 0 else why.value.decode()
 
 
 # dynamic scenes (tb_update_positions .. tb_commit_geometry)
@@ -1151,6 +1234,58 @@ class TracerBoy:
         out = np.empty(n, QUERY_HIT_DTYPE if mode == RAYS_CLOSEST else np.uint8)
         self._check(self._L.tb_trace_rays(self._ctx, mode, n, _np_ptr(rays), _np_ptr(out)))
         return out
+
+    # -- radiance queries ---------------------------------------------------
+    def TraceRadiance(self, rays, samples=1, first_sample=0, seed_advance=0.0, mode=RADIANCE_RAY, settings=None, time=0.0, out=None):
+        """tb_trace_radiance: the path tracer on the caller's rays; per ray (sum r, sum g, sum b, accepted samples) of the samples
+        [first_sample, first_sample + samples), summed in sample order.  mode RADIANCE_HEMISPHERE: the directions are unit normals and every sample
+        starts along a cosine-weighted direction about it (pi * sum / count is the irradiance).  A numpy array -- RADIANCE_RAY_DTYPE
+        (make_radiance_rays), or float32 (n, 8) -- takes the host path and returns a float32 (n, 4) array; a torch tensor, float32 (n, 8), contiguous,
+        16-B aligned, on the context's device, takes the device path with zero copy after torch's current stream on that device is synchronised, and
+        returns a tensor.  out given (float32 (n, 4), of the rays' kind): the sums start from it, and it is returned.  Anything else: ValueError,
+        before any library call."""
+        on_device = _check_radiance_call(rays, samples, first_sample, seed_advance, mode, out, getattr(self, "_device", 0))
+        n = int(rays.shape[0])
+        flags = mode | (RADIANCE_ACCUMULATE if out is not None else 0) | (RADIANCE_DEVICE if on_device else 0)
+        call = abi.TbRadianceCall(int(first_sample), int(samples), float(seed_advance), flags)
+        s = C.byref(settings) if settings is not None else None
+        if on_device:
+            import torch
+            if out is None:
+                out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()
+            self._check(self._L.tb_trace_radiance(self._ctx, s, time, C.byref(call), n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+            return out
+        if out is None:
+            out = np.empty((n, 4), np.float32)
+        self._check(self._L.tb_trace_radiance(self._ctx, s, time, C.byref(call), n, _np_ptr(rays), _np_ptr(out)))
+        return out
+
+    def MakeCameraRays(self, width, height, frame, window=None, settings=None, time=0.0, device=False):
+        """tb_make_camera_rays: (rays, seed_advance) -- the renderer's camera rays of frame `frame` for the pixels of window = (x0, y0, x1, y1)
+        (half-open; default the whole width x height picture), row-major in the window, and how far path_begin moved the seed: TraceRadiance(rays, 1,
+        frame, seed_advance) adds what Render adds to the accumulation in that frame.  rays: a RADIANCE_RAY_DTYPE array, or (device) a float32
+        (n, 8) tensor on the context's device."""
+        for name, v in (("width", width), ("height", height)):
+            _check_count("MakeCameraRays", name, v, 1, 16384)
+        _check_count("MakeCameraRays", "frame", frame, 0, 0xffffffff)
+        x0, y0, x1, y1 = (0, 0, width, height) if window is None else window
+        for name, v in (("x0", x0), ("y0", y0), ("x1", x1), ("y1", y1)):
+            _check_count("MakeCameraRays", name, v, 0, 16384)
+        if not (x0 < x1 <= width and y0 < y1 <= height):
+            raise ValueError("MakeCameraRays: the window (%d, %d, %d, %d) is empty or leaves the %d x %d picture" % (x0, y0, x1, y1, width, height))
+        n = (x1 - x0) * (y1 - y0)
+        advance = C.c_float(0.0)
+        s = C.byref(settings) if settings is not None else None
+        if device:
+            import torch
+            rays = torch.empty((n, 8), dtype=torch.float32, device="cuda:%d" % getattr(self, "_device", 0))
+            torch.cuda.current_stream(rays.device).synchronize()
+            self._check(self._L.tb_make_camera_rays(self._ctx, s, time, width, height, x0, y0, x1, y1, frame, RADIANCE_DEVICE, C.c_void_p(rays.data_ptr()), C.byref(advance)))
+        else:
+            rays = np.empty(n, RADIANCE_RAY_DTYPE)
+            self._check(self._L.tb_make_camera_rays(self._ctx, s, time, width, height, x0, y0, x1, y1, frame, 0, _np_ptr(rays), C.byref(advance)))
+        return rays, advance.value
 
     # -- dynamic scenes (DESIGN.md section 21) ----------------------------------------------------
     def _update_vertices(self, what, fn_name, a, first):

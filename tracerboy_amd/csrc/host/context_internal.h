@@ -18,6 +18,7 @@
  *   context_visualize.cpp the path inspector: a pixel's paths recorded again, the ray buffer, the overlay and its kernel seam
  *   context_dynamic.cpp dynamic scenes: staged vertices and instance transforms, the refit commit, the host copies' refresh
  *   context_rays.cpp    ray queries: tb_trace_rays, closest hits and any-hit occlusion of a caller's rays, host arrays or device buffers
+ *   context_radiance.cpp radiance queries: tb_trace_radiance, the path tracer on a caller's rays, and tb_make_camera_rays
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -239,6 +240,10 @@ struct tb_context {
     /* ray queries (context_rays.cpp).  counter: the work counter of the any-hit walk's refilling form, made at its first
      * launch and kept: the device path of tb_trace_rays allocates nothing per call */
     struct RayQueries { DevBuf counter; } rq;
+    /* radiance queries (context_radiance.cpp).  counter: the work counter of the refilling form, made at its first launch and
+     * kept; overflow: the query's half of a split stack.  lastMs, lastVariant, lastForm, lastLaunches: options last_radiance_us,
+     * last_radiance_variant (the feature set's id, -1 before the first query), last_radiance_form, last_radiance_launches */
+    struct Radiance { DevBuf counter, overflow; tbctx::DevEvent ev[2]; float lastMs = 0.0f; int lastVariant = -1, lastForm = 0; uint32_t lastLaunches = 0; } rad;
     /* dynamic geometry (context_dynamic.cpp): made at the first tb_update_* / tb_set_instance_transforms of a scene, released
      * with the scene (releaseScene); a context that never updates holds none of it.  positions / normals: the staged arrays, 3 floats per vertex
      * (normals at the first tb_update_normals); triVerts, triSlot, nodeSlot, schedule, rootBox: the tables of refit_launch.h, made once per

@@ -82,6 +82,10 @@ const Query kQueries[] = {
     Q("visualize_depth_source", c->vis.depthSource)
     /* dynamic scenes: the kernels of the last refit (HIP events); the scene holds a dynamic state; its host geometry is stale */
     Q("last_refit_us", microseconds(c->dyn ? c->dyn->lastMs : 0.0f)) Q("dynamic_state", c->dyn ? 1 : 0) Q("host_geometry_stale", c->dyn && c->dyn->hostStale ? 1 : 0)
+    /* radiance queries: the last query's launches (HIP events), its feature set (the ids of last_variant), its form (0 one ray
+     * per lane, 1 the refilling grid) and how many launches it was split into */
+    Q("last_radiance_us", microseconds(c->rad.lastMs)) Q("last_radiance_variant", c->rad.lastVariant) Q("last_radiance_form", c->rad.lastForm)
+    Q("last_radiance_launches", c->rad.lastLaunches)
     Q("last_copy_waves", c->lastCopyWaves)
     Q("last_adaptive", c->lastAdaptive ? 1 : 0) /* the adaptive launch: did the last call run it */
     /* sample budgets: one is set; the last call was planned under it (its live pixels: last_live_pixels) */

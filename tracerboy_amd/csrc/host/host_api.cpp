@@ -124,6 +124,31 @@ int tb_plan_launch(const tb_plan_input* in, tb_launch_plan* out)
     return TB_OK;
 }
 
+/* Why tb_trace_radiance refuses its arguments before it looks at the context or allocates anything: pure tests, in the order
+ * the header lists them.  What needs the context -- a scene, a group, real-time settings, whose memory a device pointer is -- is asked there. */
+static const char* radianceRefusal(const TbRadianceCall* call, uint64_t n, const void* rays, const void* out)
+{
+    if (!call) return "null call";
+    if (call->mode_and_flags & ~(0xffu | TB_RADIANCE_DEVICE | TB_RADIANCE_ACCUMULATE)) return "unknown flag bits";
+    const uint32_t mode = call->mode_and_flags & 0xffu;
+    if (mode != TB_RADIANCE_RAY && mode != TB_RADIANCE_HEMISPHERE) return "unknown mode";
+    if (call->num_samples == 0) return "num_samples is 0";
+    if (call->num_samples > (1u << 24)) return "more than 2^24 samples per ray";
+    if ((uint64_t)call->first_sample + call->num_samples > (1ull << 32)) return "first_sample + num_samples passes 2^32";
+    if (!(call->seed_advance - call->seed_advance == 0.0f)) return "seed_advance is not finite";
+    if (n > (1ull << 31)) return "more than 2^31 rays";
+    if (n && (!rays || !out)) return "null pointer";
+    if (n && (call->mode_and_flags & TB_RADIANCE_DEVICE) && ((((uintptr_t)rays) | ((uintptr_t)out)) & 15u)) return "device arrays are not 16-B aligned";
+    return nullptr;
+}
+
+int tb_radiance_refusal(const TbRadianceCall* call, uint64_t n, const void* rays, const void* out, char* why, uint32_t whyBytes)
+{
+    const char* no = radianceRefusal(call, n, rays, out);
+    if (why && whyBytes) { strncpy(why, no ? no : "", whyBytes - 1); why[whyBytes - 1] = 0; }
+    return no ? TB_E_INVALID : TB_OK;
+}
+
 int tb_unpack_gathered_host(uint32_t W, uint32_t H, uint32_t world, uint32_t tw, uint32_t th, const float* const* perRank, float* full)
 {
     if (!perRank || !full || world == 0 || tw == 0 || th == 0) return TB_E_INVALID;
