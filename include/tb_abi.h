@@ -181,6 +181,13 @@ typedef struct TbRadianceCall { uint32_t first_sample, num_samples; float seed_a
 TB_STATIC_ASSERT(sizeof(TbRadianceRay) == 32, "a radiance ray is 8 dwords");
 TB_STATIC_ASSERT(sizeof(TbRadianceCall) == 16, "a radiance call is 4 dwords");
 
+/* ---- lightmap baking (tracerboy_hip.h tb_bake_lightmap) -------------------
+ * What the rasteriser found for one texel of the atlas.  triangle: the scene's triangle number (0xffffffff: none, the other fields 0); cls: 0 the
+ * triangle covers the texel's centre, 1 it only touches the texel's square; w0, w1: the weights of the triangle's vertices 0 and 1 at the point
+ * the texel's ray starts from (vertex 2 has the rest). */
+typedef struct TbBakeTexel { uint32_t triangle, cls; float w0, w1; } TbBakeTexel;
+TB_STATIC_ASSERT(sizeof(TbBakeTexel) == 16, "a bake texel is 4 dwords");
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

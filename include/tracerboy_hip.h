@@ -636,6 +636,50 @@ int tb_radiance_refusal(const TbRadianceCall* call, uint64_t n, const void* rays
 int tb_make_camera_rays(tb_context* ctx, const tb_output_settings* settings_or_null, float time, uint32_t width, uint32_t height,
                         uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t frame, uint32_t flags, TbRadianceRay* out, float* seed_advance_out);
 
+/* ---- lightmap baking -----------------------------------------------------------
+ * One call from lightmap UVs to an RGBA32F atlas, all of it on the device: the triangles of a one-level scene are rasterised into a width x height
+ * atlas by their lightmap UVs (texel (x, y) has its centre at u * width = x + 0.5, v * height = y + 0.5; row 0 is v = 0; no wrap), every texel that
+ * a triangle owns becomes a ray record of the radiance query -- origin on the triangle, direction the interpolated unit normal, seed (x, y) --, the
+ * atlas in row-major order is traced by tb_trace_radiance's kernels in TB_RADIANCE_HEMISPHERE mode with seed_advance 0 over the samples
+ * [first_sample, first_sample + num_samples), and the sums are resolved (rgb = PI * sum / accepted count, alpha 1; texels without a triangle
+ * (0, 0, 0, 0)) and dilated: dilate_passes times every texel with alpha 0 that has a 3 x 3 neighbour with alpha > 0 becomes the mean of those
+ * neighbours, with alpha 2^-pass (1/2 in the first pass, 1/4 in the second ...), so a reader can tell rasterised texels from filled ones.
+ * kernels/bake_launch.h states every rule operation by operation; tests/bake_cases.py restates them in numpy, and the two agree on bits.
+ *   A texel whose centre a triangle covers (class 0) belongs to the lowest-numbered such triangle; a texel whose square a triangle only touches
+ *   (class 1, the conservative half-texel offset) belongs to the lowest-numbered such triangle unless some triangle covers its centre; there its
+ *   ray starts at the point of the triangle nearest to the centre in barycentric terms (negative weights clamped to 0, the rest renormalised).
+ *   The origin is not offset along the normal: MIN_T keeps a path off the surface it starts on.
+ *   Triangles are numbered as tb_host_scene_triangles numbers them (the scene's geometries back to back), vertices as section 21 numbers them.
+ * uv_or_null: 2 floats per vertex of the scene; null: the UV field of the scene's vertex records as loaded -- loads flip V (FlipTextureUVs), so a
+ * file's (u, v) arrives as (u, 1 - v).  rgba_out: width x height x 4 floats, row 0 first.  Positions and normals are what the last
+ * tb_commit_geometry left.  Synchronous.  The context keeps the atlas's rays, texel records and sums until the next bake, a scene load or a
+ * rebuild (tb_read_bake); they are allocated at the first bake, reused while the size holds, and freed with the scene.
+ * flags: TB_BAKE_DEVICE -- uv_or_null and rgba_out are device pointers of the context's device, uv 4-B and rgba_out 16-B aligned.
+ * TB_BAKE_ACCUMULATE -- nothing is rasterised (uv_or_null is not read): the samples are added to the sums the last bake of the same size left,
+ * which are then resolved and dilated again; by section 22's contract bakes of 3 and then 5 samples equal one of 8, bit for bit.  Refused
+ * (TB_E_INVALID) when no bake of that size is held or a tb_commit_geometry has changed the scene since it was rasterised.
+ * Refusals, in this order, each leaving the last bake as it was: tb_bake_refusal's (TB_E_INVALID: a null call, a side of 0 or above 8192, unknown
+ * flag bits, num_samples 0 or above 2^24, first_sample + num_samples above 2^32, more than 16 passes, a null rgba_out, misaligned device
+ * pointers); TB_E_NO_SCENE; TB_E_UNSUPPORTED for a tb_create_multi group, a two-level scene (section 21 refuses vertex access there for the same
+ * reason) and real-time settings; pointers that are not memory of the context's device; TB_BAKE_ACCUMULATE's two.
+ * tb_get_option: "last_bake_raster_us", "last_bake_trace_us", "last_bake_finish_us" (GPU microseconds of the rasteriser, the query and resolve +
+ * dilate; HIP events), "last_bake_covered" (texels with a triangle).
+ * tb_read_bake: what the last bake rasterised and summed, each width x height records in row-major order, to the host pointers that are not null.
+ * tb_run_bake_raster / tb_run_bake_dilate: the kernel seam, like tb_run_fsr_easu: host arrays, temporary device buffers, no scene -- the
+ * rasteriser on n_vertices positions, normals (3 floats each) and uvs (2 floats each) and n_triangles x 3 vertex numbers (one at or past
+ * n_vertices is TB_E_INVALID); `passes` fill passes on a width x height RGBA32F picture. */
+#define TB_BAKE_DEVICE     0x100u   /* the value and meaning of TB_RAYS_DEVICE */
+#define TB_BAKE_ACCUMULATE 0x200u
+typedef struct tb_bake_call { uint32_t width, height, first_sample, num_samples, dilate_passes, flags; } tb_bake_call;
+int tb_bake_lightmap(tb_context* ctx, const tb_output_settings* settings_or_null, float time, const tb_bake_call* call, const float* uv_or_null,
+                     float* rgba_out);
+/* host only, no context: why tb_bake_lightmap refuses these arguments before it looks at its context -- TB_OK, or TB_E_INVALID with the reason in why */
+int tb_bake_refusal(const tb_bake_call* call, const void* uv_or_null, const void* rgba_out, char* why_or_null, uint32_t why_bytes);
+int tb_read_bake(tb_context* ctx, TbRadianceRay* rays_or_null, TbBakeTexel* texels_or_null, float* sums_or_null);
+int tb_run_bake_raster(tb_context* ctx, uint32_t width, uint32_t height, uint32_t n_vertices, const float* positions, const float* normals,
+                       const float* uvs, uint32_t n_triangles, const uint32_t* tri_vertex_index, TbRadianceRay* rays_out, TbBakeTexel* texels_out);
+int tb_run_bake_dilate(tb_context* ctx, uint32_t width, uint32_t height, uint32_t passes, const float* rgba_in, float* rgba_out);
+
 /* ---- dynamic scenes (no reference counterpart: its scene is frozen once LoadScene returns) -------------------------
  * Vertices and instance transforms are STAGED by the three calls below; nothing a render or a trace reads changes until tb_commit_geometry, which
  * waits for the context's stream and then applies everything staged.  A commit with nothing staged is TB_OK and does nothing.

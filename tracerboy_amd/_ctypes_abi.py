@@ -208,6 +208,20 @@ class TbRadianceCall(C.Structure):
     _fields_ = [("first_sample", C.c_uint32), ("num_samples", C.c_uint32), ("seed_advance", C.c_float), ("mode_and_flags", C.c_uint32)]
 
 
+class TbBakeTexel(C.Structure):
+    """What the lightmap rasteriser found for a texel (tb_abi.h): the triangle (0xffffffff: none), the class, the weights of its vertices 0 and 1."""
+    _fields_ = [("triangle", C.c_uint32), ("cls", C.c_uint32), ("w0", C.c_float), ("w1", C.c_float)]
+
+
+class tb_bake_call(C.Structure):
+    """A call of tb_bake_lightmap (tracerboy_hip.h): the atlas, the samples [first_sample, first_sample + num_samples), the fill passes, TB_BAKE_* flags."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("first_sample", C.c_uint32), ("num_samples", C.c_uint32),
+                ("dilate_passes", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(TbBakeTexel) == 16 and C.sizeof(tb_bake_call) == 24
+
+
 class tb_nn_info(C.Structure):
     """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
     _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]

@@ -121,6 +121,11 @@ def lib():
         "tb_trace_radiance": (C.c_int, [vp, P(abi.tb_output_settings), C.c_float, P(abi.TbRadianceCall), C.c_uint64, vp, vp]),
         "tb_radiance_refusal": (C.c_int, [P(abi.TbRadianceCall), C.c_uint64, vp, vp, C.c_char_p, C.c_uint32]),
         "tb_make_camera_rays": (C.c_int, [vp, P(abi.tb_output_settings), C.c_float] + [C.c_uint32] * 8 + [vp, P(C.c_float)]),
+        "tb_bake_lightmap": (C.c_int, [vp, P(abi.tb_output_settings), C.c_float, P(abi.tb_bake_call), vp, vp]),
+        "tb_bake_refusal": (C.c_int, [P(abi.tb_bake_call), vp, vp, C.c_char_p, C.c_uint32]),
+        "tb_read_bake": (C.c_int, [vp, vp, vp, vp]),
+        "tb_run_bake_raster": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]),
+        "tb_run_bake_dilate": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
         "tb_update_positions": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_update_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -372,6 +377,57 @@ def RadianceRefusal(call, n, rays_address, out_address):
     """tb_radiance_refusal (host only): why tb_trace_radiance refuses these arguments before it looks at its context -- None, or the reason."""
     why = C.create_string_buffer(96)
     rc = lib().tb_radiance_refusal(C.byref(call) if call is not None else None, n, C.c_void_p(rays_address or None), C.c_void_p(out_address or None), why, 96)
+    return None if rc == 0 else why.value.decode()
+
+
+# lightmap baking (tb_bake_lightmap .. tb_run_bake_dilate; tb_abi.h TbBakeTexel)
+BAKE_DEVICE, BAKE_ACCUMULATE = 0x100, 0x200
+BAKE_MAX_SIDE, BAKE_MAX_DILATE, BAKE_NO_TRIANGLE = 8192, 16, 0xffffffff
+BAKE_TEXEL_DTYPE = np.dtype([("triangle", np.uint32), ("cls", np.uint32), ("w0", np.float32), ("w1", np.float32)])
+assert BAKE_TEXEL_DTYPE.itemsize == 16
+
+
+def _check_bake_call(width, height, samples, uv, first_sample, dilate, accumulate, out, device):
+    """What BakeLightmap accepts, checked before any library call: True for the device path (uv and / or out are torch tensors), False for the host
+    path (numpy arrays or None); ValueError otherwise.  That uv has one pair per vertex of the scene is checked by the caller."""
+    _check_count("BakeLightmap", "width", width, 1, BAKE_MAX_SIDE)
+    _check_count("BakeLightmap", "height", height, 1, BAKE_MAX_SIDE)
+    _check_count("BakeLightmap", "samples", samples, 1, 1 << 24)
+    _check_count("BakeLightmap", "first_sample", first_sample, 0, (1 << 32) - samples)
+    _check_count("BakeLightmap", "dilate", dilate, 0, BAKE_MAX_DILATE)
+    if not isinstance(accumulate, (bool, np.bool_)):
+        raise ValueError("BakeLightmap: accumulate is True or False, not %r" % (accumulate,))
+    given = [a for a in (uv, out) if a is not None]
+    on_device = any(_is_torch_tensor(a) for a in given)
+    if on_device and not all(_is_torch_tensor(a) for a in given):
+        raise ValueError("BakeLightmap: uv and out are both numpy arrays or both torch tensors")
+    for name, a, shape, align in (("uv", uv, None, 4), ("out", out, (height, width, 4), 16)):
+        if a is None:
+            continue
+        if on_device:
+            import torch
+            if a.dtype != torch.float32 or (a.dim() != 2 or a.shape[1] != 2 if shape is None else tuple(a.shape) != shape):
+                raise ValueError("BakeLightmap: the tensor %s is float32 of shape %s, not %s %s" % (name, shape or "(numVertices, 2)", a.dtype, tuple(a.shape)))
+            if not a.is_contiguous():
+                raise ValueError("BakeLightmap: the tensor %s is not contiguous" % name)
+            if a.device.type != "cuda" or a.device.index != device:
+                raise ValueError("BakeLightmap: the tensor %s is on %s, the context on cuda:%d" % (name, a.device, device))
+            if a.data_ptr() % align:
+                raise ValueError("BakeLightmap: the tensor %s is not %d-B aligned" % (name, align))
+        else:
+            if not isinstance(a, np.ndarray):
+                raise ValueError("BakeLightmap: %s is a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
+            if a.dtype != np.float32 or (a.ndim != 2 or a.shape[1] != 2 if shape is None else a.shape != shape):
+                raise ValueError("BakeLightmap: %s is float32 of shape %s, not %s %s" % (name, shape or "(numVertices, 2)", a.dtype, a.shape))
+            if not a.flags["C_CONTIGUOUS"] or (name == "out" and not a.flags["WRITEABLE"]):
+                raise ValueError("BakeLightmap: %s is contiguous%s" % (name, " and writeable" if name == "out" else ""))
+    return on_device
+
+
+def BakeRefusal(call, uv_address, out_address):
+    """tb_bake_refusal (host only): why tb_bake_lightmap refuses these arguments before it looks at its context -- None, or the reason."""
+    why = C.create_string_buffer(96)
+    rc = lib().tb_bake_refusal(C.byref(call) if call is not None else None, C.c_void_p(uv_address or None), C.c_void_p(out_address or None), why, 96)
     return None if rc == 0 else why.value.decode()
 
 
@@ -1286,6 +1342,73 @@ class TracerBoy:
             rays = np.empty(n, RADIANCE_RAY_DTYPE)
             self._check(self._L.tb_make_camera_rays(self._ctx, s, time, width, height, x0, y0, x1, y1, frame, 0, _np_ptr(rays), C.byref(advance)))
         return rays, advance.value
+
+    # -- lightmap baking ---------------------------------------------------
+    def BakeLightmap(self, width, height, samples, uv=None, first_sample=0, dilate=2, accumulate=False, settings=None, time=0.0, out=None):
+        """tb_bake_lightmap: the scene's triangles rasterised into a width x height atlas by their lightmap UVs, every owned texel traced over the
+        samples [first_sample, first_sample + samples) of its cosine-weighted hemisphere, the sums resolved to irradiance (alpha 1) and the gutters
+        filled by `dilate` 3 x 3 passes (alpha 2^-pass).  Returns the (height, width, 4) float32 picture, row 0 = v 0.  uv: (numVertices, 2) float32,
+        one pair per vertex of the scene; None: the UV field of the scene's vertex records (loads flip V).  accumulate: add the samples to the last
+        bake of this size instead of rasterising again.  uv and out may be numpy arrays (the host path) or contiguous torch tensors on the
+        context's device (zero copy, after torch's current stream there is synchronised; the picture is then a tensor).  Anything else:
+        ValueError, before any library call."""
+        on_device = _check_bake_call(width, height, samples, uv, first_sample, dilate, accumulate, out, getattr(self, "_device", 0))
+        if uv is not None and not accumulate:
+            info = abi.tb_scene_info()
+            if self._L.tb_scene_info_get(self._ctx, C.byref(info)) == 0 and int(uv.shape[0]) != info.numVertices:
+                raise ValueError("BakeLightmap: uv has %d pairs, the scene %d vertices" % (int(uv.shape[0]), info.numVertices))
+        call = abi.tb_bake_call(int(width), int(height), int(first_sample), int(samples), int(dilate),
+                                (BAKE_ACCUMULATE if accumulate else 0) | (BAKE_DEVICE if on_device else 0))
+        s = C.byref(settings) if settings is not None else None
+        if on_device:
+            import torch
+            dev = torch.device("cuda:%d" % getattr(self, "_device", 0))
+            if out is None:
+                out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._check(self._L.tb_bake_lightmap(self._ctx, s, time, C.byref(call), C.c_void_p(uv.data_ptr() or None) if uv is not None else None,
+                                                 C.c_void_p(out.data_ptr() or None)))
+            return out
+        if out is None:
+            out = np.empty((height, width, 4), np.float32)
+        self._check(self._L.tb_bake_lightmap(self._ctx, s, time, C.byref(call), _np_ptr(uv) if uv is not None else None, _np_ptr(out)))
+        return out
+
+    def ReadBake(self):
+        """tb_read_bake: (rays, texels, sums) of the last bake -- RADIANCE_RAY_DTYPE and BAKE_TEXEL_DTYPE arrays of shape (height, width) and the
+        float32 (height, width, 4) sums (sum r, sum g, sum b, accepted samples) the picture was resolved from."""
+        w, h = int(self._L.tb_get_option(self._ctx, b"bake_width")), int(self._L.tb_get_option(self._ctx, b"bake_height"))
+        if not w or not h:
+            self._check(self._L.tb_read_bake(self._ctx, None, None, None))   # the library's own refusal: no bake is held
+        rays = np.empty((h, w), RADIANCE_RAY_DTYPE); texels = np.empty((h, w), BAKE_TEXEL_DTYPE); sums = np.empty((h, w, 4), np.float32)
+        self._check(self._L.tb_read_bake(self._ctx, _np_ptr(rays), _np_ptr(texels), _np_ptr(sums)))
+        return rays, texels, sums
+
+    def RunBakeRaster(self, width, height, positions, normals, uvs, tri_vertex_index):
+        """bake_cover + bake_texels on host arrays, no scene: positions, normals (n, 3) and uvs (n, 2) float32, tri_vertex_index (t, 3) uint32.
+        Returns (rays, texels): RADIANCE_RAY_DTYPE and BAKE_TEXEL_DTYPE arrays of shape (height, width)."""
+        _check_count("RunBakeRaster", "width", width, 1, BAKE_MAX_SIDE)
+        _check_count("RunBakeRaster", "height", height, 1, BAKE_MAX_SIDE)
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        uv = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2); tri = np.ascontiguousarray(tri_vertex_index, np.uint32).reshape(-1, 3)
+        if nrm.shape[0] != p.shape[0] or uv.shape[0] != p.shape[0]:
+            raise ValueError("RunBakeRaster: positions, normals and uvs have one entry per vertex")
+        if tri.size and int(tri.max()) >= p.shape[0]:
+            raise ValueError("RunBakeRaster: a vertex number is not below the number of vertices")
+        rays = np.empty((height, width), RADIANCE_RAY_DTYPE); texels = np.empty((height, width), BAKE_TEXEL_DTYPE)
+        self._check(self._L.tb_run_bake_raster(self._ctx, width, height, p.shape[0], _np_ptr(p), _np_ptr(nrm), _np_ptr(uv), tri.shape[0], _np_ptr(tri),
+                                               _np_ptr(rays), _np_ptr(texels)))
+        return rays, texels
+
+    def RunBakeDilate(self, rgba, passes):
+        """bake_dilate on a host picture: `passes` 3 x 3 fill passes of an (H, W, 4) float32 array; returns the filled picture."""
+        a = np.ascontiguousarray(rgba, np.float32)
+        if a.ndim != 3 or a.shape[2] != 4 or not a.shape[0] or not a.shape[1] or a.shape[0] > BAKE_MAX_SIDE or a.shape[1] > BAKE_MAX_SIDE:
+            raise ValueError("RunBakeDilate: rgba is an (H, W, 4) picture with sides of 1 to %d" % BAKE_MAX_SIDE)
+        _check_count("RunBakeDilate", "passes", passes, 0, BAKE_MAX_DILATE)
+        out = np.empty_like(a)
+        self._check(self._L.tb_run_bake_dilate(self._ctx, a.shape[1], a.shape[0], passes, _np_ptr(a), _np_ptr(out)))
+        return out
 
     # -- dynamic scenes (DESIGN.md section 21) ----------------------------------------------------
     def _update_vertices(self, what, fn_name, a, first):

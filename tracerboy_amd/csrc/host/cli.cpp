@@ -208,6 +208,46 @@ static int compareFiles(int argc, char** argv)
     return 0;
 }
 
+/* scene.pbrt --bake-lightmap WxH --bake-samples N [--bake-dilate P] [--device I] --out lm.pfm|.exr (tb_bake_lightmap): the
+ * scene's own UVs, default settings, samples [0, N), P fill passes (default 2); the RGBA32F atlas is written as it is.  A bake is no render: every
+ * other flag -- render, denoise, upscale, resume, --ranks ... -- is refused here (exit status 2), before any device call. */
+static bool isBake(int argc, char** argv) { for (int i = 2; i < argc; i++) if (!strcmp(argv[i], "--bake-lightmap")) return true; return false; }
+static int bakeLightmap(int argc, char** argv)
+{
+    std::string out; int device = 0; unsigned long long w = 0, h = 0; long long samples = 0, dilate = 2; bool sized = false;
+    for (int i = 2; i < argc; i += 2) {
+        const std::string k = argv[i];
+        if (k != "--bake-lightmap" && k != "--bake-samples" && k != "--bake-dilate" && k != "--out" && k != "--device") {
+            fprintf(stderr, "--bake-lightmap goes with --bake-samples, --bake-dilate, --device and --out only, not %s: a bake is no render\n", k.c_str()); return 2; }
+        if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", k.c_str()); return 2; }
+        const char* v = argv[i + 1]; char* end = nullptr;
+        if (k == "--bake-lightmap") { w = strtoull(v, &end, 10); const char* x = end; h = (x != v && *x == 'x') ? strtoull(x + 1, &end, 10) : 0;
+            if (x == v || *x != 'x' || end == x + 1 || *end || w < 1 || h < 1 || w > 8192 || h > 8192) { fprintf(stderr, "--bake-lightmap is WxH, both 1 to 8192\n"); return 2; }
+            sized = true; }
+        else if (k == "--bake-samples") { samples = strtoll(v, &end, 10);
+            if (end == v || *end || samples < 1 || samples > (1ll << 24)) { fprintf(stderr, "--bake-samples is 1 to 2^24\n"); return 2; } }
+        else if (k == "--bake-dilate") { dilate = strtoll(v, &end, 10);
+            if (end == v || *end || dilate < 0 || dilate > 16) { fprintf(stderr, "--bake-dilate is 0 to 16\n"); return 2; } }
+        else if (k == "--out") out = v; else device = atoi(v);
+    }
+    if (!sized || samples < 1) { fprintf(stderr, "--bake-lightmap WxH needs --bake-samples N\n"); return 2; }
+    const bool floatFile = out.size() >= 4 && (out.compare(out.size() - 4, 4, ".pfm") == 0 || out.compare(out.size() - 4, 4, ".exr") == 0);
+    if (!floatFile) { fprintf(stderr, "--bake-lightmap writes --out lm.pfm or lm.exr: the atlas is linear RGBA32F\n"); return 2; }
+    tb_context* ctx = nullptr;
+    int rc = tb_create(&ctx, device);
+    if (rc) return fail(nullptr, "tb_create", rc);
+    if ((rc = tb_load_scene(ctx, argv[1]))) return fail(ctx, "tb_load_scene", rc);
+    std::vector<float> rgba((size_t)w * h * 4);
+    const tb_bake_call call = {(uint32_t)w, (uint32_t)h, 0u, (uint32_t)samples, (uint32_t)dilate, 0u};
+    if ((rc = tb_bake_lightmap(ctx, nullptr, 0.0f, &call, nullptr, rgba.data()))) return fail(ctx, "tb_bake_lightmap", rc);
+    if ((rc = tb_write_image_f32(out.c_str(), (uint32_t)w, (uint32_t)h, rgba.data()))) return fail(ctx, "tb_write_image_f32", rc);
+    printf("{\"bake\": \"%llux%llu\", \"samples\": %lld, \"dilate\": %lld, \"covered\": %lld, \"raster_us\": %lld, \"trace_us\": %lld, \"finish_us\": %lld}\n", w, h, samples,
+        dilate, (long long)tb_get_option(ctx, "last_bake_covered"), (long long)tb_get_option(ctx, "last_bake_raster_us"),
+        (long long)tb_get_option(ctx, "last_bake_trace_us"), (long long)tb_get_option(ctx, "last_bake_finish_us"));
+    tb_destroy(ctx);
+    return 0;
+}
+
 /* ---- RCCL, loaded at run time: the handful of entry points the gather needs (rccl.h) ---- */
 struct RcclId { char internal[128]; };                 /* ncclUniqueId */
 struct Rccl {
@@ -280,6 +320,7 @@ int main(int argc, char** argv)
     if (argc < 2) { fprintf(stderr,
         "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C --reference FILE --metrics-out FILE --metrics-every N --error-map f.pfm --visualize-rays X,Y --visualize-frames A:B --visualize-width R --visualize-depth D --visualize-count N --paths-out f.jsonl]\n       tracerboy-hip --compare A B [--metrics-out FILE --device I]\n"); return 2; }
     if (!strcmp(argv[1], "--compare")) return compareFiles(argc, argv);
+    if (isBake(argc, argv)) return bakeLightmap(argc, argv);
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);
     uint32_t W = 0, H = 0, spp = 64; int depth = -1, device = 0, builder = 0, blue = -1, ranks = 1; float t = 0.0f;

@@ -19,6 +19,7 @@
  *   context_dynamic.cpp dynamic scenes: staged vertices and instance transforms, the refit commit, the host copies' refresh
  *   context_rays.cpp    ray queries: tb_trace_rays, closest hits and any-hit occlusion of a caller's rays, host arrays or device buffers
  *   context_radiance.cpp radiance queries: tb_trace_radiance, the path tracer on a caller's rays, and tb_make_camera_rays
+ *   context_bake.cpp    lightmap baking: tb_bake_lightmap, a UV atlas rasterised, its texels traced by the radiance query, resolved and dilated
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -260,6 +261,18 @@ struct tb_context {
         tbctx::DevEvent ev[2]; float lastMs = 0.0f;
     };
     std::unique_ptr<Dynamic> dyn;
+    /* lightmap baking (context_bake.cpp): made at the first tb_bake_lightmap of a scene, released with the scene
+     * (releaseScene); a context that never bakes holds none of it.  rays, texels, sums: the atlas in row-major order, what tb_read_bake returns and
+     * TB_BAKE_ACCUMULATE adds to; rgba: the resolve's and the fill passes' ping-pong; scratch: the rasteriser's (bake_launch.h); triVerts,
+     * positions: the scene's triangles and vertices as the rasteriser reads them, positions of scene generation positionsOf.  held: the buffers
+     * hold a finished bake of width x height, rasterised at scene generation rasterOf.  ev: before the raster, after it, before the resolve,
+     * after the last fill pass (options last_bake_raster_us, last_bake_finish_us; the trace between is the radiance query's own two events) */
+    struct Bake {
+        DevBuf rays, texels, sums, rgba[2], scratch, triVerts, positions, covered;
+        uint32_t width = 0, height = 0, rasterOf = 0, positionsOf = 0xffffffffu, lastCovered = 0; bool held = false;
+        tbctx::DevEvent ev[4]; float lastRasterMs = 0.0f, lastTraceMs = 0.0f, lastFinishMs = 0.0f;
+    };
+    std::unique_ptr<Bake> bake;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;

@@ -86,6 +86,11 @@ const Query kQueries[] = {
      * per lane, 1 the refilling grid) and how many launches it was split into */
     Q("last_radiance_us", microseconds(c->rad.lastMs)) Q("last_radiance_variant", c->rad.lastVariant) Q("last_radiance_form", c->rad.lastForm)
     Q("last_radiance_launches", c->rad.lastLaunches)
+    /* lightmap baking: the last bake's rasteriser, its query's launches, its resolve and fill passes (HIP events); the texels
+     * that have a triangle */
+    Q("last_bake_raster_us", microseconds(c->bake ? c->bake->lastRasterMs : 0.0f)) Q("last_bake_trace_us", microseconds(c->bake ? c->bake->lastTraceMs : 0.0f))
+    Q("last_bake_finish_us", microseconds(c->bake ? c->bake->lastFinishMs : 0.0f)) Q("last_bake_covered", c->bake ? c->bake->lastCovered : 0u)
+    Q("bake_width", c->bake && c->bake->held ? c->bake->width : 0u) Q("bake_height", c->bake && c->bake->held ? c->bake->height : 0u) /* of the bake held; 0: none */
     Q("last_copy_waves", c->lastCopyWaves)
     Q("last_adaptive", c->lastAdaptive ? 1 : 0) /* the adaptive launch: did the last call run it */
     /* sample budgets: one is set; the last call was planned under it (its live pixels: last_live_pixels) */

@@ -2,7 +2,7 @@
  * caller's rays, per ray the sum of its samples out, on host arrays (staged like the test hooks, nothing kept) or on device buffers.
  * Reads the scene, the camera and the options; writes nothing of the context but the query's own work counter and overflow stacks. */
 #include "context_internal.h"
-#include "../kernels/rad_launch.h"
+#include "radiance_trace.h"
 
 #include <cstdlib>
 
@@ -37,6 +37,44 @@ int variantIdOf(uint32_t features)
 
 } // namespace
 
+/* The launch of a query on device buffers, waited for: the feature set, the stack plan, the form and the grid, the frame constants, rad_launch between
+ * the query's two events.  tb_trace_radiance and tb_bake_lightmap (context_bake.cpp) both end here.  who: the entry point's name, for the refusal. */
+int tbctx::traceRadianceOnDevice(tb_context* c, const char* who, const tb_output_settings& s, float time, const RadCall& k, uint64_t n, const TbRadianceRay* rays,
+    TbFloat4* out)
+{
+    /* the feature set: pickVariantAndPlan's loop over the sets the kernel is compiled for */
+    uint32_t need = c->sceneFeatures | settingsFeatureMask(c, s, false);
+    const bool alphaTest = opt<OPT_alpha_test>(c) != 0;
+    if (alphaTest) need |= PT_FEAT_EXT;
+    const int numSets = (int)(sizeof(kRadFeatureSets) / sizeof(kRadFeatureSets[0]));
+    RadPlan plan{};
+    plan.features = kRadFeatureSets[numSets - 1];
+    for (int i = 0; i < numSets; i++) if ((need & ~kRadFeatureSets[i]) == 0) { plan.features = kRadFeatureSets[i]; break; }
+    plan.stack = guide_stack_plan(c->ds.stackDepth, (uint32_t)std::max<int64_t>(0, opt<OPT_stack_overflow_max>(c)),
+        (uint32_t)std::max<int64_t>(0, std::min<int64_t>(opt<OPT_stack_lds_cap>(c), 0xffff)));
+    if (!plan.stack.ok) return fail(c, TB_E_UNSUPPORTED, std::string(who) + ": traversal stack of depth " + std::to_string(c->ds.stackDepth) +
+        " does not fit LDS; unsupported");
+    plan.form = (uint32_t)diagnostic("TB_RAD_FORM", 0, 1, defaultForm(n, k.numSamples, c->ds.numTris));
+    plan.chunk = (uint32_t)diagnostic("TB_RAD_CHUNK", 16, 65536, RAD_CHUNK);
+    plan.refillMin = (uint32_t)diagnostic("TB_RAD_REFILL", 1, 64, RAD_REFILL_MIN);
+    plan.maxPaths = (uint32_t)diagnostic("TB_RAD_MAX_PATHS", 1, 0xffffffffll, RAD_MAX_PATHS);
+    HIP_TRY(rad_plan_grid(&plan, n, (uint32_t)diagnostic("TB_RAD_GRID", 1, 65535, 0)));
+    if (plan.stack.overflowEntries) ensure(c->rad.overflow, (size_t)plan.stack.overflowEntries * plan.stack.lanes * 4);
+    if (plan.form && !c->rad.counter.p) ensure(c->rad.counter, 64);
+    TbDeviceScene ds = c->ds; ds.alphaTest = alphaTest ? 1u : 0u;
+    TbPerFrameConstants pf;
+    MakeFrameConstants(c->scene, c->camera, s, k.firstSample, time, 0xffffffffu, 0xffffffffu, pf);
+    if (pf.OutputMode == TB_OUTPUT_TYPE_HEATMAP) pf.OutputMode = TB_OUTPUT_TYPE_LIT; /* a query has no heatmap: the path goes on past its first hit */
+    HIP_TRY(hipEventRecord(c->rad.ev[0].create(), c->stream));
+    HIP_TRY(rad_launch(c->stream, &ds, &pf, &k, &plan, plan.stack.overflowEntries ? (uint32_t*)c->rad.overflow.p : nullptr, (uint32_t*)c->rad.counter.p, n,
+        rays, out, &c->rad.lastLaunches));
+    HIP_TRY(hipEventRecord(c->rad.ev[1].create(), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hipEventElapsedTime(&c->rad.lastMs, c->rad.ev[0], c->rad.ev[1]) != hipSuccess) c->rad.lastMs = 0.0f;
+    c->rad.lastVariant = variantIdOf(plan.features); c->rad.lastForm = (int)plan.form;
+    return TB_OK;
+}
+
 extern "C" int tb_trace_radiance(tb_context* c, const tb_output_settings* settings, float time, const TbRadianceCall* call, uint64_t n,
     const TbRadianceRay* rays, TbFloat4* out)
 {
@@ -56,39 +94,11 @@ extern "C" int tb_trace_radiance(tb_context* c, const tb_output_settings* settin
             if (const char* no = devicePointerRefusal(c, rays, rayBytes)) return fail(c, TB_E_INVALID, std::string("tb_trace_radiance: rays: ") + no);
             if (const char* no = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_trace_radiance: out: ") + no);
         }
-        /* the feature set: pickVariantAndPlan's loop over the sets the kernel is compiled for */
-        uint32_t need = c->sceneFeatures | settingsFeatureMask(c, s, false);
-        const bool alphaTest = opt<OPT_alpha_test>(c) != 0;
-        if (alphaTest) need |= PT_FEAT_EXT;
-        const int numSets = (int)(sizeof(kRadFeatureSets) / sizeof(kRadFeatureSets[0]));
-        RadPlan plan{};
-        plan.features = kRadFeatureSets[numSets - 1];
-        for (int i = 0; i < numSets; i++) if ((need & ~kRadFeatureSets[i]) == 0) { plan.features = kRadFeatureSets[i]; break; }
-        plan.stack = guide_stack_plan(c->ds.stackDepth, (uint32_t)std::max<int64_t>(0, opt<OPT_stack_overflow_max>(c)),
-            (uint32_t)std::max<int64_t>(0, std::min<int64_t>(opt<OPT_stack_lds_cap>(c), 0xffff)));
-        if (!plan.stack.ok) return fail(c, TB_E_UNSUPPORTED, "tb_trace_radiance: traversal stack of depth " + std::to_string(c->ds.stackDepth) +
-            " does not fit LDS; unsupported");
-        plan.form = (uint32_t)diagnostic("TB_RAD_FORM", 0, 1, defaultForm(n, call->num_samples, c->ds.numTris));
-        plan.chunk = (uint32_t)diagnostic("TB_RAD_CHUNK", 16, 65536, RAD_CHUNK);
-        plan.refillMin = (uint32_t)diagnostic("TB_RAD_REFILL", 1, 64, RAD_REFILL_MIN);
-        plan.maxPaths = (uint32_t)diagnostic("TB_RAD_MAX_PATHS", 1, 0xffffffffll, RAD_MAX_PATHS);
-        HIP_TRY(rad_plan_grid(&plan, n, (uint32_t)diagnostic("TB_RAD_GRID", 1, 65535, 0)));
-        if (plan.stack.overflowEntries) ensure(c->rad.overflow, (size_t)plan.stack.overflowEntries * plan.stack.lanes * 4);
-        if (plan.form && !c->rad.counter.p) ensure(c->rad.counter, 64);
         DevBuf dRays, dOut; /* the host path's staging: temporary, like the test hooks' */
         if (!device) { dRays = staged(rays, rayBytes); dOut = accumulate ? staged(out, outBytes) : scratch(outBytes); }
-        TbDeviceScene ds = c->ds; ds.alphaTest = alphaTest ? 1u : 0u;
-        TbPerFrameConstants pf;
-        MakeFrameConstants(c->scene, c->camera, s, call->first_sample, time, 0xffffffffu, 0xffffffffu, pf);
-        if (pf.OutputMode == TB_OUTPUT_TYPE_HEATMAP) pf.OutputMode = TB_OUTPUT_TYPE_LIT; /* a query has no heatmap: the path goes on past its first hit */
-        RadCall k{call->first_sample, call->num_samples, (call->mode_and_flags & 0xffu) == TB_RADIANCE_HEMISPHERE ? 1u : 0u, accumulate ? 1u : 0u, call->seed_advance};
-        HIP_TRY(hipEventRecord(c->rad.ev[0].create(), c->stream));
-        HIP_TRY(rad_launch(c->stream, &ds, &pf, &k, &plan, plan.stack.overflowEntries ? (uint32_t*)c->rad.overflow.p : nullptr, (uint32_t*)c->rad.counter.p, n,
-            device ? rays : (const TbRadianceRay*)dRays.p, device ? out : (TbFloat4*)dOut.p, &c->rad.lastLaunches));
-        HIP_TRY(hipEventRecord(c->rad.ev[1].create(), c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (hipEventElapsedTime(&c->rad.lastMs, c->rad.ev[0], c->rad.ev[1]) != hipSuccess) c->rad.lastMs = 0.0f;
-        c->rad.lastVariant = variantIdOf(plan.features); c->rad.lastForm = (int)plan.form;
+        const RadCall k{call->first_sample, call->num_samples, (call->mode_and_flags & 0xffu) == TB_RADIANCE_HEMISPHERE ? 1u : 0u, accumulate ? 1u : 0u, call->seed_advance};
+        const int rc = traceRadianceOnDevice(c, "tb_trace_radiance", s, time, k, n, device ? rays : (const TbRadianceRay*)dRays.p, device ? out : (TbFloat4*)dOut.p);
+        if (rc != TB_OK) return rc;
         if (!device) copyBack(out, dOut);
         return TB_OK;
     });

@@ -149,6 +149,32 @@ int tb_radiance_refusal(const TbRadianceCall* call, uint64_t n, const void* rays
     return no ? TB_E_INVALID : TB_OK;
 }
 
+/* Why tb_bake_lightmap refuses its arguments before it looks at the context: pure tests, in the order the header lists them. */
+static const char* bakeRefusal(const tb_bake_call* call, const void* uv, const void* rgbaOut)
+{
+    if (!call) return "null call";
+    if (call->width == 0 || call->height == 0) return "a side of the atlas is 0";
+    if (call->width > 8192u || call->height > 8192u) return "a side of the atlas is above 8192";
+    if (call->flags & ~(TB_BAKE_DEVICE | TB_BAKE_ACCUMULATE)) return "unknown flag bits";
+    if (call->num_samples == 0) return "num_samples is 0";
+    if (call->num_samples > (1u << 24)) return "more than 2^24 samples per texel";
+    if ((uint64_t)call->first_sample + call->num_samples > (1ull << 32)) return "first_sample + num_samples passes 2^32";
+    if (call->dilate_passes > 16u) return "more than 16 dilate passes";
+    if (!rgbaOut) return "null rgba_out";
+    if (call->flags & TB_BAKE_DEVICE) {
+        if ((uintptr_t)rgbaOut & 15u) return "the device picture is not 16-B aligned";
+        if ((uintptr_t)uv & 3u) return "the device UVs are not 4-B aligned";
+    }
+    return nullptr;
+}
+
+int tb_bake_refusal(const tb_bake_call* call, const void* uv, const void* rgbaOut, char* why, uint32_t whyBytes)
+{
+    const char* no = bakeRefusal(call, uv, rgbaOut);
+    if (why && whyBytes) { strncpy(why, no ? no : "", whyBytes - 1); why[whyBytes - 1] = 0; }
+    return no ? TB_E_INVALID : TB_OK;
+}
+
 int tb_unpack_gathered_host(uint32_t W, uint32_t H, uint32_t world, uint32_t tw, uint32_t th, const float* const* perRank, float* full)
 {
     if (!perRank || !full || world == 0 || tw == 0 || th == 0) return TB_E_INVALID;
