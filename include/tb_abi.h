@@ -374,4 +374,27 @@ typedef struct TbRayStats {
     uint64_t hitsShaded, materialFetches, lightSamples, samples, rays;
 } TbRayStats;
 
+/* ---- scenes from caller arrays (tracerboy_hip.h tb_load_meshes; no reference counterpart: its scenes come from files) ---- */
+#define TB_MESH_NORMALS_FLAT   0u      /* the loader's rule for a mesh without normals: the last triangle to touch a vertex wins */
+#define TB_MESH_NORMALS_SMOOTH 1u      /* include/tb_normals.h: area-weighted sums of the face vectors */
+#define TB_MESH_DEVICE         0x100u  /* every array pointer of every mesh is a device pointer (the value and meaning of TB_RAYS_DEVICE) */
+typedef struct tb_mesh_desc {
+    const float* positions; uint32_t n_vertices;          /* xyz triples, world space */
+    const uint32_t* indices; uint32_t n_triangles;        /* 3 per triangle, mesh-local */
+    const float* normals_or_null;                         /* xyz per vertex, stored AS GIVEN (like tb_update_normals: the caller normalises) */
+    const float* uvs_or_null;                             /* uv per vertex, stored as given (no V flip: these are not file UVs); null: (0, 0) */
+    uint32_t material;                                    /* index into the call's material table */
+    uint32_t normals_mode;                                /* read when normals_or_null is null: TB_MESH_NORMALS_FLAT or TB_MESH_NORMALS_SMOOTH */
+} tb_mesh_desc;
+struct tb_camera;
+typedef struct tb_scene_desc {
+    const tb_mesh_desc* meshes; uint32_t n_meshes;
+    const TbMaterial* materials; uint32_t n_materials;
+    const struct tb_camera* camera_or_null;
+    const float* env_rgba_or_null; uint32_t env_width, env_height;   /* RGBA32F, top row first, always host memory; null: none (black) */
+    float env_scale[3];                                               /* EnvironmentMapColorScale; read only with an environment */
+    uint32_t film_width, film_height;                                 /* 0: 1920 x 1080 */
+    uint32_t flags;                                                   /* 0 or TB_MESH_DEVICE */
+} tb_scene_desc;
+
 #endif /* TB_ABI_H */

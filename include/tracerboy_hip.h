@@ -723,6 +723,44 @@ int tb_set_instance_transforms(tb_context* ctx, uint32_t first_instance, uint32_
 int tb_commit_geometry(tb_context* ctx, uint32_t flags);
 int tb_geometry_vertex_range(tb_context* ctx, uint32_t geometry, uint32_t* first_vertex, uint32_t* n_vertices);
 
+/* ---- scenes from caller arrays; smooth normals recomputed on the device (no reference counterpart) -----------------
+ * tb_load_meshes: a scene from vertices and faces in memory instead of a .pbrt / .pbf file (tb_abi.h tb_mesh_desc, tb_scene_desc).  Every mesh becomes
+ * one geometry (hit-group record) in the order given, its vertices numbered back to back -- section 21's numbering: tb_geometry_vertex_range(g) is
+ * mesh g.  Positions, indices, the per-triangle arrays and the hit-group records come out of the functions the PBRT conversion uses, with positions,
+ * normals and UVs stored as given.  A vertex record is Normal (given, flat or smooth), UV (given or 0) and Tangent (0, 0, 1).  A mesh whose material
+ * carries TB_MAT_LIGHT gets one area TbLight per triangle (LightColor the material's emissive; N0..N2 the vertex records' normals where normals were
+ * given or smooth, the loader's face normal in flat mode); the library sets no flag on the caller's behalf and makes no directional lights.  The scene
+ * is one-level; materials are copied as given, FlipTextureUVs is 0, the environment (host memory, also under TB_MESH_DEVICE) gets the identity
+ * transform and env_scale; without one the scene has none, as a file without one.  camera_or_null: taken as it stands; null: the procedural scenes'
+ * look-at camera with eye = c + (0, 0.35 d, d), target c, 35 degrees, c the centre of the vertices' bounds and d twice their diagonal (1 where that
+ * is 0).  Then the scene is built and uploaded as a loaded one is: every option a file load honours applies ("bvh_builder", "scene_in_lds",
+ * "node_order" ...), and renders, queries, bakes, updates, render states and the scene digest work as on a loaded scene.
+ * TB_MESH_DEVICE: positions, indices, normals and UVs of every mesh are device pointers of the context's device, checked as section 20 checks its
+ * pointers (device memory, this device, long enough).  They are read to the host ONCE, by copies on the context's stream, and then pass the host
+ * checks below: the tree build and every host consumer work from the host copy.  A build that never leaves the device is not offered.
+ * Refusals, in this order, the message naming the mesh and the element where there is one; a refused call leaves the context's scene as it was.
+ * tb_meshes_refusal's (TB_E_INVALID): a null desc; no meshes or no materials; a null positions or indices pointer; 0 vertices or 0 triangles; a
+ * material index at or past n_materials; an unknown normals mode or flag bit; an environment with a side of 0 or above 16384; more than 2^24 - 1
+ * triangles or 2^27 - 1 vertices in total, index bytes past 2^32.  TB_E_UNSUPPORTED: a tb_create_multi group; a material that names a texture.
+ * TB_E_INVALID: under TB_MESH_DEVICE a pointer that is not memory of the context's device.  TB_E_INVALID: an index at or past its mesh's n_vertices;
+ * a position, normal, UV or environment value that is not finite.
+ * tb_host_scene_from_meshes: the host half (host arrays only; TB_MESH_DEVICE is TB_E_INVALID), for tb_host_scene_* and the oracle.
+ * tb_host_smooth_normals: include/tb_normals.h's rule over one mesh, 3 floats per vertex into normals_out; a vertex that no triangle names keeps
+ * what normals_out holds.  TB_E_INVALID: a null pointer, an index at or past n_vertices.
+ * tb_recompute_normals: staged like tb_update_normals -- a MARK on the vertices first_vertex .. first_vertex + n_vertices.  The next
+ * tb_commit_geometry makes their normals again by that rule, on the device, per mesh, from the positions as that commit leaves them, and writes them
+ * into the Normal field of the vertex records; UVs and tangents stay.  A face vector is taken over all three of its vertices, marked or not.  Order
+ * inside one commit: staged positions, the refit, staged explicit normals, marked ranges -- a recomputation wins over tb_update_normals for the same
+ * vertex.  A commit with only marks staged counts as a change.  Vertices of a geometry whose material carries TB_MAT_LIGHT are skipped and stay as
+ * they are (section 21 does not let them move, and their TbLights carry their normals), so a whole-scene call works on a scene with a light.
+ * Refusals as for tb_update_normals: no scene, a range past the end, a group, a two-level scene, a pre-split tree; n_vertices 0 is TB_OK.  The
+ * tables (per triangle its vertex numbers in geometry order, per vertex the face-vector slots of its corners) are made at the first call and
+ * released with the scene; "last_refit_us" includes the two launches. */
+int tb_load_meshes(tb_context* ctx, const tb_scene_desc* desc);
+int tb_meshes_refusal(const tb_scene_desc* desc, char* why_or_null, uint32_t why_bytes);   /* host only, pure, like tb_bake_refusal */
+int tb_host_smooth_normals(const float* positions, uint32_t n_vertices, const uint32_t* indices, uint32_t n_triangles, float* normals_out);
+int tb_recompute_normals(tb_context* ctx, uint32_t first_vertex, uint32_t n_vertices);
+
 /* ---- neural still denoiser -----------------------------------------------------
  * <-> the reference's TAAUpscaler::OIDN path (TracerBoy.cpp:3306-3322; OpenImageDenoise.cpp:855-1039): the OIDN U-Net -- 16 convolutions of 3 x 3,
  * four 2 x 2 max-pools on the way down, four nearest upsamples x 2 on the way up, each concatenated in front of the skip tensor of its size, ReLU
@@ -916,6 +954,8 @@ typedef struct tb_host_scene tb_host_scene;
  * triangles with the emptiest boxes, <= 127) << 24 -- option "presplit"; a zero field leaves the library's own choice. */
 int tb_host_scene_load(const char* pbrt_path, int bvh_builder, int load_flags, tb_host_scene** out, char* err, uint32_t err_len);
 int tb_host_scene_procedural(int kind, uint32_t target_triangles, uint32_t seed, int bvh_builder, tb_host_scene** out, char* err, uint32_t err_len);
+/* the host half of tb_load_meshes (above): host arrays only */
+int tb_host_scene_from_meshes(const tb_scene_desc* desc, int bvh_builder, tb_host_scene** out, char* err, uint32_t err_len);
 void tb_host_scene_free(tb_host_scene* s);
 int tb_host_scene_view_get(tb_host_scene* s, TbSceneView* view);          /* pointers owned by s */
 int tb_host_scene_camera(tb_host_scene* s, tb_camera* cam);

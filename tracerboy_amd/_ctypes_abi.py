@@ -243,6 +243,20 @@ class tb_conv_desc(C.Structure):
 
 
 TB_UPDATE_DEVICE, TB_GEOMETRY_REBUILD = 0x100, 1  # include/tracerboy_hip.h: tb_update_positions / tb_update_normals flags; tb_commit_geometry flags
+TB_MESH_NORMALS_FLAT, TB_MESH_NORMALS_SMOOTH, TB_MESH_DEVICE = 0, 1, 0x100  # include/tb_abi.h: tb_mesh_desc.normals_mode; tb_scene_desc.flags
+
+
+class tb_mesh_desc(C.Structure):
+    """include/tb_abi.h tb_mesh_desc: one mesh of a scene from arrays (tb_load_meshes)."""
+    _fields_ = [("positions", C.c_void_p), ("n_vertices", C.c_uint32), ("indices", C.c_void_p), ("n_triangles", C.c_uint32),
+                ("normals_or_null", C.c_void_p), ("uvs_or_null", C.c_void_p), ("material", C.c_uint32), ("normals_mode", C.c_uint32)]
+
+
+class tb_scene_desc(C.Structure):
+    """include/tb_abi.h tb_scene_desc: the meshes, materials, camera, environment and film of a scene from arrays."""
+    _fields_ = [("meshes", C.POINTER(tb_mesh_desc)), ("n_meshes", C.c_uint32), ("materials", C.POINTER(TbMaterial)), ("n_materials", C.c_uint32),
+                ("camera_or_null", C.POINTER(tb_camera)), ("env_rgba_or_null", C.c_void_p), ("env_width", C.c_uint32), ("env_height", C.c_uint32),
+                ("env_scale", C.c_float * 3), ("film_width", C.c_uint32), ("film_height", C.c_uint32), ("flags", C.c_uint32)]
 TB_COMPARE_SSIM, TB_COMPARE_SUMS = 1, 2          # tb_compare_settings.flags
 TB_COMPARE_MEAN, TB_COMPARE_DENOISED = 0, 1      # tb_compare's surface
 

@@ -131,6 +131,11 @@ def lib():
         "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
         "tb_commit_geometry": (C.c_int, [vp, C.c_uint32]),
         "tb_geometry_vertex_range": (C.c_int, [vp, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
+        "tb_load_meshes": (C.c_int, [vp, P(abi.tb_scene_desc)]),
+        "tb_meshes_refusal": (C.c_int, [P(abi.tb_scene_desc), C.c_char_p, C.c_uint32]),
+        "tb_host_scene_from_meshes": (C.c_int, [P(abi.tb_scene_desc), C.c_int, P(vp), C.c_char_p, C.c_uint32]),
+        "tb_host_smooth_normals": (C.c_int, [vp, C.c_uint32, vp, C.c_uint32, vp]),
+        "tb_recompute_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
         "tb_default_compare_settings": (None, [P(abi.tb_compare_settings)]),
         "tb_run_compare": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, P(abi.tb_compare_settings), P(abi.tb_compare_result), vp, vp]),
         "tb_set_reference": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -459,6 +464,130 @@ def _check_vertex_array(what, a, first, device):
     return _is_torch_tensor(a)
 
 
+# scenes from arrays (tb_load_meshes)
+MESH_NORMALS_FLAT, MESH_NORMALS_SMOOTH, MESH_DEVICE = 0, 1, 0x100
+
+
+class Mesh:
+    """One mesh of a scene from arrays.  positions (n, 3) float32, indices (m, 3) uint32, normals (n, 3) / uvs (n, 2) float32 or None: numpy arrays,
+    or all of them contiguous torch tensors on the context's device (indices then uint32 or non-negative int32).  material: an index into the call's
+    material table.  smooth: read without normals -- True: include/tb_normals.h's smooth normals, False: the loader's flat ones."""
+
+    def __init__(self, positions, indices, normals=None, uvs=None, material=0, smooth=False):
+        self.positions, self.indices, self.normals, self.uvs, self.material, self.smooth = positions, indices, normals, uvs, material, smooth
+
+
+def _check_meshes(what, meshes, device):
+    """What LoadMeshes / HostScene.from_meshes accept, checked before any library call: True when the arrays are torch tensors (the device path), False for
+    numpy arrays; ValueError otherwise (device None: host arrays only)."""
+    meshes = list(meshes)
+    kinds = set()
+    for k, m in enumerate(meshes):
+        if not isinstance(m, Mesh):
+            raise ValueError("%s: mesh %d is an api.Mesh, not %s" % (what, k, type(m).__name__))
+        if isinstance(m.material, bool) or not isinstance(m.material, (int, np.integer)) or m.material < 0 or m.material > 0xffffffff:
+            raise ValueError("%s: mesh %d: material is an index, not %r" % (what, k, m.material))
+        for name, a, cols, optional in (("positions", m.positions, 3, False), ("indices", m.indices, 3, False), ("normals", m.normals, 3, True), ("uvs", m.uvs, 2, True)):
+            if a is None:
+                if optional:
+                    continue
+                raise ValueError("%s: mesh %d: %s is missing" % (what, k, name))
+            index = name == "indices"
+            if _is_torch_tensor(a):
+                import torch
+                kinds.add("torch")
+                if device is None:
+                    raise ValueError("%s: mesh %d: %s is a torch tensor; a host scene takes numpy arrays" % (what, k, name))
+                ok = (a.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))) if index else a.dtype == torch.float32
+                if not ok or a.dim() != 2 or a.shape[1] != cols:
+                    raise ValueError("%s: mesh %d: %s is %s of shape (n, %d), not %s %s" % (what, k, name, "uint32 / int32" if index else "float32", cols, a.dtype, tuple(a.shape)))
+                if not a.is_contiguous():
+                    raise ValueError("%s: mesh %d: the tensor %s is not contiguous" % (what, k, name))
+                if a.device.type != "cuda" or a.device.index != device:
+                    raise ValueError("%s: mesh %d: %s is on %s, the context on cuda:%d" % (what, k, name, a.device, device))
+            elif isinstance(a, np.ndarray):
+                kinds.add("numpy")
+                if a.dtype != (np.uint32 if index else np.float32) or a.ndim != 2 or a.shape[1] != cols:
+                    raise ValueError("%s: mesh %d: %s is %s of shape (n, %d), not %s %s" % (what, k, name, "uint32" if index else "float32", cols, a.dtype, a.shape))
+                if not a.flags["C_CONTIGUOUS"]:
+                    raise ValueError("%s: mesh %d: the array %s is not contiguous" % (what, k, name))
+            else:
+                raise ValueError("%s: mesh %d: %s is a numpy array or a torch tensor, not %s" % (what, k, name, type(a).__name__))
+            if not index and name != "positions" and int(a.shape[0]) != int(m.positions.shape[0]):
+                raise ValueError("%s: mesh %d: %s has %d rows, the mesh %d vertices" % (what, k, name, a.shape[0], m.positions.shape[0]))
+            if int(a.shape[0]) > 0xffffffff:
+                raise ValueError("%s: mesh %d: %s has too many rows" % (what, k, name))
+    if len(kinds) > 1:
+        raise ValueError("%s: numpy arrays and torch tensors are mixed" % what)
+    on_device = kinds == {"torch"}
+    if on_device:
+        import torch
+        for k, m in enumerate(meshes):
+            if m.indices.dtype == torch.int32 and m.indices.numel() and int(m.indices.min()) < 0:
+                raise ValueError("%s: mesh %d: an int32 index is negative" % (what, k))
+    return on_device
+
+
+def _scene_desc(what, meshes, materials, camera, environment, env_scale, film, device):
+    """(tb_scene_desc, what keeps its arrays alive) from the Python arguments; every check of _check_meshes first."""
+    meshes = list(meshes)
+    on_device = _check_meshes(what, meshes, device)
+    keep = []
+    mats = list(materials)
+    for i, mt in enumerate(mats):
+        if not isinstance(mt, abi.TbMaterial):
+            raise ValueError("%s: material %d is a TbMaterial, not %s" % (what, i, type(mt).__name__))
+    if environment is not None:
+        if not isinstance(environment, np.ndarray) or environment.dtype != np.float32 or environment.ndim != 3 or environment.shape[2] != 4 or \
+                not environment.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s: environment is a contiguous float32 numpy array of shape (H, W, 4)" % what)
+    if len(tuple(env_scale)) != 3 or len(tuple(film)) != 2:
+        raise ValueError("%s: env_scale has 3 values and film 2" % what)
+    ptr = (lambda a: C.c_void_p(a.data_ptr() or None)) if on_device else _np_ptr
+    md = (abi.tb_mesh_desc * max(len(meshes), 1))()
+    for k, m in enumerate(meshes):
+        md[k].positions = ptr(m.positions); md[k].n_vertices = int(m.positions.shape[0])
+        md[k].indices = ptr(m.indices); md[k].n_triangles = int(m.indices.shape[0])
+        md[k].normals_or_null = ptr(m.normals) if m.normals is not None else None
+        md[k].uvs_or_null = ptr(m.uvs) if m.uvs is not None else None
+        md[k].material = int(m.material); md[k].normals_mode = MESH_NORMALS_SMOOTH if m.smooth else MESH_NORMALS_FLAT
+        keep.append((m.positions, m.indices, m.normals, m.uvs))
+    ma = (abi.TbMaterial * max(len(mats), 1))(*mats)
+    d = abi.tb_scene_desc()
+    d.meshes = C.cast(md, C.POINTER(abi.tb_mesh_desc)) if meshes else None; d.n_meshes = len(meshes)
+    d.materials = C.cast(ma, C.POINTER(abi.TbMaterial)) if mats else None; d.n_materials = len(mats)
+    if camera is not None:
+        cam = abi.tb_camera.from_buffer_copy(camera); keep.append(cam)
+        d.camera_or_null = C.pointer(cam)
+    if environment is not None:
+        d.env_rgba_or_null = _np_ptr(environment); d.env_height, d.env_width = int(environment.shape[0]), int(environment.shape[1])
+        keep.append(environment)
+    d.env_scale = (C.c_float * 3)(*[float(x) for x in env_scale])
+    d.film_width, d.film_height = int(film[0]), int(film[1])
+    d.flags = MESH_DEVICE if on_device else 0
+    keep += [md, ma]
+    return d, keep, on_device
+
+
+def MeshesRefusal(desc):
+    """tb_meshes_refusal (host only, pure): why tb_load_meshes refuses this tb_scene_desc before it looks at its context -- None, or the reason."""
+    why = C.create_string_buffer(160)
+    rc = lib().tb_meshes_refusal(C.byref(desc) if desc is not None else None, why, 160)
+    return None if rc == 0 else why.value.decode()
+
+
+def HostSmoothNormals(positions, indices, out=None):
+    """tb_host_smooth_normals: include/tb_normals.h's rule over one mesh -- (n, 3) float32 positions, (m, 3) uint32 indices -> (n, 3) normals; a
+    vertex that no triangle names keeps what `out` holds ((0, 1, 0) when out is None)."""
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); i = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    if out is None:
+        out = np.zeros_like(p); out[:, 1] = 1.0
+    rc = lib().tb_host_smooth_normals(_np_ptr(p), p.shape[0], _np_ptr(i), i.shape[0], _np_ptr(out))
+    if rc != 0:
+        raise TracerBoyError(rc, "tb_host_smooth_normals: a null pointer or an index at or past the vertices")
+    return out
+
+
 PATH_FRAME_DTYPE = np.dtype([("sum", np.float32, 4), ("frame", np.uint32), ("first_ray", np.uint32), ("num_rays", np.uint32), ("flags", np.uint32)])
 VISUALIZER_RAY_DTYPE = np.dtype([("Origin", np.float32, 3), ("Direction", np.float32, 3), ("HitT", np.float32), ("BounceCount", np.float32)])
 assert PATH_FRAME_DTYPE.itemsize == 32 and VISUALIZER_RAY_DTYPE.itemsize == 32
@@ -628,6 +757,18 @@ class HostScene:
             rc = lib().tb_host_scene_procedural(kind, tris, seed, bvh_builder, C.byref(self._h), err, 512)
         if rc != 0:
             raise TracerBoyError(rc, err.value.decode(errors="replace"))
+
+    @classmethod
+    def from_meshes(cls, meshes, materials, camera=None, environment=None, env_scale=(1, 1, 1), film=(0, 0), bvh_builder=0):
+        """tb_host_scene_from_meshes: the host half of TracerBoy.LoadMeshes (numpy arrays only)."""
+        d, keep, _ = _scene_desc("HostScene.from_meshes", meshes, materials, camera, environment, env_scale, film, None)
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = lib().tb_host_scene_from_meshes(C.byref(d), bvh_builder, C.byref(self._h), err, 512)
+        if rc != 0:
+            raise TracerBoyError(rc, err.value.decode(errors="replace"))
+        return self
 
     def close(self):
         if self._h:
@@ -801,10 +942,23 @@ class TracerBoy:
     # -- TracerBoy interface --------------------------------------------------------------------
     def LoadScene(self, sceneFileName):
         """TracerBoy::LoadScene (TracerBoy.cpp:1065): blocking."""
+        self._num_vertices = None
         self._check(self._L.tb_load_scene(self._ctx, os.fsencode(sceneFileName)))
 
     def LoadProcedural(self, kind, target_triangles, seed=1234):
+        self._num_vertices = None
         self._check(self._L.tb_load_procedural(self._ctx, kind, target_triangles, seed))
+
+    def LoadMeshes(self, meshes, materials, camera=None, environment=None, env_scale=(1, 1, 1), film=(0, 0)):
+        """tb_load_meshes: a scene from api.Mesh objects and TbMaterials instead of a file.  Arrays: numpy, or contiguous torch
+        tensors on the context's device (read to the host once).  Wrong arrays: ValueError, before any library call."""
+        meshes = list(meshes)
+        d, keep, on_device = _scene_desc("LoadMeshes", meshes, materials, camera, environment, env_scale, film, getattr(self, "_device", 0))
+        if on_device:
+            import torch
+            torch.cuda.current_stream(meshes[0].positions.device).synchronize()
+        self._num_vertices = None
+        self._check(self._L.tb_load_meshes(self._ctx, C.byref(d)))
 
     def Render(self, width, height, n_frames=1, outputSettings=None, time_seed=0.0, sync=True):
         """TracerBoy::Render x n_frames (TracerBoy.cpp:2677); one sample per pixel per frame."""
@@ -1432,6 +1586,18 @@ class TracerBoy:
     def UpdateNormals(self, a, first=0):
         """tb_update_normals: stage new shading normals (the Normal field of the vertex records) of the vertices first .. first + n; a as for UpdatePositions."""
         self._update_vertices("UpdateNormals", "tb_update_normals", a, first)
+
+    def RecomputeNormals(self, first=0, n=None):
+        """tb_recompute_normals: mark the vertices first .. first + n (None: to the end); the next CommitGeometry makes their smooth normals again on
+        the device from the positions it leaves (include/tb_normals.h).  Vertices of emissive geometries are skipped."""
+        for name, v in (("first", first), ("n", 0 if n is None else n)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > 0xffffffff:
+                raise ValueError("RecomputeNormals: %s is a vertex count, not %r" % (name, v))
+        if n is None:
+            if getattr(self, "_num_vertices", None) is None:       # asked once per load: the question brings stale host copies up
+                self._num_vertices = int(self.SceneInfo().numVertices)
+            n = max(self._num_vertices - first, 0)
+        self._check(self._L.tb_recompute_normals(self._ctx, first, n))
 
     def SetInstanceTransforms(self, m, first=0):
         """tb_set_instance_transforms: stage objectToWorld of the instances first .. first + n of a two-level scene; m: float32 (n, 3, 4) or (n, 12)."""

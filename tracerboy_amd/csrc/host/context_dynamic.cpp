@@ -87,6 +87,55 @@ void makeTables(tb_context* c, Dynamic& d)
     d.ready = true;
 }
 
+/* The tables of a normal recomputation (refit_launch.h RefitNormalTables), from the scene's per-triangle arrays, which no commit changes: the
+ * triangles' vertex numbers in geometry order, and per vertex the face-vector slots of the corners that name it -- triangles ascending, corners
+ * 0, 1, 2, which inside one mesh is ascending primitive index: include/tb_normals.h's order.  Emissive geometries' vertices get an empty row. */
+void makeNormalTables(tb_context* c, Dynamic& d)
+{
+    const HostScene& s = c->scene;
+    const size_t N = s.triGeometry.size(), V = numVertices(c);
+    auto emissive = [&](size_t t) {
+        const uint32_t g = s.triGeometry[t];
+        if (g >= s.hitGroups.size()) return true; /* no such geometry: not walked */
+        const uint32_t m = s.hitGroups[g].MaterialIndex;
+        return m < s.materials.size() && (s.materials[m].Flags & TB_MAT_LIGHT) != 0;
+    };
+    std::vector<uint32_t> rowStart(V + 1, 0u);
+    for (size_t t = 0; t < N; t++) for (int k = 0; k < 3; k++) {
+        const uint32_t v = s.triVertexIndex[3 * t + k];
+        if (v >= V) throw std::runtime_error("dynamic geometry: a vertex index is out of range");
+        if (!emissive(t)) rowStart[v + 1]++;
+    }
+    for (size_t v = 0; v < V; v++) {
+        if ((uint64_t)rowStart[v] + rowStart[v + 1] > 0xffffffffull) throw std::runtime_error("dynamic geometry: too many corners");
+        rowStart[v + 1] += rowStart[v];
+    }
+    std::vector<uint32_t> slots(rowStart[V]), fill(rowStart.begin(), rowStart.end() - 1);
+    for (size_t t = 0; t < N; t++) if (!emissive(t)) for (int k = 0; k < 3; k++) slots[fill[s.triVertexIndex[3 * t + k]]++] = (uint32_t)t;
+    d.normalSlots = rowStart[V];
+    uploadInto(c, d.normalTriVerts, s.triVertexIndex); uploadInto(c, d.normalRowStart, rowStart); uploadInto(c, d.normalSlotTable, slots);
+    ensure(d.faceVectors, std::max<size_t>(16, 12ull * N));
+    HIP_TRY(hipStreamSynchronize(c->stream)); /* the vectors above go out of scope */
+    d.normalTablesReady = true;
+}
+
+/* the normals of the marked ranges again, chained on the stream after the refit's launches and the explicit normals */
+void recomputeNormals(tb_context* c, Dynamic& d, bool afterRefit)
+{
+    RefitNormalTables t{};
+    t.positions = (const float*)d.positions.p; t.triVerts = (const uint32_t*)d.normalTriVerts.p; t.rowStart = (const uint32_t*)d.normalRowStart.p;
+    t.slots = (const uint32_t*)d.normalSlotTable.p; t.faceVectors = (float*)d.faceVectors.p; t.vertexBuffer = (float*)c->ds.vertexBuffer;
+    t.numTris = (uint32_t)c->scene.triGeometry.size(); t.numVertices = numVertices(c); t.numSlots = d.normalSlots;
+    HIP_TRY(hipEventRecord(d.evNormals[0].create(), c->stream));
+    HIP_TRY(refit_launch_face_vectors(c->stream, &t));
+    for (const auto& r : d.markedNormals) HIP_TRY(refit_launch_vertex_normals(c->stream, &t, r.first, r.second - r.first));
+    HIP_TRY(hipEventRecord(d.evNormals[1].create(), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, d.evNormals[0], d.evNormals[1]));
+    d.lastMs = (afterRefit ? d.lastMs : 0.0f) + ms;
+}
+
 void addRange(Ranges& r, uint32_t first, uint32_t n) { if (n) r.emplace_back(first, first + n); }
 void mergeRanges(Ranges& r)
 {
@@ -311,6 +360,22 @@ int tb_update_normals(tb_context* c, uint32_t flags, uint32_t first, uint32_t n,
     return stageVertices(c, "tb_update_normals", true, flags, first, n, xyz);
 }
 
+int tb_recompute_normals(tb_context* c, uint32_t first, uint32_t n)
+{
+    TB_REFUSE_PEER(c);
+    if (c && !c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED, "tb_recompute_normals: not supported for a multi-device group");
+    return guarded(c, [&]() {
+        int code; const float nothing = 0.0f; /* the call brings no array: updateRefusal's pointer test has nothing to refuse */
+        if (const char* why = updateRefusal(c, "tb_recompute_normals", 0, first, n, &nothing, code)) return fail(c, code, std::string("tb_recompute_normals: ") + why);
+        if (n == 0) return TB_OK;
+        Dynamic& d = dynamicOf(c);
+        if (!d.ready) makeTables(c, d);
+        if (!d.normalTablesReady) makeNormalTables(c, d);
+        addRange(d.markedNormals, first, n);
+        return TB_OK;
+    });
+}
+
 int tb_geometry_vertex_range(tb_context* c, uint32_t geometry, uint32_t* first, uint32_t* count)
 {
     if (!c || !first || !count) return TB_E_INVALID;
@@ -359,8 +424,8 @@ int tb_commit_geometry(tb_context* c, uint32_t flags)
         const bool rebuild = (flags & TB_GEOMETRY_REBUILD) != 0;
         bool transforms = false;
         for (uint8_t s : d.transformStaged) transforms = transforms || s != 0;
-        mergeRanges(d.dirtyPositions); mergeRanges(d.dirtyNormals);
-        const bool vertices = !d.dirtyPositions.empty(), normals = !d.dirtyNormals.empty();
+        mergeRanges(d.dirtyPositions); mergeRanges(d.dirtyNormals); mergeRanges(d.markedNormals);
+        const bool vertices = !d.dirtyPositions.empty(), marks = !d.markedNormals.empty(), normals = !d.dirtyNormals.empty() || marks;
         if (!vertices && !normals && !transforms && !(rebuild && d.refitSinceBuild)) return TB_OK;
         if (rebuild && twoLevel(c)) return fail(c, TB_E_UNSUPPORTED, "tb_commit_geometry: TB_GEOMETRY_REBUILD of a two-level scene is not supported");
         int g = movedEmissiveGeometry(c, d.dirtyPositions, d.positions, false);
@@ -371,9 +436,10 @@ int tb_commit_geometry(tb_context* c, uint32_t flags)
         if (vertices) refit(c, d);
         for (const auto& r : d.dirtyNormals)
             HIP_TRY(refit_launch_normals(c->stream, (float*)c->ds.vertexBuffer, (const float*)d.normals.p, r.first, r.second - r.first));
+        if (marks) recomputeNormals(c, d, vertices); /* last: a recomputation wins over an explicit normal of the same vertex */
         if (normals) { HIP_TRY(hipStreamSynchronize(c->stream)); d.vertexBufferStale = true; }
         if (vertices || normals) d.hostStale = true;
-        d.dirtyPositions.clear(); d.dirtyNormals.clear();
+        d.dirtyPositions.clear(); d.dirtyNormals.clear(); d.markedNormals.clear();
         if (rebuild) {   /* what a fresh load of the moved scene builds: the host positions, then finalizeScene, which drops this state with the scene's buffers */
             refreshHostScene(c);
             const tb_camera camera = c->camera;

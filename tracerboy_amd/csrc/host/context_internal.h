@@ -20,6 +20,7 @@
  *   context_rays.cpp    ray queries: tb_trace_rays, closest hits and any-hit occlusion of a caller's rays, host arrays or device buffers
  *   context_radiance.cpp radiance queries: tb_trace_radiance, the path tracer on a caller's rays, and tb_make_camera_rays
  *   context_bake.cpp    lightmap baking: tb_bake_lightmap, a UV atlas rasterised, its texels traced by the radiance query, resolved and dilated
+ *   context_meshes.cpp  scenes from caller arrays: tb_load_meshes, device arrays read to the host once, the swap into the context
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -259,6 +260,12 @@ struct tb_context {
         std::vector<std::pair<uint32_t, uint32_t>> dirtyPositions, dirtyNormals;
         std::vector<float> transforms; std::vector<uint8_t> transformStaged;
         tbctx::DevEvent ev[2]; float lastMs = 0.0f;
+        /* tb_recompute_normals: the marked vertex ranges since the last commit; the tables of a recomputation
+         * (refit_launch.h RefitNormalTables) and the face vectors, made at the first call only; the events around its two launches */
+        std::vector<std::pair<uint32_t, uint32_t>> markedNormals;
+        bool normalTablesReady = false; uint32_t normalSlots = 0;
+        DevBuf normalTriVerts, normalRowStart, normalSlotTable, faceVectors;
+        tbctx::DevEvent evNormals[2];
     };
     std::unique_ptr<Dynamic> dyn;
     /* lightmap baking (context_bake.cpp): made at the first tb_bake_lightmap of a scene, released with the scene

@@ -258,6 +258,38 @@ int tb_host_scene_procedural(int kind, uint32_t tris, uint32_t seed, int builder
     } catch (const std::exception& e) { return hostFail(err, errLen, TB_E_INVALID, e.what()); }
 }
 
+/* Why tb_load_meshes refuses its arguments before it looks at the context or reads a value: pure tests, in the header's order. */
+int tb_meshes_refusal(const tb_scene_desc* desc, char* why, uint32_t whyBytes)
+{
+    const std::string no = MeshesRefusal(desc);
+    if (why && whyBytes) { strncpy(why, no.c_str(), whyBytes - 1); why[whyBytes - 1] = 0; }
+    return no.empty() ? TB_OK : TB_E_INVALID;
+}
+
+int tb_host_scene_from_meshes(const tb_scene_desc* desc, int builder, tb_host_scene** out, char* err, uint32_t errLen)
+{
+    if (!out) return TB_E_INVALID;
+    *out = nullptr;
+    try {
+        { const std::string no = MeshesRefusal(desc); if (!no.empty()) return hostFail(err, errLen, TB_E_INVALID, "tb_host_scene_from_meshes: " + no); }
+        if (desc->flags & TB_MESH_DEVICE) return hostFail(err, errLen, TB_E_INVALID, "tb_host_scene_from_meshes: host arrays only (TB_MESH_DEVICE needs a context)");
+        std::unique_ptr<tb_host_scene> h(new tb_host_scene());
+        std::string why;
+        const int rc = MeshesToScene(*desc, h->scene, why);
+        if (rc != TB_OK) return hostFail(err, errLen, rc, "tb_host_scene_from_meshes: " + why);
+        applyBuilderWord(h->scene, builder); BuildBvh(h->scene, builderOfWord(builder));
+        *out = h.release(); return TB_OK;
+    } catch (const std::exception& e) { return hostFail(err, errLen, TB_E_INVALID, e.what()); }
+}
+
+int tb_host_smooth_normals(const float* positions, uint32_t nv, const uint32_t* indices, uint32_t nt, float* normalsOut)
+{
+    if ((nv && (!positions || !normalsOut)) || (nt && !indices)) return TB_E_INVALID;
+    for (uint64_t i = 0; i < 3ull * nt; i++) if (indices[i] >= nv) return TB_E_INVALID;
+    try { SmoothNormals(positions, nv, indices, nt, normalsOut); } catch (const std::exception&) { return TB_E_INVALID; }
+    return TB_OK;
+}
+
 void tb_host_scene_free(tb_host_scene* s) { delete s; }
 
 int tb_host_scene_view_get(tb_host_scene* s, TbSceneView* v) { if (!s || !v) return TB_E_INVALID; fillView(s->scene, v); return TB_OK; }

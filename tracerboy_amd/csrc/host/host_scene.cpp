@@ -6,6 +6,7 @@
  * flat std::vectors that the context uploads once.
  */
 #include "host_scene.h"
+#include "../../../include/tb_normals.h"
 
 #include <cmath>
 #include <cstring>
@@ -178,16 +179,36 @@ inline bool usable(const PbrtMesh& mesh)
     return true;
 }
 
-/* area lights, one per triangle (TracerBoy.cpp:1526-1576); instanced emitters get their world positions */
-void AppendAreaLights(HostScene& out, const PbrtMesh& mesh, const Affine& xf)
+/* A mesh as plain arrays, what the PBRT conversion and MeshesToScene both hand to AppendAreaLights / AppendGeometry.  normals / uvs / tangents may be
+ * null (count 0).  asGiven (scenes from arrays): positions, normals and UVs are stored as they come -- no transform, no normalisation --; otherwise xf
+ * is baked into positions and attributes as the reference does. */
+struct MeshArrays {
+    const Vec3* vertex; size_t numVertices;
+    const uint32_t* index; size_t numTriangles;
+    const Vec3* normal; size_t numNormals;
+    const Vec2* texcoord; size_t numTexcoords;
+    const Vec3* tangents; size_t numTangents;
+    bool asGiven;
+};
+static_assert(sizeof(Vec3) == 12 && sizeof(Vec2) == 8, "Vec3 / Vec2 are packed floats: caller arrays are read as them");
+
+inline MeshArrays ArraysOf(const PbrtMesh& mesh)
 {
-    const Vec3 emissive = mesh.areaLightL;
-    const uint32_t numTris = (uint32_t)(mesh.index.size() / 3);
+    return MeshArrays{mesh.vertex.data(), mesh.vertex.size(), mesh.index.data(), mesh.index.size() / 3, mesh.normal.data(), mesh.normal.size(),
+        mesh.texcoord.data(), mesh.texcoord.size(), mesh.tangents.data(), mesh.tangents.size(), false};
+}
+
+/* area lights, one per triangle (TracerBoy.cpp:1526-1576); instanced emitters get their world positions */
+void AppendAreaLights(HostScene& out, const MeshArrays& mesh, const Vec3& emissive, const Affine& xf)
+{
+    const uint32_t numTris = (uint32_t)mesh.numTriangles;
+    auto P = [&](uint32_t v) { return mesh.asGiven ? mesh.vertex[v] : xf * mesh.vertex[v]; };
+    auto N = [&](uint32_t v) { return mesh.asGiven ? mesh.normal[v] : xfmNormal(xf, mesh.normal[v]); };
     for (uint32_t i = 0; i < numTris; i++) {
         TbLight light; memset(&light, 0, sizeof light);
         light.LightType = TB_LIGHT_TYPE_AREA;
         light.LightColor = F3(emissive);
-        Vec3 p0 = xf * mesh.vertex[mesh.index[3 * i]], p1 = xf * mesh.vertex[mesh.index[3 * i + 1]], p2 = xf * mesh.vertex[mesh.index[3 * i + 2]];
+        Vec3 p0 = P(mesh.index[3 * i]), p1 = P(mesh.index[3 * i + 1]), p2 = P(mesh.index[3 * i + 2]);
         {
             Vec3 v0 = p1 - p0, v1 = p2 - p0;
             float v0Length = sqrtf(dot(v0, v0)), v1Length = sqrtf(dot(v1, v1));
@@ -195,10 +216,10 @@ void AppendAreaLights(HostScene& out, const PbrtMesh& mesh, const Affine& xf)
             light.SurfaceArea = (float)(v0Length * v1Length * sinf(angle) / 2.0);
         }
         light.P0 = F3(p0); light.P1 = F3(p1); light.P2 = F3(p2);
-        if (!mesh.normal.empty()) {
-            light.N0 = F3(xfmNormal(xf, mesh.normal[mesh.index[3 * i]]));
-            light.N1 = F3(xfmNormal(xf, mesh.normal[mesh.index[3 * i + 1]]));
-            light.N2 = F3(xfmNormal(xf, mesh.normal[mesh.index[3 * i + 2]]));
+        if (mesh.numNormals) {
+            light.N0 = F3(N(mesh.index[3 * i]));
+            light.N1 = F3(N(mesh.index[3 * i + 1]));
+            light.N2 = F3(N(mesh.index[3 * i + 2]));
         } else {
             Vec3 n = normalize(cross(p1 - p0, p2 - p0));
             light.N0 = light.N1 = light.N2 = F3(n);
@@ -223,18 +244,18 @@ struct GeometrySlot { uint32_t vertexBufferOffset, indexBufferOffset, materialIn
 /* vertex / position / index buffers and the builder's per-triangle arrays (TracerBoy.cpp:1595-1802).  xf is baked into the
  * positions and attributes (identity for the geometry of an instanced structure: bBakeTransformIntoVertexBuffer, :1623-1624);
  * geometryIndexForTris is what a triangle reports as GeometryContributionToHitGroupIndex. */
-GeometrySlot AppendGeometry(HostScene& out, const PbrtMesh& mesh, const Affine& xf, uint32_t geometryIndexForTris, uint32_t materialIndex)
+GeometrySlot AppendGeometry(HostScene& out, const MeshArrays& mesh, const Affine& xf, uint32_t geometryIndexForTris, uint32_t materialIndex)
 {
-    const uint32_t numTris = (uint32_t)(mesh.index.size() / 3);
+    const uint32_t numTris = (uint32_t)mesh.numTriangles;
     const uint32_t firstVertex = (uint32_t)(out.positions.size() / 3);
     const uint32_t vertexBufferOffset = (uint32_t)(out.vertexBuffer.size() * 4);
-    const bool bNormalsProvided = !mesh.normal.empty();
-    for (size_t v = 0; v < mesh.vertex.size(); v++) {
-        Vec3 P = xf * mesh.vertex[v];
+    const bool bNormalsProvided = mesh.numNormals != 0;
+    for (size_t v = 0; v < mesh.numVertices; v++) {
+        Vec3 P = mesh.asGiven ? mesh.vertex[v] : xf * mesh.vertex[v];
         Vec3 N(0, 1, 0), T(0, 0, 1);
-        if (bNormalsProvided && v < mesh.normal.size()) N = normalize(xfmNormal(xf, mesh.normal[v]));
-        if (v < mesh.tangents.size()) T = normalize(xfmNormal(xf, mesh.tangents[v]));
-        Vec2 uv; if (v < mesh.texcoord.size()) uv = mesh.texcoord[v];
+        if (bNormalsProvided && v < mesh.numNormals) N = mesh.asGiven ? mesh.normal[v] : normalize(xfmNormal(xf, mesh.normal[v]));
+        if (v < mesh.numTangents) T = normalize(xfmNormal(xf, mesh.tangents[v]));
+        Vec2 uv; if (v < mesh.numTexcoords) uv = mesh.texcoord[v];
         const float vert[8] = {N.x, N.y, N.z, uv.x, uv.y, T.x, T.y, T.z};
         out.vertexBuffer.insert(out.vertexBuffer.end(), vert, vert + 8);
         out.positions.push_back(P.x); out.positions.push_back(P.y); out.positions.push_back(P.z);
@@ -244,7 +265,7 @@ GeometrySlot AppendGeometry(HostScene& out, const PbrtMesh& mesh, const Affine& 
     const uint32_t geometryFlag = (out.materials[materialIndex].Flags & TB_MAT_NO_ALPHA) ? 1u : 0u; /* USE_ANYHIT 1, :1756-1760 */
     for (uint32_t i = 0; i < numTris; i++) {
         uint32_t ix = mesh.index[3 * i], iy = mesh.index[3 * i + 1], iz = mesh.index[3 * i + 2];
-        if (ix >= mesh.vertex.size() || iy >= mesh.vertex.size() || iz >= mesh.vertex.size()) throw std::runtime_error("triangle index out of range");
+        if (ix >= mesh.numVertices || iy >= mesh.numVertices || iz >= mesh.numVertices) throw std::runtime_error("triangle index out of range");
         out.indexBuffer.push_back(ix); out.indexBuffer.push_back(iy); out.indexBuffer.push_back(iz);
         if (!bNormalsProvided) { /* flat normals :1710-1729 */
             Vec3 edge1 = mesh.vertex[iz] - mesh.vertex[ix], edge2 = mesh.vertex[iz] - mesh.vertex[iy];
@@ -366,9 +387,9 @@ void ConvertScene(const PbrtScene& in, HostScene& out, const ConvertOptions& opt
             const PbrtMesh& mesh = *fs.mesh;
             if (!usable(mesh)) continue;
             const Affine xf = fs.baked ? Affine() : fs.xfm;
-            if (mesh.hasAreaLight) AppendAreaLights(out, mesh, xf);
+            if (mesh.hasAreaLight) AppendAreaLights(out, ArraysOf(mesh), mesh.areaLightL, xf);
             const uint32_t materialIndex = MaterialOf(mesh, tracker, textures);
-            const GeometrySlot g = AppendGeometry(out, mesh, xf, (uint32_t)out.hitGroups.size(), materialIndex);
+            const GeometrySlot g = AppendGeometry(out, ArraysOf(mesh), xf, (uint32_t)out.hitGroups.size(), materialIndex);
             growWorld(mesh, xf);
             AppendHitGroup(out, g);
         }
@@ -413,7 +434,7 @@ void ConvertScene(const PbrtScene& in, HostScene& out, const ConvertOptions& opt
         if (insts.size() > 0x00ffffffu) throw std::runtime_error("more than 2^24-1 instances");
         for (BlasDef& d : defs) {
             HostScene::Blas b; b.firstTri = (uint32_t)out.triGeometry.size();
-            for (const PbrtMeshSP& m : d.meshes) d.slots.push_back(AppendGeometry(out, *m, Affine(), (uint32_t)d.slots.size(), MaterialOf(*m, tracker,
+            for (const PbrtMeshSP& m : d.meshes) d.slots.push_back(AppendGeometry(out, ArraysOf(*m), Affine(), (uint32_t)d.slots.size(), MaterialOf(*m, tracker,
                 textures)));
             b.numTris = (uint32_t)out.triGeometry.size() - b.firstTri;
             out.blas.push_back(b);
@@ -424,7 +445,7 @@ void ConvertScene(const PbrtScene& in, HostScene& out, const ConvertOptions& opt
             const BlasDef& d = defs[i.blas];
             for (size_t g = 0; g < d.slots.size(); g++) {
                 AppendHitGroup(out, d.slots[g]);
-                if (d.meshes[g]->hasAreaLight) AppendAreaLights(out, *d.meshes[g], i.xfm);
+                if (d.meshes[g]->hasAreaLight) AppendAreaLights(out, ArraysOf(*d.meshes[g]), d.meshes[g]->areaLightL, i.xfm);
                 growWorld(*d.meshes[g], i.xfm);
             }
             out.instances.push_back(hi);
@@ -458,6 +479,139 @@ void ConvertScene(const PbrtScene& in, HostScene& out, const ConvertOptions& opt
     out.config.EnvMapTransformVy = {envL.vy.x, envL.vy.y, envL.vy.z, 0.0f};
     out.config.EnvMapTransformVz = {envL.vz.x, envL.vz.y, envL.vz.z, 0.0f};
     out.config.EnvironmentMapColorScale = F3(envScale);
+}
+
+/* ---- scenes from caller arrays (include/tracerboy_hip.h tb_load_meshes) ------------------------------------------ */
+
+void SmoothNormals(const float* positions, uint32_t numVertices, const uint32_t* indices, uint32_t numTriangles, float* normalsOut)
+{
+    std::vector<tb3> acc(numVertices, tb3_splat(0.0f));
+    std::vector<uint8_t> named(numVertices, 0);
+    auto P = [&](uint32_t v) { return tb3_make(positions[3ull * v], positions[3ull * v + 1], positions[3ull * v + 2]); };
+    for (uint32_t t = 0; t < numTriangles; t++) {
+        const uint32_t i[3] = {indices[3ull * t], indices[3ull * t + 1], indices[3ull * t + 2]};
+        if (i[0] >= numVertices || i[1] >= numVertices || i[2] >= numVertices) continue; /* the callers have refused such a mesh */
+        const tb3 f = tb_face_vector(P(i[0]), P(i[1]), P(i[2]));
+        for (int k = 0; k < 3; k++) { acc[i[k]] = tb_normal_accumulate(acc[i[k]], f); named[i[k]] = 1; }
+    }
+    for (uint32_t v = 0; v < numVertices; v++) if (named[v]) {
+        const tb3 n = tb_normal_finish(acc[v]);
+        normalsOut[3ull * v] = n.x; normalsOut[3ull * v + 1] = n.y; normalsOut[3ull * v + 2] = n.z;
+    }
+}
+
+namespace {
+std::string meshName(uint32_t m) { return "mesh " + std::to_string(m) + ": "; }
+bool allFinite(const float* p, size_t n, size_t& at) { for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) { at = i; return false; } return true; }
+}
+
+std::string MeshesRefusal(const tb_scene_desc* desc)
+{
+    if (!desc) return "null desc";
+    if (!desc->meshes || desc->n_meshes == 0) return "no meshes";
+    if (!desc->materials || desc->n_materials == 0) return "no materials";
+    for (uint32_t m = 0; m < desc->n_meshes; m++) {
+        const tb_mesh_desc& d = desc->meshes[m];
+        if (!d.positions) return meshName(m) + "null positions";
+        if (!d.indices) return meshName(m) + "null indices";
+        if (d.n_vertices == 0) return meshName(m) + "0 vertices";
+        if (d.n_triangles == 0) return meshName(m) + "0 triangles";
+        if (d.material >= desc->n_materials) return meshName(m) + "material " + std::to_string(d.material) + " is at or past the " +
+            std::to_string(desc->n_materials) + " materials";
+        if (d.normals_mode != TB_MESH_NORMALS_FLAT && d.normals_mode != TB_MESH_NORMALS_SMOOTH) return meshName(m) + "unknown normals mode " +
+            std::to_string(d.normals_mode);
+    }
+    if (desc->flags & ~TB_MESH_DEVICE) return "unknown flag bits";
+    if (desc->env_rgba_or_null && (desc->env_width == 0 || desc->env_height == 0)) return "a side of the environment is 0";
+    if (desc->env_rgba_or_null && (desc->env_width > 16384u || desc->env_height > 16384u)) return "a side of the environment is above 16384";
+    uint64_t tris = 0, verts = 0, indexWords = 0;
+    for (uint32_t m = 0; m < desc->n_meshes; m++) {
+        tris += desc->meshes[m].n_triangles; verts += desc->meshes[m].n_vertices;
+        indexWords = (indexWords + 3u) / 4u * 4u + 3ull * desc->meshes[m].n_triangles; /* every mesh's indices start 16-B aligned */
+    }
+    if (tris > 0x00ffffffull) return "more than 2^24 - 1 triangles in total";
+    if (verts > 0x07ffffffull) return "more than 2^27 - 1 vertices in total";
+    if (indexWords * 4u > 0xffffffffull) return "the index buffer passes 2^32 bytes";
+    return std::string();
+}
+
+std::string MeshesUnsupported(const tb_scene_desc& desc)
+{
+    for (uint32_t i = 0; i < desc.n_materials; i++) {
+        const TbMaterial& mt = desc.materials[i];
+        if (mt.albedoIndex != TB_INVALID_TEXTURE || mt.alphaIndex != TB_INVALID_TEXTURE || mt.normalMapIndex != TB_INVALID_TEXTURE ||
+            mt.emissiveIndex != TB_INVALID_TEXTURE || mt.specularMapIndex != TB_INVALID_TEXTURE)
+            return "material " + std::to_string(i) + " names a texture: textures from arrays are not supported";
+    }
+    return std::string();
+}
+
+int MeshesToScene(const tb_scene_desc& desc, HostScene& out, std::string& why)
+{
+    why = MeshesRefusal(&desc);
+    if (!why.empty()) return TB_E_INVALID;
+    why = MeshesUnsupported(desc);
+    if (!why.empty()) return TB_E_UNSUPPORTED;
+    size_t at = 0;
+    for (uint32_t m = 0; m < desc.n_meshes; m++) {
+        const tb_mesh_desc& d = desc.meshes[m];
+        for (size_t i = 0; i < 3ull * d.n_triangles; i++) if (d.indices[i] >= d.n_vertices) {
+            why = meshName(m) + "index " + std::to_string(d.indices[i]) + " (triangle " + std::to_string(i / 3) + ", corner " + std::to_string(i % 3) +
+                ") is at or past its " + std::to_string(d.n_vertices) + " vertices"; return TB_E_INVALID; }
+        if (!allFinite(d.positions, 3ull * d.n_vertices, at)) { why = meshName(m) + "the position of vertex " + std::to_string(at / 3) + " is not finite";
+            return TB_E_INVALID; }
+        if (d.normals_or_null && !allFinite(d.normals_or_null, 3ull * d.n_vertices, at)) {
+            why = meshName(m) + "the normal of vertex " + std::to_string(at / 3) + " is not finite"; return TB_E_INVALID; }
+        if (d.uvs_or_null && !allFinite(d.uvs_or_null, 2ull * d.n_vertices, at)) {
+            why = meshName(m) + "the UV of vertex " + std::to_string(at / 2) + " is not finite"; return TB_E_INVALID; }
+    }
+    if (desc.env_rgba_or_null) {
+        if (!allFinite(desc.env_rgba_or_null, 4ull * desc.env_width * desc.env_height, at)) {
+            why = "environment texel " + std::to_string(at / 4) + " is not finite"; return TB_E_INVALID; }
+        if (!allFinite(desc.env_scale, 3, at)) { why = "env_scale is not finite"; return TB_E_INVALID; }
+    }
+
+    out = HostScene();
+    out.filmWidth = desc.film_width ? (int)desc.film_width : 1920; out.filmHeight = desc.film_height ? (int)desc.film_height : 1080;
+    out.materials.assign(desc.materials, desc.materials + desc.n_materials);
+    tb3 mn = tb3_splat(3.402823466e+38f), mx = tb3_splat(-3.402823466e+38f);
+    std::vector<float> smooth;
+    for (uint32_t m = 0; m < desc.n_meshes; m++) {
+        const tb_mesh_desc& d = desc.meshes[m];
+        const float* normals = d.normals_or_null;
+        if (!normals && d.normals_mode == TB_MESH_NORMALS_SMOOTH) {
+            smooth.assign(3ull * d.n_vertices, 0.0f);
+            for (uint32_t v = 0; v < d.n_vertices; v++) smooth[3ull * v + 1] = 1.0f; /* a vertex no triangle names: (0, 1, 0) */
+            SmoothNormals(d.positions, d.n_vertices, d.indices, d.n_triangles, smooth.data());
+            normals = smooth.data();
+        }
+        const MeshArrays arrays{(const Vec3*)d.positions, d.n_vertices, d.indices, d.n_triangles, (const Vec3*)normals, normals ? d.n_vertices : 0u,
+            (const Vec2*)d.uvs_or_null, d.uvs_or_null ? d.n_vertices : 0u, nullptr, 0, true};
+        const TbMaterial& mt = out.materials[d.material];
+        if (mt.Flags & TB_MAT_LIGHT) AppendAreaLights(out, arrays, Vec3(mt.emissive.x, mt.emissive.y, mt.emissive.z), Affine());
+        AppendHitGroup(out, AppendGeometry(out, arrays, Affine(), (uint32_t)out.hitGroups.size(), d.material));
+        for (uint32_t v = 0; v < d.n_vertices; v++) { const tb3 p = tb3_make(d.positions[3ull * v], d.positions[3ull * v + 1], d.positions[3ull * v + 2]);
+            mn = tb3_min(mn, p); mx = tb3_max(mx, p); }
+    }
+    out.sceneMin[0] = mn.x; out.sceneMin[1] = mn.y; out.sceneMin[2] = mn.z; out.sceneMax[0] = mx.x; out.sceneMax[1] = mx.y; out.sceneMax[2] = mx.z;
+    if (desc.camera_or_null) out.camera = *desc.camera_or_null;
+    else { /* the procedural scenes' camera, placed by the bounds: eye = c + (0, 0.35 d, d), d twice the diagonal */
+        const tb3 c = (mn + mx) * 0.5f;
+        const float diagonal = tb3_length(mx - mn), d = diagonal > 0.0f ? 2.0f * diagonal : 1.0f;
+        const float eye[3] = {c.x, c.y + 0.35f * d, c.z + d}, target[3] = {c.x, c.y, c.z};
+        SetLookAtCamera(out, eye, target, 35.0f);
+    }
+    memset(&out.config, 0, sizeof out.config);
+    out.config.CameraLensHeight = out.camera.LensHeight;
+    out.config.FlipTextureUVs = 0u; /* the UVs are the caller's, not a file's */
+    out.config.EnvMapTransformVx = {1, 0, 0, 0}; out.config.EnvMapTransformVy = {0, 1, 0, 0}; out.config.EnvMapTransformVz = {0, 0, 1, 0};
+    out.config.EnvironmentMapColorScale = {1, 1, 1};
+    if (desc.env_rgba_or_null) {
+        const TbFloat4* texels = (const TbFloat4*)desc.env_rgba_or_null;
+        out.envMap.assign(texels, texels + (size_t)desc.env_width * desc.env_height); out.envWidth = desc.env_width; out.envHeight = desc.env_height;
+        out.config.EnvironmentMapColorScale = {desc.env_scale[0], desc.env_scale[1], desc.env_scale[2]};
+    }
+    return TB_OK;
 }
 
 void DefaultOutputSettings(tb_output_settings& s) /* TracerBoy.h:290-360 */

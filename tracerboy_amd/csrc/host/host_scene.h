@@ -102,6 +102,17 @@ void WaveStageSize(uint32_t& seed, uint32_t& waves, uint32_t& feelerPercent, uin
 
 /* Procedural stand-ins (procedural.cpp) */
 void MakeProceduralScene(HostScene& out, int kind, uint32_t targetTriangles, uint32_t seed);
+/* their camera, shared with scenes from arrays: at `eye` looking at `target`, up (0, 1, 0), lens height 2, the focal distance of the field of view */
+void SetLookAtCamera(HostScene& s, const float eye[3], const float target[3], float fovDeg);
+
+/* Scenes from caller arrays (host_scene.cpp).  MeshesRefusal: the argument tests of tb_meshes_refusal, empty when there is
+ * none.  MeshesToScene: those, then the value checks, then the scene, one geometry per mesh through the functions the PBRT conversion uses; every
+ * pointer of desc is host memory.  Returns TB_OK, or the code with the cause in why and `out` untouched.  SmoothNormals: include/tb_normals.h's
+ * rule over one mesh; vertices no triangle names are not written. */
+std::string MeshesRefusal(const tb_scene_desc* desc);
+std::string MeshesUnsupported(const tb_scene_desc& desc); /* a material that names a texture; desc has passed MeshesRefusal */
+int MeshesToScene(const tb_scene_desc& desc, HostScene& out, std::string& why);
+void SmoothNormals(const float* positions, uint32_t numVertices, const uint32_t* indices, uint32_t numTriangles, float* normalsOut);
 
 /* images (images.cpp): Radiance RGBE .hdr and .pfm -> RGBA32F, top row first; PNG / PFM writers for the output stage */
 bool WritePngRGBA8(const std::string& file, uint32_t W, uint32_t H, const uint8_t* rgba, std::string& err);

@@ -128,8 +128,11 @@ void addMesh(HostScene& s, const MeshOut& m, uint32_t materialIndex, bool isLigh
     s.hitGroups.push_back(rec);
 }
 
-void setCamera(HostScene& s, tb3 eye, tb3 target, float fovDeg)
+} // namespace
+
+void SetLookAtCamera(HostScene& s, const float eyeXyz[3], const float targetXyz[3], float fovDeg)
 {
+    const tb3 eye = tb3_make(eyeXyz[0], eyeXyz[1], eyeXyz[2]), target = tb3_make(targetXyz[0], targetXyz[1], targetXyz[2]);
     tb3 view = tb3_normalize(target - eye), up0 = tb3_make(0, 1, 0);
     tb3 right = tb3_normalize(tb3_cross(up0, view)), up = tb3_cross(view, right);
     s.camera.LensHeight = 2.0f;
@@ -138,8 +141,6 @@ void setCamera(HostScene& s, tb3 eye, tb3 target, float fovDeg)
     const tb3 v[4] = {pos, look, right, up}; float* d[4] = {s.camera.Position, s.camera.LookAt, s.camera.Right, s.camera.Up};
     for (int i = 0; i < 4; i++) { d[i][0] = v[i].x; d[i][1] = v[i].y; d[i][2] = v[i].z; }
 }
-
-} // namespace
 
 void MakeProceduralScene(HostScene& s, int kind, uint32_t targetTriangles, uint32_t seed)
 {
@@ -203,7 +204,8 @@ void MakeProceduralScene(HostScene& s, int kind, uint32_t targetTriangles, uint3
     float sky = kind == 0 ? 1.0f : 0.05f;
     s.config.EnvironmentMapColorScale = {sky, sky, sky};
     float dist = kind == 0 ? 9.0f : (kind == 1 ? 16.0f : 26.0f);
-    setCamera(s, tb3_make(0.0f, dist * 0.35f, dist), tb3_make(0.0f, kind == 0 ? 1.0f : 0.8f, 0.0f), kind == 0 ? 20.1143f : 35.0f);
+    const float eye[3] = {0.0f, dist * 0.35f, dist}, target[3] = {0.0f, kind == 0 ? 1.0f : 0.8f, 0.0f};
+    SetLookAtCamera(s, eye, target, kind == 0 ? 20.1143f : 35.0f);
     s.config.CameraLensHeight = s.camera.LensHeight;
     tb3 mn = tb3_splat(3.4e38f), mx = tb3_splat(-3.4e38f);
     for (size_t i = 0; i + 2 < s.positions.size(); i += 3) { tb3 p = tb3_make(s.positions[i], s.positions[i + 1], s.positions[i + 2]); mn = tb3_min(mn, p);

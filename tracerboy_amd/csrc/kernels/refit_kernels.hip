@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "tb_math.h"
 #include "tb_vec.h"
+#include "tb_normals.h"
 #include "tb_abi.h"
 #include "refit_launch.h"
 
@@ -90,6 +91,44 @@ __global__ __launch_bounds__(BLOCK) void refit_normals(float* vertexBuffer, cons
     n[0] = staged[3ull * v]; n[1] = staged[3ull * v + 1]; n[2] = staged[3ull * v + 2];
 }
 
+/* Smooth normals again from the positions as they stand (tb_recompute_normals; include/tb_normals.h states the rule, DESIGN.md section 24 the shape).
+ * Two launches: every face vector once, 12 B per triangle, coalesced by triangle; then one lane per marked vertex walks its row of the vertex ->
+ * corner table, which lists the face-vector slots of its corners in the rule's order (ascending primitive, corners 0, 1, 2), adds them in that order,
+ * normalises and stores the Normal field.  The second launch reads what the first wrote: visible at the kernel boundary.  No atomics, no LDS, no fence;
+ * every loop is bounded by the table, every index it forms is checked against the table's sizes.  An empty row (a vertex no triangle names, a vertex
+ * of an emissive geometry) writes nothing. */
+__global__ __launch_bounds__(BLOCK) void refit_face_vectors(RefitNormalTables t)
+{
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= t.numTris) return;
+    const uint32_t i0 = t.triVerts[3ull * k], i1 = t.triVerts[3ull * k + 1], i2 = t.triVerts[3ull * k + 2];
+    if (i0 >= t.numVertices || i1 >= t.numVertices || i2 >= t.numVertices) return;
+    const float* p0 = t.positions + 3ull * i0, * p1 = t.positions + 3ull * i1, * p2 = t.positions + 3ull * i2;
+    const tb3 f = tb_face_vector(tb3_make(p0[0], p0[1], p0[2]), tb3_make(p1[0], p1[1], p1[2]), tb3_make(p2[0], p2[1], p2[2]));
+    float* o = t.faceVectors + 3ull * k;
+    o[0] = f.x; o[1] = f.y; o[2] = f.z;
+}
+
+__global__ __launch_bounds__(BLOCK) void refit_vertex_normals(RefitNormalTables t, uint32_t firstVertex, uint32_t numVertices)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= numVertices) return;
+    const uint64_t v = (uint64_t)firstVertex + i;
+    if (v >= t.numVertices) return;
+    const uint32_t begin = t.rowStart[v], rowEnd = t.rowStart[v + 1], end = rowEnd < t.numSlots ? rowEnd : t.numSlots;
+    if (begin >= end) return;
+    tb3 acc = tb3_splat(0.0f);
+    for (uint32_t j = begin; j < end; j++) {
+        const uint32_t slot = t.slots[j];
+        if (slot >= t.numTris) continue;
+        const float* f = t.faceVectors + 3ull * slot;
+        acc = tb_normal_accumulate(acc, tb3_make(f[0], f[1], f[2]));
+    }
+    const tb3 n = tb_normal_finish(acc);
+    float* o = t.vertexBuffer + 8ull * v; /* TbVertex: Normal leads the record */
+    o[0] = n.x; o[1] = n.y; o[2] = n.z;
+}
+
 inline uint32_t blocksFor(uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); }
 /* hipGetLastError is sticky: an error an earlier call left unread (tb_sync asks never-recorded events for a time) is not this launch's */
 inline void forgetEarlierErrors() { (void)hipGetLastError(); }
@@ -109,6 +148,22 @@ extern "C" hipError_t refit_launch_normals(hipStream_t stream, float* vertexBuff
     if (!numVertices) return hipSuccess;
     forgetEarlierErrors();
     hipLaunchKernelGGL(refit_normals, dim3(blocksFor(numVertices)), dim3(BLOCK), 0, stream, vertexBuffer, staged, firstVertex, numVertices);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t refit_launch_face_vectors(hipStream_t stream, const RefitNormalTables* t)
+{
+    if (!t->numTris) return hipSuccess;
+    forgetEarlierErrors();
+    hipLaunchKernelGGL(refit_face_vectors, dim3(blocksFor(t->numTris)), dim3(BLOCK), 0, stream, *t);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t refit_launch_vertex_normals(hipStream_t stream, const RefitNormalTables* t, uint32_t firstVertex, uint32_t numVertices)
+{
+    if (!numVertices) return hipSuccess;
+    forgetEarlierErrors();
+    hipLaunchKernelGGL(refit_vertex_normals, dim3(blocksFor(numVertices)), dim3(BLOCK), 0, stream, *t, firstVertex, numVertices);
     return hipGetLastError();
 }
 
