@@ -188,6 +188,17 @@ TB_STATIC_ASSERT(sizeof(TbRadianceCall) == 16, "a radiance call is 4 dwords");
 typedef struct TbBakeTexel { uint32_t triangle, cls; float w0, w1; } TbBakeTexel;
 TB_STATIC_ASSERT(sizeof(TbBakeTexel) == 16, "a bake texel is 4 dwords");
 
+/* ---- light probes (tracerboy_hip.h tb_bake_probes) -------------------------
+ * One probe, 32 floats: the nine SH coefficients of the radiance around it per colour channel (SH[j * 3 + c], basis order of kernels/probe_launch.h),
+ * the sum of the solid-angle weights of the rays that counted, and what the closest-hit query found along the same directions: how many rays hit,
+ * how many of those met a triangle from behind (dot(normal, direction) > 0), the smallest and the mean hit distance (-1 without hits).  The counts
+ * are floats: they are sums of ones, exact up to 2^24.  A grid of probes: probe (i, j, k) has the number (k * count[1] + j) * count[0] + i and sits
+ * at origin + (i, j, k) * spacing. */
+typedef struct TbProbe { float SH[27]; float Weight, Hits, Backfaces, MinDistance, MeanDistance; } TbProbe;
+typedef struct tb_probe_grid { float origin[3], spacing[3]; uint32_t count[3]; } tb_probe_grid;
+TB_STATIC_ASSERT(sizeof(TbProbe) == 128, "a probe is 32 dwords");
+TB_STATIC_ASSERT(sizeof(tb_probe_grid) == 36, "a probe grid is 9 dwords");
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

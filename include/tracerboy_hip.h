@@ -680,6 +680,60 @@ int tb_run_bake_raster(tb_context* ctx, uint32_t width, uint32_t height, uint32_
                        const float* uvs, uint32_t n_triangles, const uint32_t* tri_vertex_index, TbRadianceRay* rays_out, TbBakeTexel* texels_out);
 int tb_run_bake_dilate(tb_context* ctx, uint32_t width, uint32_t height, uint32_t passes, const float* rgba_in, float* rgba_out);
 
+/* ---- light probes ---------------------------------------------------------------
+ * The other half of a baker: lightmaps light the static surfaces, probes light what moves between them.  tb_bake_probes takes n positions and
+ * returns n TbProbe records (tb_abi.h), all of it on the device: every probe looks along the texel centres of a resolution x resolution octahedral
+ * map (2 .. 64; the directions are fixed, samples vary the paths), each direction is a ray of the radiance query -- ray mode, seed_advance 0, seed
+ * (first_probe_number + i, texel), the samples [first_sample, first_sample + num_samples) -- and a ray of tb_trace_rays in TB_RAYS_CLOSEST mode
+ * with TMax +inf; the mean radiance per direction, weighted by the texel's solid angle, is projected onto the nine real SH basis functions of
+ * orders 0 to 2 and normalised by the sum of the weights, so a constant radiance L gives SH[0] = 2 sqrt(pi) L whatever the resolution; the hits
+ * give the statistics a sampler needs to leave out probes inside geometry.  kernels/probe_launch.h states every rule operation by operation;
+ * tests/probe_cases.py restates them in numpy, and the two agree on bits.  A probe with a coordinate that is not finite is not traced: its record
+ * is zeros with both distances -1.  One-level and two-level scenes.  Synchronous.
+ * positions_xyz: 3 floats per probe; probes_out: n records.  flags: TB_PROBES_DEVICE -- both are device pointers of the context's device,
+ * positions 4-B and probes_out 16-B aligned.  TB_PROBES_KEEP_MAPS -- the context keeps every ray's sums and hit record for tb_read_probe_maps
+ * (64 B a ray); without it it keeps the records and the buffers of one batch.  TB_PROBES_ACCUMULATE -- the samples are added to the sums the last
+ * bake kept: bakes of 3 and then 5 samples equal one of 8, bit for bit.  It needs a bake held with its maps, of the same n and resolution, traced
+ * of the scene as it is now (no load, rebuild or tb_commit_geometry since): else TB_E_INVALID; the maps stay kept.
+ * A bake runs in batches of whole probes of at most TB_PROBE_MAX_RAYS rays (environment, read at every call; default 2^20, that is 128 MB for
+ * the four per-ray buffers); the split does not change a byte of the answer.  The buffers are made at the first bake and released with the scene.
+ * Refusals, in this order, each leaving the last bake as it was: tb_probes_refusal's (TB_E_INVALID: a null call; a resolution outside [2, 64];
+ * n x resolution^2 above 2^31; n, or first_probe_number + n, above 2^24 -- the seed must be an exact float; num_samples 0 or above 2^24;
+ * first_sample + num_samples above 2^32; unknown flag bits; with n > 0 a null pointer or a misaligned device pointer); TB_E_NO_SCENE;
+ * TB_E_UNSUPPORTED for a tb_create_multi group and real-time settings; n = 0: TB_OK, nothing is launched; pointers that are not memory of the
+ * context's device; TB_PROBES_ACCUMULATE's three.
+ * tb_get_option: "last_probes_rays_us", "last_probes_trace_us", "last_probes_hits_us", "last_probes_project_us" (GPU microseconds of the four
+ * stages, summed over the batches; HIP events), "last_probes_batches", "probes_held" (the probes of the bake held; 0: none), "probes_resolution",
+ * "probes_maps_held".
+ * tb_read_probe_maps: what the last bake with TB_PROBES_KEEP_MAPS summed and hit, n x resolution^2 records each in probe-major order (4 floats;
+ * TbQueryHit), to the host pointers that are not null.
+ * tb_sample_probes: the consumer's half.  n points with unit normals against a grid of probes (tb_abi.h tb_probe_grid; probes in the grid's
+ * numbering, count[0] x count[1] x count[2] <= 2^24 of them): trilinear weights over the eight probes around the point (clamped to the grid), a
+ * probe counting iff its Weight > 0 and its Backfaces <= backface_limit x resolution^2, the weights renormalised over those that count;
+ * rgba_out[i] = (irradiance r, g, b at the normal, the sum of the counting weights) -- zeros where none counts.  flags: 0 (host arrays, staged)
+ * or TB_PROBES_DEVICE (probes and rgba_out 16-B, points and normals 4-B aligned).  Needs no scene.
+ * tb_sh9_irradiance (host, pure): the irradiance of one record at a unit normal, the sampler's own text.  tb_probe_directions (host, pure): the
+ * M x M directions (3 floats each) and solid angles of a map, to the pointers that are not null; TB_E_INVALID for M outside [2, 64].
+ * tb_run_probe_rays / tb_run_probe_project: the kernel seam, like tb_run_bake_raster: host arrays, temporary device buffers, no scene; at most
+ * 2^24 rays. */
+#define TB_PROBES_DEVICE     0x100u   /* the value and meaning of TB_RAYS_DEVICE */
+#define TB_PROBES_ACCUMULATE 0x200u
+#define TB_PROBES_KEEP_MAPS  0x400u
+typedef struct tb_probe_call { uint32_t n, first_probe_number, resolution, first_sample, num_samples, flags; } tb_probe_call;
+int tb_bake_probes(tb_context* ctx, const tb_output_settings* settings_or_null, float time, const tb_probe_call* call, const float* positions_xyz,
+                   TbProbe* probes_out);
+/* host only, no context: why tb_bake_probes refuses these arguments before it looks at its context -- TB_OK, or TB_E_INVALID with the reason in why */
+int tb_probes_refusal(const tb_probe_call* call, const void* positions_xyz, const void* probes_out, char* why_or_null, uint32_t why_bytes);
+int tb_read_probe_maps(tb_context* ctx, float* sums_or_null, TbQueryHit* hits_or_null);
+int tb_sample_probes(tb_context* ctx, uint32_t flags, const tb_probe_grid* grid, uint32_t resolution, float backface_limit, const TbProbe* probes,
+                     uint64_t n, const float* points_xyz, const float* normals_xyz, float* rgba_out);
+int tb_sh9_irradiance(const TbProbe* probe, const float* normal_xyz, float* rgb_out);
+int tb_probe_directions(uint32_t resolution, float* dirs_out_or_null, float* weights_out_or_null);
+int tb_run_probe_rays(tb_context* ctx, uint32_t n, uint32_t resolution, uint32_t first_probe_number, const float* positions_xyz,
+                      TbRadianceRay* radiance_rays_out, TbQueryRay* query_rays_out);
+int tb_run_probe_project(tb_context* ctx, uint32_t n, uint32_t resolution, const float* positions_xyz, const float* sums, const TbQueryHit* hits,
+                         TbProbe* probes_out);
+
 /* ---- dynamic scenes (no reference counterpart: its scene is frozen once LoadScene returns) -------------------------
  * Vertices and instance transforms are STAGED by the three calls below; nothing a render or a trace reads changes until tb_commit_geometry, which
  * waits for the context's stream and then applies everything staged.  A commit with nothing staged is TB_OK and does nothing.

@@ -222,6 +222,27 @@ class tb_bake_call(C.Structure):
 assert C.sizeof(TbBakeTexel) == 16 and C.sizeof(tb_bake_call) == 24
 
 
+class TbProbe(C.Structure):
+    """One light probe (tb_abi.h): 27 SH coefficients (j * 3 + channel), then the weight sum and the hit statistics."""
+    _fields_ = [("SH", C.c_float * 27), ("Weight", C.c_float), ("Hits", C.c_float), ("Backfaces", C.c_float), ("MinDistance", C.c_float),
+                ("MeanDistance", C.c_float)]
+
+
+class tb_probe_grid(C.Structure):
+    """A grid of probes (tb_abi.h): probe (i, j, k) has the number (k * count[1] + j) * count[0] + i and sits at origin + (i, j, k) * spacing."""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("count", C.c_uint32 * 3)]
+
+
+class tb_probe_call(C.Structure):
+    """A call of tb_bake_probes (tracerboy_hip.h): n probes numbered from first_probe_number, the map's resolution, the samples
+    [first_sample, first_sample + num_samples), TB_PROBES_* flags."""
+    _fields_ = [("n", C.c_uint32), ("first_probe_number", C.c_uint32), ("resolution", C.c_uint32), ("first_sample", C.c_uint32),
+                ("num_samples", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(TbProbe) == 128 and C.sizeof(tb_probe_grid) == 36 and C.sizeof(tb_probe_call) == 24
+
+
 class tb_nn_info(C.Structure):
     """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
     _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]

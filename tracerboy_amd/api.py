@@ -126,6 +126,14 @@ def lib():
         "tb_read_bake": (C.c_int, [vp, vp, vp, vp]),
         "tb_run_bake_raster": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]),
         "tb_run_bake_dilate": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+        "tb_bake_probes": (C.c_int, [vp, P(abi.tb_output_settings), C.c_float, P(abi.tb_probe_call), vp, vp]),
+        "tb_probes_refusal": (C.c_int, [P(abi.tb_probe_call), vp, vp, C.c_char_p, C.c_uint32]),
+        "tb_read_probe_maps": (C.c_int, [vp, vp, vp]),
+        "tb_sample_probes": (C.c_int, [vp, C.c_uint32, P(abi.tb_probe_grid), C.c_uint32, C.c_float, vp, C.c_uint64, vp, vp, vp]),
+        "tb_sh9_irradiance": (C.c_int, [vp, vp, vp]),
+        "tb_probe_directions": (C.c_int, [C.c_uint32, vp, vp]),
+        "tb_run_probe_rays": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "tb_run_probe_project": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
         "tb_update_positions": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_update_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -434,6 +442,129 @@ def BakeRefusal(call, uv_address, out_address):
     why = C.create_string_buffer(96)
     rc = lib().tb_bake_refusal(C.byref(call) if call is not None else None, C.c_void_p(uv_address or None), C.c_void_p(out_address or None), why, 96)
     return None if rc == 0 else why.value.decode()
+
+
+# light probes (tb_bake_probes .. tb_run_probe_project; tb_abi.h TbProbe, tb_probe_grid)
+PROBES_DEVICE, PROBES_ACCUMULATE, PROBES_KEEP_MAPS = 0x100, 0x200, 0x400
+PROBE_MIN_RES, PROBE_MAX_RES, PROBE_MAX_PROBES = 2, 64, 1 << 24
+PROBE_DTYPE = np.dtype([("SH", np.float32, (9, 3)), ("Weight", np.float32), ("Hits", np.float32), ("Backfaces", np.float32), ("MinDistance", np.float32),
+                        ("MeanDistance", np.float32)])
+assert PROBE_DTYPE.itemsize == 128
+
+
+class ProbeGrid:
+    """A grid of probes: count = (nx, ny, nz) probes, probe (i, j, k) with the number (k * ny + j) * nx + i at origin + (i, j, k) * spacing."""
+
+    def __init__(self, origin, spacing, count):
+        o = np.asarray(origin, np.float64); sp = np.asarray(spacing, np.float64)
+        if o.shape != (3,) or sp.shape != (3,) or not np.isfinite(o).all() or not np.isfinite(sp).all():
+            raise ValueError("ProbeGrid: origin and spacing are three finite numbers each")
+        if len(count) != 3:
+            raise ValueError("ProbeGrid: count is three whole numbers")
+        self.count = tuple(_check_count("ProbeGrid", "count", v, 1, PROBE_MAX_PROBES) for v in count)
+        if self.count[0] * self.count[1] * self.count[2] > PROBE_MAX_PROBES:
+            raise ValueError("ProbeGrid: more than 2^24 probes")
+        self.origin = tuple(float(np.float32(v)) for v in o); self.spacing = tuple(float(np.float32(v)) for v in sp)
+
+    @classmethod
+    def in_bounds(cls, lo, hi, count):
+        """The grid whose probes sit at the centres of count[0] x count[1] x count[2] equal cells of the box [lo, hi]."""
+        lo = np.asarray(lo, np.float64); hi = np.asarray(hi, np.float64); k = np.asarray(count, np.float64)
+        if lo.shape != (3,) or hi.shape != (3,) or k.shape != (3,) or (k < 1).any():
+            raise ValueError("ProbeGrid.in_bounds: lo, hi and count have three entries each")
+        cell = (hi - lo) / k
+        return cls(lo + 0.5 * cell, cell, count)
+
+    @property
+    def n(self):
+        return self.count[0] * self.count[1] * self.count[2]
+
+    def c_struct(self):
+        return abi.tb_probe_grid((C.c_float * 3)(*self.origin), (C.c_float * 3)(*self.spacing), (C.c_uint32 * 3)(*self.count))
+
+
+def probe_grid_positions(grid):
+    """The (n, 3) float32 positions of a ProbeGrid's probes in its numbering: origin + (i, j, k) * spacing, one rounded product and one rounded sum."""
+    nx, ny, nz = grid.count
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    ijk = np.stack([i.ravel(), j.ravel(), k.ravel()], axis=1).astype(np.float32)
+    return np.ascontiguousarray(np.asarray(grid.origin, np.float32) + ijk * np.asarray(grid.spacing, np.float32))
+
+
+def _check_float_rows(what, name, a, width, align, device, rows=None):
+    """A float32 (n, width) numpy array (False) or torch tensor on the context's device (True), contiguous; ValueError otherwise."""
+    shape = "(%s, %d)" % ("n" if rows is None else rows, width)
+    if _is_torch_tensor(a):
+        import torch
+        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != width or (rows is not None and a.shape[0] != rows):
+            raise ValueError("%s: the tensor %s is float32 of shape %s, not %s %s" % (what, name, shape, a.dtype, tuple(a.shape)))
+        if not a.is_contiguous():
+            raise ValueError("%s: the tensor %s is not contiguous" % (what, name))
+        if a.device.type != "cuda" or a.device.index != device:
+            raise ValueError("%s: the tensor %s is on %s, the context on cuda:%d" % (what, name, a.device, device))
+        if a.data_ptr() % align:
+            raise ValueError("%s: the tensor %s is not %d-B aligned" % (what, name, align))
+        return True
+    if not isinstance(a, np.ndarray):
+        raise ValueError("%s: %s is a numpy array or a torch tensor, not %s" % (what, name, type(a).__name__))
+    if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != width or (rows is not None and a.shape[0] != rows):
+        raise ValueError("%s: %s is float32 of shape %s, not %s %s" % (what, name, shape, a.dtype, a.shape))
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError("%s: %s is not contiguous" % (what, name))
+    return False
+
+
+def _check_probe_call(positions, resolution, samples, first_sample, first_number, keep_maps, accumulate, device):
+    """What BakeProbes accepts, checked before any library call: True for a torch tensor of positions (the device path), False for a numpy array."""
+    _check_count("BakeProbes", "resolution", resolution, PROBE_MIN_RES, PROBE_MAX_RES)
+    _check_count("BakeProbes", "samples", samples, 1, 1 << 24)
+    _check_count("BakeProbes", "first_sample", first_sample, 0, (1 << 32) - samples)
+    for name, v in (("keep_maps", keep_maps), ("accumulate", accumulate)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("BakeProbes: %s is True or False, not %r" % (name, v))
+    on_device = _check_float_rows("BakeProbes", "positions", positions, 3, 4, device)
+    n = int(positions.shape[0])
+    if n > PROBE_MAX_PROBES or n * resolution * resolution > 1 << 31:
+        raise ValueError("BakeProbes: %d probes of %d x %d rays are more than 2^24 probes or 2^31 rays" % (n, resolution, resolution))
+    _check_count("BakeProbes", "first_number", first_number, 0, PROBE_MAX_PROBES - n)
+    return on_device
+
+
+def _is_probe_array(probes, what, rows):
+    """True for a PROBE_DTYPE array of `rows` records, contiguous (ValueError if it is one of another shape); False for anything else."""
+    if not (isinstance(probes, np.ndarray) and probes.dtype == PROBE_DTYPE):
+        return False
+    if probes.ndim != 1 or not probes.flags["C_CONTIGUOUS"] or probes.shape[0] != rows:
+        raise ValueError("%s: probes are a contiguous PROBE_DTYPE array of %d records" % (what, rows))
+    return True
+
+
+def ProbesRefusal(call, positions_address, probes_address):
+    """tb_probes_refusal (host only): why tb_bake_probes refuses these arguments before it looks at its context -- None, or the reason."""
+    why = C.create_string_buffer(96)
+    rc = lib().tb_probes_refusal(C.byref(call) if call is not None else None, C.c_void_p(positions_address or None), C.c_void_p(probes_address or None), why, 96)
+    return None if rc == 0 else why.value.decode()
+
+
+def sh9_irradiance(probe, normal):
+    """tb_sh9_irradiance (host only): the float32 (3,) irradiance of one PROBE_DTYPE record at a unit normal, by the sampler's own arithmetic."""
+    rec = np.ascontiguousarray(probe, PROBE_DTYPE).reshape(1)
+    nrm = np.ascontiguousarray(normal, np.float32)
+    if nrm.shape != (3,):
+        raise ValueError("sh9_irradiance: the normal has three components")
+    out = np.empty(3, np.float32)
+    if lib().tb_sh9_irradiance(_np_ptr(rec), _np_ptr(nrm), _np_ptr(out)) != 0:
+        raise ValueError("sh9_irradiance: refused")
+    return out
+
+
+def probe_directions(resolution):
+    """tb_probe_directions (host only): the float32 (M * M, 3) unit directions and (M * M,) solid angles of an M x M octahedral map."""
+    _check_count("probe_directions", "resolution", resolution, PROBE_MIN_RES, PROBE_MAX_RES)
+    d = np.empty((resolution * resolution, 3), np.float32); w = np.empty(resolution * resolution, np.float32)
+    if lib().tb_probe_directions(resolution, _np_ptr(d), _np_ptr(w)) != 0:
+        raise ValueError("probe_directions: refused")
+    return d, w
 
 
 # dynamic scenes (tb_update_positions .. tb_commit_geometry)
@@ -1562,6 +1693,93 @@ class TracerBoy:
         _check_count("RunBakeDilate", "passes", passes, 0, BAKE_MAX_DILATE)
         out = np.empty_like(a)
         self._check(self._L.tb_run_bake_dilate(self._ctx, a.shape[1], a.shape[0], passes, _np_ptr(a), _np_ptr(out)))
+        return out
+
+    # -- light probes -------------------------------------------------------
+    def BakeProbes(self, positions, resolution=16, samples=64, first_sample=0, first_number=0, keep_maps=False, accumulate=False, settings=None, time=0.0):
+        """tb_bake_probes: one SH9 probe per position -- the radiance along the resolution x resolution directions of an octahedral map, `samples`
+        paths each (the samples [first_sample, first_sample + samples)), projected onto nine SH basis functions, and the hit statistics of the same
+        directions.  positions: float32 (n, 3), a numpy array (returns a PROBE_DTYPE array (n,)) or a contiguous torch tensor on the context's
+        device (zero copy, after torch's current stream there is synchronised; returns a float32 (n, 32) tensor).  first_number: the number of the
+        first probe, which seeds its paths -- a probe keeps its record wherever it stands in a call.  keep_maps: the context keeps every ray's sums and
+        hits (ReadProbeMaps); accumulate: add the samples to the bake kept.  Anything else: ValueError, before any library call."""
+        on_device = _check_probe_call(positions, resolution, samples, first_sample, first_number, keep_maps, accumulate, getattr(self, "_device", 0))
+        n = int(positions.shape[0])
+        flags = (PROBES_KEEP_MAPS if keep_maps else 0) | (PROBES_ACCUMULATE if accumulate else 0) | (PROBES_DEVICE if on_device else 0)
+        call = abi.tb_probe_call(n, int(first_number), int(resolution), int(first_sample), int(samples), flags)
+        s = C.byref(settings) if settings is not None else None
+        if on_device:
+            import torch
+            out = torch.empty((n, 32), dtype=torch.float32, device=positions.device)
+            torch.cuda.current_stream(positions.device).synchronize()
+            self._check(self._L.tb_bake_probes(self._ctx, s, time, C.byref(call), C.c_void_p(positions.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty(n, PROBE_DTYPE)
+        self._check(self._L.tb_bake_probes(self._ctx, s, time, C.byref(call), _np_ptr(positions), _np_ptr(out)))
+        return out
+
+    def ReadProbeMaps(self):
+        """tb_read_probe_maps: (sums, hits) of the last bake that kept its maps -- float32 (n, M * M, 4) (sum r, sum g, sum b, accepted samples) and
+        QUERY_HIT_DTYPE (n, M * M), ray t = y * M + x of probe i at [i, t]."""
+        n, m = int(self._L.tb_get_option(self._ctx, b"probes_held")), int(self._L.tb_get_option(self._ctx, b"probes_resolution"))
+        if not n or not int(self._L.tb_get_option(self._ctx, b"probes_maps_held")):
+            self._check(self._L.tb_read_probe_maps(self._ctx, None, None))   # the library's own refusal: no maps are held
+        sums = np.empty((n, m * m, 4), np.float32); hits = np.empty((n, m * m), QUERY_HIT_DTYPE)
+        self._check(self._L.tb_read_probe_maps(self._ctx, _np_ptr(sums), _np_ptr(hits)))
+        return sums, hits
+
+    def SampleProbes(self, grid, probes, points, normals, resolution=16, backface_limit=0.25):
+        """tb_sample_probes: float (n, 4) -- the irradiance (r, g, b) of a probe grid at the points with the unit normals, and the sum of the
+        trilinear weights of the probes that counted (0: none was near, the irradiance is zeros).  grid: a ProbeGrid; probes: its records as
+        BakeProbes returned them (resolution: that bake's); a probe counts iff its Weight > 0 and its Backfaces <= backface_limit * resolution^2
+        (0.25 is DDGI's convention).  numpy arrays all, or torch tensors on the context's device all.  Anything else: ValueError, before any
+        library call."""
+        if not isinstance(grid, ProbeGrid):
+            raise ValueError("SampleProbes: grid is a ProbeGrid")
+        _check_count("SampleProbes", "resolution", resolution, PROBE_MIN_RES, PROBE_MAX_RES)
+        if isinstance(backface_limit, bool) or not isinstance(backface_limit, (int, float, np.integer, np.floating)) or np.isnan(backface_limit):
+            raise ValueError("SampleProbes: backface_limit is a number, not %r" % (backface_limit,))
+        device = getattr(self, "_device", 0)
+        on_device = False if _is_probe_array(probes, "SampleProbes", grid.n) else _check_float_rows("SampleProbes", "probes", probes, 32, 16, device, rows=grid.n)
+        if _check_float_rows("SampleProbes", "points", points, 3, 4, device) != on_device or \
+                _check_float_rows("SampleProbes", "normals", normals, 3, 4, device, rows=int(points.shape[0])) != on_device:
+            raise ValueError("SampleProbes: probes, points and normals are numpy arrays all, or torch tensors all")
+        n = int(points.shape[0])
+        g = grid.c_struct()
+        if on_device:
+            import torch
+            out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()
+            self._check(self._L.tb_sample_probes(self._ctx, PROBES_DEVICE, C.byref(g), resolution, float(backface_limit), C.c_void_p(probes.data_ptr() or None), n,
+                                                 C.c_void_p(points.data_ptr() or None), C.c_void_p(normals.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty((n, 4), np.float32)
+        self._check(self._L.tb_sample_probes(self._ctx, 0, C.byref(g), resolution, float(backface_limit), _np_ptr(probes), n, _np_ptr(points), _np_ptr(normals),
+                                             _np_ptr(out)))
+        return out
+
+    def RunProbeRays(self, positions, resolution, first_number=0):
+        """probe_rays on host positions (n, 3), no scene: (RADIANCE_RAY_DTYPE, QUERY_RAY_DTYPE) arrays of shape (n, M * M)."""
+        _check_count("RunProbeRays", "resolution", resolution, PROBE_MIN_RES, PROBE_MAX_RES)
+        p = np.ascontiguousarray(positions, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or not p.shape[0] or p.shape[0] * resolution * resolution > 1 << 24:
+            raise ValueError("RunProbeRays: positions are (n, 3), 1 <= n, at most 2^24 rays")
+        _check_count("RunProbeRays", "first_number", first_number, 0, PROBE_MAX_PROBES - p.shape[0])
+        rad = np.empty((p.shape[0], resolution * resolution), RADIANCE_RAY_DTYPE); qry = np.empty(rad.shape, QUERY_RAY_DTYPE)
+        self._check(self._L.tb_run_probe_rays(self._ctx, p.shape[0], resolution, first_number, _np_ptr(p), _np_ptr(rad), _np_ptr(qry)))
+        return rad, qry
+
+    def RunProbeProject(self, positions, resolution, sums, hits):
+        """probe_project on host arrays, no scene: positions (n, 3), sums float32 (n, M * M, 4), hits QUERY_HIT_DTYPE (n, M * M); PROBE_DTYPE (n,)."""
+        _check_count("RunProbeProject", "resolution", resolution, PROBE_MIN_RES, PROBE_MAX_RES)
+        p = np.ascontiguousarray(positions, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or not p.shape[0] or p.shape[0] * resolution * resolution > 1 << 24:
+            raise ValueError("RunProbeProject: positions are (n, 3), 1 <= n, at most 2^24 rays")
+        sm = np.ascontiguousarray(sums, np.float32); ht = np.ascontiguousarray(hits)
+        if sm.shape != (p.shape[0], resolution * resolution, 4) or ht.dtype != QUERY_HIT_DTYPE or ht.shape != sm.shape[:2]:
+            raise ValueError("RunProbeProject: sums are float32 (n, M * M, 4) and hits QUERY_HIT_DTYPE (n, M * M)")
+        out = np.empty(p.shape[0], PROBE_DTYPE)
+        self._check(self._L.tb_run_probe_project(self._ctx, p.shape[0], resolution, _np_ptr(p), _np_ptr(sm), _np_ptr(ht), _np_ptr(out)))
         return out
 
     # -- dynamic scenes (DESIGN.md section 21) ----------------------------------------------------

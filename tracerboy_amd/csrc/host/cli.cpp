@@ -248,6 +248,73 @@ static int bakeLightmap(int argc, char** argv)
     return 0;
 }
 
+/* scene.pbrt --bake-probes NXxNYxNZ [--probe-bounds x0,y0,z0,x1,y1,z1] [--probe-res M] [--probe-samples S] [--device I] --out probes.jsonl (DESIGN.md
+ * section 25; tb_bake_probes): NX x NY x NZ probes at the centres of equal cells of the bounds (default: the scene's box), an M x M map each (default
+ * 16), samples [0, S) (default 64), default settings; one JSON line per probe: its number, position, 27 coefficients, five statistics.  A bake is no
+ * render: every other flag is refused here (exit status 2), before any device call. */
+static bool isProbeBake(int argc, char** argv) { for (int i = 2; i < argc; i++) if (!strcmp(argv[i], "--bake-probes")) return true; return false; }
+static int bakeProbes(int argc, char** argv)
+{
+    std::string out; int device = 0; unsigned long long count[3] = {0, 0, 0}; long long res = 16, samples = 64; double bounds[6]; bool sized = false, bounded = false;
+    for (int i = 2; i < argc; i += 2) {
+        const std::string k = argv[i];
+        if (k != "--bake-probes" && k != "--probe-bounds" && k != "--probe-res" && k != "--probe-samples" && k != "--out" && k != "--device") {
+            fprintf(stderr, "--bake-probes goes with --probe-bounds, --probe-res, --probe-samples, --device and --out only, not %s: a bake is no render\n", k.c_str()); return 2; }
+        if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", k.c_str()); return 2; }
+        const char* v = argv[i + 1]; char* end = nullptr;
+        if (k == "--bake-probes") {
+            const char* at = v; bool ok = true;
+            for (int a = 0; a < 3 && ok; a++) {
+                ok = *at >= '0' && *at <= '9';
+                if (ok) { count[a] = strtoull(at, &end, 10); ok = count[a] >= 1 && count[a] <= (1ull << 24) && *end == (a < 2 ? 'x' : '\0'); at = end + 1; }
+            }
+            if (!ok || count[0] * count[1] * count[2] > (1ull << 24)) { fprintf(stderr, "--bake-probes is NXxNYxNZ, each at least 1, at most 2^24 probes\n"); return 2; }
+            sized = true; }
+        else if (k == "--probe-bounds") {
+            const char* at = v; bool ok = true;
+            for (int a = 0; a < 6 && ok; a++) { bounds[a] = strtod(at, &end); ok = end != at && std::isfinite(bounds[a]) && *end == (a < 5 ? ',' : '\0'); at = end + 1; }
+            if (!ok) { fprintf(stderr, "--probe-bounds is x0,y0,z0,x1,y1,z1, six finite numbers\n"); return 2; }
+            bounded = true; }
+        else if (k == "--probe-res") { res = strtoll(v, &end, 10);
+            if (end == v || *end || res < 2 || res > 64) { fprintf(stderr, "--probe-res is 2 to 64\n"); return 2; } }
+        else if (k == "--probe-samples") { samples = strtoll(v, &end, 10);
+            if (end == v || *end || samples < 1 || samples > (1ll << 24)) { fprintf(stderr, "--probe-samples is 1 to 2^24\n"); return 2; } }
+        else if (k == "--out") out = v; else device = atoi(v);
+    }
+    if (!sized) { fprintf(stderr, "--bake-probes needs NXxNYxNZ\n"); return 2; }
+    const uint64_t n = count[0] * count[1] * count[2];
+    if (n * (uint64_t)(res * res) > (1ull << 31)) { fprintf(stderr, "--bake-probes: more than 2^31 rays\n"); return 2; }
+    if (out.size() < 7 || out.compare(out.size() - 6, 6, ".jsonl") != 0) { fprintf(stderr, "--bake-probes writes --out probes.jsonl\n"); return 2; }
+    tb_context* ctx = nullptr;
+    int rc = tb_create(&ctx, device);
+    if (rc) return fail(nullptr, "tb_create", rc);
+    if ((rc = tb_load_scene(ctx, argv[1]))) return fail(ctx, "tb_load_scene", rc);
+    if (!bounded) { tb_scene_info info; if ((rc = tb_scene_info_get(ctx, &info))) return fail(ctx, "tb_scene_info_get", rc);
+        for (int a = 0; a < 3; a++) { bounds[a] = info.sceneMin[a]; bounds[3 + a] = info.sceneMax[a]; } }
+    std::vector<float> positions(3 * n); std::vector<TbProbe> probes(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t at[3] = {i % count[0], (i / count[0]) % count[1], i / (count[0] * count[1])};
+        for (int a = 0; a < 3; a++) positions[3 * i + a] = (float)(bounds[a] + ((double)at[a] + 0.5) * (bounds[3 + a] - bounds[a]) / (double)count[a]);
+    }
+    const tb_probe_call call = {(uint32_t)n, 0u, (uint32_t)res, 0u, (uint32_t)samples, 0u};
+    if ((rc = tb_bake_probes(ctx, nullptr, 0.0f, &call, positions.data(), probes.data()))) return fail(ctx, "tb_bake_probes", rc);
+    FILE* f = fopen(out.c_str(), "w");
+    if (!f) { fprintf(stderr, "cannot open %s\n", out.c_str()); tb_destroy(ctx); return 1; }
+    for (uint64_t i = 0; i < n; i++) {
+        const TbProbe& p = probes[i];
+        fprintf(f, "{\"probe\": %llu, \"position\": [%.9g, %.9g, %.9g], \"sh\": [", (unsigned long long)i, positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]);
+        for (int k = 0; k < 27; k++) fprintf(f, "%s%.9g", k ? ", " : "", p.SH[k]);
+        fprintf(f, "], \"weight\": %.9g, \"hits\": %.9g, \"backfaces\": %.9g, \"min_distance\": %.9g, \"mean_distance\": %.9g}\n", p.Weight, p.Hits, p.Backfaces,
+            p.MinDistance, p.MeanDistance);
+    }
+    if (fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", out.c_str()); tb_destroy(ctx); return 1; }
+    printf("{\"probes\": \"%llux%llux%llu\", \"resolution\": %lld, \"samples\": %lld, \"batches\": %lld, \"rays_us\": %lld, \"trace_us\": %lld, \"hits_us\": %lld, \"project_us\": %lld}\n",
+        count[0], count[1], count[2], res, samples, (long long)tb_get_option(ctx, "last_probes_batches"), (long long)tb_get_option(ctx, "last_probes_rays_us"),
+        (long long)tb_get_option(ctx, "last_probes_trace_us"), (long long)tb_get_option(ctx, "last_probes_hits_us"), (long long)tb_get_option(ctx, "last_probes_project_us"));
+    tb_destroy(ctx);
+    return 0;
+}
+
 /* ---- RCCL, loaded at run time: the handful of entry points the gather needs (rccl.h) ---- */
 struct RcclId { char internal[128]; };                 /* ncclUniqueId */
 struct Rccl {
@@ -318,8 +385,9 @@ static int spawnRanks(int argc, char** argv, int world)
 int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr,
-        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C --reference FILE --metrics-out FILE --metrics-every N --error-map f.pfm --visualize-rays X,Y --visualize-frames A:B --visualize-width R --visualize-depth D --visualize-count N --paths-out f.jsonl]\n       tracerboy-hip --compare A B [--metrics-out FILE --device I]\n"); return 2; }
+        "usage: tracerboy-hip scene.pbrt [--width W --height H --spp N --depth D --seed-time T --device I --builder lbvh|sah|lbvh-gpu|treelets|treelets-gpu --blue-noise 0|1 --tonemap 0..7 --exposure E|auto --out f.png|f.pfm|f.exr --ranks N --adaptive P --adaptive-after F --adaptive-chunk C --adaptive-test frame|call --save-state f.tbs --resume f.tbs --add g.tbs --frames A:B --checkpoint-every N --denoise --denoise-iterations N --denoise-guides K --denoise-demodulate --upscale WxH --render-scale F --fsr-sharpness S --denoise-neural f.tza --upscale-neural f.bin --crop X0,Y0,X1,Y1 --spp-map FILE --noise-target T --noise-after F --noise-chunk C --reference FILE --metrics-out FILE --metrics-every N --error-map f.pfm --visualize-rays X,Y --visualize-frames A:B --visualize-width R --visualize-depth D --visualize-count N --paths-out f.jsonl]\n       tracerboy-hip scene.pbrt --bake-probes NXxNYxNZ [--probe-bounds x0,y0,z0,x1,y1,z1 --probe-res M --probe-samples S --device I] --out probes.jsonl\n       tracerboy-hip --compare A B [--metrics-out FILE --device I]\n"); return 2; }
     if (!strcmp(argv[1], "--compare")) return compareFiles(argc, argv);
+    if (isProbeBake(argc, argv)) return bakeProbes(argc, argv);
     if (isBake(argc, argv)) return bakeLightmap(argc, argv);
     std::string scene = argv[1], out = "frame.png";
     tb_post_settings post; tb_default_post_settings(&post);

@@ -20,6 +20,7 @@
  *   context_rays.cpp    ray queries: tb_trace_rays, closest hits and any-hit occlusion of a caller's rays, host arrays or device buffers
  *   context_radiance.cpp radiance queries: tb_trace_radiance, the path tracer on a caller's rays, and tb_make_camera_rays
  *   context_bake.cpp    lightmap baking: tb_bake_lightmap, a UV atlas rasterised, its texels traced by the radiance query, resolved and dilated
+ *   context_probes.cpp  light probes: tb_bake_probes, SH9 records of the radiance and the distances around points, and tb_sample_probes
  *   context_meshes.cpp  scenes from caller arrays: tb_load_meshes, device arrays read to the host once, the swap into the context
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
@@ -280,6 +281,18 @@ struct tb_context {
         tbctx::DevEvent ev[4]; float lastRasterMs = 0.0f, lastTraceMs = 0.0f, lastFinishMs = 0.0f;
     };
     std::unique_ptr<Bake> bake;
+    /* light probes (context_probes.cpp): made at the first tb_bake_probes of a scene, released with the scene (releaseScene);
+     * a context that never bakes probes holds none of it.  radRays, queryRays: the two ray records of one batch; sums, hits: what the two queries
+     * answered -- of one batch, or, where the bake keeps its maps (TB_PROBES_KEEP_MAPS), of every ray of the bake, which tb_read_probe_maps
+     * returns and TB_PROBES_ACCUMULATE adds to; records: the n probes; positions: the host path's copy of the caller's.  held: records holds a
+     * finished bake of n probes at `resolution`, traced at scene generation bakedOf; mapsHeld: sums and hits hold all of its rays.  ev: around the
+     * stages of a batch (options last_probes_*_us, summed over the batches; the trace is the radiance query's own two events) */
+    struct Probes {
+        DevBuf radRays, queryRays, sums, hits, records, positions;
+        uint64_t n = 0; uint32_t resolution = 0, bakedOf = 0, lastBatches = 0; bool held = false, mapsHeld = false;
+        tbctx::DevEvent ev[5]; float lastRaysMs = 0.0f, lastTraceMs = 0.0f, lastHitsMs = 0.0f, lastProjectMs = 0.0f;
+    };
+    std::unique_ptr<Probes> probes;
     tb_output_settings lastSettings{}; bool haveLastSettings = false;
     float lastTime = 0.0f;
     uint32_t selX = 0xffffffffu, selY = 0xffffffffu;
@@ -393,6 +406,9 @@ void BuildTlasGpu(tb_context* c, HostScene& s, const std::vector<float>& blasBox
 void refreshHostScene(tb_context* c);
 /* context_rays.cpp: why a device pointer the caller gave is refused -- `bytes` from it must lie inside one allocation of the context's device; null: it is not */
 const char* devicePointerRefusal(const tb_context* c, const void* p, size_t bytes);
+/* context_rays.cpp: the closest-hit launch of tb_trace_rays on n device rays into n device hit records, on the context's stream, not waited for.
+ * tb_trace_rays and tb_bake_probes (context_probes.cpp) both end here.  The caller has checked the scene and the pointers. */
+void traceClosestOnDevice(tb_context* c, uint32_t n, const TbQueryRay* rays, TbQueryHit* hits);
 /* context_render.cpp */
 bool historyRelevantChange(const tb_output_settings& a, const tb_output_settings& b);
 int deviceCUs(tb_context* c);

@@ -91,6 +91,12 @@ const Query kQueries[] = {
     Q("last_bake_raster_us", microseconds(c->bake ? c->bake->lastRasterMs : 0.0f)) Q("last_bake_trace_us", microseconds(c->bake ? c->bake->lastTraceMs : 0.0f))
     Q("last_bake_finish_us", microseconds(c->bake ? c->bake->lastFinishMs : 0.0f)) Q("last_bake_covered", c->bake ? c->bake->lastCovered : 0u)
     Q("bake_width", c->bake && c->bake->held ? c->bake->width : 0u) Q("bake_height", c->bake && c->bake->held ? c->bake->height : 0u) /* of the bake held; 0: none */
+    /* light probes: the last bake's four stages summed over its batches (HIP events; the trace is the radiance query's own), its
+     * batches, and what is held */
+    Q("last_probes_rays_us", microseconds(c->probes ? c->probes->lastRaysMs : 0.0f)) Q("last_probes_trace_us", microseconds(c->probes ? c->probes->lastTraceMs : 0.0f))
+    Q("last_probes_hits_us", microseconds(c->probes ? c->probes->lastHitsMs : 0.0f)) Q("last_probes_project_us", microseconds(c->probes ? c->probes->lastProjectMs : 0.0f))
+    Q("last_probes_batches", c->probes ? c->probes->lastBatches : 0u) Q("probes_held", c->probes && c->probes->held ? c->probes->n : 0u)
+    Q("probes_resolution", c->probes && c->probes->held ? c->probes->resolution : 0u) Q("probes_maps_held", c->probes && c->probes->held && c->probes->mapsHeld ? 1 : 0)
     Q("last_copy_waves", c->lastCopyWaves)
     Q("last_adaptive", c->lastAdaptive ? 1 : 0) /* the adaptive launch: did the last call run it */
     /* sample budgets: one is set; the last call was planned under it (its live pixels: last_live_pixels) */

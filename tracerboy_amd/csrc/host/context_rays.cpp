@@ -52,6 +52,11 @@ int refillDiagnostic()
 
 } // namespace
 
+void tbctx::traceClosestOnDevice(tb_context* c, uint32_t n, const TbQueryRay* rays, TbQueryHit* hits)
+{
+    HIP_TRY(rq_launch_closest(c->stream, &c->ds, n, rays, hits, nullptr));
+}
+
 extern "C" int tb_trace_rays(tb_context* c, uint32_t modeAndFlags, uint64_t n, const TbQueryRay* rays, void* out)
 {
     TB_REFUSE_PEER(c);
@@ -71,7 +76,7 @@ extern "C" int tb_trace_rays(tb_context* c, uint32_t modeAndFlags, uint64_t n, c
         const TbQueryRay* r = device ? rays : (const TbQueryRay*)dRays.p;
         void* o = device ? out : dOut.p;
         const int diag = closest ? -2 : refillDiagnostic();
-        if (closest) HIP_TRY(rq_launch_closest(c->stream, &c->ds, (uint32_t)n, r, (TbQueryHit*)o, nullptr));
+        if (closest) traceClosestOnDevice(c, (uint32_t)n, r, (TbQueryHit*)o);
         else if (c->ds.numInstances || diag == -1) HIP_TRY(rq_launch_closest(c->stream, &c->ds, (uint32_t)n, r, nullptr, (uint8_t*)o));
         else {
             const uint32_t refill = diag >= 0 ? (uint32_t)diag : rq_refill_for(c->ds.numTris);

@@ -10,6 +10,7 @@ void releaseScene(tb_context* c)
     c->sceneBufs.clear();
     c->dyn.reset(); /* the dynamic state belongs to the scene's buffers and topology (context_dynamic.cpp) */
     c->bake.reset(); /* and so does a bake (context_bake.cpp) */
+    c->probes.reset(); /* and so do baked probes (context_probes.cpp) */
     memset(&c->ds, 0, sizeof c->ds);
 }
 

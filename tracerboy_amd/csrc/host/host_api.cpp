@@ -7,6 +7,7 @@
 #include "options.h"
 #include "tb_state.h"
 #include "wave_cost.h"
+#include "../kernels/probe_launch.h"
 
 #include <cstring>
 #include <memory>
@@ -173,6 +174,53 @@ int tb_bake_refusal(const tb_bake_call* call, const void* uv, const void* rgbaOu
     const char* no = bakeRefusal(call, uv, rgbaOut);
     if (why && whyBytes) { strncpy(why, no ? no : "", whyBytes - 1); why[whyBytes - 1] = 0; }
     return no ? TB_E_INVALID : TB_OK;
+}
+
+/* Why tb_bake_probes refuses its arguments before it looks at the context: pure tests, in the order the header lists them. */
+static const char* probesRefusal(const tb_probe_call* call, const void* positions, const void* probesOut)
+{
+    if (!call) return "null call";
+    if (call->resolution < PROBE_MIN_RES || call->resolution > PROBE_MAX_RES) return "the resolution is outside [2, 64]";
+    if ((uint64_t)call->n * call->resolution * call->resolution > (1ull << 31)) return "more than 2^31 rays";
+    if (call->n > (1u << 24) || (uint64_t)call->first_probe_number + call->n > (1ull << 24)) return "probe numbers above 2^24: the seed is not an exact float";
+    if (call->num_samples == 0) return "num_samples is 0";
+    if (call->num_samples > (1u << 24)) return "more than 2^24 samples per ray";
+    if ((uint64_t)call->first_sample + call->num_samples > (1ull << 32)) return "first_sample + num_samples passes 2^32";
+    if (call->flags & ~(TB_PROBES_DEVICE | TB_PROBES_ACCUMULATE | TB_PROBES_KEEP_MAPS)) return "unknown flag bits";
+    if (call->n && (!positions || !probesOut)) return "null pointer";
+    if (call->n && (call->flags & TB_PROBES_DEVICE)) {
+        if ((uintptr_t)positions & 3u) return "the device positions are not 4-B aligned";
+        if ((uintptr_t)probesOut & 15u) return "the device probe records are not 16-B aligned";
+    }
+    return nullptr;
+}
+
+int tb_probes_refusal(const tb_probe_call* call, const void* positions, const void* probesOut, char* why, uint32_t whyBytes)
+{
+    const char* no = probesRefusal(call, positions, probesOut);
+    if (why && whyBytes) { strncpy(why, no ? no : "", whyBytes - 1); why[whyBytes - 1] = 0; }
+    return no ? TB_E_INVALID : TB_OK;
+}
+
+int tb_sh9_irradiance(const TbProbe* probe, const float* normal, float* rgbOut)
+{
+    if (!probe || !normal || !rgbOut) return TB_E_INVALID;
+    float Y[9];
+    probe_basis(normal[0], normal[1], normal[2], Y);
+    for (int ch = 0; ch < 3; ch++) rgbOut[ch] = probe_sh9_channel(probe->SH + ch, 3, Y);
+    return TB_OK;
+}
+
+int tb_probe_directions(uint32_t M, float* dirsOut, float* weightsOut)
+{
+    if (M < PROBE_MIN_RES || M > PROBE_MAX_RES) return TB_E_INVALID;
+    for (uint32_t t = 0; t < M * M; t++) {
+        float d[3], w;
+        probe_direction(M, t % M, t / M, d, &w);
+        if (dirsOut) memcpy(dirsOut + 3ull * t, d, 12);
+        if (weightsOut) weightsOut[t] = w;
+    }
+    return TB_OK;
 }
 
 int tb_unpack_gathered_host(uint32_t W, uint32_t H, uint32_t world, uint32_t tw, uint32_t th, const float* const* perRank, float* full)
