@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from adversarial_cases import brute_force_closest as _brute_force_closest
 
 
 def test_hash13_seed_values(built):
@@ -142,27 +143,6 @@ def test_no_nan_and_weights_count_frames(cornell_host, settings):
     st = r["stats"]
     assert st.samples == 48 * 32 * 5
     assert st.rays >= st.samples and st.boxesTested > st.trianglesTested > 0
-
-
-def _brute_force_closest(tri, o, d, tmin=0.001):
-    """Nearest intersection of each ray with ANY triangle, Moeller-Trumbore in float64: geometry, not the reference's arithmetic.
-    tri (T, 3, 3), o / d (R, 3) -> t (R,) (inf on a miss), edge (R,) = how close the winning hit is to a triangle edge."""
-    tri = tri.astype(np.float64); o = o.astype(np.float64); d = d.astype(np.float64)
-    best_t = np.full(len(o), np.inf); best_edge = np.zeros(len(o))
-    e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
-    for r0 in range(0, len(o), 64):
-        oo, dd = o[r0:r0 + 64, None, :], d[r0:r0 + 64, None, :]
-        p = np.cross(dd, e2[None]); det = (e1[None] * p).sum(-1)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = 1.0 / det
-            s = oo - tri[None, :, 0]; u = (s * p).sum(-1) * inv
-            q = np.cross(s, e1[None]); v = (dd * q).sum(-1) * inv; t = (e2[None] * q).sum(-1) * inv
-        ok = (np.abs(det) > 1e-14) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > tmin)
-        t = np.where(ok, t, np.inf)
-        k = t.argmin(axis=1); rows = np.arange(t.shape[0])
-        best_t[r0:r0 + 64] = t[rows, k]
-        best_edge[r0:r0 + 64] = np.minimum(np.minimum(u[rows, k], v[rows, k]), 1 - u[rows, k] - v[rows, k])
-    return best_t, best_edge
 
 
 @pytest.mark.parametrize("scene", ["cornell", "teapot"])
