@@ -199,6 +199,17 @@ typedef struct tb_probe_grid { float origin[3], spacing[3]; uint32_t count[3]; }
 TB_STATIC_ASSERT(sizeof(TbProbe) == 128, "a probe is 32 dwords");
 TB_STATIC_ASSERT(sizeof(tb_probe_grid) == 36, "a probe grid is 9 dwords");
 
+/* ---- point queries (tracerboy_hip.h tb_nearest_points; the rule: tb_nearest.h) ----
+ * A point of a query, 16 B and 16-B aligned on the device: a triangle counts iff the Distance its record would carry is <= MaxDistance (+inf:
+ * every triangle; a NaN or a negative value: none).  A record, 32 B: the nearest point of the scene's triangles, its distance -- tb_math.h's
+ * square root of the rule's D2, negated under TB_NEAREST_SIGNED where the point lies behind the winning triangle --, the weights of that
+ * triangle's vertices 1 and 2 at Point, and its primitiveIndex and geometryIndex.  A miss is Point = 0, Distance = +inf, U = V = 0, Prim = Geom =
+ * 0xffffffff. */
+typedef struct TbQueryPoint { float Position[3]; float MaxDistance; } TbQueryPoint;
+typedef struct TbNearest { float Point[3]; float Distance; float U, V; uint32_t Prim, Geom; } TbNearest;
+TB_STATIC_ASSERT(sizeof(TbQueryPoint) == 16, "a query point is 4 dwords");
+TB_STATIC_ASSERT(sizeof(TbNearest) == 32, "a nearest-point record is 8 dwords");
+
 /* SharedShaderStructs.h:141-161 */
 typedef struct TbMaterial {
     TbFloat3 albedo;       uint32_t albedoIndex;

@@ -734,6 +734,43 @@ int tb_run_probe_rays(tb_context* ctx, uint32_t n, uint32_t resolution, uint32_t
 int tb_run_probe_project(tb_context* ctx, uint32_t n, uint32_t resolution, const float* positions_xyz, const float* sums, const TbQueryHit* hits,
                          TbProbe* probes_out);
 
+/* ---- point queries (no reference counterpart) ---------------------------------------------------------------------
+ * The tree as a service for POINTS: for each of n points (tb_abi.h TbQueryPoint) the nearest point of the scene's triangles, a TbNearest record.
+ * include/tb_nearest.h states the rule operation by operation -- the nearest point of one triangle, which triangles count (Distance <=
+ * MaxDistance), the tie-break (smaller Geom, then smaller Prim) and the pruning slack of the walk -- and host and device give the same bits; the
+ * answer is a function of the triangle set and the point alone, whatever the tree.  Synchronous like tb_trace_rays, on host arrays (staged,
+ * nothing kept) or, with TB_NEAREST_DEVICE, on device pointers of the context's device (16-B aligned; nothing is allocated).  The kernel is a
+ * nearest-first walk of the layout-B tree in memory, one point per lane; layout C and LDS-resident scenes change nothing, option "alpha_test" does
+ * not apply (the query is geometry alone), positions are what the last tb_commit_geometry left.  A position that is not finite is a miss.
+ * TB_NEAREST_SIGNED: Distance is negated where the point lies behind the NEAREST TRIANGLE (dot(p - Point, face vector) < 0; the face vector is
+ * tb_normals.h's).  That is exact where the nearest point is interior to a triangle and for convex closed meshes; near edges and vertices of a
+ * mesh that is not convex the sign can be wrong.
+ * tb_bake_distance_field: the same walk over the cells of a grid (tb_abi.h tb_probe_grid: cell (i, j, k) at origin + (i, j, k) * spacing, one
+ * rounded product and one rounded sum per axis, number (k * count[1] + j) * count[0] + i), positions made in the kernel and never stored; out is
+ * one float per cell, the Distance of the cell's record (signed under the flag, +inf on a miss), every cell with MaxDistance = max_distance.
+ * out is a host array or, with TB_NEAREST_DEVICE, a 4-B aligned device pointer.
+ * Refusals, in this order: a peer handle (TB_E_INVALID); TB_E_UNSUPPORTED for a tb_create_multi group ("multi-device group"); tb_nearest_refusal's
+ * (TB_E_INVALID: unknown flag bits; n > 2^31; a null pointer with n > 0; misaligned device pointers; a null grid, a count of 0, more than 2^31
+ * cells, an origin or a spacing that is not finite); TB_E_NO_SCENE; TB_E_UNSUPPORTED for a two-level scene ("two-level": a transform with
+ * non-uniform scale does not keep nearest points; load with option "flatten_instances" = 1); n = 0: TB_OK, nothing is launched; pointers that are
+ * not memory of the context's device, or too short (TB_E_INVALID).
+ * tb_get_option "last_nearest_us": GPU microseconds of the last query's kernel (HIP events).
+ * tb_nearest_refusal (host only, pure, like tb_bake_refusal): grid_or_null = null judges a tb_nearest_points call, else a tb_bake_distance_field
+ * call (n and points are not read).
+ * tb_host_scene_nearest: the rule on the host, over a one-level host scene's layout-B arrays (TB_E_UNSUPPORTED for a two-level one).  flags:
+ * TB_NEAREST_SIGNED and exactly one of TB_NEAREST_HOST_BRUTE -- every triangle, in order, through the header's rule -- and TB_NEAREST_HOST_WALK
+ * -- the kernel's walk and pruning rule as scalar C++.  tb_host_scene_nearest_excess: the measurement behind TB_NEAREST_SLACK_ULPS
+ * (scripts/nearest_slack.py): over the n points, the largest sqrt(tb_box_d2) - sqrt(D2) of a box above the brute-force winner's leaf (the root's
+ * box included), in units of 2^-23 x tb_nearest_scale; 0 where every such box is nearer than its triangle. */
+#define TB_NEAREST_SIGNED     0x1u
+#define TB_NEAREST_DEVICE     0x100u    /* the value and meaning of TB_RAYS_DEVICE */
+#define TB_NEAREST_HOST_BRUTE 0x1000u   /* tb_host_scene_nearest only */
+#define TB_NEAREST_HOST_WALK  0x2000u   /* tb_host_scene_nearest only */
+int tb_nearest_points(tb_context* ctx, uint32_t flags, uint64_t n, const TbQueryPoint* points, TbNearest* out);
+int tb_bake_distance_field(tb_context* ctx, uint32_t flags, const tb_probe_grid* grid, float max_distance, float* out);
+int tb_nearest_refusal(uint32_t flags, uint64_t n, const void* points, const void* out, const tb_probe_grid* grid_or_null, char* why_or_null,
+                       uint32_t why_bytes);
+
 /* ---- dynamic scenes (no reference counterpart: its scene is frozen once LoadScene returns) -------------------------
  * Vertices and instance transforms are STAGED by the three calls below; nothing a render or a trace reads changes until tb_commit_geometry, which
  * waits for the context's stream and then applies everything staged.  A commit with nothing staged is TB_OK and does nothing.
@@ -1053,6 +1090,9 @@ int tb_host_scene_wave_stage(tb_host_scene* s, tb_wave_stage_info* out);
 int tb_host_pbrt_dump(const char* pbrt_path, const char* out_path, char* err, uint32_t err_len);
 int tb_host_scene_triangles(tb_host_scene* s, const float** positions, uint32_t* num_vertices, const uint32_t** tri_vertex_index,
                             const uint32_t** tri_geometry, const uint32_t** tri_primitive, const uint32_t** tri_flags, uint32_t* num_triangles);
+/* point queries on the host (section 27 above): the rule of tb_nearest.h by brute force or by the kernel's walk, and the pruning slack's measurement */
+int tb_host_scene_nearest(tb_host_scene* scene, uint32_t flags, uint64_t n, const TbQueryPoint* points, TbNearest* out);
+int tb_host_scene_nearest_excess(tb_host_scene* scene, uint64_t n, const TbQueryPoint* points, float* worst_out);
 
 #ifdef __cplusplus
 }

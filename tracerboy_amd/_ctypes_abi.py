@@ -243,6 +243,20 @@ class tb_probe_call(C.Structure):
 assert C.sizeof(TbProbe) == 128 and C.sizeof(tb_probe_grid) == 36 and C.sizeof(tb_probe_call) == 24
 
 
+class TbQueryPoint(C.Structure):
+    """A point of tb_nearest_points (tb_abi.h): a triangle counts iff the Distance of its record is <= MaxDistance."""
+    _fields_ = [("Position", C.c_float * 3), ("MaxDistance", C.c_float)]
+
+
+class TbNearest(C.Structure):
+    """A record of tb_nearest_points (tb_abi.h): the nearest point, its distance, the weights of the triangle's vertices 1 and 2; a miss is
+    Point = 0, Distance = +inf, U = V = 0, Prim = Geom = 0xffffffff."""
+    _fields_ = [("Point", C.c_float * 3), ("Distance", C.c_float), ("U", C.c_float), ("V", C.c_float), ("Prim", C.c_uint32), ("Geom", C.c_uint32)]
+
+
+assert C.sizeof(TbQueryPoint) == 16 and C.sizeof(TbNearest) == 32
+
+
 class tb_nn_info(C.Structure):
     """include/tracerboy_hip.h tb_nn_info: the channel counts of a weights file's 16 layers (tb_nn_weights_info)."""
     _fields_ = [("in_channels", C.c_uint32), ("out_channels", C.c_uint32 * 16), ("in_channels_of", C.c_uint32 * 16), ("weight_bytes", C.c_uint64)]

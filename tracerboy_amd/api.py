@@ -134,6 +134,11 @@ def lib():
         "tb_probe_directions": (C.c_int, [C.c_uint32, vp, vp]),
         "tb_run_probe_rays": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
         "tb_run_probe_project": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+        "tb_nearest_points": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp]),
+        "tb_bake_distance_field": (C.c_int, [vp, C.c_uint32, P(abi.tb_probe_grid), C.c_float, vp]),
+        "tb_nearest_refusal": (C.c_int, [C.c_uint32, C.c_uint64, vp, vp, P(abi.tb_probe_grid), C.c_char_p, C.c_uint32]),
+        "tb_host_scene_nearest": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp]),
+        "tb_host_scene_nearest_excess": (C.c_int, [vp, C.c_uint64, vp, P(C.c_float)]),
         "tb_update_positions": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_update_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -567,6 +572,69 @@ def probe_directions(resolution):
     return d, w
 
 
+# point queries (tb_nearest_points, tb_bake_distance_field; tb_abi.h TbQueryPoint / TbNearest; the rule: include/tb_nearest.h)
+NEAREST_SIGNED, NEAREST_DEVICE, NEAREST_HOST_BRUTE, NEAREST_HOST_WALK = 1, 0x100, 0x1000, 0x2000
+NEAREST_NONE = 0xffffffff
+QUERY_POINT_DTYPE = np.dtype([("Position", np.float32, 3), ("MaxDistance", np.float32)])
+NEAREST_DTYPE = np.dtype([("Point", np.float32, 3), ("Distance", np.float32), ("U", np.float32), ("V", np.float32), ("Prim", np.uint32), ("Geom", np.uint32)])
+assert QUERY_POINT_DTYPE.itemsize == 16 and NEAREST_DTYPE.itemsize == 32
+
+
+def make_query_points(positions, max_distance=np.inf):
+    """(n, 3) positions packed into QUERY_POINT_DTYPE; max_distance: a scalar or n values (inf: every triangle counts)."""
+    p = np.asarray(positions, np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("make_query_points: positions are an (n, 3) array")
+    points = np.zeros(p.shape[0], QUERY_POINT_DTYPE)
+    points["Position"] = p
+    points["MaxDistance"] = np.broadcast_to(np.asarray(max_distance, np.float32), (p.shape[0],))
+    return points
+
+
+def _check_flag(what, name, v):
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("%s: %s is True or False, not %r" % (what, name, v))
+    return bool(v)
+
+
+def _check_query_points(what, points, device, allow_tensor=True):
+    """What NearestPoints accepts, checked before any library call: True for a torch tensor (the device path), False for a numpy array (the host
+    path); ValueError otherwise."""
+    if _is_torch_tensor(points):
+        if not allow_tensor:
+            raise ValueError("%s: points are a numpy array, not a torch tensor" % what)
+        return _check_float_rows(what, "of points", points, 4, 16, device)
+    if not isinstance(points, np.ndarray):
+        raise ValueError("%s: points are a numpy array%s, not %s" % (what, " or a torch tensor" if allow_tensor else "", type(points).__name__))
+    if points.dtype == QUERY_POINT_DTYPE:
+        if points.ndim != 1:
+            raise ValueError("%s: an array of QUERY_POINT_DTYPE has one dimension, not %d" % (what, points.ndim))
+    elif points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError("%s: points are QUERY_POINT_DTYPE or float32 of shape (n, 4), not %s %s" % (what, points.dtype, points.shape))
+    if not points.flags["C_CONTIGUOUS"]:
+        raise ValueError("%s: the array of points is not contiguous" % what)
+    return False
+
+
+def _check_distance_field(grid, signed, max_distance, device):
+    if not isinstance(grid, ProbeGrid):
+        raise ValueError("BakeDistanceField: grid is a ProbeGrid, not %s" % type(grid).__name__)
+    _check_flag("BakeDistanceField", "signed", signed); _check_flag("BakeDistanceField", "device", device)
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
+        raise ValueError("BakeDistanceField: max_distance is a number, not %r" % (max_distance,))
+    if grid.n > 1 << 31:
+        raise ValueError("BakeDistanceField: more than 2^31 cells")
+
+
+def NearestRefusal(flags, n, points_address, out_address, grid=None):
+    """tb_nearest_refusal (host only): why tb_nearest_points -- with a grid (abi.tb_probe_grid): tb_bake_distance_field -- refuses these arguments before
+    it looks at its context: None, or the reason."""
+    why = C.create_string_buffer(96)
+    rc = lib().tb_nearest_refusal(flags, n, C.c_void_p(points_address or None), C.c_void_p(out_address or None), C.byref(grid) if grid is not None else None,
+                                  why, 96)
+    return None if rc == 0 else why.value.decode()
+
+
 # dynamic scenes (tb_update_positions .. tb_commit_geometry)
 UPDATE_DEVICE, GEOMETRY_REBUILD = 0x100, 1
 
@@ -959,6 +1027,27 @@ class HostScene:
         nb = np.frombuffer(C.string_at(nodes, nn.value * 64), dtype=np.uint32).reshape(nn.value, 16).copy()
         tb = np.frombuffer(C.string_at(tris, nt.value * 48), dtype=np.uint32).reshape(nt.value, 12).copy()
         return nb, tb, root.value
+
+    def nearest(self, points, signed=False, walk=False):
+        """tb_host_scene_nearest: the NEAREST_DTYPE records of include/tb_nearest.h's rule for QUERY_POINT_DTYPE (or float32 (n, 4)) points, by brute
+        force over every triangle or, walk=True, by the kernel's walk and pruning rule as scalar C++."""
+        _check_query_points("HostScene.nearest", points, 0, allow_tensor=False)
+        flags = (NEAREST_SIGNED if _check_flag("HostScene.nearest", "signed", signed) else 0) | \
+            (NEAREST_HOST_WALK if _check_flag("HostScene.nearest", "walk", walk) else NEAREST_HOST_BRUTE)
+        out = np.empty(points.shape[0], NEAREST_DTYPE)
+        rc = lib().tb_host_scene_nearest(self._h, flags, points.shape[0], _np_ptr(points), _np_ptr(out))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_nearest")
+        return out
+
+    def nearest_excess(self, points):
+        """tb_host_scene_nearest_excess: the largest sqrt(box d2) - sqrt(D2) over the boxes above a brute-force winner, in 2^-23 x the scale."""
+        _check_query_points("HostScene.nearest_excess", points, 0, allow_tensor=False)
+        worst = C.c_float()
+        rc = lib().tb_host_scene_nearest_excess(self._h, points.shape[0], _np_ptr(points), C.byref(worst))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_nearest_excess")
+        return worst.value
 
     def lds_image(self):
         """(image bytes as uint8, tb_lds_image_info): the walk's LDS image as a context uploads it for an LDS-resident scene."""
@@ -1574,6 +1663,45 @@ class TracerBoy:
             return out
         out = np.empty(n, QUERY_HIT_DTYPE if mode == RAYS_CLOSEST else np.uint8)
         self._check(self._L.tb_trace_rays(self._ctx, mode, n, _np_ptr(rays), _np_ptr(out)))
+        return out
+
+    # -- point queries ------------------------------------------------------
+    def NearestPoints(self, points, signed=False):
+        """tb_nearest_points: for every point the nearest point of the scene's triangles (include/tb_nearest.h has the rule).  A numpy array --
+        QUERY_POINT_DTYPE (make_query_points), or float32 of shape (n, 4): position, MaxDistance -- takes the host path and returns a NEAREST_DTYPE
+        array.  A torch tensor, float32 (n, 4), contiguous, 16-B aligned, on the context's device, takes the device path with zero copy: torch's
+        current stream on that device is synchronised first, and the result is a float32 (n, 8) tensor -- Point, Distance, U, V, then Prim and Geom
+        through .view(torch.int32).  signed: Distance is negative behind the nearest triangle.  Anything else: ValueError, before any library call."""
+        on_device = _check_query_points("NearestPoints", points, getattr(self, "_device", 0))
+        flags = NEAREST_SIGNED if _check_flag("NearestPoints", "signed", signed) else 0
+        n = int(points.shape[0])
+        if on_device:
+            import torch
+            out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()
+            self._check(self._L.tb_nearest_points(self._ctx, flags | NEAREST_DEVICE, n, C.c_void_p(points.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty(n, NEAREST_DTYPE)
+        self._check(self._L.tb_nearest_points(self._ctx, flags, n, _np_ptr(points), _np_ptr(out)))
+        return out
+
+    def BakeDistanceField(self, grid, signed=False, max_distance=np.inf, device=False):
+        """tb_bake_distance_field: float32 of shape (count[2], count[1], count[0]) -- for every cell of the ProbeGrid the Distance of NearestPoints at
+        origin + (i, j, k) * spacing with MaxDistance = max_distance (+inf where nothing is that near); the positions are made in the kernel.
+        device=True: a torch tensor on the context's device that torch allocated, zero copy; else a numpy array."""
+        _check_distance_field(grid, signed, max_distance, device)
+        flags = NEAREST_SIGNED if signed else 0
+        g = grid.c_struct()
+        shape = (grid.count[2], grid.count[1], grid.count[0])
+        if device:
+            import torch
+            dev = torch.device("cuda", getattr(self, "_device", 0))
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._check(self._L.tb_bake_distance_field(self._ctx, flags | NEAREST_DEVICE, C.byref(g), float(max_distance), C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty(shape, np.float32)
+        self._check(self._L.tb_bake_distance_field(self._ctx, flags, C.byref(g), float(max_distance), _np_ptr(out)))
         return out
 
     # -- radiance queries (DESIGN.md section 22) ---------------------------------------------------

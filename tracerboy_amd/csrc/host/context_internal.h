@@ -21,6 +21,7 @@
  *   context_radiance.cpp radiance queries: tb_trace_radiance, the path tracer on a caller's rays, and tb_make_camera_rays
  *   context_bake.cpp    lightmap baking: tb_bake_lightmap, a UV atlas rasterised, its texels traced by the radiance query, resolved and dilated
  *   context_probes.cpp  light probes: tb_bake_probes, SH9 records of the radiance and the distances around points, and tb_sample_probes
+ *   context_nearest.cpp point queries: tb_nearest_points and tb_bake_distance_field, the nearest surface point by a distance-ordered walk
  *   context_meshes.cpp  scenes from caller arrays: tb_load_meshes, device arrays read to the host once, the swap into the context
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
@@ -243,6 +244,8 @@ struct tb_context {
     /* ray queries (context_rays.cpp).  counter: the work counter of the any-hit walk's refilling form, made at its first
      * launch and kept: the device path of tb_trace_rays allocates nothing per call */
     struct RayQueries { DevBuf counter; } rq;
+    /* point queries (context_nearest.cpp): the events around the last query's kernel; lastMs: option last_nearest_us */
+    struct PointQueries { tbctx::DevEvent ev[2]; float lastMs = 0.0f; } pq;
     /* radiance queries (context_radiance.cpp).  counter: the work counter of the refilling form, made at its first launch and
      * kept; overflow: the query's half of a split stack.  lastMs, lastVariant, lastForm, lastLaunches: options last_radiance_us,
      * last_radiance_variant (the feature set's id, -1 before the first query), last_radiance_form, last_radiance_launches */

@@ -86,6 +86,7 @@ const Query kQueries[] = {
      * per lane, 1 the refilling grid) and how many launches it was split into */
     Q("last_radiance_us", microseconds(c->rad.lastMs)) Q("last_radiance_variant", c->rad.lastVariant) Q("last_radiance_form", c->rad.lastForm)
     Q("last_radiance_launches", c->rad.lastLaunches)
+    Q("last_nearest_us", microseconds(c->pq.lastMs)) /* point queries: the last query's kernel (HIP events) */
     /* lightmap baking: the last bake's rasteriser, its query's launches, its resolve and fill passes (HIP events); the texels
      * that have a triangle */
     Q("last_bake_raster_us", microseconds(c->bake ? c->bake->lastRasterMs : 0.0f)) Q("last_bake_trace_us", microseconds(c->bake ? c->bake->lastTraceMs : 0.0f))

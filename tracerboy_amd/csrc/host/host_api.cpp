@@ -8,10 +8,14 @@
 #include "tb_state.h"
 #include "wave_cost.h"
 #include "../kernels/probe_launch.h"
+#include "tb_nearest.h"
 
+#include <cmath>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
+#include <thread>
 
 using namespace tbhost;
 using namespace tbctx;
@@ -475,6 +479,170 @@ int tb_host_scene_wave_stage(tb_host_scene* h, tb_wave_stage_info* o)
     o->before.inner_trips = r.innerBefore; o->before.leaf_trips = r.leafBefore; o->before.cost = r.costBefore;
     o->after.inner_trips = r.innerAfter; o->after.leaf_trips = r.leafAfter; o->after.cost = r.costAfter;
     o->milliseconds = r.milliseconds;
+    return TB_OK;
+}
+
+/* ---- point queries on the host (the rule: include/tb_nearest.h) ------------- */
+/* Why tb_nearest_points (grid null) or tb_bake_distance_field refuses its arguments before it looks at the context: pure tests, in the header's order. */
+static const char* nearestRefusal(uint32_t flags, uint64_t n, const void* points, const void* out, const tb_probe_grid* grid, bool isGrid)
+{
+    if (flags & ~(TB_NEAREST_SIGNED | TB_NEAREST_DEVICE)) return "unknown flag bits";
+    if (!isGrid) {
+        if (n > (1ull << 31)) return "more than 2^31 points";
+        if (n && (!points || !out)) return "null pointer";
+        if (n && (flags & TB_NEAREST_DEVICE)) {
+            if ((uintptr_t)points & 15u) return "device points are not 16-B aligned";
+            if ((uintptr_t)out & 15u) return "device records are not 16-B aligned";
+        }
+        return nullptr;
+    }
+    if (!grid) return "null grid";
+    if (!grid->count[0] || !grid->count[1] || !grid->count[2]) return "a count of the grid is 0";
+    if ((uint64_t)grid->count[0] * grid->count[1] > (1ull << 31) || (uint64_t)grid->count[0] * grid->count[1] * grid->count[2] > (1ull << 31))
+        return "more than 2^31 cells";
+    for (int k = 0; k < 3; k++) if (!(tb_abs(grid->origin[k]) < tb_u2f(0x7f800000u)) || !(tb_abs(grid->spacing[k]) < tb_u2f(0x7f800000u)))
+        return "the grid's origin or spacing is not finite";
+    if (!out) return "null pointer";
+    if ((flags & TB_NEAREST_DEVICE) && ((uintptr_t)out & 3u)) return "the device distances are not 4-B aligned";
+    return nullptr;
+}
+
+int tb_nearest_refusal(uint32_t flags, uint64_t n, const void* points, const void* out, const tb_probe_grid* grid, char* why, uint32_t whyBytes)
+{
+    const char* no = nearestRefusal(flags, n, points, out, grid, grid != nullptr);
+    if (why && whyBytes) { strncpy(why, no ? no : "", whyBytes - 1); why[whyBytes - 1] = 0; }
+    return no ? TB_E_INVALID : TB_OK;
+}
+
+namespace {
+
+struct NearestBest { float d2 = tb_u2f(0x7f800000u); uint32_t geom = TB_NEAREST_NONE, prim = TB_NEAREST_NONE; float u = 0.0f, v = 0.0f; tb3 point{0.0f, 0.0f, 0.0f};
+    bool behind = false; };
+
+tb3 cornerOf(const float* v) { return tb3_make(v[0], v[1], v[2]); }
+
+/* the candidate rule on one triangle; true: it is the best now */
+bool nearestOffer(NearestBest& best, tb3 p, float limit, const TbTriB& t)
+{
+    const tb3 v0 = cornerOf(t.v0), v1 = cornerOf(t.v1), v2 = cornerOf(t.v2);
+    const TbNearestOnTriangle r = tb_nearest_on_triangle(p, v0, v1, v2);
+    if (!(r.D2 <= limit) || !tb_nearest_better(r.D2, t.geometryIndex, t.primitiveIndex, best.d2, best.geom, best.prim)) return false;
+    best.d2 = r.D2; best.geom = t.geometryIndex; best.prim = t.primitiveIndex; best.u = r.U; best.v = r.V; best.point = r.Point;
+    best.behind = tb_nearest_behind(p, r.Point, v0, v1, v2);
+    return true;
+}
+
+TbNearest nearestRecord(const NearestBest& best, bool isSigned)
+{
+    TbNearest o; memset(&o, 0, sizeof o);
+    o.Distance = tb_u2f(0x7f800000u); o.Prim = o.Geom = TB_NEAREST_NONE;
+    if (best.geom == TB_NEAREST_NONE && best.prim == TB_NEAREST_NONE) return o;
+    const float d = tb_sqrt(best.d2);
+    o.Point[0] = best.point.x; o.Point[1] = best.point.y; o.Point[2] = best.point.z;
+    o.Distance = isSigned && best.behind ? -d : d; o.U = best.u; o.V = best.v; o.Prim = best.prim; o.Geom = best.geom;
+    return o;
+}
+
+void rootBoxOf(const HostScene& s, tb3& c, tb3& h)
+{
+    const TbAabbNode* root = (const TbAabbNode*)(s.bvhA.data() + 16);
+    c = cornerOf(root->center); h = cornerOf(root->halfDim);
+}
+tb3 childCentre(const TbNodeB& n, int k) { return tb3_make(n.cx[k], n.cy[k], n.cz[k]); }
+tb3 childHalf(const TbNodeB& n, int k) { return tb3_make(n.hx[k], n.hy[k], n.hz[k]); }
+
+/* pq_kernels.hip's walk, one point: nearest child first, the farther one pushed iff its bound does not exceed the culling value of the moment */
+NearestBest nearestWalk(const HostScene& s, tb3 p, float limit, std::vector<uint32_t>& stack)
+{
+    NearestBest best;
+    tb3 rc, rh; rootBoxOf(s, rc, rh);
+    const float slack = tb_nearest_slack(tb_nearest_scale(p, rc, rh));
+    float cull = tb_nearest_cull(limit, slack);
+    if (tb_box_d2(p, rc, rh) > cull) return best;
+    stack.clear();
+    uint32_t ref = s.rootRefB;
+    for (;;) {
+        if (!(ref & TB_BVH_LEAF_FLAG)) {
+            const TbNodeB& n = s.nodesB[ref];
+            const float dl = tb_box_d2(p, childCentre(n, 0), childHalf(n, 0)), dr = tb_box_d2(p, childCentre(n, 1), childHalf(n, 1));
+            const bool lh = !(dl > cull), rh2 = !(dr > cull);
+            if (lh && rh2) { const bool rightFirst = dr < dl; stack.push_back(rightFirst ? n.left : n.right); ref = rightFirst ? n.right : n.left; continue; }
+            if (lh || rh2) { ref = rh2 ? n.right : n.left; continue; }
+        } else if (nearestOffer(best, p, limit, s.trisB[ref & ~TB_BVH_LEAF_FLAG])) cull = tb_nearest_cull(best.d2, slack);
+        if (stack.empty()) return best;
+        ref = stack.back(); stack.pop_back();
+    }
+}
+
+bool nearestSceneOk(const tb_host_scene* h) { return h && h->scene.instances.empty() && !h->scene.trisB.empty() && h->scene.bvhA.size() >= 48; }
+
+} // namespace
+
+int tb_host_scene_nearest(tb_host_scene* h, uint32_t flags, uint64_t n, const TbQueryPoint* points, TbNearest* out)
+{
+    const uint32_t form = flags & (TB_NEAREST_HOST_BRUTE | TB_NEAREST_HOST_WALK);
+    if (!h || (flags & ~(TB_NEAREST_SIGNED | TB_NEAREST_HOST_BRUTE | TB_NEAREST_HOST_WALK)) || (form != TB_NEAREST_HOST_BRUTE && form != TB_NEAREST_HOST_WALK) ||
+        (n && (!points || !out))) return TB_E_INVALID;
+    if (!h->scene.instances.empty()) return TB_E_UNSUPPORTED;
+    if (!nearestSceneOk(h)) return TB_E_INVALID;
+    const HostScene& s = h->scene;
+    auto range = [&](uint64_t first, uint64_t end) {
+        std::vector<uint32_t> stack;
+        for (uint64_t i = first; i < end; i++) {
+            const tb3 p = cornerOf(points[i].Position);
+            const float limit = tb_nearest_limit(points[i].MaxDistance);
+            NearestBest best;
+            if (tb_nearest_finite3(p) && limit >= 0.0f) {
+                if (form == TB_NEAREST_HOST_WALK) best = nearestWalk(s, p, limit, stack);
+                else for (const TbTriB& t : s.trisB) nearestOffer(best, p, limit, t);
+            }
+            out[i] = nearestRecord(best, (flags & TB_NEAREST_SIGNED) != 0);
+        }
+    };
+    /* a point's record depends on nothing but the point: a large brute force is dealt over a few threads */
+    const uint64_t work = form == TB_NEAREST_HOST_BRUTE ? n * (uint64_t)s.trisB.size() : n * 64u;
+    const uint64_t threads = work < (1ull << 22) ? 1u : std::min<uint64_t>(std::min<uint64_t>(8u, std::max(1u, std::thread::hardware_concurrency())), n);
+    std::vector<std::thread> pool;
+    uint64_t t = 0;
+    try { for (; t + 1 < threads; t++) pool.emplace_back(range, n * t / threads, n * (t + 1) / threads); } catch (const std::exception&) {}
+    range(n * t / threads, n); /* the calling thread takes the last share, and what no thread could be started for */
+    for (std::thread& th : pool) th.join();
+    return TB_OK;
+}
+
+int tb_host_scene_nearest_excess(tb_host_scene* h, uint64_t n, const TbQueryPoint* points, float* worstOut)
+{
+    if (!h || !worstOut || (n && !points)) return TB_E_INVALID;
+    if (!h->scene.instances.empty()) return TB_E_UNSUPPORTED;
+    if (!nearestSceneOk(h)) return TB_E_INVALID;
+    const HostScene& s = h->scene;
+    /* per sorted triangle the boxes above it, the root's first: found once, by a walk of the whole tree */
+    std::vector<std::vector<std::pair<tb3, tb3>>> above(s.trisB.size());
+    {
+        tb3 rc, rh; rootBoxOf(s, rc, rh);
+        std::vector<std::pair<tb3, tb3>> path(1, std::make_pair(rc, rh));
+        std::function<void(uint32_t)> down = [&](uint32_t ref) {
+            if (ref & TB_BVH_LEAF_FLAG) { above[ref & ~TB_BVH_LEAF_FLAG] = path; return; }
+            const TbNodeB& nd = s.nodesB[ref];
+            for (int k = 0; k < 2; k++) { path.push_back(std::make_pair(childCentre(nd, k), childHalf(nd, k))); down(k ? nd.right : nd.left); path.pop_back(); }
+        };
+        down(s.rootRefB);
+    }
+    double worst = 0.0;
+    for (uint64_t i = 0; i < n; i++) {
+        const tb3 p = cornerOf(points[i].Position);
+        const float limit = tb_nearest_limit(points[i].MaxDistance);
+        if (!tb_nearest_finite3(p) || !(limit >= 0.0f)) continue;
+        NearestBest best; size_t winner = 0;
+        for (size_t t = 0; t < s.trisB.size(); t++) if (nearestOffer(best, p, limit, s.trisB[t])) winner = t;
+        if (best.geom == TB_NEAREST_NONE && best.prim == TB_NEAREST_NONE) continue;
+        const double unit = (double)tb_nearest_scale(p, above[winner][0].first, above[winner][0].second) * 1.1920928955078125e-7;
+        for (const auto& box : above[winner]) {
+            const double excess = sqrt((double)tb_box_d2(p, box.first, box.second)) - sqrt((double)best.d2);
+            if (unit > 0.0 && excess / unit > worst) worst = excess / unit;
+        }
+    }
+    *worstOut = (float)worst;
     return TB_OK;
 }
 
