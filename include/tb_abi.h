@@ -202,7 +202,9 @@ TB_STATIC_ASSERT(sizeof(tb_probe_grid) == 36, "a probe grid is 9 dwords");
 /* ---- point queries (tracerboy_hip.h tb_nearest_points; the rule: tb_nearest.h) ----
  * A point of a query, 16 B and 16-B aligned on the device: a triangle counts iff the Distance its record would carry is <= MaxDistance (+inf:
  * every triangle; a NaN or a negative value: none).  A record, 32 B: the nearest point of the scene's triangles, its distance -- tb_math.h's
- * square root of the rule's D2, negated under TB_NEAREST_SIGNED where the point lies behind the winning triangle --, the weights of that
+ * square root of the rule's D2, negated under TB_NEAREST_SIGNED where the point lies behind the winning triangle (exact where the nearest point is
+ * interior to a triangle; wrong for about one point in twenty near edges or vertices whose faces meet at an acute angle, a regular tetrahedron
+ * included; see section 28: tb_nearest_points_winding negates where the winding number says inside) --, the weights of that
  * triangle's vertices 1 and 2 at Point, and its primitiveIndex and geometryIndex.  A miss is Point = 0, Distance = +inf, U = V = 0, Prim = Geom =
  * 0xffffffff. */
 typedef struct TbQueryPoint { float Position[3]; float MaxDistance; } TbQueryPoint;

@@ -45,8 +45,8 @@
  *
  * Sign (TB_NEAREST_SIGNED).  Distance is negated iff dot(p - Point, tb_face_vector(v0, v1, v2)) < 0 for the winning triangle; on its plane, and
  * for a face vector of zero, it stays positive.  This is the side of the NEAREST TRIANGLE: exact where the nearest point is interior to a
- * triangle, and for convex closed meshes; near the edges and vertices of a mesh that is not convex it can be wrong (no pseudonormals, no winding
- * numbers, no ray parity). */
+ * triangle; wrong for about one point in twenty near edges or vertices whose faces meet at an acute angle, a regular tetrahedron included; see
+ * section 28 (tb_winding.h has the robust sign). */
 #ifndef TB_NEAREST_H
 #define TB_NEAREST_H
 

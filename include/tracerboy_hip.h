@@ -743,8 +743,8 @@ int tb_run_probe_project(tb_context* ctx, uint32_t n, uint32_t resolution, const
  * nearest-first walk of the layout-B tree in memory, one point per lane; layout C and LDS-resident scenes change nothing, option "alpha_test" does
  * not apply (the query is geometry alone), positions are what the last tb_commit_geometry left.  A position that is not finite is a miss.
  * TB_NEAREST_SIGNED: Distance is negated where the point lies behind the NEAREST TRIANGLE (dot(p - Point, face vector) < 0; the face vector is
- * tb_normals.h's).  That is exact where the nearest point is interior to a triangle and for convex closed meshes; near edges and vertices of a
- * mesh that is not convex the sign can be wrong.
+ * tb_normals.h's).  That is exact where the nearest point is interior to a triangle; wrong for about one point in twenty near edges or vertices
+ * whose faces meet at an acute angle, a regular tetrahedron included; see section 28 (tb_nearest_points_winding has the robust sign).
  * tb_bake_distance_field: the same walk over the cells of a grid (tb_abi.h tb_probe_grid: cell (i, j, k) at origin + (i, j, k) * spacing, one
  * rounded product and one rounded sum per axis, number (k * count[1] + j) * count[0] + i), positions made in the kernel and never stored; out is
  * one float per cell, the Distance of the cell's record (signed under the flag, +inf on a miss), every cell with MaxDistance = max_distance.
@@ -769,6 +769,44 @@ int tb_run_probe_project(tb_context* ctx, uint32_t n, uint32_t resolution, const
 int tb_nearest_points(tb_context* ctx, uint32_t flags, uint64_t n, const TbQueryPoint* points, TbNearest* out);
 int tb_bake_distance_field(tb_context* ctx, uint32_t flags, const tb_probe_grid* grid, float max_distance, float* out);
 int tb_nearest_refusal(uint32_t flags, uint64_t n, const void* points, const void* out, const tb_probe_grid* grid_or_null, char* why_or_null,
+                       uint32_t why_bytes);
+
+/* ---- winding numbers (no reference counterpart) -------------------------------------------------------------------
+ * Robust inside / outside: for each of n points (tb_abi.h TbQueryPoint; MaxDistance is not read) the generalized winding number of the scene's
+ * triangles, w = (sum of the triangles' signed solid angles) / 4 pi, one float per point: 1 inside a closed mesh whose face vectors point outward,
+ * 0 outside, -1 inside an inward-facing one, 2 inside two shells, and a graceful in-between on open meshes and soups.  include/tb_winding.h states
+ * the rule operation by operation -- the solid angle of one triangle, the moments of a subtree, the far-field test L2 > (beta r)^2 under which a
+ * subtree is replaced by its dipole, and the order of the sum -- and host and device give the same bits; w is a function of (tree topology,
+ * triangles, point, beta).  beta >= 1; larger is more exact and slower, +inf sums every triangle (the exact form); 3 is the default of the Python
+ * layer.  tb_winding_inside (tb_winding.h; api.winding_inside) is |w| >= 0.5.  A position that is not finite gives the NaN 0x7fc00000.
+ * Synchronous like tb_nearest_points, on host arrays (staged, nothing kept) or, with TB_WINDING_DEVICE, on device pointers of the context's device
+ * (points 16-B aligned, numbers 4-B).  The subtree moments (64 B per node) are made on the device at the first call of a scene and again at the
+ * first call after a tb_commit_geometry; a rebuild or a new scene drops them; beyond them nothing is allocated per call on the device path.
+ * tb_bake_winding_field: the same walk over the cells of a grid, tb_bake_distance_field's cell rule, one float per cell.
+ * tb_nearest_points_winding, tb_bake_distance_field_winding: the UNSIGNED point query of section 27, unchanged, then a pass of the walk that sets
+ * the sign bit of Distance where the record is a hit and tb_winding_inside(w): every byte is the unsigned answer's but that bit; a miss stays
+ * +inf.  TB_NEAREST_SIGNED is refused here (TB_E_INVALID): the two signs are different rules.
+ * TB_WINDING_HOST_WALK (tb_winding_numbers only, host arrays only): the kernel's walk as scalar C++ over the context's own host copies of the tree
+ * as the device holds it now -- what the device must give on bits, whatever built or refitted the tree.
+ * Refusals, in tb_nearest_points's order: a peer handle (TB_E_INVALID); TB_E_UNSUPPORTED for a tb_create_multi group ("multi-device group");
+ * tb_winding_refusal's (TB_E_INVALID: unknown flag bits; n > 2^31; a null pointer with n > 0; misaligned device pointers; the grid's, as
+ * tb_nearest_refusal's; a beta that is a NaN or < 1); TB_E_NO_SCENE; TB_E_UNSUPPORTED for a two-level scene ("two-level") and for a tree of pre-split
+ * references ("pre-split": under option "presplit" a cut triangle lies in the tree once per reference, and a sum over the leaves would count it
+ * as often -- the refit refuses the same trees; tb_host_scene_winding refuses them too); n = 0: TB_OK, nothing is launched; pointers that are not
+ * memory of the context's device, or too short (TB_E_INVALID).
+ * tb_get_option "last_winding_us": GPU microseconds of the last call's walk; "last_winding_fit_us": of the last moment fit (HIP events).
+ * tb_winding_refusal (host only, pure): grid_or_null = null judges a tb_winding_numbers call, else a tb_bake_winding_field call.
+ * tb_host_scene_winding: the rule on the host over a one-level host scene's layout-B arrays (TB_E_UNSUPPORTED for a two-level one and for a tree of
+ * pre-split references).  flags: exactly
+ * one of TB_WINDING_HOST_BRUTE -- every triangle of the array in order, the exact form; beta is checked, not used -- and TB_WINDING_HOST_WALK. */
+#define TB_WINDING_DEVICE     0x100u    /* the value and meaning of TB_RAYS_DEVICE */
+#define TB_WINDING_HOST_BRUTE 0x1000u   /* tb_host_scene_winding only */
+#define TB_WINDING_HOST_WALK  0x2000u   /* tb_host_scene_winding and tb_winding_numbers */
+int tb_winding_numbers(tb_context* ctx, uint32_t flags, uint64_t n, const TbQueryPoint* points, float beta, float* out);
+int tb_bake_winding_field(tb_context* ctx, uint32_t flags, const tb_probe_grid* grid, float beta, float* out);
+int tb_nearest_points_winding(tb_context* ctx, uint32_t flags, uint64_t n, const TbQueryPoint* points, float beta, TbNearest* out);
+int tb_bake_distance_field_winding(tb_context* ctx, uint32_t flags, const tb_probe_grid* grid, float max_distance, float beta, float* out);
+int tb_winding_refusal(uint32_t flags, uint64_t n, const void* points, const void* out, const tb_probe_grid* grid_or_null, float beta, char* why_or_null,
                        uint32_t why_bytes);
 
 /* ---- dynamic scenes (no reference counterpart: its scene is frozen once LoadScene returns) -------------------------
@@ -1093,6 +1131,8 @@ int tb_host_scene_triangles(tb_host_scene* s, const float** positions, uint32_t*
 /* point queries on the host (section 27 above): the rule of tb_nearest.h by brute force or by the kernel's walk, and the pruning slack's measurement */
 int tb_host_scene_nearest(tb_host_scene* scene, uint32_t flags, uint64_t n, const TbQueryPoint* points, TbNearest* out);
 int tb_host_scene_nearest_excess(tb_host_scene* scene, uint64_t n, const TbQueryPoint* points, float* worst_out);
+/* winding numbers on the host (section 28 above): the rule of tb_winding.h by brute force or by the kernel's walk */
+int tb_host_scene_winding(tb_host_scene* scene, uint32_t flags, uint64_t n, const TbQueryPoint* points, float beta, float* out);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,12 @@ def lib():
         "tb_nearest_refusal": (C.c_int, [C.c_uint32, C.c_uint64, vp, vp, P(abi.tb_probe_grid), C.c_char_p, C.c_uint32]),
         "tb_host_scene_nearest": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp]),
         "tb_host_scene_nearest_excess": (C.c_int, [vp, C.c_uint64, vp, P(C.c_float)]),
+        "tb_winding_numbers": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, C.c_float, vp]),
+        "tb_bake_winding_field": (C.c_int, [vp, C.c_uint32, P(abi.tb_probe_grid), C.c_float, vp]),
+        "tb_nearest_points_winding": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, C.c_float, vp]),
+        "tb_bake_distance_field_winding": (C.c_int, [vp, C.c_uint32, P(abi.tb_probe_grid), C.c_float, C.c_float, vp]),
+        "tb_winding_refusal": (C.c_int, [C.c_uint32, C.c_uint64, vp, vp, P(abi.tb_probe_grid), C.c_float, C.c_char_p, C.c_uint32]),
+        "tb_host_scene_winding": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, C.c_float, vp]),
         "tb_update_positions": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_update_normals": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "tb_set_instance_transforms": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
@@ -635,6 +641,33 @@ def NearestRefusal(flags, n, points_address, out_address, grid=None):
     return None if rc == 0 else why.value.decode()
 
 
+# winding numbers (tb_winding_numbers .. tb_bake_distance_field_winding; the rule: include/tb_winding.h)
+WINDING_DEVICE, WINDING_HOST_BRUTE, WINDING_HOST_WALK = 0x100, 0x1000, 0x2000
+WINDING_BETA = 3.0   # the smallest of 2, 3, 4 whose measured error bound is below 0.25 (tests/winding_cases.py W_BETA_TOL)
+
+
+def winding_inside(w):
+    """tb_winding_inside of include/tb_winding.h: |w| >= 0.5, whichever way the mesh faces; a NaN is not inside."""
+    with np.errstate(invalid="ignore"):
+        return np.abs(np.asarray(w, np.float32)) >= np.float32(0.5)
+
+
+def _check_beta(what, beta, name="beta"):
+    """beta is a number >= 1 (inf: the exact form); ValueError otherwise"""
+    if isinstance(beta, (bool, np.bool_)) or not isinstance(beta, (int, float, np.integer, np.floating)) or not float(beta) >= 1.0:
+        raise ValueError("%s: %s is a number >= 1, not %r" % (what, name, beta))
+    return float(beta)
+
+
+def WindingRefusal(flags, n, points_address, out_address, grid=None, beta=WINDING_BETA):
+    """tb_winding_refusal (host only): why tb_winding_numbers -- with a grid (abi.tb_probe_grid): tb_bake_winding_field -- refuses these arguments
+    before it looks at its context: None, or the reason."""
+    why = C.create_string_buffer(96)
+    rc = lib().tb_winding_refusal(flags, n, C.c_void_p(points_address or None), C.c_void_p(out_address or None), C.byref(grid) if grid is not None else None,
+                                  beta, why, 96)
+    return None if rc == 0 else why.value.decode()
+
+
 # dynamic scenes (tb_update_positions .. tb_commit_geometry)
 UPDATE_DEVICE, GEOMETRY_REBUILD = 0x100, 1
 
@@ -1038,6 +1071,18 @@ class HostScene:
         rc = lib().tb_host_scene_nearest(self._h, flags, points.shape[0], _np_ptr(points), _np_ptr(out))
         if rc != 0:
             raise TracerBoyError(rc, "tb_host_scene_nearest")
+        return out
+
+    def winding(self, points, beta=WINDING_BETA, walk=False):
+        """tb_host_scene_winding: float32 (n,), include/tb_winding.h's winding number of the scene's triangles at QUERY_POINT_DTYPE (or float32
+        (n, 4)) points -- the exact sum over every triangle in order or, walk=True, the kernel's walk with far subtrees as dipoles (beta=inf: none)."""
+        _check_query_points("HostScene.winding", points, 0, allow_tensor=False)
+        beta = _check_beta("HostScene.winding", beta)
+        flags = WINDING_HOST_WALK if _check_flag("HostScene.winding", "walk", walk) else WINDING_HOST_BRUTE
+        out = np.empty(points.shape[0], np.float32)
+        rc = lib().tb_host_scene_winding(self._h, flags, points.shape[0], _np_ptr(points), beta, _np_ptr(out))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_winding")
         return out
 
     def nearest_excess(self, points):
@@ -1666,31 +1711,94 @@ class TracerBoy:
         return out
 
     # -- point queries ------------------------------------------------------
-    def NearestPoints(self, points, signed=False):
+    def NearestPoints(self, points, signed=False, winding_beta=None):
         """tb_nearest_points: for every point the nearest point of the scene's triangles (include/tb_nearest.h has the rule).  A numpy array --
         QUERY_POINT_DTYPE (make_query_points), or float32 of shape (n, 4): position, MaxDistance -- takes the host path and returns a NEAREST_DTYPE
         array.  A torch tensor, float32 (n, 4), contiguous, 16-B aligned, on the context's device, takes the device path with zero copy: torch's
         current stream on that device is synchronised first, and the result is a float32 (n, 8) tensor -- Point, Distance, U, V, then Prim and Geom
-        through .view(torch.int32).  signed: Distance is negative behind the nearest triangle.  Anything else: ValueError, before any library call."""
+        through .view(torch.int32).  signed: Distance is negative behind the nearest triangle.  winding_beta, a number >= 1
+        (tb_nearest_points_winding): Distance is negative where the winding number says inside, the robust sign; not together
+        with signed.  Anything else: ValueError, before any library call."""
         on_device = _check_query_points("NearestPoints", points, getattr(self, "_device", 0))
         flags = NEAREST_SIGNED if _check_flag("NearestPoints", "signed", signed) else 0
+        beta = None if winding_beta is None else _check_beta("NearestPoints", winding_beta, "winding_beta")
+        if beta is not None and signed:
+            raise ValueError("NearestPoints: signed and winding_beta are two rules for the sign: give one")
         n = int(points.shape[0])
+
+        def call(flags, p, o):
+            if beta is None:
+                return self._L.tb_nearest_points(self._ctx, flags, n, p, o)
+            return self._L.tb_nearest_points_winding(self._ctx, flags, n, p, beta, o)
         if on_device:
             import torch
             out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
             torch.cuda.current_stream(points.device).synchronize()
-            self._check(self._L.tb_nearest_points(self._ctx, flags | NEAREST_DEVICE, n, C.c_void_p(points.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
+            self._check(call(flags | NEAREST_DEVICE, C.c_void_p(points.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
             return out
         out = np.empty(n, NEAREST_DTYPE)
-        self._check(self._L.tb_nearest_points(self._ctx, flags, n, _np_ptr(points), _np_ptr(out)))
+        self._check(call(flags, _np_ptr(points), _np_ptr(out)))
         return out
 
-    def BakeDistanceField(self, grid, signed=False, max_distance=np.inf, device=False):
+    def BakeDistanceField(self, grid, signed=False, max_distance=np.inf, device=False, winding_beta=None):
         """tb_bake_distance_field: float32 of shape (count[2], count[1], count[0]) -- for every cell of the ProbeGrid the Distance of NearestPoints at
         origin + (i, j, k) * spacing with MaxDistance = max_distance (+inf where nothing is that near); the positions are made in the kernel.
-        device=True: a torch tensor on the context's device that torch allocated, zero copy; else a numpy array."""
+        device=True: a torch tensor on the context's device that torch allocated, zero copy; else a numpy array.  winding_beta: as NearestPoints'
+        (tb_bake_distance_field_winding)."""
         _check_distance_field(grid, signed, max_distance, device)
+        beta = None if winding_beta is None else _check_beta("BakeDistanceField", winding_beta, "winding_beta")
+        if beta is not None and signed:
+            raise ValueError("BakeDistanceField: signed and winding_beta are two rules for the sign: give one")
         flags = NEAREST_SIGNED if signed else 0
+        g = grid.c_struct()
+        shape = (grid.count[2], grid.count[1], grid.count[0])
+
+        def call(flags, o):
+            if beta is None:
+                return self._L.tb_bake_distance_field(self._ctx, flags, C.byref(g), float(max_distance), o)
+            return self._L.tb_bake_distance_field_winding(self._ctx, flags, C.byref(g), float(max_distance), beta, o)
+        if device:
+            import torch
+            dev = torch.device("cuda", getattr(self, "_device", 0))
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._check(call(flags | NEAREST_DEVICE, C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty(shape, np.float32)
+        self._check(call(flags, _np_ptr(out)))
+        return out
+
+    # -- winding numbers (DESIGN.md section 28) ----------------------------------------------------
+    def WindingNumbers(self, points, beta=WINDING_BETA, host_walk=False):
+        """tb_winding_numbers: for every point the generalized winding number of the scene's triangles (include/tb_winding.h has the rule; 1 inside
+        a closed outward-facing mesh, 0 outside; api.winding_inside(w) is the test).  points as NearestPoints' -- MaxDistance is not read: a numpy
+        array takes the host path and returns float32 (n,); a torch tensor on the context's device the device path with zero copy, and returns a
+        float32 (n,) tensor.  beta >= 1: a subtree farther than beta radii is one dipole; inf sums every triangle.  host_walk=True (numpy only): the
+        same walk as scalar C++ over the context's host copies of the tree, which the device equals on bits."""
+        on_device = _check_query_points("WindingNumbers", points, getattr(self, "_device", 0))
+        beta = _check_beta("WindingNumbers", beta)
+        if _check_flag("WindingNumbers", "host_walk", host_walk) and on_device:
+            raise ValueError("WindingNumbers: host_walk takes a numpy array")
+        n = int(points.shape[0])
+        if on_device:
+            import torch
+            out = torch.empty((n,), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()
+            self._check(self._L.tb_winding_numbers(self._ctx, WINDING_DEVICE, n, C.c_void_p(points.data_ptr() or None), beta, C.c_void_p(out.data_ptr() or None)))
+            return out
+        out = np.empty(n, np.float32)
+        self._check(self._L.tb_winding_numbers(self._ctx, WINDING_HOST_WALK if host_walk else 0, n, _np_ptr(points), beta, _np_ptr(out)))
+        return out
+
+    def BakeWindingField(self, grid, beta=WINDING_BETA, device=False):
+        """tb_bake_winding_field: float32 of shape (count[2], count[1], count[0]) -- for every cell of the ProbeGrid the WindingNumbers at
+        origin + (i, j, k) * spacing; the positions are made in the kernel.  device=True: a torch tensor on the context's device, zero copy."""
+        if not isinstance(grid, ProbeGrid):
+            raise ValueError("BakeWindingField: grid is a ProbeGrid, not %s" % type(grid).__name__)
+        beta = _check_beta("BakeWindingField", beta)
+        _check_flag("BakeWindingField", "device", device)
+        if grid.n > 1 << 31:
+            raise ValueError("BakeWindingField: more than 2^31 cells")
         g = grid.c_struct()
         shape = (grid.count[2], grid.count[1], grid.count[0])
         if device:
@@ -1698,10 +1806,10 @@ class TracerBoy:
             dev = torch.device("cuda", getattr(self, "_device", 0))
             out = torch.empty(shape, dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()
-            self._check(self._L.tb_bake_distance_field(self._ctx, flags | NEAREST_DEVICE, C.byref(g), float(max_distance), C.c_void_p(out.data_ptr() or None)))
+            self._check(self._L.tb_bake_winding_field(self._ctx, WINDING_DEVICE, C.byref(g), beta, C.c_void_p(out.data_ptr() or None)))
             return out
         out = np.empty(shape, np.float32)
-        self._check(self._L.tb_bake_distance_field(self._ctx, flags, C.byref(g), float(max_distance), _np_ptr(out)))
+        self._check(self._L.tb_bake_winding_field(self._ctx, 0, C.byref(g), beta, _np_ptr(out)))
         return out
 
     # -- radiance queries ---------------------------------------------------

@@ -52,12 +52,12 @@ def device_flags(src):
 
 HOST_SRCS = ["host/pbrt_loader.cpp", "host/pbf_loader.cpp", "host/host_scene.cpp", "host/images.cpp", "host/image_decode.cpp", "host/image_formats.cpp", "host/bvh_build.cpp", "host/procedural.cpp", "host/context.cpp", "host/context_queries.cpp", "host/context_scene.cpp", "host/context_render.cpp", "host/context_group.cpp",
              "host/context_realtime.cpp", "host/context_post.cpp", "host/host_api.cpp", "host/render_state.cpp", "host/context_denoise.cpp", "host/context_budget.cpp", "host/context_guides.cpp", "host/context_upscale.cpp", "host/pbrt_dump.cpp",
-             "host/nn_weights.cpp", "host/context_neural.cpp", "host/sr_weights.cpp", "host/context_sr.cpp", "host/context_compare.cpp", "host/context_visualize.cpp", "host/context_rays.cpp", "host/context_dynamic.cpp", "host/context_radiance.cpp", "host/context_bake.cpp", "host/context_meshes.cpp", "host/context_probes.cpp", "host/context_nearest.cpp"]
+             "host/nn_weights.cpp", "host/context_neural.cpp", "host/sr_weights.cpp", "host/context_sr.cpp", "host/context_compare.cpp", "host/context_visualize.cpp", "host/context_rays.cpp", "host/context_dynamic.cpp", "host/context_radiance.cpp", "host/context_bake.cpp", "host/context_meshes.cpp", "host/context_probes.cpp", "host/context_nearest.cpp", "host/context_winding.cpp"]
 KERNEL_SRCS = ["kernels/pt_kernels.hip", "kernels/post_kernels.hip", "kernels/bvh_kernels.hip", "kernels/rt_kernels.hip", "kernels/pt_variant_matte.hip", "kernels/pt_variant_matte5.hip", "kernels/pt_variant_matte6.hip", "kernels/pt_variant_env.hip", "kernels/pt_variant_env5.hip", "kernels/pt_variant_surf.hip",
                "kernels/pt_variant_sss.hip", "kernels/pt_variant_sss4.hip",
                "kernels/pt_variant_vol.hip", "kernels/pt_variant_vol4.hip", "kernels/pt_variant_full.hip",
                "kernels/pt_split_matte.hip", "kernels/pt_split_env.hip", "kernels/pt_split_surf.hip", "kernels/pt_split_sss.hip",
-               "kernels/state_kernels.hip", "kernels/dn_kernels.hip", "kernels/guide_kernels.hip", "kernels/fsr_kernels.hip", "kernels/nn_kernels.hip", "kernels/nn_convk_kernels.hip", "kernels/cmp_kernels.hip", "kernels/vis_kernels.hip", "kernels/rq_kernels.hip", "kernels/refit_kernels.hip", "kernels/rad_kernels.hip", "kernels/bake_kernels.hip", "kernels/probe_kernels.hip", "kernels/pq_kernels.hip"]
+               "kernels/state_kernels.hip", "kernels/dn_kernels.hip", "kernels/guide_kernels.hip", "kernels/fsr_kernels.hip", "kernels/nn_kernels.hip", "kernels/nn_convk_kernels.hip", "kernels/cmp_kernels.hip", "kernels/vis_kernels.hip", "kernels/rq_kernels.hip", "kernels/refit_kernels.hip", "kernels/rad_kernels.hip", "kernels/bake_kernels.hip", "kernels/probe_kernels.hip", "kernels/pq_kernels.hip", "kernels/wn_kernels.hip"]
 
 
 def _deps_digest():

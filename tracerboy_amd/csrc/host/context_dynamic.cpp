@@ -12,6 +12,46 @@
 using namespace tbhost;
 using namespace tbctx;
 
+/* The slots and the schedule of a bottom-up pass over the host's tree, whose child refs never go stale (refit_launch.h RefitTables: triSlot, nodeSlot,
+ * schedule; levelFirst: the nodes of height h are schedule[levelFirst[h - 1] .. levelFirst[h])).  The refit's tables and the winding numbers' moment
+ * fit (context_winding.cpp) are both made of it. */
+void tbctx::treeSchedule(const HostScene& s, std::vector<uint32_t>& triSlot, std::vector<uint32_t>& nodeSlot, std::vector<uint32_t>& schedule,
+    std::vector<uint32_t>& levelFirst)
+{
+    const size_t N = s.trisB.size(), numNodes = s.nodesB.size();
+    triSlot.assign(N, REFIT_ROOT_SLOT); nodeSlot.assign(numNodes, REFIT_ROOT_SLOT); schedule.clear();
+    std::vector<uint32_t> height(numNodes, 0);
+    levelFirst.assign(1, 0u);
+    if (!(s.rootRefB & TB_BVH_LEAF_FLAG)) {
+        std::vector<uint32_t> walk; walk.reserve(numNodes);
+        std::vector<uint32_t> st(1, s.rootRefB);
+        if (s.rootRefB >= numNodes) throw std::runtime_error("dynamic geometry: the root is out of range");
+        while (!st.empty()) {
+            const uint32_t x = st.back(); st.pop_back(); walk.push_back(x);
+            if (walk.size() > numNodes) throw std::runtime_error("dynamic geometry: the tree is not a tree");
+            const uint32_t child[2] = {s.nodesB[x].left, s.nodesB[x].right};
+            for (uint32_t side = 0; side < 2; side++) {
+                const uint32_t r = child[side], i = r & ~TB_BVH_LEAF_FLAG;
+                if (r & TB_BVH_LEAF_FLAG) { if (i >= N) throw std::runtime_error("dynamic geometry: a leaf is out of range"); triSlot[i] = x * 2 + side; }
+                else { if (i >= numNodes) throw std::runtime_error("dynamic geometry: a node is out of range"); nodeSlot[i] = x * 2 + side; st.push_back(i); }
+            }
+        }
+        uint32_t maxHeight = 0;
+        for (size_t w = walk.size(); w-- > 0;) { /* children come after their parent in a pre-order walk */
+            const uint32_t x = walk[w]; uint32_t h = 0;
+            for (uint32_t r : {s.nodesB[x].left, s.nodesB[x].right}) if (!(r & TB_BVH_LEAF_FLAG)) h = std::max(h, height[r]);
+            height[x] = h + 1; maxHeight = std::max(maxHeight, h + 1);
+        }
+        std::vector<uint32_t> count(maxHeight + 1, 0u);
+        for (uint32_t x : walk) count[height[x]]++;
+        levelFirst.assign(maxHeight + 1, 0u); /* the nodes of height h: schedule[levelFirst[h - 1] .. levelFirst[h]) */
+        for (uint32_t h = 1; h <= maxHeight; h++) levelFirst[h] = levelFirst[h - 1] + count[h];
+        schedule.resize(walk.size());
+        std::vector<uint32_t> fill(levelFirst.begin(), levelFirst.end() - 1);
+        for (uint32_t x : walk) schedule[fill[height[x] - 1]++] = x;
+    }
+}
+
 namespace {
 
 typedef tb_context::Dynamic Dynamic;
@@ -19,12 +59,6 @@ typedef std::vector<std::pair<uint32_t, uint32_t>> Ranges; /* [first, end) */
 
 uint32_t numVertices(const tb_context* c) { return (uint32_t)(c->scene.positions.size() / 3); }
 bool twoLevel(const tb_context* c) { return !c->scene.instances.empty(); }
-
-template <class T> void uploadInto(tb_context* c, DevBuf& b, const std::vector<T>& v)
-{
-    ensure(b, std::max<size_t>(16, v.size() * sizeof(T)));
-    if (!v.empty()) HIP_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-}
 
 Dynamic& dynamicOf(tb_context* c) { if (!c->dyn) c->dyn.reset(new Dynamic()); return *c->dyn; }
 
@@ -50,36 +84,8 @@ void makeTables(tb_context* c, Dynamic& d)
             d.hostTriVerts[3 * k + j] = v;
         }
     }
-    std::vector<uint32_t> triSlot(N, REFIT_ROOT_SLOT), nodeSlot(numNodes, REFIT_ROOT_SLOT), height(numNodes, 0), schedule;
-    d.levelFirst.assign(1, 0u);
-    if (!(s.rootRefB & TB_BVH_LEAF_FLAG)) {
-        std::vector<uint32_t> walk; walk.reserve(numNodes);
-        std::vector<uint32_t> st(1, s.rootRefB);
-        if (s.rootRefB >= numNodes) throw std::runtime_error("dynamic geometry: the root is out of range");
-        while (!st.empty()) {
-            const uint32_t x = st.back(); st.pop_back(); walk.push_back(x);
-            if (walk.size() > numNodes) throw std::runtime_error("dynamic geometry: the tree is not a tree");
-            const uint32_t child[2] = {s.nodesB[x].left, s.nodesB[x].right};
-            for (uint32_t side = 0; side < 2; side++) {
-                const uint32_t r = child[side], i = r & ~TB_BVH_LEAF_FLAG;
-                if (r & TB_BVH_LEAF_FLAG) { if (i >= N) throw std::runtime_error("dynamic geometry: a leaf is out of range"); triSlot[i] = x * 2 + side; }
-                else { if (i >= numNodes) throw std::runtime_error("dynamic geometry: a node is out of range"); nodeSlot[i] = x * 2 + side; st.push_back(i); }
-            }
-        }
-        uint32_t maxHeight = 0;
-        for (size_t w = walk.size(); w-- > 0;) { /* children come after their parent in a pre-order walk */
-            const uint32_t x = walk[w]; uint32_t h = 0;
-            for (uint32_t r : {s.nodesB[x].left, s.nodesB[x].right}) if (!(r & TB_BVH_LEAF_FLAG)) h = std::max(h, height[r]);
-            height[x] = h + 1; maxHeight = std::max(maxHeight, h + 1);
-        }
-        std::vector<uint32_t> count(maxHeight + 1, 0u);
-        for (uint32_t x : walk) count[height[x]]++;
-        d.levelFirst.assign(maxHeight + 1, 0u); /* the nodes of height h: schedule[levelFirst[h - 1] .. levelFirst[h]) */
-        for (uint32_t h = 1; h <= maxHeight; h++) d.levelFirst[h] = d.levelFirst[h - 1] + count[h];
-        schedule.resize(walk.size());
-        std::vector<uint32_t> fill(d.levelFirst.begin(), d.levelFirst.end() - 1);
-        for (uint32_t x : walk) schedule[fill[height[x] - 1]++] = x;
-    }
+    std::vector<uint32_t> triSlot, nodeSlot, schedule;
+    treeSchedule(s, triSlot, nodeSlot, schedule, d.levelFirst);
     uploadInto(c, d.triVerts, d.hostTriVerts); uploadInto(c, d.triSlot, triSlot); uploadInto(c, d.nodeSlot, nodeSlot); uploadInto(c, d.schedule, schedule);
     uploadInto(c, d.positions, s.positions); uploadInto(c, d.levelFirstDevice, d.levelFirst);
     ensure(d.rootBox, 32);

@@ -22,6 +22,7 @@
  *   context_bake.cpp    lightmap baking: tb_bake_lightmap, a UV atlas rasterised, its texels traced by the radiance query, resolved and dilated
  *   context_probes.cpp  light probes: tb_bake_probes, SH9 records of the radiance and the distances around points, and tb_sample_probes
  *   context_nearest.cpp point queries: tb_nearest_points and tb_bake_distance_field, the nearest surface point by a distance-ordered walk
+ *   context_winding.cpp winding numbers: tb_winding_numbers, tb_bake_winding_field and the winding-signed point queries; the subtree moments
  *   context_meshes.cpp  scenes from caller arrays: tb_load_meshes, device arrays read to the host once, the swap into the context
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
@@ -272,6 +273,17 @@ struct tb_context {
         tbctx::DevEvent evNormals[2];
     };
     std::unique_ptr<Dynamic> dyn;
+    /* winding numbers (context_winding.cpp): made at the first winding call of a scene, released with the scene
+     * (releaseScene); a context that never asks holds none of it.  triSlot, nodeSlot, schedule, levelFirst: the refit's slots and schedule
+     * (treeSchedule), made once per topology; moments, areas, root: the subtree moments of wn_launch.h, fitted at scene generation fittedOf -- a
+     * commit moves the generation on, so the next call fits them again.  ev / evFit: around the walk and the fit (options last_winding_us,
+     * last_winding_fit_us) */
+    struct Winding {
+        DevBuf triSlot, nodeSlot, schedule, levelFirstDevice, moments, areas, root;
+        std::vector<uint32_t> levelFirst; bool tablesReady = false, fitted = false; uint32_t fittedOf = 0;
+        tbctx::DevEvent ev[2], evFit[2]; float lastMs = 0.0f, lastFitMs = 0.0f;
+    };
+    std::unique_ptr<Winding> wn;
     /* lightmap baking (context_bake.cpp): made at the first tb_bake_lightmap of a scene, released with the scene
      * (releaseScene); a context that never bakes holds none of it.  rays, texels, sums: the atlas in row-major order, what tb_read_bake returns and
      * TB_BAKE_ACCUMULATE adds to; rgba: the resolve's and the fill passes' ping-pong; scratch: the rasteriser's (bake_launch.h); triVerts,
@@ -380,6 +392,12 @@ template <class T> const T* upload(tb_context* c, const std::vector<T>& v)
     c->sceneBufs.push_back(std::move(b));
     return (const T*)c->sceneBufs.back().p;
 }
+/* v into a buffer the context keeps (at least 16 B), on the stream, not waited for: the tables of a refit and of the winding numbers' moment fit */
+template <class T> void uploadInto(tb_context* c, DevBuf& b, const std::vector<T>& v)
+{
+    ensure(b, std::max<size_t>(16, v.size() * sizeof(T)));
+    if (!v.empty()) HIP_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+}
 /* The test hooks' staging (tb_trace_closest, tb_device_math, tb_run_*): temporary buffers only, nothing of the context but its stream.  staged: a
  * buffer of its own holding a copy of a host array; scratch: one to write into; copyBack: all of it to the host, where the caller gave a pointer --
  * d.bytes is what the hook asked for, since ensure makes a buffer hold exactly that */
@@ -407,6 +425,9 @@ void BuildTlasGpu(tb_context* c, HostScene& s, const std::vector<float>& blasBox
 /* context_dynamic.cpp: the host copies of the geometry (HostScene::bvhA, nodesB, trisB, positions, vertexBuffer, sceneMin / sceneMax) as the device
  * holds them now.  Every reader of those members outside the load path calls it first; it does nothing unless a commit has left them stale */
 void refreshHostScene(tb_context* c);
+/* context_dynamic.cpp: the slots and the height-ordered schedule of a bottom-up pass over s's layout-B tree (refit_launch.h RefitTables) */
+void treeSchedule(const tbhost::HostScene& s, std::vector<uint32_t>& triSlot, std::vector<uint32_t>& nodeSlot, std::vector<uint32_t>& schedule,
+    std::vector<uint32_t>& levelFirst);
 /* context_rays.cpp: why a device pointer the caller gave is refused -- `bytes` from it must lie inside one allocation of the context's device; null: it is not */
 const char* devicePointerRefusal(const tb_context* c, const void* p, size_t bytes);
 /* context_rays.cpp: the closest-hit launch of tb_trace_rays on n device rays into n device hit records, on the context's stream, not waited for.

@@ -87,6 +87,8 @@ const Query kQueries[] = {
     Q("last_radiance_us", microseconds(c->rad.lastMs)) Q("last_radiance_variant", c->rad.lastVariant) Q("last_radiance_form", c->rad.lastForm)
     Q("last_radiance_launches", c->rad.lastLaunches)
     Q("last_nearest_us", microseconds(c->pq.lastMs)) /* point queries: the last query's kernel (HIP events) */
+    /* winding numbers: the last call's walk and the last moment fit (HIP events) */
+    Q("last_winding_us", microseconds(c->wn ? c->wn->lastMs : 0.0f)) Q("last_winding_fit_us", microseconds(c->wn ? c->wn->lastFitMs : 0.0f))
     /* lightmap baking: the last bake's rasteriser, its query's launches, its resolve and fill passes (HIP events); the texels
      * that have a triangle */
     Q("last_bake_raster_us", microseconds(c->bake ? c->bake->lastRasterMs : 0.0f)) Q("last_bake_trace_us", microseconds(c->bake ? c->bake->lastTraceMs : 0.0f))

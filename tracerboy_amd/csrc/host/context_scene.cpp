@@ -11,6 +11,7 @@ void releaseScene(tb_context* c)
     c->dyn.reset(); /* the dynamic state belongs to the scene's buffers and topology (context_dynamic.cpp) */
     c->bake.reset(); /* and so does a bake (context_bake.cpp) */
     c->probes.reset(); /* and so do baked probes (context_probes.cpp) */
+    c->wn.reset(); /* and the winding numbers' tables and moments (context_winding.cpp) */
     memset(&c->ds, 0, sizeof c->ds);
 }
 

@@ -1,0 +1,188 @@
+/* context_winding.cpp -- winding numbers (include/tracerboy_hip.h tb_winding_numbers, tb_bake_winding_field,
+ * tb_nearest_points_winding, tb_bake_distance_field_winding): robust inside / outside by the rule of include/tb_winding.h, on host arrays (staged
+ * like the point queries') or on device buffers.  The subtree moments belong to the scene: made lazily, fitted again after a commit, released with
+ * the scene.  Reads the scene; writes nothing of the context but them and the kernels' times. */
+#include "context_internal.h"
+#include "winding_host.h"
+#include "../kernels/pq_launch.h"
+#include "../kernels/refit_launch.h"
+#include "../kernels/wn_launch.h"
+
+using namespace tbhost;
+using namespace tbctx;
+
+namespace {
+
+typedef tb_context::Winding Winding;
+
+int sceneRefusal(tb_context* c, const char* who)
+{
+    if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
+    if (c->ds.numInstances) return fail(c, TB_E_UNSUPPORTED, std::string(who) + ": not supported for a two-level scene (load with option flatten_instances = 1)");
+    /* a pre-split triangle lies in the tree once per reference, and a sum over the leaves would count it as often (the refit refuses the same trees) */
+    if (c->scene.trisB.size() != c->scene.triGeometry.size()) return fail(c, TB_E_UNSUPPORTED, std::string(who) +
+        ": not supported for a tree of pre-split references (option presplit): its leaves hold a triangle more than once");
+    return TB_OK;
+}
+
+/* the moments of the tree as the device holds it now: the tables once per topology, the fit once per scene generation */
+Winding& momentsOf(tb_context* c)
+{
+    if (!c->wn) c->wn.reset(new Winding());
+    Winding& w = *c->wn;
+    if (!w.tablesReady) {
+        std::vector<uint32_t> triSlot, nodeSlot, schedule;
+        treeSchedule(c->scene, triSlot, nodeSlot, schedule, w.levelFirst);
+        if (triSlot.size() != c->ds.numTris || nodeSlot.size() != c->ds.numNodes) throw std::runtime_error("winding numbers: the host's tree is not the device's");
+        uploadInto(c, w.triSlot, triSlot); uploadInto(c, w.nodeSlot, nodeSlot); uploadInto(c, w.schedule, schedule); uploadInto(c, w.levelFirstDevice, w.levelFirst);
+        ensure(w.moments, std::max<size_t>(64, (size_t)c->ds.numNodes * sizeof(TbMomentsB)));
+        ensure(w.areas, std::max<size_t>(16, (size_t)c->ds.numNodes * 8));
+        ensure(w.root, 32);
+        HIP_TRY(hipStreamSynchronize(c->stream)); /* the vectors above go out of scope */
+        w.tablesReady = true;
+    }
+    if (!w.fitted || w.fittedOf != c->sceneGeneration) {
+        WnTables t{};
+        t.triSlot = (const uint32_t*)w.triSlot.p; t.nodeSlot = (const uint32_t*)w.nodeSlot.p; t.schedule = (const uint32_t*)w.schedule.p;
+        t.tris = c->ds.tris; t.nodes = c->ds.nodes; t.moments = (TbMomentsB*)w.moments.p; t.areas = (float*)w.areas.p; t.root = (float*)w.root.p;
+        t.numTris = c->ds.numTris; t.numNodes = c->ds.numNodes;
+        const uint32_t numLevels = (uint32_t)w.levelFirst.size() - 1;
+        HIP_TRY(hipEventRecord(w.evFit[0].create(), c->stream));
+        HIP_TRY(wn_launch_fit(c->stream, &t, w.levelFirst.data(), numLevels, (const uint32_t*)w.levelFirstDevice.p,
+            refit_fused_first_level(w.levelFirst.data(), numLevels)));
+        HIP_TRY(hipEventRecord(w.evFit[1].create(), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipEventElapsedTime(&w.lastFitMs, w.evFit[0], w.evFit[1]));
+        w.fitted = true; w.fittedOf = c->sceneGeneration;
+    }
+    return w;
+}
+
+template <class Launch> void timedWalk(tb_context* c, Winding& w, Launch launch)
+{
+    HIP_TRY(hipEventRecord(w.ev[0].create(), c->stream));
+    HIP_TRY(launch());
+    HIP_TRY(hipEventRecord(w.ev[1].create(), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&w.lastMs, w.ev[0], w.ev[1]));
+}
+
+int refusePeerOrGroup(tb_context* c, const char* who)
+{
+    if (c && !c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED, std::string(who) + ": not supported for a multi-device group: a query's points are answered on one device");
+    return TB_OK;
+}
+
+} // namespace
+
+extern "C" int tb_winding_numbers(tb_context* c, uint32_t flags, uint64_t n, const TbQueryPoint* points, float beta, float* out)
+{
+    TB_REFUSE_PEER(c);
+    if (const int rc = refusePeerOrGroup(c, "tb_winding_numbers")) return rc;
+    return guarded(c, [&]() {
+        char why[96];
+        if (tb_winding_refusal(flags, n, points, out, nullptr, beta, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_winding_numbers: ") + why);
+        if (const int rc = sceneRefusal(c, "tb_winding_numbers")) return rc;
+        if (n == 0) return TB_OK;
+        if (flags & TB_WINDING_HOST_WALK) { /* the kernel's walk over the host copies of what the device holds */
+            refreshHostScene(c);
+            const HostScene& s = c->scene;
+            const tbwinding::Tree tree{s.nodesB.data(), s.nodesB.size(), s.trisB.data(), s.trisB.size(), s.rootRefB};
+            tbwinding::run(tree, true, n, points, beta, out);
+            return TB_OK;
+        }
+        const bool device = (flags & TB_WINDING_DEVICE) != 0;
+        const size_t pointBytes = (size_t)n * sizeof(TbQueryPoint), outBytes = (size_t)n * sizeof(float);
+        DevBuf dPoints, dOut;
+        if (device) {
+            if (const char* no = devicePointerRefusal(c, points, pointBytes)) return fail(c, TB_E_INVALID, std::string("tb_winding_numbers: points: ") + no);
+            if (const char* no = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_winding_numbers: out: ") + no);
+        } else { dPoints = staged(points, pointBytes); dOut = scratch(outBytes); }
+        const TbQueryPoint* p = device ? points : (const TbQueryPoint*)dPoints.p;
+        float* o = device ? out : (float*)dOut.p;
+        Winding& w = momentsOf(c);
+        timedWalk(c, w, [&]() { return wn_launch_points(c->stream, &c->ds, (const TbMomentsB*)w.moments.p, (const float*)w.root.p, WN_WRITE, (uint32_t)n, p, beta, o); });
+        if (!device) copyBack(out, dOut);
+        return TB_OK;
+    });
+}
+
+extern "C" int tb_bake_winding_field(tb_context* c, uint32_t flags, const tb_probe_grid* grid, float beta, float* out)
+{
+    TB_REFUSE_PEER(c);
+    if (const int rc = refusePeerOrGroup(c, "tb_bake_winding_field")) return rc;
+    return guarded(c, [&]() {
+        char why[96];
+        if (flags & ~TB_WINDING_DEVICE) return fail(c, TB_E_INVALID, "tb_bake_winding_field: unknown flag bits");
+        if (!grid) return fail(c, TB_E_INVALID, "tb_bake_winding_field: null grid");
+        if (tb_winding_refusal(flags, 0, nullptr, out, grid, beta, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_bake_winding_field: ") + why);
+        if (const int rc = sceneRefusal(c, "tb_bake_winding_field")) return rc;
+        const bool device = (flags & TB_WINDING_DEVICE) != 0;
+        const size_t outBytes = (size_t)grid->count[0] * grid->count[1] * grid->count[2] * sizeof(float);
+        DevBuf dOut;
+        if (device) { if (const char* no = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_bake_winding_field: out: ") + no); }
+        else dOut = scratch(outBytes);
+        float* o = device ? out : (float*)dOut.p;
+        Winding& w = momentsOf(c);
+        timedWalk(c, w, [&]() { return wn_launch_grid(c->stream, &c->ds, (const TbMomentsB*)w.moments.p, (const float*)w.root.p, WN_WRITE, grid, beta, o); });
+        if (!device) copyBack(out, dOut);
+        return TB_OK;
+    });
+}
+
+extern "C" int tb_nearest_points_winding(tb_context* c, uint32_t flags, uint64_t n, const TbQueryPoint* points, float beta, TbNearest* out)
+{
+    TB_REFUSE_PEER(c);
+    if (const int rc = refusePeerOrGroup(c, "tb_nearest_points_winding")) return rc;
+    return guarded(c, [&]() {
+        char why[96];
+        if (flags & ~TB_NEAREST_DEVICE) return fail(c, TB_E_INVALID, "tb_nearest_points_winding: unknown flag bits (TB_NEAREST_SIGNED is the other rule's)");
+        if (tb_nearest_refusal(flags, n, points, out, nullptr, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_nearest_points_winding: ") + why);
+        if (!(beta >= 1.0f)) return fail(c, TB_E_INVALID, "tb_nearest_points_winding: beta is a NaN or below 1");
+        if (const int rc = sceneRefusal(c, "tb_nearest_points_winding")) return rc;
+        if (n == 0) return TB_OK;
+        const bool device = (flags & TB_NEAREST_DEVICE) != 0;
+        const size_t pointBytes = (size_t)n * sizeof(TbQueryPoint), outBytes = (size_t)n * sizeof(TbNearest);
+        DevBuf dPoints, dOut;
+        if (device) {
+            if (const char* no = devicePointerRefusal(c, points, pointBytes)) return fail(c, TB_E_INVALID, std::string("tb_nearest_points_winding: points: ") + no);
+            if (const char* no = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_nearest_points_winding: out: ") + no);
+        } else { dPoints = staged(points, pointBytes); dOut = scratch(outBytes); }
+        const TbQueryPoint* p = device ? points : (const TbQueryPoint*)dPoints.p;
+        TbNearest* o = device ? out : (TbNearest*)dOut.p;
+        Winding& w = momentsOf(c);
+        timedWalk(c, w, [&]() { /* the unsigned query, unchanged, then the sign pass: chained on the stream */
+            const hipError_t e = pq_launch_nearest(c->stream, &c->ds, 0u, (uint32_t)n, p, o);
+            return e != hipSuccess ? e : wn_launch_points(c->stream, &c->ds, (const TbMomentsB*)w.moments.p, (const float*)w.root.p, WN_SIGN_RECORDS, (uint32_t)n, p, beta, o);
+        });
+        if (!device) copyBack(out, dOut);
+        return TB_OK;
+    });
+}
+
+extern "C" int tb_bake_distance_field_winding(tb_context* c, uint32_t flags, const tb_probe_grid* grid, float maxDistance, float beta, float* out)
+{
+    TB_REFUSE_PEER(c);
+    if (const int rc = refusePeerOrGroup(c, "tb_bake_distance_field_winding")) return rc;
+    return guarded(c, [&]() {
+        char why[96];
+        if (flags & ~TB_NEAREST_DEVICE) return fail(c, TB_E_INVALID, "tb_bake_distance_field_winding: unknown flag bits (TB_NEAREST_SIGNED is the other rule's)");
+        if (!grid) return fail(c, TB_E_INVALID, "tb_bake_distance_field_winding: null grid");
+        if (tb_nearest_refusal(flags, 0, nullptr, out, grid, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_bake_distance_field_winding: ") + why);
+        if (!(beta >= 1.0f)) return fail(c, TB_E_INVALID, "tb_bake_distance_field_winding: beta is a NaN or below 1");
+        if (const int rc = sceneRefusal(c, "tb_bake_distance_field_winding")) return rc;
+        const bool device = (flags & TB_NEAREST_DEVICE) != 0;
+        const size_t outBytes = (size_t)grid->count[0] * grid->count[1] * grid->count[2] * sizeof(float);
+        DevBuf dOut;
+        if (device) { if (const char* no = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_bake_distance_field_winding: out: ") + no); }
+        else dOut = scratch(outBytes);
+        float* o = device ? out : (float*)dOut.p;
+        Winding& w = momentsOf(c);
+        timedWalk(c, w, [&]() {
+            const hipError_t e = pq_launch_field(c->stream, &c->ds, 0u, grid, maxDistance, o);
+            return e != hipSuccess ? e : wn_launch_grid(c->stream, &c->ds, (const TbMomentsB*)w.moments.p, (const float*)w.root.p, WN_SIGN_CELLS, grid, beta, o);
+        });
+        if (!device) copyBack(out, dOut);
+        return TB_OK;
+    });
+}

@@ -9,6 +9,7 @@
 #include "wave_cost.h"
 #include "../kernels/probe_launch.h"
 #include "tb_nearest.h"
+#include "winding_host.h"
 
 #include <cmath>
 #include <cstring>
@@ -643,6 +644,37 @@ int tb_host_scene_nearest_excess(tb_host_scene* h, uint64_t n, const TbQueryPoin
         }
     }
     *worstOut = (float)worst;
+    return TB_OK;
+}
+
+/* ---- winding numbers on the host (the rule: include/tb_winding.h; the scalar code: winding_host.h) ------------- */
+/* Why tb_winding_numbers (grid null) or tb_bake_winding_field refuses its arguments before it looks at the context: pure tests, in tb_nearest_refusal's
+ * order, then beta. */
+int tb_winding_refusal(uint32_t flags, uint64_t n, const void* points, const void* out, const tb_probe_grid* grid, float beta, char* why, uint32_t whyBytes)
+{
+    const char* no = nullptr;
+    if (flags & ~(TB_WINDING_DEVICE | (grid ? 0u : TB_WINDING_HOST_WALK))) no = "unknown flag bits";
+    else if ((flags & TB_WINDING_DEVICE) && (flags & TB_WINDING_HOST_WALK)) no = "the host walk takes host arrays: flag bits that exclude each other";
+    else if (!grid) {
+        if (n > (1ull << 31)) no = "more than 2^31 points";
+        else if (n && (!points || !out)) no = "null pointer";
+        else if (n && (flags & TB_WINDING_DEVICE) && ((uintptr_t)points & 15u)) no = "device points are not 16-B aligned";
+        else if (n && (flags & TB_WINDING_DEVICE) && ((uintptr_t)out & 3u)) no = "the device numbers are not 4-B aligned";
+    } else no = nearestRefusal(flags & TB_WINDING_DEVICE, 0, nullptr, out, grid, true);
+    if (!no && !(beta >= 1.0f)) no = "beta is a NaN or below 1";
+    if (why && whyBytes) { strncpy(why, no ? no : "", whyBytes - 1); why[whyBytes - 1] = 0; }
+    return no ? TB_E_INVALID : TB_OK;
+}
+
+int tb_host_scene_winding(tb_host_scene* h, uint32_t flags, uint64_t n, const TbQueryPoint* points, float beta, float* out)
+{
+    if (!h || (flags != TB_WINDING_HOST_BRUTE && flags != TB_WINDING_HOST_WALK) || (n && (!points || !out)) || !(beta >= 1.0f)) return TB_E_INVALID;
+    if (!h->scene.instances.empty()) return TB_E_UNSUPPORTED;
+    if (!nearestSceneOk(h)) return TB_E_INVALID;
+    const HostScene& s = h->scene;
+    if (s.trisB.size() != s.triGeometry.size()) return TB_E_UNSUPPORTED; /* pre-split references: a sum over the leaves would count a triangle twice */
+    const tbwinding::Tree tree{s.nodesB.data(), s.nodesB.size(), s.trisB.data(), s.trisB.size(), s.rootRefB};
+    try { tbwinding::run(tree, flags == TB_WINDING_HOST_WALK, n, points, beta, out); } catch (const std::exception&) { return TB_E_INVALID; }
     return TB_OK;
 }
 
