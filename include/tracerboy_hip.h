@@ -374,7 +374,8 @@ uint64_t tb_state_digest_host(const void* words, uint64_t n_words);
  * Builder 1: "reinsertion_passes" (-1 = the library's choice), "reinsertion_share" (percent of the subtrees a pass tries, largest first),
  * "presplit" (percent of extra references from cutting the triangles with the largest, emptiest boxes before the build; 0 = off, the default:
  * measured to raise box tests), "wave_tree" (-1 = the library's choice: on where reinsertion passes run, 0 = off, 1 = on: for a scene that will be LDS-resident the tree is then
- * optimised for what a 64-lane wave pays, host/wave_cost.h; every other scene's tree is untouched).  Launch policy: "frame_group", "guided_groups" (0 never, 1 = calls that wait [default], 2 always: the frame
+ * optimised for what a 64-lane wave pays, host/wave_cost.h; every other scene's tree is untouched), "wave_tree_threads" (the workers of that
+ * search: 0 = min(16, the CPUs the process may run on), 1 = serial; the tree is the same bytes for every count).  Launch policy: "frame_group", "guided_groups" (0 never, 1 = calls that wait [default], 2 always: the frame
  * groups of a region shrink over the last groups of a launch), "primary_prepass", "overlap_launches", "costly_first" (+ "costly_late_samples"), "high_occupancy", "stack_lds_cap",
  * "compact_hits", "camera_constants", "texture_use_hint", "node_layout", "node_order" -- each described where launch_plan.h / context_render.cpp use it.
  * Adaptive sampling: "adaptive" (0/1), "adaptive_min_frames", "adaptive_test" (0 = the skip test runs before every frame
@@ -1112,7 +1113,15 @@ typedef struct tb_wave_trips { uint64_t inner_trips, leaf_trips, idle_passes, in
 /* what the wave stage did when the scene was built: ran = 0 where it did not run (option off, another builder, a scene that is not LDS-resident);
  * before / after: its model rays over the tree it was given and the tree it returned (trips and cost only); depth_limit in nodes */
 typedef struct tb_wave_stage_info { uint32_t ran, rays, seed, park_min, depth_limit, moves, evaluations, inner_insts, leaf_insts, reserved;
-    tb_wave_trips before, after; double milliseconds; } tb_wave_stage_info;
+    tb_wave_trips before, after; double milliseconds;
+    /* the search (docs/experiments/r13.md): places whose rays were priced, those of them abandoned because the partial sum had passed the best price,
+     * rays walked again for them (the others kept their steps), workers, passes run, places per cut subtree (0 = every legal one), winners refused
+     * because they raised the price of the validation rays, and that price before and after.  With more than one worker `abandoned` and
+     * `rays_rewalked` depend on which worker finished first; the tree does not. */
+    uint64_t places_priced, abandoned, rays_checked, rays_rewalked, places_screened;
+    uint32_t threads, passes, places, validation_rejects, cuts_skipped, screen_waves, screen_keep, reserved2;
+    double validation_before, validation_after;
+    } tb_wave_stage_info;
 /* up to 64 step strings of 'I' (inner node visited) and 'L' (triangle tested), each ended by a 0, replayed in lock step */
 int tb_wave_replay(const char* const* steps, uint32_t lanes, uint32_t park_min, tb_wave_trips* out);
 /* n rays over the tree of a one-level host scene with the kernels' rule: steps per ray and, where steps != null, the step strings back to back, each
@@ -1124,6 +1133,13 @@ int tb_host_scene_wave_rays(tb_host_scene* s, uint32_t seed, uint32_t waves, int
 /* ... and what they cost over the scene's tree (park_min 0: that of a scene in LDS) */
 int tb_host_scene_wave_cost(tb_host_scene* s, uint32_t seed, uint32_t waves, int feeler_percent, uint32_t park_min, tb_wave_trips* out);
 int tb_host_scene_wave_stage(tb_host_scene* s, tb_wave_stage_info* out);
+/* Builds the tree of a one-level host scene again with builder 1 and the wave stage on, for comparisons: the stage's model rays from `seed`, `waves`
+ * and `feeler_percent` (0 / 0 / -1: its own); `places` per cut subtree: 0 = every legal place (the stage as it runs), K > 0 = the stage as it was
+ * before it priced them all -- the K best by induced area, four passes, no validation rays; 3 gives that stage's tree byte for byte; `keep`: how
+ * many places of a cut go on from the screen (the first 8 waves) to all waves, 0 = the stage's own 4, a number no cut reaches = no screen; `threads`:
+ * option "wave_tree_threads" (0 = min(16, the CPUs the process may run on), 1 = serial; the same tree for every count).  out may be null. */
+int tb_host_scene_wave_search(tb_host_scene* s, uint32_t seed, uint32_t waves, int feeler_percent, uint32_t places, uint32_t keep, int threads,
+    tb_wave_stage_info* out);
 /* Diagnostic: the build's own parse of a PBRT file in the record format of oracle/ref_dump.cpp. */
 int tb_host_pbrt_dump(const char* pbrt_path, const char* out_path, char* err, uint32_t err_len);
 int tb_host_scene_triangles(tb_host_scene* s, const float** positions, uint32_t* num_vertices, const uint32_t** tri_vertex_index,

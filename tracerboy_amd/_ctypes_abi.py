@@ -332,7 +332,10 @@ class tb_wave_trips(C.Structure):
 class tb_wave_stage_info(C.Structure):
     """include/tracerboy_hip.h tb_wave_stage_info: what builder 1's wave stage did when a host scene was built."""
     _fields_ = [(n, C.c_uint32) for n in ("ran", "rays", "seed", "park_min", "depth_limit", "moves", "evaluations", "inner_insts", "leaf_insts",
-                                          "reserved")] + [("before", tb_wave_trips), ("after", tb_wave_trips), ("milliseconds", C.c_double)]
+                                          "reserved")] + [("before", tb_wave_trips), ("after", tb_wave_trips), ("milliseconds", C.c_double)] + \
+               [(n, C.c_uint64) for n in ("places_priced", "abandoned", "rays_checked", "rays_rewalked", "places_screened")] + \
+               [(n, C.c_uint32) for n in ("threads", "passes", "places", "validation_rejects", "cuts_skipped", "screen_waves", "screen_keep", "reserved2")] + \
+               [("validation_before", C.c_double), ("validation_after", C.c_double)]
 
 
 class tb_state_info(C.Structure):

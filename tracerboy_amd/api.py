@@ -204,6 +204,7 @@ def lib():
         "tb_host_scene_wave_rays": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32]),
         "tb_host_scene_wave_cost": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, P(abi.tb_wave_trips)]),
         "tb_host_scene_wave_stage": (C.c_int, [vp, P(abi.tb_wave_stage_info)]),
+        "tb_host_scene_wave_search": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, P(abi.tb_wave_stage_info)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export what the header declares
@@ -1113,6 +1114,17 @@ class HostScene:
         rc = lib().tb_host_scene_wave_stage(self._h, C.byref(info))
         if rc != 0:
             raise TracerBoyError(rc, "tb_host_scene_wave_stage")
+        return info
+
+    def wave_search(self, seed=0, waves=0, feeler_percent=-1, places=0, keep=0, threads=0):
+        """Builds this scene's tree again with builder 1 and the wave stage on (tb_host_scene_wave_search) and returns its tb_wave_stage_info: the
+        stage's model rays from seed / waves / feeler_percent (0 / 0 / -1: its own), `places` per cut subtree (0 = every legal place, 3 = the three
+        best by induced area: the stage as it was before it priced them all), `keep` places of a cut from the screen to all waves (0 = the stage's
+        own, a number no cut reaches = no screen), `threads` workers (0 = the library's choice, 1 = serial)."""
+        info = abi.tb_wave_stage_info()
+        rc = lib().tb_host_scene_wave_search(self._h, seed, waves, feeler_percent, places, keep, threads, C.byref(info))
+        if rc != 0:
+            raise TracerBoyError(rc, "tb_host_scene_wave_search")
         return info
 
     def wave_rays(self, seed=0, waves=0, feeler_percent=-1):

@@ -29,9 +29,14 @@
 #include <cstring>
 #include <cstdlib>
 #include <exception>
+#include <functional>
+#include <limits>
 #include <stdexcept>
 #include <thread>
 #include <mutex>
+#ifdef __linux__
+#include <sched.h>
+#endif
 
 namespace tbhost {
 
@@ -463,19 +468,42 @@ void optimizeByReinsertion(const HostScene& s, Tree& t, int maxPasses, double mi
  * The passes above minimise what a random single ray pays.  The kernel of an LDS-resident scene walks 64 rays in lock step and pays for the longest
  * lane of each wave: about 21 inner trips per wave-level walk against 7.4 inner steps per ray on cornell-box.  This stage takes the tree the area
  * passes left and goes on with the same cut-and-reinsert move, judged by what a wave pays: wave_cost.h walks a fixed set of model rays, made from
- * the scene's surfaces alone, replays them 64 at a time under the LDS steps' schedule and prices the trips in wave instructions.  For each cut
- * subtree only the kWaveStagePlaces best places by induced area are priced (the ranking the branch-and-bound above descends by); a move is kept
- * when the price falls, so the stage never returns a tree it prices above the one it was given.  Node 0 stays the root.  A move may not deepen the
+ * the scene's surfaces alone, replays them 64 at a time under the LDS steps' schedule and prices the trips in wave instructions.  The subtrees are
+ * cut largest area first, and for each EVERY legal place is priced -- every node of the remaining tree but node 0 and the place the subtree came
+ * from -- not the few that rank first by induced area: that ranking is the criterion the stage exists to get away from (round 13,
+ * docs/experiments/r13.md; before, the three best by area were priced, which HostScene::waveSearchPlaces = 3 still does, byte for byte).  A move
+ * is kept when the price falls -- among places of equal price the one that ranks first by induced area, so the order of evaluation has no say --
+ * and when it does not raise the price of a second, fixed set of rays the search never optimises for (kWaveStageValidationSeed: as many waves,
+ * the same share of feelers): 1 536 rays are few enough to fit a tree to.  So the stage never returns a tree it prices above the one it was given.
+ * Passes go on until one moves nothing, at most kWaveStagePasses; a subtree that found no better place in the very tree it is in is not cut again.
+ * What keeps that inside the load-time bound (cornell-box on one core: over 15 s without, 2.4 s with; waveCandidate below):
+ *   - exact: a ray keeps its steps unless it visited a node that reads other bits now and, gone through visit by visit, comes out otherwise there;
+ *     it is walked again only from that visit on, with the slabs of every unchanged box remembered; a wave whose lanes all kept their steps keeps
+ *     its trips; a sum that has passed the best price is abandoned;
+ *   - not exact: every place is first priced on kWaveStageScreenWaves of the waves, and only the kWaveStageScreenKeep cheapest go on to all of
+ *     them.  On cornell-box 4 is the least that gives the tree of the search without a screen, byte for byte (2 and 3 give trees of the same price
+ *     on the search's rays, the validation rays and two held-out seeds); the search is no longer exhaustive where a scene needs more;
+ *   - workers: the places of one cut are priced side by side by min(16, CPUs of the affinity mask) threads (option "wave_tree_threads"); they share
+ *     only the bound that lets them stop early, and the winner is chosen afterwards by price and rank: the same bytes for every count.
+ * Node 0 stays the root.  A move may not deepen the
  * tree beyond what the area passes allow, nor beyond the depth at which the scene stays LDS-resident and the six-wave copy's workgroups still fit
  * (LdsCopyFits, launch_plan.h) where they did.  It runs only for scenes that will be LDS-resident -- the size test of lds_image.h, from the counts
  * -- so every other tree is byte for byte what the area passes left.
  * Size: 24 waves of 64 rays, 42 % of them feelers (the share of feelers among the rays of the oracle's cornell-box log at depth 8: 0.423).  The
- * 36 triangles of cornell-box are searched in 0.6 s on one core (409 trees priced; 48 waves find the same gain in 1.1 s).  Priced on the oracle's
- * ray log of cornell-box 64 x 64 x 32 (scripts/wave_tree_price.py): 190.1 -> 180.7 wave instructions per sample, -5.0 %, where the model rays
- * say -7.7 %; searches from two other seeds price at -4.7 % and -3.8 %.  (Model rays that all leave towards the scene's centre instead of either
- * side by the hash: -3.7 % / -4.3 % on the log, dropped.) */
+ * 36 triangles of cornell-box: ten moves in four passes, 14 245 places screened and 988 priced on all waves, 25 winners refused by the validation
+ * rays.  Priced on the oracle's ray log of cornell-box 64 x 64 x 32 (scripts/wave_tree_price.py): 190.1 wave instructions per sample without the
+ * stage, 180.7 with the three best places by area (-5.0 %), 174.7 with every place (-8.1 %; -3.3 % against the three places), where the model
+ * rays say -7.7 % and -13.2 %.  (Round 11: model rays that all leave towards the scene's centre instead of either side by the hash priced no
+ * better on the log and were dropped.) */
 constexpr bool kWaveTreeByDefault = true; /* option wave_tree = -1 */
-constexpr uint32_t kWaveStageWaves = 24, kWaveStageFeelerPercent = 42, kWaveStageSeed = 0x7b01u, kWaveStagePasses = 4, kWaveStagePlaces = 3;
+constexpr uint32_t kWaveStageWaves = 24, kWaveStageFeelerPercent = 42, kWaveStageSeed = 0x7b01u, kWaveStageValidationSeed = 0x2c9au;
+constexpr uint32_t kWaveStagePlaces = 0;        /* places priced per cut subtree: 0 = every legal one */
+constexpr uint32_t kWaveStagePasses = 12;       /* a cap: the search ends with the first pass that moves nothing (cornell-box: see r13.md) */
+constexpr uint32_t kWaveStagePassesByArea = 4;  /* the passes of the search by area rank (HostScene::waveSearchPlaces > 0), as they were */
+constexpr uint32_t kWaveStageMaxThreads = 16;
+/* the screen: every place is priced on the first kWaveStageScreenWaves waves, the kWaveStageScreenKeep cheapest of them on all (r13.md: pricing every
+ * place on all 24 waves takes one core 9 s on cornell-box with every exact shortcut in) */
+constexpr uint32_t kWaveStageScreenWaves = 8, kWaveStageScreenKeep = 4;
 
 bool willBeLdsResident(const HostScene& s, uint32_t N, uint32_t depthNodes)
 {
@@ -484,34 +512,201 @@ bool willBeLdsResident(const HostScene& s, uint32_t N, uint32_t depthNodes)
         WalkStackDepth(depthNodes)) <= s.ldsSceneBudget;
 }
 
+/* What the rays of the stage did on the tree the candidates of a cut are compared with: each ray's steps, the inner nodes it visited (as a set, and
+ * one by one with the state of the walk there), each wave's trips. */
+struct WaveBase {
+    WaveTree wt; uint32_t depth = 0;
+    std::vector<char> steps; std::vector<uint32_t> off /* rays + 1 */, nI, nL; std::vector<uint64_t> visited; /* a WaveMaskSet set per ray */
+    WaveRecord rec; std::vector<uint32_t> visitOff; /* rays + 1 */
+    std::vector<WaveTrips> wave; WaveTrips total;
+    std::vector<float> enter, leave; /* 2N - 1 per ray: where the ray enters and leaves each node's box (WaveBoxSlabs) */
+};
+
+/* a walk's box test over a tree most of whose boxes are those of a WaveBase: for a box of the same bits the ray's remembered slabs, else the test itself */
+struct WaveBoxKept {
+    const float* enter; const float* leave; const uint8_t* same;
+    bool operator()(float& resultT, float closest, const WaveTree& t, const WaveRay& r, uint32_t n) const
+    {
+        if (!same[n]) return WaveBoxTest(resultT, closest, r, t.center[n], t.half[n]);
+        resultT = enter[n];
+        return resultT < tb_min(leave[n], closest);
+    }
+};
+
+void waveBaseOf(WaveBase& b, uint32_t N, const uint32_t* left, const uint32_t* right, const tb3* lmn, const tb3* lmx, const std::vector<WaveRay>& rays,
+    uint32_t parkMin)
+{
+    b.depth = WaveTreeFit(b.wt, N, left, right, lmn, lmx);
+    const size_t R = rays.size(), W = (R + kWaveLanes - 1) / kWaveLanes;
+    b.steps.clear(); b.off.assign(R + 1, 0); b.nI.assign(R, 0); b.nL.assign(R, 0); b.visited.assign(2 * R, 0); b.wave.assign(W, WaveTrips{}); b.total = WaveTrips{};
+    b.rec.visits.clear(); b.rec.stacks.clear(); b.visitOff.assign(R + 1, 0);
+    for (size_t r = 0; r < R; r++) { b.off[r] = (uint32_t)b.steps.size(); b.visitOff[r] = (uint32_t)b.rec.visits.size();
+        WaveWalk(b.wt, rays[r], b.steps, &b.visited[2 * r], &b.rec); }
+    b.off[R] = (uint32_t)b.steps.size(); b.visitOff[R] = (uint32_t)b.rec.visits.size();
+    const size_t M = 2 * (size_t)N - 1;
+    b.enter.resize(R * M); b.leave.resize(R * M);
+    for (size_t r = 0; r < R; r++) for (size_t n = 0; n < M; n++) WaveBoxSlabs(b.enter[r * M + n], b.leave[r * M + n], rays[r], b.wt.center[n], b.wt.half[n]);
+    for (size_t r = 0; r < R; r++) { b.nI[r] = b.visitOff[r + 1] - b.visitOff[r]; b.nL[r] = b.off[r + 1] - b.off[r] - b.nI[r]; }
+    const char* base = b.steps.empty() ? "" : b.steps.data();
+    const char* ptr[kWaveLanes]; uint32_t len[kWaveLanes];
+    for (size_t w = 0; w < W; w++) {
+        const uint32_t lanes = (uint32_t)std::min<size_t>(kWaveLanes, R - w * kWaveLanes);
+        for (uint32_t l = 0; l < lanes; l++) { const size_t r = w * kWaveLanes + l; ptr[l] = base + b.off[r]; len[l] = b.off[r + 1] - b.off[r]; }
+        b.wave[w] = WaveReplay(ptr, len, lanes, parkMin); b.total.add(b.wave[w]);
+    }
+}
+
+struct WaveCandidate { WaveTrips trips; uint32_t depth = 0; bool priced = false, complete = false; uint64_t suspects = 0, rewalked = 0; };
+struct WaveScratch { WaveTree wt; std::vector<uint32_t> left, right, from; std::vector<char> arena; std::vector<uint8_t> differs, todo, sameBox; std::vector<double> floor; };
+
+inline bool sameBits(const tb3& a, const tb3& b) { return memcmp(&a, &b, sizeof(tb3)) == 0; }
+
+/* The price of the topology in sc.left / sc.right, worked out from `b` -- the exact shortcuts of the search.
+ *   - At an inner node a walk reads the two children, in the image's order, and their boxes; before it starts, the root's box.  A ray that in b's
+ *     tree visited no node where any of that is other bits now takes the same steps in this tree: it keeps its string.
+ *   - A ray that did visit such a node is a suspect.  Its recorded visits are gone through in order: at a node that reads other bits the two box
+ *     tests are made again with the `closest` the walk had there, and if the node puts on the stack what it put there before (WavePushes), the
+ *     walk goes on as it did -- children that changed places, a changed child the ray misses as it missed the old one.  The first visit that
+ *     comes out otherwise is where the ray is walked again from, with the stack, the `closest` and the steps it had there; a suspect that passes
+ *     every visit keeps its string.  A box test over a box of the same bits takes the ray's remembered slabs (WaveBoxKept).
+ *   - A wave none of whose lanes was walked again, or all of whose lanes came back with the steps they had, keeps its trips.
+ *   - The sum over the waves is abandoned as soon as it has passed `bound`, the best complete price so far.  Before any ray is walked it
+ *     holds, for a wave with lanes to walk, a floor -- no wave takes fewer inner trips than its longest kept lane has inner steps, nor fewer leaf
+ *     passes than that lane has leaf steps -- which the wave's own price then replaces.
+ * Only the first waveLimit waves are priced (the screen prices a part).  out.complete: the sum was carried to the end, out.trips is the tree's
+ * price over those waves.  Costs are sums of small whole numbers, exact in a double. */
+void waveCandidate(const WaveBase& b, WaveScratch& sc, uint32_t N, const tb3* lmn, const tb3* lmx, const std::vector<WaveRay>& rays, uint32_t parkMin,
+    uint32_t depthLimit, size_t waveLimit, const std::atomic<double>& bound, WaveCandidate& out)
+{
+    out = WaveCandidate{};
+    out.depth = WaveTreeFit(sc.wt, N, sc.left.data(), sc.right.data(), lmn, lmx);
+    if (out.depth > depthLimit) return;
+    out.priced = true;
+    const WaveTree& c = sc.wt; const WaveTree& o = b.wt;
+    const bool all = !sameBits(c.center[0], o.center[0]) || !sameBits(c.half[0], o.half[0]);
+    uint64_t changed[2] = {0, 0};
+    const size_t M = 2 * (size_t)N - 1;
+    sc.sameBox.resize(M);
+    for (size_t n = 0; n < M; n++) sc.sameBox[n] = sameBits(c.center[n], o.center[n]) && sameBits(c.half[n], o.half[n]) ? 1 : 0;
+    auto kept = [&](size_t r) { return WaveBoxKept{&b.enter[r * M], &b.leave[r * M], sc.sameBox.data()}; };
+    sc.differs.assign(N - 1, 0);
+    for (uint32_t i = 0; i + 1 < N; i++) { const uint32_t l = c.left[i], r = c.right[i];
+        if (l != o.left[i] || r != o.right[i] || !sameBits(c.center[l], o.center[l]) || !sameBits(c.half[l], o.half[l]) || !sameBits(c.center[r], o.center[r]) ||
+            !sameBits(c.half[r], o.half[r])) { sc.differs[i] = 1; WaveMaskSet(changed, i); } }
+    const size_t W = std::min(b.wave.size(), waveLimit), R = std::min(rays.size(), W * kWaveLanes); /* the first waveLimit waves */
+    constexpr uint32_t FROM_START = 0xffffffffu;
+    sc.todo.assign(R, 0); sc.from.resize(R); sc.floor.assign(W, -1.0);
+    double partial = 0;
+    for (size_t w = 0; w < W; w++) {
+        const size_t first = w * kWaveLanes, end = std::min(R, first + kWaveLanes);
+        bool any = false; uint32_t maxI = 0, maxL = 0;
+        for (size_t r = first; r < end; r++) {
+            if (all) { sc.todo[r] = 1; sc.from[r] = FROM_START; any = true; continue; }
+            if ((b.visited[2 * r] & changed[0]) || (b.visited[2 * r + 1] & changed[1])) {
+                out.suspects++;
+                for (uint32_t k = b.visitOff[r]; k < b.visitOff[r + 1]; k++) { const WaveVisit& v = b.rec.visits[k];
+                    if (!sc.differs[v.node]) continue;
+                    uint32_t walked, parked; WavePushesWith(kept(r), c, rays[r], v.node, v.closest, walked, parked);
+                    if (walked == v.first && parked == v.parked) continue;
+                    sc.todo[r] = 1; sc.from[r] = k; any = true; break; }
+                if (sc.todo[r]) continue;
+            }
+            maxI = std::max(maxI, b.nI[r]); maxL = std::max(maxL, b.nL[r]);
+        }
+        if (!any) { out.trips.add(b.wave[w]); partial += b.wave[w].cost(); }
+        else { sc.floor[w] = (double)maxI * kWaveInnerInsts + (double)maxL * kWaveLeafInsts; partial += sc.floor[w]; }
+    }
+    if (partial > bound.load(std::memory_order_relaxed)) return;
+    const char* keep = b.steps.empty() ? "" : b.steps.data();
+    const char* ptr[kWaveLanes]; uint32_t len[kWaveLanes]; size_t at[kWaveLanes + 1]; uint32_t stack[kWaveWalkStack];
+    for (size_t w = 0; w < W; w++) {
+        if (sc.floor[w] < 0.0) continue;
+        const size_t first = w * kWaveLanes; const uint32_t lanes = (uint32_t)(std::min(R, first + kWaveLanes) - first);
+        sc.arena.clear();
+        for (uint32_t l = 0; l < lanes; l++) { const size_t r = first + l; at[l] = sc.arena.size();
+            if (!sc.todo[r]) continue;
+            out.rewalked++;
+            if (sc.from[r] == FROM_START) { WaveWalk(c, rays[r], sc.arena); continue; }
+            const WaveVisit& v = b.rec.visits[sc.from[r]]; /* the steps before that visit, then the walk from it: the node back on the stack it was taken from */
+            sc.arena.insert(sc.arena.end(), keep + b.off[r], keep + b.off[r] + v.step);
+            if (v.top) memcpy(stack, &b.rec.stacks[v.rest], v.top * sizeof(uint32_t));
+            stack[v.top] = v.node;
+            WaveWalkOnWith(kept(r), c, rays[r], stack, (int)v.top + 1, v.closest, sc.arena, at[l], nullptr, nullptr); }
+        at[lanes] = sc.arena.size();
+        const char* fresh = sc.arena.empty() ? "" : sc.arena.data();
+        bool same = true;
+        for (uint32_t l = 0; l < lanes; l++) { const size_t r = first + l;
+            if (!sc.todo[r]) { ptr[l] = keep + b.off[r]; len[l] = b.off[r + 1] - b.off[r]; continue; }
+            ptr[l] = fresh + at[l]; len[l] = (uint32_t)(at[l + 1] - at[l]);
+            if (same && (len[l] != b.off[r + 1] - b.off[r] || memcmp(ptr[l], keep + b.off[r], len[l]) != 0)) same = false; }
+        const WaveTrips tr = same ? b.wave[w] : WaveReplay(ptr, len, lanes, parkMin);
+        out.trips.add(tr); partial += tr.cost() - sc.floor[w];
+        if (partial > bound.load(std::memory_order_relaxed)) return;
+    }
+    out.complete = true;
+}
+
+
+/* the stage's workers: what was asked for (option "wave_tree_threads"), or the CPUs this process may run on -- never the machine's -- and at most
+ * kWaveStageMaxThreads */
+uint32_t waveStageWorkers(int asked)
+{
+    unsigned n = 1;
+    if (asked >= 1) n = (unsigned)asked;
+    else {
+#ifdef __linux__
+        cpu_set_t set; CPU_ZERO(&set);
+        if (sched_getaffinity(0, sizeof set, &set) == 0) n = (unsigned)std::max(CPU_COUNT(&set), 1);
+#endif
+    }
+    return std::min<unsigned>(n, kWaveStageMaxThreads);
+}
+
 void optimizeForWaves(const HostScene& s, Tree& t, HostScene::WaveStageReport& rep)
 {
     const uint32_t N = t.N; if (N < 4) return;
     const auto started = std::chrono::steady_clock::now();
     const uint32_t M = 2 * N - 1, NONE = 0xffffffffu;
     auto isLeaf = [&](uint32_t x) { return x >= N - 1; };
+    /* the search: every legal place and the validation rays, or (for comparisons) the best few places by induced area as the stage was */
+    const uint32_t placesLimit = s.waveSearchPlaces ? s.waveSearchPlaces : kWaveStagePlaces;
+    const bool byArea = placesLimit != 0;
+    const uint32_t maxPasses = byArea ? kWaveStagePassesByArea : kWaveStagePasses;
+    const uint32_t seed = s.waveSearchSeed ? s.waveSearchSeed : kWaveStageSeed, waves = s.waveSearchWaves ? s.waveSearchWaves : kWaveStageWaves;
+    const uint32_t feelers = s.waveSearchFeelerPercent < 0 ? kWaveStageFeelerPercent : (uint32_t)std::min(s.waveSearchFeelerPercent, 100);
     /* the leaves: bounds for the fit, triangles for the walk */
     std::vector<tb3> lmn(N), lmx(N);
-    WaveTree wt; wt.v0.resize(N); wt.v1.resize(N); wt.v2.resize(N);
+    WaveTree tris; tris.v0.resize(N); tris.v1.resize(N); tris.v2.resize(N);
     for (uint32_t k = 0; k < N; k++) { const Bounds b = boundsOfRef(s, t, t.order[k]); lmn[k] = b.mn; lmx[k] = b.mx;
-        const uint32_t tri = triOfRef(t, t.order[k]); wt.v0[k] = P(s, tri, 0); wt.v1[k] = P(s, tri, 1); wt.v2[k] = P(s, tri, 2); }
+        const uint32_t tri = triOfRef(t, t.order[k]); tris.v0[k] = P(s, tri, 0); tris.v1[k] = P(s, tri, 1); tris.v2[k] = P(s, tri, 2); }
     WaveSurfaces surf; WaveSurfacesOf(s, surf);
-    std::vector<WaveRay> rays;
-    WaveModelRays(surf, kWaveStageSeed, kWaveStageWaves, kWaveStageFeelerPercent, rays);
+    std::vector<WaveRay> rays, check;
+    WaveModelRays(surf, seed, waves, feelers, rays);
     if (rays.empty()) return;
-    std::vector<char> arena;
-    uint32_t depthNow = 0;
-    auto price = [&]() { depthNow = WaveTreeFit(wt, N, t.left.data(), t.right.data(), lmn.data(), lmx.data()); rep.evaluations++;
-        return WaveCostOfTree(wt, rays, kLdsSceneParkMin, arena); };
-    WaveTrips cur = price();
+    /* the validation rays: as many waves of a second fixed seed, the same share of feelers.  A move the search's rays like may not raise their price */
+    WaveModelRays(surf, kWaveStageValidationSeed, waves, feelers, check);
+    WaveBase base; base.wt = tris;
+    WaveTree checked = tris; std::vector<char> arena;
+    auto rebase = [&]() { waveBaseOf(base, N, t.left.data(), t.right.data(), lmn.data(), lmx.data(), rays, kLdsSceneParkMin); };
+    rep.evaluations++;
+    auto priceCheck = [&]() { WaveTreeFit(checked, N, t.left.data(), t.right.data(), lmn.data(), lmx.data());
+        return WaveCostOfTree(checked, check, kLdsSceneParkMin, arena).cost(); };
+    rebase();
+    WaveTrips cur = base.total;
+    double curCheck = priceCheck();
     /* depth limits, in nodes like HostScene::bvhMaxDepth: the area passes' step, the LDS budget, the six-wave copy */
-    const uint32_t d0 = depthNow, image = (uint32_t)LdsImageBytes(N - 1, N);
+    const uint32_t d0 = base.depth, image = (uint32_t)LdsImageBytes(N - 1, N);
     const bool sixFit = LdsCopyFits(6, WalkStackDepth(d0), image);
     auto depthOk = [&](uint32_t d) { return d <= (d0 <= 31u ? 31u : (d0 <= 39u ? 39u : d0)) && willBeLdsResident(s, N, d) &&
         (!sixFit || LdsCopyFits(6, WalkStackDepth(d), image)); };
     uint32_t depthLimit = d0; while (depthOk(depthLimit + 1)) depthLimit++;
-    rep.ran = 1; rep.rays = (uint32_t)rays.size(); rep.seed = kWaveStageSeed; rep.parkMin = kLdsSceneParkMin; rep.depthLimit = depthLimit;
+    rep.ran = 1; rep.rays = (uint32_t)rays.size(); rep.seed = seed; rep.parkMin = kLdsSceneParkMin; rep.depthLimit = depthLimit;
     rep.innerBefore = cur.inner; rep.leafBefore = cur.leaf; rep.costBefore = cur.cost();
+    rep.places = placesLimit; rep.validationBefore = curCheck;
+    const uint32_t workers = waveStageWorkers(s.waveTreeThreads);
+    rep.threads = workers;
+    std::vector<WaveScratch> scratch(workers);
+    for (WaveScratch& sc : scratch) sc.wt = tris;
 
     std::vector<uint32_t> parent(M, NONE);
     for (uint32_t i = 0; i + 1 < N; i++) { parent[t.left[i]] = i; parent[t.right[i]] = i; }
@@ -527,37 +722,109 @@ void optimizeForWaves(const HostScene& s, Tree& t, HostScene::WaveStageReport& r
     auto replaceChild = [&](uint32_t p, uint32_t from, uint32_t to) { if (t.left[p] == from) t.left[p] = to; else t.right[p] = to; parent[to] = p; };
     struct Place { float induced; uint32_t node; };
     std::vector<Place> places; std::vector<uint32_t> cand(M - 1), inTree;
-    for (uint32_t pass = 0; pass < kWaveStagePasses; pass++) {
+    std::vector<WaveCandidate> priced, screened; std::vector<size_t> finalists;
+    const size_t screenWaves = !byArea && base.wave.size() > kWaveStageScreenWaves ? kWaveStageScreenWaves : 0;
+    const std::vector<WaveRay> screenRays(rays.begin(), rays.begin() + (s.waveSearchVerify ? std::min(rays.size(), screenWaves * kWaveLanes) : 0));
+    const uint32_t screenKeep = s.waveSearchKeep ? s.waveSearchKeep : kWaveStageScreenKeep; /* finalists of the screen */
+    rep.screenWaves = (uint32_t)screenWaves; rep.screenKeep = screenWaves ? screenKeep : 0;
+    /* fn(k, scratch) for every k below count, on the workers */
+    auto forEach = [&](size_t count, const std::function<void(size_t, WaveScratch&)>& fn) {
+        std::atomic<size_t> next{0}; std::exception_ptr failed; std::mutex fm;
+        auto work = [&](WaveScratch& sc) {
+            try { for (size_t k = next++; k < count; k = next++) fn(k, sc); }
+            catch (...) { std::lock_guard<std::mutex> lock(fm); if (!failed) failed = std::current_exception(); next = count; } };
+        const size_t helpers = std::min<size_t>(workers, count);
+        if (helpers <= 1) work(scratch[0]);
+        else { std::vector<std::thread> th; for (size_t i = 1; i < helpers; i++) th.emplace_back(work, std::ref(scratch[i]));
+            work(scratch[0]); for (auto& one : th) one.join(); }
+        if (failed) std::rethrow_exception(failed); };
+    std::vector<uint32_t> triedAt(M, 0); /* 1 + the moves made when the subtree was last cut and put back */
+    for (uint32_t pass = 0; pass < maxPasses; pass++) {
         bool moved = false;
+        rep.passes = pass + 1;
         refitBelow(0);
         for (uint32_t x = 1; x < M; x++) cand[x - 1] = x;
         std::stable_sort(cand.begin(), cand.end(), [&](uint32_t a, uint32_t b) { return sa[a] > sa[b]; });
         for (uint32_t x : cand) {
             const uint32_t p = parent[x]; if (p == NONE || p == 0) continue; /* children of the root stay: node 0 remains the root */
+            /* a subtree that found no better place in this very tree need not be cut again: the search is a function of the tree alone */
+            if (!byArea && triedAt[x] == rep.moves + 1u) { rep.cutsSkipped++; continue; }
+            triedAt[x] = rep.moves + 1u;
             const uint32_t g = parent[p], oldLeft = t.left[p], oldRight = t.right[p], sib = oldLeft == x ? oldRight : oldLeft;
             const bool pWasLeft = t.left[g] == p;
             replaceChild(g, p, sib); parent[p] = NONE;
             refitBelow(x); const Bounds bx = box[x];
             refitBelow(0); inTree = pre;
+            /* the places, ranked by induced area: the order in which ties of the price are settled (and all that a search by area prices) */
             places.clear();
             for (uint32_t y : inTree) { if (y == 0 || y == sib) continue;
                 Bounds u = box[y]; grow(u, bx); float induced = area(u);
                 for (uint32_t a = parent[y]; a != NONE; a = parent[a]) { Bounds w = box[a]; grow(w, bx); induced += area(w) - sa[a]; }
                 places.push_back(Place{induced, y}); }
             std::stable_sort(places.begin(), places.end(), [](const Place& a, const Place& b) { return a.induced < b.induced; });
-            uint32_t best = NONE; WaveTrips bestTrips = cur;
-            for (size_t k = 0; k < places.size() && k < kWaveStagePlaces; k++) {
-                const uint32_t y = places[k].node, q = parent[y];
-                replaceChild(q, y, p); t.left[p] = y; t.right[p] = x; parent[y] = p; parent[x] = p;
-                const WaveTrips tr = price();
-                if (depthNow <= depthLimit && tr.cost() < bestTrips.cost()) { best = y; bestTrips = tr; }
-                replaceChild(q, p, y); parent[p] = NONE;
+            if (byArea && places.size() > placesLimit) places.resize(placesLimit);
+            /* Every place is priced from the tree as it was before the cut.  First on the screen's waves alone, of which the screenKeep
+             * cheapest go on (among equals the place that ranks first); then those on all waves.  The workers of a round share nothing but a
+             * bound -- the price that a place has to beat to stay in the round -- which only makes them stop sooner on one that cannot. */
+            auto hang = [&](WaveScratch& sc, uint32_t y) { const uint32_t q = parent[y];
+                sc.left = t.left; sc.right = t.right;
+                if (sc.left[q] == y) sc.left[q] = p; else sc.right[q] = p;
+                sc.left[p] = y; sc.right[p] = x; };
+            auto verify = [&](WaveScratch& sc, const WaveCandidate& got, const std::vector<WaveRay>& over, double boundNow) { /* tests: a plain walk of every ray */
+                if (!s.waveSearchVerify || !got.priced) return;
+                const WaveTrips plain = WaveCostOfTree(sc.wt, over, kLdsSceneParkMin, sc.arena);
+                if (got.complete ? plain.inner != got.trips.inner || plain.leaf != got.trips.leaf || plain.idle != got.trips.idle : !(plain.cost() > boundNow))
+                    throw std::logic_error("wave stage: a shortcut changed a price"); };
+            finalists.clear();
+            const bool screen = screenWaves && places.size() > screenKeep;
+            if (screen) {
+                screened.assign(places.size(), WaveCandidate{});
+                std::atomic<double> bound{std::numeric_limits<double>::infinity()}; std::mutex bm; std::vector<double> cheapest;
+                forEach(places.size(), [&](size_t k, WaveScratch& sc) {
+                    hang(sc, places[k].node);
+                    waveCandidate(base, sc, N, lmn.data(), lmx.data(), rays, kLdsSceneParkMin, depthLimit, screenWaves, bound, screened[k]);
+                    verify(sc, screened[k], screenRays, bound.load(std::memory_order_relaxed));
+                    if (!screened[k].complete) return;
+                    std::lock_guard<std::mutex> lock(bm);
+                    cheapest.insert(std::upper_bound(cheapest.begin(), cheapest.end(), screened[k].trips.cost()), screened[k].trips.cost());
+                    if (cheapest.size() > screenKeep) cheapest.pop_back();
+                    if (cheapest.size() == screenKeep) bound.store(cheapest.back(), std::memory_order_relaxed); });
+                for (size_t k = 0; k < places.size(); k++) { rep.evaluations++; if (!screened[k].priced) continue;
+                    rep.placesScreened++; rep.raysChecked += screened[k].suspects; rep.raysRewalked += screened[k].rewalked;
+                    if (!screened[k].complete) rep.abandoned++; else finalists.push_back(k); }
+                std::stable_sort(finalists.begin(), finalists.end(), [&](size_t a, size_t b) { return screened[a].trips.cost() < screened[b].trips.cost(); });
+                if (finalists.size() > screenKeep) finalists.resize(screenKeep);
+                std::sort(finalists.begin(), finalists.end()); /* back in rank order */
+            } else for (size_t k = 0; k < places.size(); k++) finalists.push_back(k);
+            priced.assign(places.size(), WaveCandidate{});
+            {
+                std::atomic<double> bound{cur.cost()};
+                forEach(finalists.size(), [&](size_t f, WaveScratch& sc) { const size_t k = finalists[f];
+                    hang(sc, places[k].node);
+                    waveCandidate(base, sc, N, lmn.data(), lmx.data(), rays, kLdsSceneParkMin, depthLimit, base.wave.size(), bound, priced[k]);
+                    verify(sc, priced[k], rays, bound.load(std::memory_order_relaxed));
+                    if (priced[k].complete) { const double c = priced[k].trips.cost(); double seen = bound.load(std::memory_order_relaxed);
+                        while (c < seen && !bound.compare_exchange_weak(seen, c, std::memory_order_relaxed)) {} } });
             }
-            if (best != NONE) {
-                const uint32_t q = parent[best];
-                replaceChild(q, best, p); t.left[p] = best; t.right[p] = x; parent[best] = p; parent[x] = p;
-                cur = bestTrips; moved = true; rep.moves++;
-            } else { /* back where it was, child order included */
+            /* the lowest complete price below the tree's own; among equals the place that ranks first */
+            size_t best = places.size(); double bestCost = cur.cost();
+            for (size_t k : finalists) { if (!screen) rep.evaluations++; /* a tree fitted is counted once */ if (!priced[k].priced) continue;
+                rep.placesPriced++; rep.raysChecked += priced[k].suspects; rep.raysRewalked += priced[k].rewalked; if (!priced[k].complete) { rep.abandoned++; continue; }
+                if (priced[k].trips.cost() < bestCost) { best = k; bestCost = priced[k].trips.cost(); } }
+            bool keep = best != places.size();
+            if (keep) {
+                const uint32_t y = places[best].node, q = parent[y];
+                replaceChild(q, y, p); t.left[p] = y; t.right[p] = x; parent[y] = p; parent[x] = p;
+                if (!byArea) { const double c = priceCheck();
+                    if (c > curCheck) { keep = false; rep.validationRejects++; replaceChild(q, p, y); parent[p] = NONE; } else curCheck = c; }
+            }
+            if (keep) {
+                rebase(); /* every ray walked over the tree as it is now: what the shortcuts gave must be that */
+                if (base.total.inner != priced[best].trips.inner || base.total.leaf != priced[best].trips.leaf || base.depth != priced[best].depth)
+                    throw std::logic_error("wave stage: a place was priced wrongly");
+                cur = base.total; moved = true; rep.moves++;
+            }
+            else { /* back where it was, child order included */
                 if (pWasLeft) t.left[g] = p; else t.right[g] = p;
                 parent[p] = g; t.left[p] = oldLeft; t.right[p] = oldRight; parent[sib] = p; parent[x] = p;
             }
@@ -565,6 +832,7 @@ void optimizeForWaves(const HostScene& s, Tree& t, HostScene::WaveStageReport& r
         if (!moved) break;
     }
     rep.innerAfter = cur.inner; rep.leafAfter = cur.leaf; rep.costAfter = cur.cost();
+    rep.validationAfter = byArea ? priceCheck() : curCheck;
     rep.milliseconds = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count();
 }
 

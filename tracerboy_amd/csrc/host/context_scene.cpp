@@ -273,7 +273,7 @@ void finalizeScene(tb_context* c, bool build)
     const bool twoLevel = !s.instances.empty();
     s.reinsertionPasses = (int)opt<OPT_reinsertion_passes>(c); s.reinsertionShare = (int)opt<OPT_reinsertion_share>(c);
     s.presplitPercent = (int)std::max<int64_t>(0, std::min<int64_t>(400, opt<OPT_presplit>(c)));
-    s.waveTree = (int)opt<OPT_wave_tree>(c);
+    s.waveTree = (int)opt<OPT_wave_tree>(c); s.waveTreeThreads = (int)std::min<int64_t>(opt<OPT_wave_tree_threads>(c), 1024);
     s.ldsSceneBudget = opt<OPT_scene_in_lds>(c) != 0 ? (uint32_t)std::max<int64_t>(0, std::min<int64_t>(0x7fffffff, opt<OPT_lds_scene_budget>(c))) : 0u;
     if (build) {
     /* every bottom-level structure and the top level on the GPU (GpuBVH2Builder.cpp:498-501: the same passes, no treelets at the top) */

@@ -480,7 +480,20 @@ int tb_host_scene_wave_stage(tb_host_scene* h, tb_wave_stage_info* o)
     o->before.inner_trips = r.innerBefore; o->before.leaf_trips = r.leafBefore; o->before.cost = r.costBefore;
     o->after.inner_trips = r.innerAfter; o->after.leaf_trips = r.leafAfter; o->after.cost = r.costAfter;
     o->milliseconds = r.milliseconds;
+    o->places_priced = r.placesPriced; o->abandoned = r.abandoned; o->rays_checked = r.raysChecked; o->rays_rewalked = r.raysRewalked; o->cuts_skipped = r.cutsSkipped;
+    o->places_screened = r.placesScreened; o->screen_waves = r.screenWaves; o->screen_keep = r.screenKeep; o->threads = r.threads; o->passes = r.passes;
+    o->places = r.places; o->validation_rejects = r.validationRejects; o->validation_before = r.validationBefore; o->validation_after = r.validationAfter;
     return TB_OK;
+}
+int tb_host_scene_wave_search(tb_host_scene* h, uint32_t seed, uint32_t waves, int feelerPercent, uint32_t places, uint32_t keep, int threads, tb_wave_stage_info* out)
+{
+    if (!h || waves > (1u << 16) || threads < 0) return TB_E_INVALID;
+    HostScene& s = h->scene;
+    if (!s.instances.empty() || s.triGeometry.empty()) return TB_E_UNSUPPORTED;
+    s.waveTree = 1; s.waveSearchSeed = seed; s.waveSearchWaves = waves; s.waveSearchFeelerPercent = feelerPercent; s.waveSearchPlaces = places; s.waveSearchKeep = keep;
+    s.waveTreeThreads = threads;
+    try { BuildBvh(s, 1); } catch (const std::exception&) { return TB_E_INVALID; }
+    return out ? tb_host_scene_wave_stage(h, out) : TB_OK;
 }
 
 /* ---- point queries on the host (the rule: include/tb_nearest.h) ------------- */

@@ -60,10 +60,25 @@ struct HostScene {
      * reinsertion passes run), 0 = off, 1 = on.  It runs only for a scene that will be LDS-resident: one level, and within ldsSceneBudget bytes by the size test of lds_image.h
      * (options "lds_scene_budget" / "scene_in_lds"; 0 = no scene is) */
     int waveTree = -1;
+    /* ... its workers (option "wave_tree_threads"): 0 = min(16, the CPUs of the process's affinity mask), 1 = serial; the tree is the same bytes for
+     * every count.  And the search itself, for comparisons (tb_host_scene_wave_search): the model rays' seed, number of waves and share of feeler
+     * waves (0 / 0 / -1 = the stage's own), and how many places per cut subtree are priced: 0 = every legal place, K > 0 = the stage as it was
+     * before it priced them all -- the K best by induced area, four passes, no validation rays (K = 3 gives that stage's tree byte for byte) */
+    int waveTreeThreads = 0;
+    uint32_t waveSearchSeed = 0, waveSearchWaves = 0, waveSearchPlaces = 0, waveSearchKeep = 0 /* finalists of the screen, 0 = the stage's own */; int waveSearchFeelerPercent = -1;
+    bool waveSearchVerify = false; /* tests: every place is priced a second time by a plain walk of all rays; a difference throws */
     uint32_t ldsSceneBudget = 40u * 1024u;
-    /* what the wave stage did at the last build: costs in wave instructions over its own model rays (wave_cost.h) */
+    /* what the wave stage did at the last build: costs in wave instructions over its own model rays (wave_cost.h).  evaluations: trees fitted;
+     * placesPriced: those inside the depth limit, whose rays were priced; abandoned: of them, stopped early because the partial sum had passed the
+     * best price; raysChecked: rays that had visited a changed node and were gone through visit by visit; raysRewalked: of them, walked again from
+     * the visit that came out otherwise (all others kept their steps); cutsSkipped: subtrees not cut again in an unchanged tree; validationRejects:
+     * winners refused because they raised the price of the validation rays; validation*: that price.  With more
+     * than one worker `abandoned` and `raysRewalked` depend on which worker finished first; the tree does not. */
     struct WaveStageReport { uint32_t ran = 0, rays = 0, seed = 0, parkMin = 0, depthLimit = 0, moves = 0, evaluations = 0;
-        uint64_t innerBefore = 0, leafBefore = 0, innerAfter = 0, leafAfter = 0; double costBefore = 0, costAfter = 0, milliseconds = 0; } waveStage;
+        uint64_t innerBefore = 0, leafBefore = 0, innerAfter = 0, leafAfter = 0; double costBefore = 0, costAfter = 0, milliseconds = 0;
+        uint64_t placesPriced = 0, abandoned = 0, raysChecked = 0, raysRewalked = 0; uint32_t threads = 0, passes = 0, places = 0, validationRejects = 0, cutsSkipped = 0;
+        uint64_t placesScreened = 0; uint32_t screenWaves = 0, screenKeep = 0; /* the screen: places priced on the first screenWaves waves; screenKeep went on */
+        double validationBefore = 0, validationAfter = 0; } waveStage;
 };
 
 struct ConvertOptions {

@@ -28,7 +28,7 @@ enum : uint32_t {
     X(split_trav, 4, 0) X(split_shade, 0, 0) X(split_ready, 32, 0) X(split_refill, 16, 0) X(split_wi, 85, 0) X(split_wl, 160, 0) \
     X(split_frame_group, 8, 0) X(split_stack_cap, 0, 0) X(split_spin_limit, 1 << 21, 0) X(split_profile, 0, 0) X(split_trav_last, 0, 0) \
     X(split_shade_prio, 0, 0) \
-    X(bvh_builder, 0, 0) X(reinsertion_passes, -1, 0) X(reinsertion_share, 100, 0) X(presplit, 0, 0) X(wave_tree, -1, 0) X(node_order, 2, 0) \
+    X(bvh_builder, 0, 0) X(reinsertion_passes, -1, 0) X(reinsertion_share, 100, 0) X(presplit, 0, 0) X(wave_tree, -1, 0) X(wave_tree_threads, 0, OPT_NOT_NEGATIVE) X(node_order, 2, 0) \
     X(node_order_top_levels, 10, 0) X(scene_in_lds, 1, 0) X(lds_scene_budget, 40 * 1024, 0) \
     X(park_min, 0, OPT_NO_DEFAULT) X(flatten_instances, 0, OPT_NO_DEFAULT) X(flip_texture_uvs, 0, OPT_NO_DEFAULT) X(texture_use_hint, 0, OPT_NO_DEFAULT)
 

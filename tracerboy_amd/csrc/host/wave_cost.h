@@ -84,15 +84,27 @@ inline void WaveRayPrepare(WaveRay& r)
     r.shear = tb3_make(tb3_get(d, r.kx) / tb3_get(d, r.kz), tb3_get(d, r.ky) / tb3_get(d, r.kz), 1.0f / tb3_get(d, r.kz));
 }
 
-inline bool WaveBoxTest(float& resultT, float closest, const WaveRay& r, tb3 c, tb3 h)
+/* the part of the box test that `closest` has no hand in: where the ray enters the box (not before its origin) and where it leaves */
+inline void WaveBoxSlabs(float& enterT, float& leaveT, const WaveRay& r, tb3 c, tb3 h)
 {
     const tb3 mid = tb3_make(tb_fma(c.x, r.inv.x, -r.oinv.x), tb_fma(c.y, r.inv.y, -r.oinv.y), tb_fma(c.z, r.inv.z, -r.oinv.z));
     const tb3 maxL = tb3_make(tb_fma(h.x, r.ainv.x, mid.x), tb_fma(h.y, r.ainv.y, mid.y), tb_fma(h.z, r.ainv.z, mid.z));
     const tb3 minL = tb3_make(tb_fma(-h.x, r.ainv.x, mid.x), tb_fma(-h.y, r.ainv.y, mid.y), tb_fma(-h.z, r.ainv.z, mid.z));
-    const float minT = tb_max(tb_max(minL.x, minL.y), minL.z), maxT = tb_min(tb_min(maxL.x, maxL.y), maxL.z);
-    resultT = tb_max(minT, 0.0f);
-    return resultT < tb_min(maxT, closest);
+    const float minT = tb_max(tb_max(minL.x, minL.y), minL.z);
+    leaveT = tb_min(tb_min(maxL.x, maxL.y), maxL.z);
+    enterT = tb_max(minT, 0.0f);
 }
+inline bool WaveBoxTest(float& resultT, float closest, const WaveRay& r, tb3 c, tb3 h)
+{
+    float leaveT;
+    WaveBoxSlabs(resultT, leaveT, r, c, h);
+    return resultT < tb_min(leaveT, closest);
+}
+/* How a walk tests the box of node n: WaveBoxDirect works it out; the wave stage's search (bvh_build.cpp) has one that remembers, per ray, where
+ * the ray enters and leaves every box of the tree it compares with */
+struct WaveBoxDirect {
+    bool operator()(float& resultT, float closest, const WaveTree& t, const WaveRay& r, uint32_t n) const { return WaveBoxTest(resultT, closest, r, t.center[n], t.half[n]); }
+};
 
 /* the watertight test, two-sided; hitT comes in as `closest` and goes out as the candidate's t where one is found */
 inline void WaveTriTest(float& hitT, const WaveRay& r, tb3 v0, tb3 v1, tb3 v2)
@@ -118,14 +130,36 @@ inline void WaveTriTest(float& hitT, const WaveRay& r, tb3 v0, tb3 v1, tb3 v2)
 
 constexpr int kWaveWalkStack = 256; /* the oracle's */
 
-/* The ray's steps, appended to `steps`; the return value is the closest accepted t, r.tMax where nothing was hit */
-inline float WaveWalk(const WaveTree& t, const WaveRay& r, std::vector<char>& steps)
+/* A set of inner nodes in 128 bits (the wave stage's search, bvh_build.cpp: which nodes a ray visited, which nodes a move changed).  Nodes 0 .. 127
+ * have a bit each; a node beyond them sets every bit, so that two sets which both hold such a node always meet: a scene of more than 129 triangles
+ * loses the shortcut, never the answer. */
+inline void WaveMaskSet(uint64_t mask[2], uint32_t node) { if (node < 128u) mask[node >> 6] |= 1ull << (node & 63u); else mask[0] = mask[1] = ~0ull; }
+
+/* A walk written down so that it can be checked against another tree and taken up in the middle (the wave stage's search): per inner node visited
+ * the node, the stack below it (`top` entries from stacks[rest]), the steps the ray had taken before, `closest` as it stood, and what the node put
+ * on the stack: the child walked first and the child parked (WavePushes).  A walk is made of nothing else: the stack, `closest`, and at every node
+ * popped what that node puts on the stack -- so where another tree's node puts the same two there from the same `closest`, the walk goes on as it
+ * did, whatever else differs between the trees. */
+constexpr uint32_t kWaveNoNode = 0xffffffffu;
+struct WaveVisit { uint32_t node, rest, top, step; float closest; uint32_t first, parked; };
+struct WaveRecord { std::vector<WaveVisit> visits; std::vector<uint32_t> stacks; };
+
+/* both children tested, near child first (rt < lt goes right, ties go left), far child parked */
+template <class Box>
+inline void WavePushesWith(const Box& box, const WaveTree& t, const WaveRay& r, uint32_t node, float closest, uint32_t& first, uint32_t& parked)
 {
-    float closest = r.tMax;
-    if (!t.N || r.cannotHit) return closest;
-    float unusedT;
-    if (!WaveBoxTest(unusedT, closest, r, t.center[0], t.half[0])) return closest;
-    uint32_t stack[kWaveWalkStack]; int top = 0; stack[top++] = 0;
+    const uint32_t l = t.left[node], rr = t.right[node];
+    float lt, rt;
+    const bool lh = box(lt, closest, t, r, l), rh = box(rt, closest, t, r, rr);
+    if (lh && rh) { const bool rightFirst = rt < lt; first = rightFirst ? rr : l; parked = rightFirst ? l : rr; }
+    else { first = lh ? l : (rh ? rr : kWaveNoNode); parked = kWaveNoNode; }
+}
+
+/* the walk from a given state: `top` entries on `stack` (room for kWaveWalkStack), `closest`; stepBase: where this ray's steps begin in `steps` */
+template <class Box>
+inline float WaveWalkOnWith(const Box& box, const WaveTree& t, const WaveRay& r, uint32_t* stack, int top, float closest, std::vector<char>& steps,
+    size_t stepBase, uint64_t* visited, WaveRecord* rec)
+{
     while (top) {
         const uint32_t node = stack[--top];
         if (node >= t.N - 1) {
@@ -135,17 +169,38 @@ inline float WaveWalk(const WaveTree& t, const WaveRay& r, std::vector<char>& st
             WaveTriTest(t0, r, t.v0[k], t.v1[k], t.v2[k]);
             if (t0 < closest && t0 > kWaveMinT) closest = t0;
         } else {
-            const uint32_t l = t.left[node], rr = t.right[node];
-            float lt, rt;
-            const bool lh = WaveBoxTest(lt, closest, r, t.center[l], t.half[l]), rh = WaveBoxTest(rt, closest, r, t.center[rr], t.half[rr]);
+            uint32_t first, parked;
+            WavePushesWith(box, t, r, node, closest, first, parked);
+            if (rec) { rec->visits.push_back(WaveVisit{node, (uint32_t)rec->stacks.size(), (uint32_t)top, (uint32_t)(steps.size() - stepBase), closest, first, parked});
+                rec->stacks.insert(rec->stacks.end(), stack, stack + top); }
             steps.push_back('I');
+            if (visited) WaveMaskSet(visited, node);
             if (top + 2 > kWaveWalkStack) return closest;
-            if (lh && rh) { const bool rightFirst = rt < lt; stack[top++] = rightFirst ? l : rr; stack[top++] = rightFirst ? rr : l; }
-            else if (lh || rh) stack[top++] = rh ? rr : l;
+            if (parked != kWaveNoNode) stack[top++] = parked;
+            if (first != kWaveNoNode) stack[top++] = first;
         }
     }
     return closest;
 }
+inline float WaveWalkOn(const WaveTree& t, const WaveRay& r, uint32_t* stack, int top, float closest, std::vector<char>& steps, size_t stepBase,
+    uint64_t* visited, WaveRecord* rec)
+{
+    return WaveWalkOnWith(WaveBoxDirect{}, t, r, stack, top, closest, steps, stepBase, visited, rec);
+}
+
+
+/* The ray's steps, appended to `steps`; the return value is the closest accepted t, r.tMax where nothing was hit.  visited (may be null): the inner
+ * nodes the walk visits are added to this WaveMaskSet set; rec (may be null): the visits are appended to this record. */
+inline float WaveWalk(const WaveTree& t, const WaveRay& r, std::vector<char>& steps, uint64_t* visited = nullptr, WaveRecord* rec = nullptr)
+{
+    const float closest = r.tMax;
+    if (!t.N || r.cannotHit) return closest;
+    float unusedT;
+    if (!WaveBoxTest(unusedT, closest, r, t.center[0], t.half[0])) return closest;
+    uint32_t stack[kWaveWalkStack]; stack[0] = 0;
+    return WaveWalkOn(t, r, stack, 1, closest, steps, steps.size(), visited, rec);
+}
+
 
 struct WaveTrips {
     uint64_t inner = 0, leaf = 0, idle = 0;         /* wave trips through the inner loop's body, leaf passes a lane takes, passes none takes */
@@ -163,22 +218,22 @@ inline WaveTrips WaveReplay(const char* const* steps, const uint32_t* len, uint3
     WaveTrips w;
     if (lanes > kWaveLanes) lanes = kWaveLanes;
     if (parkMin < 1) parkMin = 1;
+    /* the lanes at an inner node and at a leaf as bit sets, kept up as the lanes step (the wave stage's search replays some 10^5 waves: only the
+     * lanes that step are touched); a lane at its string's end, or at any other character, is in neither and steps no more */
     uint32_t p[kWaveLanes] = {};
-    auto at = [&](uint32_t l, char c) { return p[l] < len[l] && steps[l][p[l]] == c; };
-    auto count = [&](char c) { uint32_t n = 0; for (uint32_t l = 0; l < lanes; l++) n += at(l, c) ? 1u : 0u; return n; };
-    uint32_t inner = count('I');
+    uint64_t inner = 0, leaf = 0;
+    auto arrive = [&](uint32_t l) { if (p[l] < len[l]) { const char c = steps[l][p[l]]; if (c == 'I') inner |= 1ull << l; else if (c == 'L') leaf |= 1ull << l; } };
+    auto step = [&](uint64_t& set) { uint64_t m = set; set = 0; while (m) { const uint32_t l = (uint32_t)__builtin_ctzll(m); m &= m - 1; p[l]++; arrive(l); } };
+    for (uint32_t l = 0; l < lanes; l++) arrive(l);
     bool busy;
     do {
         if (inner) do {
-            w.inner++; w.innerActive += inner;
-            for (uint32_t l = 0; l < lanes; l++) if (at(l, 'I')) p[l]++;
-            inner = count('I');
-        } while (inner >= parkMin);
-        const uint32_t leaf = count('L');
+            w.inner++; w.innerActive += (uint64_t)__builtin_popcountll(inner);
+            step(inner);
+        } while ((uint32_t)__builtin_popcountll(inner) >= parkMin);
         busy = inner != 0 || leaf != 0;
-        if (leaf) { w.leaf++; w.leafActive += leaf; for (uint32_t l = 0; l < lanes; l++) if (at(l, 'L')) p[l]++; }
+        if (leaf) { w.leaf++; w.leafActive += (uint64_t)__builtin_popcountll(leaf); step(leaf); }
         else w.idle++;
-        inner = count('I');
     } while (busy);
     return w;
 }
