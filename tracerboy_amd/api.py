@@ -297,32 +297,54 @@ def _is_torch_tensor(a):
     return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
 
 
+def _torch_sync(device):
+    """What torch has enqueued on its current stream of the device is done: the library reads and writes a tensor's memory on a stream of its own."""
+    import torch
+    torch.cuda.current_stream(device).synchronize()
+
+
+def _is_rows(dims, lead, columns):
+    return len(dims) >= 2 and dims[-1] == columns and (len(dims) == 2 if lead is None else tuple(dims[:-1]) == lead)
+
+
+def _rows_wanted(lead, columns, record_dtype=None):
+    """The words of _check_array's refusals: nothing is formatted for an array that passes."""
+    n_text = "n" if lead is None else ", ".join(str(r) for r in lead)
+    records = "" if record_dtype is None else "%d-B records of shape (%s,) or " % (record_dtype.itemsize, n_text)
+    return "%sfloat32 of shape (%s, %d)" % (records, n_text, columns)
+
+
+def _check_array(what, name, a, device, *, columns, record_dtype=None, align=4, rows=None, written=False, allow_tensor=True):
+    """One array of a call, checked before any library call (a wrong array must never reach a kernel as a wrong pointer): True for a torch tensor
+    (the device path), False for a numpy array (the host path); ValueError otherwise.  A tensor is float32 of shape (n, columns), contiguous, on
+    cuda:`device`, the context's, and `align`-B aligned.  A numpy array is float32 of that shape or, where the call has records, `record_dtype` of
+    shape (n,); C-contiguous; writeable where the call writes it.  rows: what stands for n -- a number, or a tuple for an array of more dimensions."""
+    lead = None if rows is None else rows if isinstance(rows, tuple) else (rows,)
+    if allow_tensor and _is_torch_tensor(a):
+        import torch
+        if a.dtype != torch.float32 or not _is_rows(tuple(a.shape), lead, columns):
+            raise ValueError("%s: the tensor %s is %s, not %s %s" % (what, name, _rows_wanted(lead, columns), a.dtype, tuple(a.shape)))
+        if not a.is_contiguous():
+            raise ValueError("%s: the tensor %s is not contiguous" % (what, name))
+        if a.device.type != "cuda" or a.device.index != device:
+            raise ValueError("%s: the tensor %s is on %s, the context on cuda:%d" % (what, name, a.device, device))
+        if a.data_ptr() % align:
+            raise ValueError("%s: the tensor %s is not %d-B aligned" % (what, name, align))
+        return True
+    if not isinstance(a, np.ndarray):
+        raise ValueError("%s: %s is a numpy array%s, not %s" % (what, name, " or a torch tensor" if allow_tensor else "", type(a).__name__))
+    records = record_dtype is not None and a.dtype == record_dtype
+    if not (a.ndim == 1 and (lead is None or a.shape == lead) if records else a.dtype == np.float32 and _is_rows(a.shape, lead, columns)):
+        raise ValueError("%s: %s is %s, not %s %s" % (what, name, _rows_wanted(lead, columns, record_dtype), a.dtype, a.shape))
+    if not a.flags["C_CONTIGUOUS"] or (written and not a.flags["WRITEABLE"]):
+        raise ValueError("%s: %s is not contiguous%s" % (what, name, " and writeable" if written else ""))
+    return False
+
+
 def _check_query_rays(rays, mode, device):
-    """What TraceRays accepts, checked before any library call (a wrong array must never reach the kernel as a wrong pointer): True for a torch
-    tensor (the device path), False for a numpy array (the host path); ValueError otherwise."""
     if mode not in (RAYS_CLOSEST, RAYS_OCCLUDED):
         raise ValueError("TraceRays: mode is RAYS_CLOSEST or RAYS_OCCLUDED, not %r" % (mode,))
-    if _is_torch_tensor(rays):
-        import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("TraceRays: a tensor of rays is float32 of shape (n, 8), not %s %s" % (rays.dtype, tuple(rays.shape)))
-        if not rays.is_contiguous():
-            raise ValueError("TraceRays: the tensor of rays is not contiguous")
-        if rays.device.type != "cuda" or rays.device.index != device:
-            raise ValueError("TraceRays: the tensor of rays is on %s, the context on cuda:%d" % (rays.device, device))
-        if rays.data_ptr() % 16:
-            raise ValueError("TraceRays: the tensor of rays is not 16-B aligned")
-        return True
-    if not isinstance(rays, np.ndarray):
-        raise ValueError("TraceRays: rays are a numpy array or a torch tensor, not %s" % type(rays).__name__)
-    if rays.dtype == QUERY_RAY_DTYPE:
-        if rays.ndim != 1:
-            raise ValueError("TraceRays: an array of QUERY_RAY_DTYPE has one dimension, not %d" % rays.ndim)
-    elif rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("TraceRays: rays are QUERY_RAY_DTYPE or float32 of shape (n, 8), not %s %s" % (rays.dtype, rays.shape))
-    if not rays.flags["C_CONTIGUOUS"]:
-        raise ValueError("TraceRays: the array of rays is not contiguous")
-    return False
+    return _check_array("TraceRays", "rays", rays, device, columns=8, record_dtype=QUERY_RAY_DTYPE, align=16)
 
 
 # radiance queries (tb_trace_radiance / tb_make_camera_rays; tb_abi.h TbRadianceRay / TbRadianceCall)
@@ -365,44 +387,29 @@ def _check_radiance_call(rays, samples, first_sample, seed_advance, mode, out, d
     _check_count("TraceRadiance", "first_sample", first_sample, 0, (1 << 32) - samples)
     if isinstance(seed_advance, bool) or not isinstance(seed_advance, (int, float, np.integer, np.floating)) or not np.isfinite(seed_advance):
         raise ValueError("TraceRadiance: seed_advance is a finite number, not %r" % (seed_advance,))
-    if _is_torch_tensor(rays):
-        import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("TraceRadiance: a tensor of rays is float32 of shape (n, 8), not %s %s" % (rays.dtype, tuple(rays.shape)))
-        if not rays.is_contiguous():
-            raise ValueError("TraceRadiance: the tensor of rays is not contiguous")
-        if rays.device.type != "cuda" or rays.device.index != device:
-            raise ValueError("TraceRadiance: the tensor of rays is on %s, the context on cuda:%d" % (rays.device, device))
-        if rays.data_ptr() % 16:
-            raise ValueError("TraceRadiance: the tensor of rays is not 16-B aligned")
-        if out is not None:
-            if not _is_torch_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (int(rays.shape[0]), 4):
-                raise ValueError("TraceRadiance: out is a float32 tensor of shape (n, 4) like the rays")
-            if not out.is_contiguous() or out.device != rays.device or out.data_ptr() % 16:
-                raise ValueError("TraceRadiance: out is contiguous, 16-B aligned and on the rays' device")
-        return True
-    if not isinstance(rays, np.ndarray):
-        raise ValueError("TraceRadiance: rays are a numpy array or a torch tensor, not %s" % type(rays).__name__)
-    if rays.dtype == RADIANCE_RAY_DTYPE:
-        if rays.ndim != 1:
-            raise ValueError("TraceRadiance: an array of RADIANCE_RAY_DTYPE has one dimension, not %d" % rays.ndim)
-    elif rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("TraceRadiance: rays are RADIANCE_RAY_DTYPE or float32 of shape (n, 8), not %s %s" % (rays.dtype, rays.shape))
-    if not rays.flags["C_CONTIGUOUS"]:
-        raise ValueError("TraceRadiance: the array of rays is not contiguous")
-    if out is not None:
-        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != (rays.shape[0], 4):
-            raise ValueError("TraceRadiance: out is a float32 numpy array of shape (n, 4) like the rays")
-        if not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
-            raise ValueError("TraceRadiance: out is contiguous and writeable")
-    return False
+    on_device = _check_array("TraceRadiance", "rays", rays, device, columns=8, record_dtype=RADIANCE_RAY_DTYPE, align=16)
+    if out is not None and _check_array("TraceRadiance", "out", out, device, columns=4, align=16, rows=int(rays.shape[0]), written=True) != on_device:
+        raise ValueError("TraceRadiance: rays and out are both numpy arrays or both torch tensors")
+    return on_device
+
+
+def _refusal(name, *args, room=96):
+    """A pure tb_*_refusal of the library asked: None, or the reason it wrote into the `room` bytes behind its arguments."""
+    why = C.create_string_buffer(room)
+    return None if getattr(lib(), name)(*args, why, room) == 0 else why.value.decode()
+
+
+def _ref(struct):
+    return C.byref(struct) if struct is not None else None
+
+
+def _address(a):
+    return C.c_void_p(a or None)
 
 
 def RadianceRefusal(call, n, rays_address, out_address):
     """tb_radiance_refusal (host only): why tb_trace_radiance refuses these arguments before it looks at its context -- None, or the reason."""
-    why = C.create_string_buffer(96)
-    rc = lib().tb_radiance_refusal(C.byref(call) if call is not None else None, n, C.c_void_p(rays_address or None), C.c_void_p(out_address or None), why, 96)
-    return None if rc == 0 else why.value.decode()
+    return _refusal("tb_radiance_refusal", _ref(call), n, _address(rays_address), _address(out_address))
 
 
 # lightmap baking (tb_bake_lightmap .. tb_run_bake_dilate; tb_abi.h TbBakeTexel)
@@ -422,38 +429,19 @@ def _check_bake_call(width, height, samples, uv, first_sample, dilate, accumulat
     _check_count("BakeLightmap", "dilate", dilate, 0, BAKE_MAX_DILATE)
     if not isinstance(accumulate, (bool, np.bool_)):
         raise ValueError("BakeLightmap: accumulate is True or False, not %r" % (accumulate,))
-    given = [a for a in (uv, out) if a is not None]
-    on_device = any(_is_torch_tensor(a) for a in given)
-    if on_device and not all(_is_torch_tensor(a) for a in given):
+    kinds = set()
+    if uv is not None:
+        kinds.add(_check_array("BakeLightmap", "uv", uv, device, columns=2))
+    if out is not None:
+        kinds.add(_check_array("BakeLightmap", "out", out, device, columns=4, align=16, rows=(height, width), written=True))
+    if len(kinds) > 1:
         raise ValueError("BakeLightmap: uv and out are both numpy arrays or both torch tensors")
-    for name, a, shape, align in (("uv", uv, None, 4), ("out", out, (height, width, 4), 16)):
-        if a is None:
-            continue
-        if on_device:
-            import torch
-            if a.dtype != torch.float32 or (a.dim() != 2 or a.shape[1] != 2 if shape is None else tuple(a.shape) != shape):
-                raise ValueError("BakeLightmap: the tensor %s is float32 of shape %s, not %s %s" % (name, shape or "(numVertices, 2)", a.dtype, tuple(a.shape)))
-            if not a.is_contiguous():
-                raise ValueError("BakeLightmap: the tensor %s is not contiguous" % name)
-            if a.device.type != "cuda" or a.device.index != device:
-                raise ValueError("BakeLightmap: the tensor %s is on %s, the context on cuda:%d" % (name, a.device, device))
-            if a.data_ptr() % align:
-                raise ValueError("BakeLightmap: the tensor %s is not %d-B aligned" % (name, align))
-        else:
-            if not isinstance(a, np.ndarray):
-                raise ValueError("BakeLightmap: %s is a numpy array or a torch tensor, not %s" % (name, type(a).__name__))
-            if a.dtype != np.float32 or (a.ndim != 2 or a.shape[1] != 2 if shape is None else a.shape != shape):
-                raise ValueError("BakeLightmap: %s is float32 of shape %s, not %s %s" % (name, shape or "(numVertices, 2)", a.dtype, a.shape))
-            if not a.flags["C_CONTIGUOUS"] or (name == "out" and not a.flags["WRITEABLE"]):
-                raise ValueError("BakeLightmap: %s is contiguous%s" % (name, " and writeable" if name == "out" else ""))
-    return on_device
+    return kinds == {True}
 
 
 def BakeRefusal(call, uv_address, out_address):
     """tb_bake_refusal (host only): why tb_bake_lightmap refuses these arguments before it looks at its context -- None, or the reason."""
-    why = C.create_string_buffer(96)
-    rc = lib().tb_bake_refusal(C.byref(call) if call is not None else None, C.c_void_p(uv_address or None), C.c_void_p(out_address or None), why, 96)
-    return None if rc == 0 else why.value.decode()
+    return _refusal("tb_bake_refusal", _ref(call), _address(uv_address), _address(out_address))
 
 
 # light probes (tb_bake_probes .. tb_run_probe_project; tb_abi.h TbProbe, tb_probe_grid)
@@ -503,29 +491,6 @@ def probe_grid_positions(grid):
     return np.ascontiguousarray(np.asarray(grid.origin, np.float32) + ijk * np.asarray(grid.spacing, np.float32))
 
 
-def _check_float_rows(what, name, a, width, align, device, rows=None):
-    """A float32 (n, width) numpy array (False) or torch tensor on the context's device (True), contiguous; ValueError otherwise."""
-    shape = "(%s, %d)" % ("n" if rows is None else rows, width)
-    if _is_torch_tensor(a):
-        import torch
-        if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != width or (rows is not None and a.shape[0] != rows):
-            raise ValueError("%s: the tensor %s is float32 of shape %s, not %s %s" % (what, name, shape, a.dtype, tuple(a.shape)))
-        if not a.is_contiguous():
-            raise ValueError("%s: the tensor %s is not contiguous" % (what, name))
-        if a.device.type != "cuda" or a.device.index != device:
-            raise ValueError("%s: the tensor %s is on %s, the context on cuda:%d" % (what, name, a.device, device))
-        if a.data_ptr() % align:
-            raise ValueError("%s: the tensor %s is not %d-B aligned" % (what, name, align))
-        return True
-    if not isinstance(a, np.ndarray):
-        raise ValueError("%s: %s is a numpy array or a torch tensor, not %s" % (what, name, type(a).__name__))
-    if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != width or (rows is not None and a.shape[0] != rows):
-        raise ValueError("%s: %s is float32 of shape %s, not %s %s" % (what, name, shape, a.dtype, a.shape))
-    if not a.flags["C_CONTIGUOUS"]:
-        raise ValueError("%s: %s is not contiguous" % (what, name))
-    return False
-
-
 def _check_probe_call(positions, resolution, samples, first_sample, first_number, keep_maps, accumulate, device):
     """What BakeProbes accepts, checked before any library call: True for a torch tensor of positions (the device path), False for a numpy array."""
     _check_count("BakeProbes", "resolution", resolution, PROBE_MIN_RES, PROBE_MAX_RES)
@@ -534,7 +499,7 @@ def _check_probe_call(positions, resolution, samples, first_sample, first_number
     for name, v in (("keep_maps", keep_maps), ("accumulate", accumulate)):
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError("BakeProbes: %s is True or False, not %r" % (name, v))
-    on_device = _check_float_rows("BakeProbes", "positions", positions, 3, 4, device)
+    on_device = _check_array("BakeProbes", "positions", positions, device, columns=3)
     n = int(positions.shape[0])
     if n > PROBE_MAX_PROBES or n * resolution * resolution > 1 << 31:
         raise ValueError("BakeProbes: %d probes of %d x %d rays are more than 2^24 probes or 2^31 rays" % (n, resolution, resolution))
@@ -542,20 +507,9 @@ def _check_probe_call(positions, resolution, samples, first_sample, first_number
     return on_device
 
 
-def _is_probe_array(probes, what, rows):
-    """True for a PROBE_DTYPE array of `rows` records, contiguous (ValueError if it is one of another shape); False for anything else."""
-    if not (isinstance(probes, np.ndarray) and probes.dtype == PROBE_DTYPE):
-        return False
-    if probes.ndim != 1 or not probes.flags["C_CONTIGUOUS"] or probes.shape[0] != rows:
-        raise ValueError("%s: probes are a contiguous PROBE_DTYPE array of %d records" % (what, rows))
-    return True
-
-
 def ProbesRefusal(call, positions_address, probes_address):
     """tb_probes_refusal (host only): why tb_bake_probes refuses these arguments before it looks at its context -- None, or the reason."""
-    why = C.create_string_buffer(96)
-    rc = lib().tb_probes_refusal(C.byref(call) if call is not None else None, C.c_void_p(positions_address or None), C.c_void_p(probes_address or None), why, 96)
-    return None if rc == 0 else why.value.decode()
+    return _refusal("tb_probes_refusal", _ref(call), _address(positions_address), _address(probes_address))
 
 
 def sh9_irradiance(probe, normal):
@@ -605,22 +559,7 @@ def _check_flag(what, name, v):
 
 
 def _check_query_points(what, points, device, allow_tensor=True):
-    """What NearestPoints accepts, checked before any library call: True for a torch tensor (the device path), False for a numpy array (the host
-    path); ValueError otherwise."""
-    if _is_torch_tensor(points):
-        if not allow_tensor:
-            raise ValueError("%s: points are a numpy array, not a torch tensor" % what)
-        return _check_float_rows(what, "of points", points, 4, 16, device)
-    if not isinstance(points, np.ndarray):
-        raise ValueError("%s: points are a numpy array%s, not %s" % (what, " or a torch tensor" if allow_tensor else "", type(points).__name__))
-    if points.dtype == QUERY_POINT_DTYPE:
-        if points.ndim != 1:
-            raise ValueError("%s: an array of QUERY_POINT_DTYPE has one dimension, not %d" % (what, points.ndim))
-    elif points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != 4:
-        raise ValueError("%s: points are QUERY_POINT_DTYPE or float32 of shape (n, 4), not %s %s" % (what, points.dtype, points.shape))
-    if not points.flags["C_CONTIGUOUS"]:
-        raise ValueError("%s: the array of points is not contiguous" % what)
-    return False
+    return _check_array(what, "points", points, device, columns=4, record_dtype=QUERY_POINT_DTYPE, align=16, allow_tensor=allow_tensor)
 
 
 def _check_distance_field(grid, signed, max_distance, device):
@@ -636,10 +575,7 @@ def _check_distance_field(grid, signed, max_distance, device):
 def NearestRefusal(flags, n, points_address, out_address, grid=None):
     """tb_nearest_refusal (host only): why tb_nearest_points -- with a grid (abi.tb_probe_grid): tb_bake_distance_field -- refuses these arguments before
     it looks at its context: None, or the reason."""
-    why = C.create_string_buffer(96)
-    rc = lib().tb_nearest_refusal(flags, n, C.c_void_p(points_address or None), C.c_void_p(out_address or None), C.byref(grid) if grid is not None else None,
-                                  why, 96)
-    return None if rc == 0 else why.value.decode()
+    return _refusal("tb_nearest_refusal", flags, n, _address(points_address), _address(out_address), _ref(grid))
 
 
 # winding numbers (tb_winding_numbers .. tb_bake_distance_field_winding; the rule: include/tb_winding.h)
@@ -663,10 +599,7 @@ def _check_beta(what, beta, name="beta"):
 def WindingRefusal(flags, n, points_address, out_address, grid=None, beta=WINDING_BETA):
     """tb_winding_refusal (host only): why tb_winding_numbers -- with a grid (abi.tb_probe_grid): tb_bake_winding_field -- refuses these arguments
     before it looks at its context: None, or the reason."""
-    why = C.create_string_buffer(96)
-    rc = lib().tb_winding_refusal(flags, n, C.c_void_p(points_address or None), C.c_void_p(out_address or None), C.byref(grid) if grid is not None else None,
-                                  beta, why, 96)
-    return None if rc == 0 else why.value.decode()
+    return _refusal("tb_winding_refusal", flags, n, _address(points_address), _address(out_address), _ref(grid), beta)
 
 
 # dynamic scenes (tb_update_positions .. tb_commit_geometry)
@@ -804,9 +737,7 @@ def _scene_desc(what, meshes, materials, camera, environment, env_scale, film, d
 
 def MeshesRefusal(desc):
     """tb_meshes_refusal (host only, pure): why tb_load_meshes refuses this tb_scene_desc before it looks at its context -- None, or the reason."""
-    why = C.create_string_buffer(160)
-    rc = lib().tb_meshes_refusal(C.byref(desc) if desc is not None else None, why, 160)
-    return None if rc == 0 else why.value.decode()
+    return _refusal("tb_meshes_refusal", _ref(desc), room=160)
 
 
 def HostSmoothNormals(positions, indices, out=None):
@@ -922,6 +853,10 @@ def DecodeImage(path):
 
 def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _tensor_ptr(a):
+    return C.c_void_p(a.data_ptr() or None)
 
 
 # -- render-state files, host only: no device, no context ----------------
@@ -1216,6 +1151,24 @@ class TracerBoy:
         if rc != 0:
             raise TracerBoyError(rc, (self._L.tb_last_error(self._ctx) or b"").decode(errors="replace"))
 
+    def _query(self, on_device, device_flag, call, tensor_shape, array_shape, dtype=np.float32, out=None):
+        """The tail of every query method, after its checks.  call(flag, ptr, o) is the entry point: ptr(a) makes the pointer of one of its
+        arrays, o is the result's.  The host path -- flag = 0 -- answers in a numpy array of array_shape and dtype.  The device path -- flag =
+        device_flag -- answers in a torch tensor of tensor_shape on the context's device, after torch's work there is done: bytes where dtype is
+        np.uint8, else float32, a record's fields as columns.  out: the caller's own result array, already checked, in place of a new one."""
+        if on_device:
+            import torch
+            dev = torch.device("cuda", getattr(self, "_device", 0))
+            if out is None:
+                out = torch.empty(tensor_shape, dtype=torch.uint8 if dtype is np.uint8 else torch.float32, device=dev)
+            _torch_sync(dev)
+            self._check(call(device_flag, _tensor_ptr, _tensor_ptr(out)))
+        else:
+            if out is None:
+                out = np.empty(array_shape, dtype)
+            self._check(call(0, _np_ptr, _np_ptr(out)))
+        return out
+
     # -- TracerBoy interface --------------------------------------------------------------------
     def LoadScene(self, sceneFileName):
         """TracerBoy::LoadScene (TracerBoy.cpp:1065): blocking."""
@@ -1232,8 +1185,7 @@ class TracerBoy:
         meshes = list(meshes)
         d, keep, on_device = _scene_desc("LoadMeshes", meshes, materials, camera, environment, env_scale, film, getattr(self, "_device", 0))
         if on_device:
-            import torch
-            torch.cuda.current_stream(meshes[0].positions.device).synchronize()
+            _torch_sync(meshes[0].positions.device)
         self._num_vertices = None
         self._check(self._L.tb_load_meshes(self._ctx, C.byref(d)))
 
@@ -1712,15 +1664,11 @@ class TracerBoy:
         integer fields through .view(torch.int32)) / a uint8 (n,) tensor that torch allocated.  Anything else: ValueError, before any library call."""
         on_device = _check_query_rays(rays, mode, getattr(self, "_device", 0))
         n = int(rays.shape[0])
-        if on_device:
-            import torch
-            out = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if mode == RAYS_CLOSEST else torch.empty((n,), dtype=torch.uint8, device=rays.device)
-            torch.cuda.current_stream(rays.device).synchronize()
-            self._check(self._L.tb_trace_rays(self._ctx, mode | RAYS_DEVICE, n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty(n, QUERY_HIT_DTYPE if mode == RAYS_CLOSEST else np.uint8)
-        self._check(self._L.tb_trace_rays(self._ctx, mode, n, _np_ptr(rays), _np_ptr(out)))
-        return out
+        closest = mode == RAYS_CLOSEST
+
+        def call(dev, ptr, o):
+            return self._L.tb_trace_rays(self._ctx, mode | dev, n, ptr(rays), o)
+        return self._query(on_device, RAYS_DEVICE, call, (n, 12) if closest else (n,), n, QUERY_HIT_DTYPE if closest else np.uint8)
 
     # -- point queries (DESIGN.md section 27) ------------------------------------------------------
     def NearestPoints(self, points, signed=False, winding_beta=None):
@@ -1738,19 +1686,11 @@ class TracerBoy:
             raise ValueError("NearestPoints: signed and winding_beta are two rules for the sign: give one")
         n = int(points.shape[0])
 
-        def call(flags, p, o):
+        def call(dev, ptr, o):
             if beta is None:
-                return self._L.tb_nearest_points(self._ctx, flags, n, p, o)
-            return self._L.tb_nearest_points_winding(self._ctx, flags, n, p, beta, o)
-        if on_device:
-            import torch
-            out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
-            torch.cuda.current_stream(points.device).synchronize()
-            self._check(call(flags | NEAREST_DEVICE, C.c_void_p(points.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty(n, NEAREST_DTYPE)
-        self._check(call(flags, _np_ptr(points), _np_ptr(out)))
-        return out
+                return self._L.tb_nearest_points(self._ctx, flags | dev, n, ptr(points), o)
+            return self._L.tb_nearest_points_winding(self._ctx, flags | dev, n, ptr(points), beta, o)
+        return self._query(on_device, NEAREST_DEVICE, call, (n, 8), n, NEAREST_DTYPE)
 
     def BakeDistanceField(self, grid, signed=False, max_distance=np.inf, device=False, winding_beta=None):
         """tb_bake_distance_field: float32 of shape (count[2], count[1], count[0]) -- for every cell of the ProbeGrid the Distance of NearestPoints at
@@ -1765,20 +1705,11 @@ class TracerBoy:
         g = grid.c_struct()
         shape = (grid.count[2], grid.count[1], grid.count[0])
 
-        def call(flags, o):
+        def call(dev, ptr, o):
             if beta is None:
-                return self._L.tb_bake_distance_field(self._ctx, flags, C.byref(g), float(max_distance), o)
-            return self._L.tb_bake_distance_field_winding(self._ctx, flags, C.byref(g), float(max_distance), beta, o)
-        if device:
-            import torch
-            dev = torch.device("cuda", getattr(self, "_device", 0))
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-            self._check(call(flags | NEAREST_DEVICE, C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty(shape, np.float32)
-        self._check(call(flags, _np_ptr(out)))
-        return out
+                return self._L.tb_bake_distance_field(self._ctx, flags | dev, C.byref(g), float(max_distance), o)
+            return self._L.tb_bake_distance_field_winding(self._ctx, flags | dev, C.byref(g), float(max_distance), beta, o)
+        return self._query(device, NEAREST_DEVICE, call, shape, shape)
 
     # -- winding numbers ----------------------------------------------------
     def WindingNumbers(self, points, beta=WINDING_BETA, host_walk=False):
@@ -1792,15 +1723,11 @@ class TracerBoy:
         if _check_flag("WindingNumbers", "host_walk", host_walk) and on_device:
             raise ValueError("WindingNumbers: host_walk takes a numpy array")
         n = int(points.shape[0])
-        if on_device:
-            import torch
-            out = torch.empty((n,), dtype=torch.float32, device=points.device)
-            torch.cuda.current_stream(points.device).synchronize()
-            self._check(self._L.tb_winding_numbers(self._ctx, WINDING_DEVICE, n, C.c_void_p(points.data_ptr() or None), beta, C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty(n, np.float32)
-        self._check(self._L.tb_winding_numbers(self._ctx, WINDING_HOST_WALK if host_walk else 0, n, _np_ptr(points), beta, _np_ptr(out)))
-        return out
+        flags = WINDING_HOST_WALK if host_walk else 0
+
+        def call(dev, ptr, o):
+            return self._L.tb_winding_numbers(self._ctx, flags | dev, n, ptr(points), beta, o)
+        return self._query(on_device, WINDING_DEVICE, call, (n,), n)
 
     def BakeWindingField(self, grid, beta=WINDING_BETA, device=False):
         """tb_bake_winding_field: float32 of shape (count[2], count[1], count[0]) -- for every cell of the ProbeGrid the WindingNumbers at
@@ -1813,16 +1740,10 @@ class TracerBoy:
             raise ValueError("BakeWindingField: more than 2^31 cells")
         g = grid.c_struct()
         shape = (grid.count[2], grid.count[1], grid.count[0])
-        if device:
-            import torch
-            dev = torch.device("cuda", getattr(self, "_device", 0))
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-            self._check(self._L.tb_bake_winding_field(self._ctx, WINDING_DEVICE, C.byref(g), beta, C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty(shape, np.float32)
-        self._check(self._L.tb_bake_winding_field(self._ctx, 0, C.byref(g), beta, _np_ptr(out)))
-        return out
+
+        def call(dev, ptr, o):
+            return self._L.tb_bake_winding_field(self._ctx, dev, C.byref(g), beta, o)
+        return self._query(device, WINDING_DEVICE, call, shape, shape)
 
     # -- radiance queries ---------------------------------------------------
     def TraceRadiance(self, rays, samples=1, first_sample=0, seed_advance=0.0, mode=RADIANCE_RAY, settings=None, time=0.0, out=None):
@@ -1835,20 +1756,12 @@ class TracerBoy:
         before any library call."""
         on_device = _check_radiance_call(rays, samples, first_sample, seed_advance, mode, out, getattr(self, "_device", 0))
         n = int(rays.shape[0])
-        flags = mode | (RADIANCE_ACCUMULATE if out is not None else 0) | (RADIANCE_DEVICE if on_device else 0)
-        call = abi.TbRadianceCall(int(first_sample), int(samples), float(seed_advance), flags)
-        s = C.byref(settings) if settings is not None else None
-        if on_device:
-            import torch
-            if out is None:
-                out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-            torch.cuda.current_stream(rays.device).synchronize()
-            self._check(self._L.tb_trace_radiance(self._ctx, s, time, C.byref(call), n, C.c_void_p(rays.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
-            return out
-        if out is None:
-            out = np.empty((n, 4), np.float32)
-        self._check(self._L.tb_trace_radiance(self._ctx, s, time, C.byref(call), n, _np_ptr(rays), _np_ptr(out)))
-        return out
+        flags = mode | (RADIANCE_ACCUMULATE if out is not None else 0)
+
+        def call(dev, ptr, o):
+            k = abi.TbRadianceCall(int(first_sample), int(samples), float(seed_advance), flags | dev)
+            return self._L.tb_trace_radiance(self._ctx, _ref(settings), time, C.byref(k), n, ptr(rays), o)
+        return self._query(on_device, RADIANCE_DEVICE, call, (n, 4), (n, 4), out=out)
 
     def MakeCameraRays(self, width, height, frame, window=None, settings=None, time=0.0, device=False):
         """tb_make_camera_rays: (rays, seed_advance) -- the renderer's camera rays of frame `frame` for the pixels of window = (x0, y0, x1, y1)
@@ -1865,15 +1778,10 @@ class TracerBoy:
             raise ValueError("MakeCameraRays: the window (%d, %d, %d, %d) is empty or leaves the %d x %d picture" % (x0, y0, x1, y1, width, height))
         n = (x1 - x0) * (y1 - y0)
         advance = C.c_float(0.0)
-        s = C.byref(settings) if settings is not None else None
-        if device:
-            import torch
-            rays = torch.empty((n, 8), dtype=torch.float32, device="cuda:%d" % getattr(self, "_device", 0))
-            torch.cuda.current_stream(rays.device).synchronize()
-            self._check(self._L.tb_make_camera_rays(self._ctx, s, time, width, height, x0, y0, x1, y1, frame, RADIANCE_DEVICE, C.c_void_p(rays.data_ptr()), C.byref(advance)))
-        else:
-            rays = np.empty(n, RADIANCE_RAY_DTYPE)
-            self._check(self._L.tb_make_camera_rays(self._ctx, s, time, width, height, x0, y0, x1, y1, frame, 0, _np_ptr(rays), C.byref(advance)))
+
+        def call(dev, ptr, o):
+            return self._L.tb_make_camera_rays(self._ctx, _ref(settings), time, width, height, x0, y0, x1, y1, frame, dev, o, C.byref(advance))
+        rays = self._query(device, RADIANCE_DEVICE, call, (n, 8), n, RADIANCE_RAY_DTYPE)
         return rays, advance.value
 
     # -- lightmap baking ---------------------------------------------------
@@ -1890,22 +1798,11 @@ class TracerBoy:
             info = abi.tb_scene_info()
             if self._L.tb_scene_info_get(self._ctx, C.byref(info)) == 0 and int(uv.shape[0]) != info.numVertices:
                 raise ValueError("BakeLightmap: uv has %d pairs, the scene %d vertices" % (int(uv.shape[0]), info.numVertices))
-        call = abi.tb_bake_call(int(width), int(height), int(first_sample), int(samples), int(dilate),
-                                (BAKE_ACCUMULATE if accumulate else 0) | (BAKE_DEVICE if on_device else 0))
-        s = C.byref(settings) if settings is not None else None
-        if on_device:
-            import torch
-            dev = torch.device("cuda:%d" % getattr(self, "_device", 0))
-            if out is None:
-                out = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-            self._check(self._L.tb_bake_lightmap(self._ctx, s, time, C.byref(call), C.c_void_p(uv.data_ptr() or None) if uv is not None else None,
-                                                 C.c_void_p(out.data_ptr() or None)))
-            return out
-        if out is None:
-            out = np.empty((height, width, 4), np.float32)
-        self._check(self._L.tb_bake_lightmap(self._ctx, s, time, C.byref(call), _np_ptr(uv) if uv is not None else None, _np_ptr(out)))
-        return out
+        def call(dev, ptr, o):
+            k = abi.tb_bake_call(int(width), int(height), int(first_sample), int(samples), int(dilate), (BAKE_ACCUMULATE if accumulate else 0) | dev)
+            return self._L.tb_bake_lightmap(self._ctx, _ref(settings), time, C.byref(k), ptr(uv) if uv is not None else None, o)
+        shape = (height, width, 4)
+        return self._query(on_device, BAKE_DEVICE, call, shape, shape, out=out)
 
     def ReadBake(self):
         """tb_read_bake: (rays, texels, sums) of the last bake -- RADIANCE_RAY_DTYPE and BAKE_TEXEL_DTYPE arrays of shape (height, width) and the
@@ -1953,18 +1850,12 @@ class TracerBoy:
         hits (ReadProbeMaps); accumulate: add the samples to the bake kept.  Anything else: ValueError, before any library call."""
         on_device = _check_probe_call(positions, resolution, samples, first_sample, first_number, keep_maps, accumulate, getattr(self, "_device", 0))
         n = int(positions.shape[0])
-        flags = (PROBES_KEEP_MAPS if keep_maps else 0) | (PROBES_ACCUMULATE if accumulate else 0) | (PROBES_DEVICE if on_device else 0)
-        call = abi.tb_probe_call(n, int(first_number), int(resolution), int(first_sample), int(samples), flags)
-        s = C.byref(settings) if settings is not None else None
-        if on_device:
-            import torch
-            out = torch.empty((n, 32), dtype=torch.float32, device=positions.device)
-            torch.cuda.current_stream(positions.device).synchronize()
-            self._check(self._L.tb_bake_probes(self._ctx, s, time, C.byref(call), C.c_void_p(positions.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty(n, PROBE_DTYPE)
-        self._check(self._L.tb_bake_probes(self._ctx, s, time, C.byref(call), _np_ptr(positions), _np_ptr(out)))
-        return out
+        flags = (PROBES_KEEP_MAPS if keep_maps else 0) | (PROBES_ACCUMULATE if accumulate else 0)
+
+        def call(dev, ptr, o):
+            k = abi.tb_probe_call(n, int(first_number), int(resolution), int(first_sample), int(samples), flags | dev)
+            return self._L.tb_bake_probes(self._ctx, _ref(settings), time, C.byref(k), ptr(positions), o)
+        return self._query(on_device, PROBES_DEVICE, call, (n, 32), n, PROBE_DTYPE)
 
     def ReadProbeMaps(self):
         """tb_read_probe_maps: (sums, hits) of the last bake that kept its maps -- float32 (n, M * M, 4) (sum r, sum g, sum b, accepted samples) and
@@ -1988,23 +1879,16 @@ class TracerBoy:
         if isinstance(backface_limit, bool) or not isinstance(backface_limit, (int, float, np.integer, np.floating)) or np.isnan(backface_limit):
             raise ValueError("SampleProbes: backface_limit is a number, not %r" % (backface_limit,))
         device = getattr(self, "_device", 0)
-        on_device = False if _is_probe_array(probes, "SampleProbes", grid.n) else _check_float_rows("SampleProbes", "probes", probes, 32, 16, device, rows=grid.n)
-        if _check_float_rows("SampleProbes", "points", points, 3, 4, device) != on_device or \
-                _check_float_rows("SampleProbes", "normals", normals, 3, 4, device, rows=int(points.shape[0])) != on_device:
+        on_device = _check_array("SampleProbes", "probes", probes, device, columns=32, record_dtype=PROBE_DTYPE, align=16, rows=grid.n)
+        if _check_array("SampleProbes", "points", points, device, columns=3) != on_device or \
+                _check_array("SampleProbes", "normals", normals, device, columns=3, rows=int(points.shape[0])) != on_device:
             raise ValueError("SampleProbes: probes, points and normals are numpy arrays all, or torch tensors all")
         n = int(points.shape[0])
         g = grid.c_struct()
-        if on_device:
-            import torch
-            out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
-            torch.cuda.current_stream(points.device).synchronize()
-            self._check(self._L.tb_sample_probes(self._ctx, PROBES_DEVICE, C.byref(g), resolution, float(backface_limit), C.c_void_p(probes.data_ptr() or None), n,
-                                                 C.c_void_p(points.data_ptr() or None), C.c_void_p(normals.data_ptr() or None), C.c_void_p(out.data_ptr() or None)))
-            return out
-        out = np.empty((n, 4), np.float32)
-        self._check(self._L.tb_sample_probes(self._ctx, 0, C.byref(g), resolution, float(backface_limit), _np_ptr(probes), n, _np_ptr(points), _np_ptr(normals),
-                                             _np_ptr(out)))
-        return out
+
+        def call(dev, ptr, o):
+            return self._L.tb_sample_probes(self._ctx, dev, C.byref(g), resolution, float(backface_limit), ptr(probes), n, ptr(points), ptr(normals), o)
+        return self._query(on_device, PROBES_DEVICE, call, (n, 4), (n, 4))
 
     def RunProbeRays(self, positions, resolution, first_number=0):
         """probe_rays on host positions (n, 3), no scene: (RADIANCE_RAY_DTYPE, QUERY_RAY_DTYPE) arrays of shape (n, M * M)."""
@@ -2036,8 +1920,7 @@ class TracerBoy:
         n = int(a.shape[0])
         fn = getattr(self._L, fn_name)
         if on_device:
-            import torch
-            torch.cuda.current_stream(a.device).synchronize()
+            _torch_sync(a.device)
             self._check(fn(self._ctx, UPDATE_DEVICE, first, n, C.c_void_p(a.data_ptr() or None)))
             self._check(self._L.tb_sync(self._ctx))                 # the tensor has been read: torch may give its memory to another
         else:

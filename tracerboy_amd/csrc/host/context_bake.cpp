@@ -2,6 +2,7 @@
  * on the device (kernels/bake_kernels.hip), its texels traced by the radiance query as it stands (context_radiance.cpp traceRadianceOnDevice), the
  * sums resolved and the gutters filled.  The atlas's rays, texel records and sums stay in the context (tb_context::Bake) from the first bake to the
  * scene's release; nothing else of the context is written. */
+#include "query_call.h"
 #include "radiance_trace.h"
 #include "../kernels/bake_launch.h"
 
@@ -14,7 +15,6 @@ typedef tb_context::Bake Bake;
 
 uint32_t numVertices(const tb_context* c) { return (uint32_t)(c->scene.positions.size() / 3); }
 DevBuf stagedAtLeast(const void* host, size_t bytes) { DevBuf d = scratch(std::max<size_t>(16, bytes)); if (bytes) HIP_TRY(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice)); return d; }
-float elapsed(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f; }
 
 /* The scene's triangles and positions where the rasteriser reads them.  The vertex numbers go up once per Bake (a rebuild releases it with the
  * scene); the positions once per scene generation: from section 21's staged array where it holds exactly what was committed (device to device),
@@ -58,17 +58,17 @@ extern "C" int tb_bake_lightmap(tb_context* c, const tb_output_settings* setting
         char why[96];
         if (tb_bake_refusal(call, uv, rgbaOut, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_bake_lightmap: ") + why);
         if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-        if (!c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED, "tb_bake_lightmap: not supported for a multi-device group: an atlas is baked on one device");
+        if (const int rc = refuseGroup(c, "tb_bake_lightmap", "an atlas is baked on one device")) return rc;
         if (!c->scene.instances.empty()) return fail(c, TB_E_UNSUPPORTED,
             "tb_bake_lightmap: a two-level scene (option flatten_instances = 0 with instances) is not supported: its vertices are in object space");
-        tb_output_settings s; if (settings) s = *settings; else DefaultOutputSettings(s);
+        const tb_output_settings s = settingsOrDefault(settings);
         if (s.RenderModeRealTime) return fail(c, TB_E_UNSUPPORTED, "tb_bake_lightmap: the real-time mode is not supported: a query has no AOVs and no history");
         const uint32_t W = call->width, H = call->height;
         const size_t n = (size_t)W * H;
         const bool device = (call->flags & TB_BAKE_DEVICE) != 0, accumulate = (call->flags & TB_BAKE_ACCUMULATE) != 0;
-        if (device) {
-            if (uv && !accumulate) if (const char* no = devicePointerRefusal(c, uv, 8ull * numVertices(c))) return fail(c, TB_E_INVALID, std::string("tb_bake_lightmap: uv: ") + no);
-            if (const char* no = devicePointerRefusal(c, rgbaOut, 16 * n)) return fail(c, TB_E_INVALID, std::string("tb_bake_lightmap: rgba_out: ") + no);
+        if (device) { /* the arrays go to and from buffers the context keeps, below: only the pointers are the seam's */
+            if (uv && !accumulate) checkDevicePointer(c, "tb_bake_lightmap", "uv", uv, 8ull * numVertices(c));
+            checkDevicePointer(c, "tb_bake_lightmap", "rgba_out", rgbaOut, 16 * n);
         }
         if (accumulate) {
             const Bake* b = c->bake.get();

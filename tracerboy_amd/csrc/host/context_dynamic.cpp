@@ -2,7 +2,7 @@
  * transforms staged by the caller, applied by a commit.  Moved vertices are refit into the tree as it stands (kernels/refit_kernels.hip: the topology,
  * and so the schedule of the bottom-up pass, is known beforehand); instance transforms rebuild the small top level.  The host copies of the geometry go
  * stale at a commit and are brought up on first demand (refreshHostScene). */
-#include "context_internal.h"
+#include "query_call.h"
 #include "lds_image.h"
 #include "tb_vec.h"
 #include "../kernels/refit_launch.h"
@@ -215,7 +215,7 @@ int stageVertices(tb_context* c, const char* what, bool normals, uint32_t flags,
         if (n == 0) return TB_OK;
         const size_t bytes = 12ull * n;
         const bool device = (flags & TB_UPDATE_DEVICE) != 0;
-        if (device) { if (const char* why = devicePointerRefusal(c, xyz, bytes)) return fail(c, TB_E_INVALID, std::string(what) + ": xyz: " + why); }
+        if (device) checkDevicePointer(c, what, "xyz", xyz, bytes);
         else for (size_t i = 0; i < 3ull * n; i++) if (!std::isfinite(xyz[i])) return fail(c, TB_E_INVALID, std::string(what) + ": a value is not finite");
         Dynamic& d = dynamicOf(c);
         if (!d.ready) makeTables(c, d);

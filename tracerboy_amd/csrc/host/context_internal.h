@@ -24,6 +24,7 @@
  *   context_nearest.cpp point queries: tb_nearest_points and tb_bake_distance_field, the nearest surface point by a distance-ordered walk
  *   context_winding.cpp winding numbers: tb_winding_numbers, tb_bake_winding_field and the winding-signed point queries; the subtree moments
  *   context_meshes.cpp  scenes from caller arrays: tb_load_meshes, device arrays read to the host once, the swap into the context
+ *   query_call.h        what the query entry points above share: a caller's arrays checked or staged, the timed launch, the common refusals
  *   host_api.cpp        every entry point that needs no device (host scenes, images, the plan); shares host_shared.h with the above, not this header
  *   options.h           the table of options      launch_plan.h  WHAT a call launches      launch_trials.h  the two trials (pure, like the plan)
  */
@@ -368,10 +369,14 @@ struct DeviceScope {
     ~DeviceScope() { if (saved >= 0) (void)hipSetDevice(saved); }
 };
 
+/* a refusal thrown below an entry point's body (query_call.h): guarded() answers it as fail(c, code, msg) */
+struct Refusal { int code; std::string msg; };
+
 template <class F> int guarded(tb_context* c, F f)
 {
     if (!c) return TB_E_INVALID;
     try { DeviceScope scope(c->device); return f(); }
+    catch (const Refusal& r) { return fail(c, r.code, r.msg); }
     catch (const std::bad_alloc&) { return fail(c, TB_E_DEVICE, "out of host memory"); }
     catch (const std::exception& e) {
         std::string m = e.what();
@@ -428,8 +433,6 @@ void refreshHostScene(tb_context* c);
 /* context_dynamic.cpp: the slots and the height-ordered schedule of a bottom-up pass over s's layout-B tree (refit_launch.h RefitTables) */
 void treeSchedule(const tbhost::HostScene& s, std::vector<uint32_t>& triSlot, std::vector<uint32_t>& nodeSlot, std::vector<uint32_t>& schedule,
     std::vector<uint32_t>& levelFirst);
-/* context_rays.cpp: why a device pointer the caller gave is refused -- `bytes` from it must lie inside one allocation of the context's device; null: it is not */
-const char* devicePointerRefusal(const tb_context* c, const void* p, size_t bytes);
 /* context_rays.cpp: the closest-hit launch of tb_trace_rays on n device rays into n device hit records, on the context's stream, not waited for.
  * tb_trace_rays and tb_bake_probes (context_probes.cpp) both end here.  The caller has checked the scene and the pointers. */
 void traceClosestOnDevice(tb_context* c, uint32_t n, const TbQueryRay* rays, TbQueryHit* hits);

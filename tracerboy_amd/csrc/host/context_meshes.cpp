@@ -1,7 +1,7 @@
 /* context_meshes.cpp -- a scene from caller arrays (include/tracerboy_hip.h tb_load_meshes): the argument tests, device arrays
  * read to the host once, the scene made by host_scene.cpp MeshesToScene into a local HostScene, then the swap and finalizeScene -- what a file load
  * does from there on.  A refused call has not touched the context's scene. */
-#include "context_internal.h"
+#include "query_call.h"
 
 using namespace tbhost;
 using namespace tbctx;

@@ -3,6 +3,7 @@
  * (context_radiance.cpp traceRadianceOnDevice, context_rays.cpp traceClosestOnDevice), projected onto nine SH basis functions per probe; and the
  * consumer's half, tb_sample_probes.  The records, and where the call asks for it the rays' answers, stay in the context (tb_context::Probes) from
  * the first bake to the scene's release; nothing else of the context is written. */
+#include "query_call.h"
 #include "radiance_trace.h"
 #include "../kernels/probe_launch.h"
 
@@ -14,8 +15,6 @@ using namespace tbctx;
 namespace {
 
 typedef tb_context::Probes Probes;
-
-float elapsed(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f; }
 
 /* TB_PROBE_MAX_RAYS, read at every call: the most rays of one batch, 1 .. 2^26; unset, empty or anything else: 2^20.  A batch is whole probes, at
  * least one.  The split changes no byte of the answer: a ray's answers depend on its record and the samples alone. */
@@ -36,16 +35,16 @@ extern "C" int tb_bake_probes(tb_context* c, const tb_output_settings* settings,
         char why[96];
         if (tb_probes_refusal(call, positions, probesOut, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_bake_probes: ") + why);
         if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-        if (!c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED, "tb_bake_probes: not supported for a multi-device group: probes are baked on one device");
-        tb_output_settings s; if (settings) s = *settings; else DefaultOutputSettings(s);
+        if (const int rc = refuseGroup(c, "tb_bake_probes", "probes are baked on one device")) return rc;
+        const tb_output_settings s = settingsOrDefault(settings);
         if (s.RenderModeRealTime) return fail(c, TB_E_UNSUPPORTED, "tb_bake_probes: the real-time mode is not supported: a query has no AOVs and no history");
         const uint64_t n = call->n; const uint32_t M = call->resolution, texels = M * M;
         if (n == 0) return TB_OK;
         const bool device = (call->flags & TB_PROBES_DEVICE) != 0, accumulate = (call->flags & TB_PROBES_ACCUMULATE) != 0;
         const bool keep = accumulate || (call->flags & TB_PROBES_KEEP_MAPS) != 0;
-        if (device) {
-            if (const char* no = devicePointerRefusal(c, positions, 12 * n)) return fail(c, TB_E_INVALID, std::string("tb_bake_probes: positions: ") + no);
-            if (const char* no = devicePointerRefusal(c, probesOut, sizeof(TbProbe) * n)) return fail(c, TB_E_INVALID, std::string("tb_bake_probes: probes_out: ") + no);
+        if (device) { /* the arrays go to and from buffers the context keeps, below: only the pointers are the seam's */
+            checkDevicePointer(c, "tb_bake_probes", "positions", positions, 12 * n);
+            checkDevicePointer(c, "tb_bake_probes", "probes_out", probesOut, sizeof(TbProbe) * n);
         }
         if (accumulate) {
             const Probes* p = c->probes.get();
@@ -117,27 +116,18 @@ extern "C" int tb_sample_probes(tb_context* c, uint32_t flags, const tb_probe_gr
         if (n > (1ull << 31)) return fail(c, TB_E_INVALID, "tb_sample_probes: more than 2^31 points");
         if (!probes || (n && (!points || !normals || !rgbaOut))) return fail(c, TB_E_INVALID, "tb_sample_probes: null pointer");
         const bool device = (flags & TB_PROBES_DEVICE) != 0;
-        if (device) {
-            if (((uintptr_t)probes & 15u) || ((uintptr_t)rgbaOut & 15u) || ((uintptr_t)points & 3u) || ((uintptr_t)normals & 3u))
-                return fail(c, TB_E_INVALID, "tb_sample_probes: device probes and rgba_out are 16-B, points and normals 4-B aligned");
-            if (const char* no = devicePointerRefusal(c, probes, sizeof(TbProbe) * numProbes)) return fail(c, TB_E_INVALID, std::string("tb_sample_probes: probes: ") + no);
-            if (n) {
-                if (const char* no = devicePointerRefusal(c, points, 12 * n)) return fail(c, TB_E_INVALID, std::string("tb_sample_probes: points: ") + no);
-                if (const char* no = devicePointerRefusal(c, normals, 12 * n)) return fail(c, TB_E_INVALID, std::string("tb_sample_probes: normals: ") + no);
-                if (const char* no = devicePointerRefusal(c, rgbaOut, 16 * n)) return fail(c, TB_E_INVALID, std::string("tb_sample_probes: rgba_out: ") + no);
-            }
-        }
+        if (device && (((uintptr_t)probes & 15u) || ((uintptr_t)rgbaOut & 15u) || ((uintptr_t)points & 3u) || ((uintptr_t)normals & 3u)))
+            return fail(c, TB_E_INVALID, "tb_sample_probes: device probes and rgba_out are 16-B, points and normals 4-B aligned");
+        if (n == 0 && !device) return TB_OK; /* nothing to stage; device probes are checked all the same */
+        QueryIo io(c, "tb_sample_probes", device);
+        const TbProbe* records = io.in("probes", probes, sizeof(TbProbe) * numProbes);
         if (n == 0) return TB_OK;
-        if (device) {
-            HIP_TRY(probe_launch_sample(c->stream, grid, resolution, backfaceLimit, probes, (uint32_t)n, points, normals, (TbFloat4*)rgbaOut));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            return TB_OK;
-        }
-        const DevBuf dProbes = staged(probes, sizeof(TbProbe) * numProbes), dPoints = staged(points, 12 * n), dNormals = staged(normals, 12 * n), dOut = scratch(16 * n);
-        HIP_TRY(probe_launch_sample(c->stream, grid, resolution, backfaceLimit, (const TbProbe*)dProbes.p, (uint32_t)n, (const float*)dPoints.p, (const float*)dNormals.p,
-            (TbFloat4*)dOut.p));
+        const float* p = io.in("points", points, 12 * n);
+        const float* nrm = io.in("normals", normals, 12 * n);
+        TbFloat4* o = (TbFloat4*)io.out("rgba_out", rgbaOut, 16 * n);
+        HIP_TRY(probe_launch_sample(c->stream, grid, resolution, backfaceLimit, records, (uint32_t)n, p, nrm, o));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        copyBack(rgbaOut, dOut);
+        io.finish();
         return TB_OK;
     });
 }

@@ -1,7 +1,7 @@
 /* context_radiance.cpp -- radiance queries (include/tracerboy_hip.h tb_trace_radiance / tb_make_camera_rays): the path tracer on a
- * caller's rays, per ray the sum of its samples out, on host arrays (staged like the test hooks, nothing kept) or on device buffers.
+ * caller's rays, per ray the sum of its samples out, on host arrays (staged by query_call.h's QueryIo, nothing kept) or on device buffers.
  * Reads the scene, the camera and the options; writes nothing of the context but the query's own work counter and overflow stacks. */
-#include "context_internal.h"
+#include "query_call.h"
 #include "radiance_trace.h"
 
 #include <cstdlib>
@@ -65,12 +65,8 @@ int tbctx::traceRadianceOnDevice(tb_context* c, const char* who, const tb_output
     TbPerFrameConstants pf;
     MakeFrameConstants(c->scene, c->camera, s, k.firstSample, time, 0xffffffffu, 0xffffffffu, pf);
     if (pf.OutputMode == TB_OUTPUT_TYPE_HEATMAP) pf.OutputMode = TB_OUTPUT_TYPE_LIT; /* a query has no heatmap: the path goes on past its first hit */
-    HIP_TRY(hipEventRecord(c->rad.ev[0].create(), c->stream));
-    HIP_TRY(rad_launch(c->stream, &ds, &pf, &k, &plan, plan.stack.overflowEntries ? (uint32_t*)c->rad.overflow.p : nullptr, (uint32_t*)c->rad.counter.p, n,
-        rays, out, &c->rad.lastLaunches));
-    HIP_TRY(hipEventRecord(c->rad.ev[1].create(), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (hipEventElapsedTime(&c->rad.lastMs, c->rad.ev[0], c->rad.ev[1]) != hipSuccess) c->rad.lastMs = 0.0f;
+    timed(c->stream, c->rad.ev, c->rad.lastMs, [&]() { return rad_launch(c->stream, &ds, &pf, &k, &plan,
+        plan.stack.overflowEntries ? (uint32_t*)c->rad.overflow.p : nullptr, (uint32_t*)c->rad.counter.p, n, rays, out, &c->rad.lastLaunches); }, true);
     c->rad.lastVariant = variantIdOf(plan.features); c->rad.lastForm = (int)plan.form;
     return TB_OK;
 }
@@ -79,27 +75,22 @@ extern "C" int tb_trace_radiance(tb_context* c, const tb_output_settings* settin
     const TbRadianceRay* rays, TbFloat4* out)
 {
     TB_REFUSE_PEER(c);
-    if (c && !c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED,
-        "tb_trace_radiance: not supported for a multi-device group: a query's rays are traced on one device");
+    if (const int rc = refuseGroup(c, "tb_trace_radiance", "a query's rays are traced on one device")) return rc;
     return guarded(c, [&]() {
         char why[96];
         if (tb_radiance_refusal(call, n, rays, out, why, sizeof why) != TB_OK) return fail(c, TB_E_INVALID, std::string("tb_trace_radiance: ") + why);
         if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-        tb_output_settings s; if (settings) s = *settings; else DefaultOutputSettings(s);
+        const tb_output_settings s = settingsOrDefault(settings);
         if (s.RenderModeRealTime) return fail(c, TB_E_UNSUPPORTED, "tb_trace_radiance: the real-time mode is not supported: a query has no AOVs and no history");
         if (n == 0) return TB_OK;
-        const bool device = (call->mode_and_flags & TB_RADIANCE_DEVICE) != 0, accumulate = (call->mode_and_flags & TB_RADIANCE_ACCUMULATE) != 0;
-        const size_t rayBytes = (size_t)n * sizeof(TbRadianceRay), outBytes = (size_t)n * sizeof(TbFloat4);
-        if (device) {
-            if (const char* no = devicePointerRefusal(c, rays, rayBytes)) return fail(c, TB_E_INVALID, std::string("tb_trace_radiance: rays: ") + no);
-            if (const char* no = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_trace_radiance: out: ") + no);
-        }
-        DevBuf dRays, dOut; /* the host path's staging: temporary, like the test hooks' */
-        if (!device) { dRays = staged(rays, rayBytes); dOut = accumulate ? staged(out, outBytes) : scratch(outBytes); }
+        const bool accumulate = (call->mode_and_flags & TB_RADIANCE_ACCUMULATE) != 0;
+        QueryIo io(c, "tb_trace_radiance", (call->mode_and_flags & TB_RADIANCE_DEVICE) != 0);
+        const TbRadianceRay* r = io.in("rays", rays, (size_t)n * sizeof(TbRadianceRay));
+        TbFloat4* o = io.out("out", out, (size_t)n * sizeof(TbFloat4), accumulate); /* the sums start from what the caller's array holds */
         const RadCall k{call->first_sample, call->num_samples, (call->mode_and_flags & 0xffu) == TB_RADIANCE_HEMISPHERE ? 1u : 0u, accumulate ? 1u : 0u, call->seed_advance};
-        const int rc = traceRadianceOnDevice(c, "tb_trace_radiance", s, time, k, n, device ? rays : (const TbRadianceRay*)dRays.p, device ? out : (TbFloat4*)dOut.p);
+        const int rc = traceRadianceOnDevice(c, "tb_trace_radiance", s, time, k, n, r, o);
         if (rc != TB_OK) return rc;
-        if (!device) copyBack(out, dOut);
+        io.finish();
         return TB_OK;
     });
 }
@@ -108,8 +99,7 @@ extern "C" int tb_make_camera_rays(tb_context* c, const tb_output_settings* sett
     uint32_t y1, uint32_t frame, uint32_t flags, TbRadianceRay* out, float* seedAdvance)
 {
     TB_REFUSE_PEER(c);
-    if (c && !c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED,
-        "tb_make_camera_rays: not supported for a multi-device group: a query's rays are traced on one device");
+    if (const int rc = refuseGroup(c, "tb_make_camera_rays", "a query's rays are traced on one device")) return rc;
     return guarded(c, [&]() {
         if (flags & ~TB_RADIANCE_DEVICE) return fail(c, TB_E_INVALID, "tb_make_camera_rays: unknown flag bits");
         if (!out || !seedAdvance) return fail(c, TB_E_INVALID, "tb_make_camera_rays: null pointer");
@@ -117,25 +107,22 @@ extern "C" int tb_make_camera_rays(tb_context* c, const tb_output_settings* sett
         if (W > 16384u || H > 16384u) return fail(c, TB_E_INVALID, "tb_make_camera_rays: a dimension above 16384");
         if (x0 >= x1 || y0 >= y1 || x1 > W || y1 > H) return fail(c, TB_E_INVALID, "tb_make_camera_rays: the window is empty or leaves the picture");
         if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
-        tb_output_settings s; if (settings) s = *settings; else DefaultOutputSettings(s);
+        const tb_output_settings s = settingsOrDefault(settings);
         if (s.FilterType != TB_FILTER_TYPE_BOX) return fail(c, TB_E_UNSUPPORTED,
             "tb_make_camera_rays: a triangle or Gaussian pixel filter is not supported: its samples carry a weight and the ray record has none");
         const bool device = (flags & TB_RADIANCE_DEVICE) != 0;
-        const size_t bytes = (size_t)(x1 - x0) * (y1 - y0) * sizeof(TbRadianceRay);
-        if (device) {
-            if ((uintptr_t)out & 15u) return fail(c, TB_E_INVALID, "tb_make_camera_rays: device rays are not 16-B aligned");
-            if (const char* no = devicePointerRefusal(c, out, bytes)) return fail(c, TB_E_INVALID, std::string("tb_make_camera_rays: out: ") + no);
-        }
-        DevBuf dOut; if (!device) dOut = scratch(bytes);
+        if (device && ((uintptr_t)out & 15u)) return fail(c, TB_E_INVALID, "tb_make_camera_rays: device rays are not 16-B aligned");
+        QueryIo io(c, "tb_make_camera_rays", device);
+        TbRadianceRay* o = io.out("out", out, (size_t)(x1 - x0) * (y1 - y0) * sizeof(TbRadianceRay));
         const DevBuf dAdvance = scratch(4);
         TbPerFrameConstants pf;
         MakeFrameConstants(c->scene, c->camera, s, frame, time, 0xffffffffu, 0xffffffffu, pf);
         TbDeviceTargets tg; memset(&tg, 0, sizeof tg); /* the camera constants alone */
         if (opt<OPT_camera_constants>(c) != 0) cameraConstants(pf, W, H, tg);
-        HIP_TRY(rad_launch_camera_rays(c->stream, &c->ds, &pf, &tg, W, H, x0, y0, x1, y1, frame, device ? out : (TbRadianceRay*)dOut.p, (float*)dAdvance.p));
+        HIP_TRY(rad_launch_camera_rays(c->stream, &c->ds, &pf, &tg, W, H, x0, y0, x1, y1, frame, o, (float*)dAdvance.p));
         HIP_TRY(hipStreamSynchronize(c->stream));
         copyBack(seedAdvance, dAdvance);
-        if (!device) copyBack(out, dOut);
+        io.finish();
         return TB_OK;
     });
 }

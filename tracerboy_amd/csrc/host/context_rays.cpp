@@ -1,27 +1,13 @@
 /* context_rays.cpp -- ray queries (include/tracerboy_hip.h tb_trace_rays): a caller's rays through the traversal the renderer
- * uses, closest-hit records or occlusion flags out, on host arrays (staged like the test hooks) or on device buffers (nothing allocated per call).
+ * uses, closest-hit records or occlusion flags out, on host arrays (staged by query_call.h's QueryIo) or on device buffers (nothing allocated per call).
  * Reads the scene; writes nothing of the context but the work counter of the any-hit walk's refilling form. */
-#include "context_internal.h"
+#include "query_call.h"
 #include "../kernels/rq_launch.h"
 
 #include <cstdlib>
 
 using namespace tbhost;
 using namespace tbctx;
-
-/* a device pointer the caller gave: `bytes` from it lie inside one allocation of the context's device */
-const char* tbctx::devicePointerRefusal(const tb_context* c, const void* p, size_t bytes)
-{
-    hipPointerAttribute_t a; hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError(); /* the refusal is ours: the runtime's error does not stay behind */
-        return "not a device pointer";
-    }
-    if (a.type != hipMemoryTypeDevice) return "not device memory";
-    if (a.device != c->device) return "memory of another device than the context's";
-    if ((size_t)((const uint8_t*)p - (const uint8_t*)base) + bytes > size) return "the array runs past its allocation";
-    return nullptr;
-}
 
 namespace {
 
@@ -60,21 +46,15 @@ void tbctx::traceClosestOnDevice(tb_context* c, uint32_t n, const TbQueryRay* ra
 extern "C" int tb_trace_rays(tb_context* c, uint32_t modeAndFlags, uint64_t n, const TbQueryRay* rays, void* out)
 {
     TB_REFUSE_PEER(c);
-    if (c && !c->group.peers.empty()) return fail(c, TB_E_UNSUPPORTED,
-        "tb_trace_rays: not supported for a multi-device group: a query's rays are traced on one device");
+    if (const int rc = refuseGroup(c, "tb_trace_rays", "a query's rays are traced on one device")) return rc;
     return guarded(c, [&]() {
         if (const char* why = raysRefusal(modeAndFlags, n, rays, out)) return fail(c, TB_E_INVALID, std::string("tb_trace_rays: ") + why);
         if (!c->hasScene) return fail(c, TB_E_NO_SCENE, "no scene loaded");
         if (n == 0) return TB_OK;
-        const bool closest = (modeAndFlags & 0xffu) == TB_RAYS_CLOSEST, device = (modeAndFlags & TB_RAYS_DEVICE) != 0;
-        const size_t rayBytes = (size_t)n * sizeof(TbQueryRay), outBytes = closest ? (size_t)n * sizeof(TbQueryHit) : (size_t)n;
-        DevBuf dRays, dOut; /* the host path's staging: temporary, like the test hooks' */
-        if (device) {
-            if (const char* why = devicePointerRefusal(c, rays, rayBytes)) return fail(c, TB_E_INVALID, std::string("tb_trace_rays: rays: ") + why);
-            if (const char* why = devicePointerRefusal(c, out, outBytes)) return fail(c, TB_E_INVALID, std::string("tb_trace_rays: out: ") + why);
-        } else { dRays = staged(rays, rayBytes); dOut = scratch(outBytes); }
-        const TbQueryRay* r = device ? rays : (const TbQueryRay*)dRays.p;
-        void* o = device ? out : dOut.p;
+        const bool closest = (modeAndFlags & 0xffu) == TB_RAYS_CLOSEST;
+        QueryIo io(c, "tb_trace_rays", (modeAndFlags & TB_RAYS_DEVICE) != 0);
+        const TbQueryRay* r = io.in("rays", rays, (size_t)n * sizeof(TbQueryRay));
+        void* o = io.out("out", out, closest ? (size_t)n * sizeof(TbQueryHit) : (size_t)n);
         const int diag = closest ? -2 : refillDiagnostic();
         if (closest) traceClosestOnDevice(c, (uint32_t)n, r, (TbQueryHit*)o);
         else if (c->ds.numInstances || diag == -1) HIP_TRY(rq_launch_closest(c->stream, &c->ds, (uint32_t)n, r, nullptr, (uint8_t*)o));
@@ -84,7 +64,7 @@ extern "C" int tb_trace_rays(tb_context* c, uint32_t modeAndFlags, uint64_t n, c
             HIP_TRY(rq_launch_occluded(c->stream, &c->ds, (uint32_t)n, r, (uint8_t*)o, (uint32_t*)c->rq.counter.p, refill));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (!device) copyBack(out, dOut);
+        io.finish();
         return TB_OK;
     });
 }
